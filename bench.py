@@ -13,7 +13,10 @@ A "step" is one pass of the hot path over the rank's shard:
     phase fit+grad : objective + gradient (adds L^-1, K^-1, fused gradient reduction)
     phase predict  : mean + variance at m = 10 000 points per emulator (inputs + outputs HBM resident)
 `value` = fits/s over the whole job = emulators x steps / time spent in the fit phase (max over ranks);
-fit+grad/s and predict pts/s are reported next to it from the same timed steps.
+fit+grad/s and predict pts/s are reported next to it from the same timed steps; `ms_per_step` = wall time of the --steps timed steps / steps.
+`--dump-outputs DIR` writes what the last timed step returned, for every emulator of the job, as float64 DIR/<name>.npy: logpost (fit
+phase), fit_grad_logpost and fit_grad_gradient (fit+grad phase), predict_mean and predict_var (predict phase; a fixed seeded sample
+of the prediction points when all of them would exceed 64 MB).  The inputs are seeded, so the same arguments give the same inputs.
 
 other_configs (N = 1): BASELINE's C2 (one n=2000 emulator, predict m=10^4), C4 (16 x n=5000, Matern-5/2, fitted nugget) and
 C5 (n=16000) timed on this GPU with their tagged kernels, each with the CPU oracle beside it (`cpu_baseline`: one / two / one of its outputs fitted
@@ -48,6 +51,7 @@ sys.path.insert(0, ROOT)
 
 FP64_MFMA_PEAK_TF = 78.6      # AMD MI355X FP64 matrix spec; tools/mfma_probe.hip measures 78.2 on this part
 HBM_PEAK_GBS = 8000.0         # MI355X_MICROARCH.md: 8.0 TB/s spec
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs: all files together
 
 
 def synth(config_id, n, d, n_out, m):
@@ -377,6 +381,48 @@ def nccl_world1(mo, B, m, dev):
     return out
 
 
+def last_step_outputs(f, f2, g, d_mean, d_var, gathered, world, per_rank, dist):
+    """--dump-outputs: what a caller of the timed path received in the last timed step, on the host, for every emulator of the
+    job (on rank 0; None on the other ranks).  N > 1: the means / variances come from the step's own gather (blocks of per_rank
+    rows, the tail of a short last shard is padding); the log-posteriors and gradients of the other ranks are gathered here,
+    outside the timed region."""
+    host = {"logpost": f, "fit_grad_logpost": f2, "fit_grad_gradient": g}
+    if world == 1:
+        host["predict_mean"], host["predict_var"] = d_mean.cpu().numpy(), d_var.cpu().numpy()
+        return {k: np.array(v, dtype=np.float64) for k, v in host.items()}
+    parts = [None] * world
+    dist.all_gather_object(parts, {k: np.array(v, dtype=np.float64) for k, v in host.items()})
+    if dist.get_rank() != 0:
+        return None
+    out = {k: np.concatenate([p[k] for p in parts]) for k in host}
+    pred = gathered.cpu().numpy()
+    rows = np.concatenate([r * per_rank + np.arange(len(p["logpost"])) for r, p in enumerate(parts)])
+    out["predict_mean"], out["predict_var"] = pred[rows, 0], pred[rows, 1]
+    return out
+
+
+def write_dump(path, arrays, seed=0):
+    """One float64 DIR/<name>.npy per array, DUMP_BUDGET_BYTES in all.  Predictions that would not fit are written for a fixed
+    sample of the prediction points (seeded, the same columns for every emulator, in increasing order)."""
+    header = 1024                                       # per .npy file, generous
+    small = sum(v.nbytes for k, v in arrays.items() if not k.startswith("predict_")) + header * len(arrays)
+    n_emu, m = arrays["predict_mean"].shape
+    keep = min(m, (DUMP_BUDGET_BYTES - small) // (2 * 8 * n_emu))
+    if keep < 1:
+        raise SystemExit("bench.py: --dump-outputs: %d emulators do not fit in %d bytes" % (n_emu, DUMP_BUDGET_BYTES))
+    sample = None
+    if keep < m:
+        sample = np.sort(np.random.default_rng(seed).choice(m, keep, replace=False))
+        arrays = dict(arrays, predict_mean=arrays["predict_mean"][:, sample], predict_var=arrays["predict_var"][:, sample])
+    os.makedirs(path, exist_ok=True)
+    files = {}
+    for name, v in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
+        files[name] = list(v.shape)
+    return {"dir": os.path.abspath(path), "dtype": "float64", "files": files,
+            "predict_points": "all %d" % m if sample is None else "%d of %d, numpy default_rng(%d).choice, sorted" % (keep, m, seed)}
+
+
 def nest_summaries(out, n, total_emus, world):
     """The driver's record keeps the contract keys plus `roofline` and `cpu_baseline` with everything nested in them, and only the
     NAMES of the other top-level keys.  So the figures a reader needs beside the dominant kernel's go INSIDE
@@ -456,9 +502,16 @@ def main():
     ap.add_argument("--no-extras", action="store_true",
                     help="only the timed steps (+ the single-stream pass): none of the untimed extras (host-buffer predict, deriv, full_cov, "
                          "fit_GP_MAP, pivot, tsunami) -- for kernel traces whose per-kernel averages should be those of the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (log-posteriors, gradient, predictive mean "
+                         "and variance of every emulator) as DIR/<name>.npy, float64, at most %d MB in all" % (DUMP_BUDGET_BYTES >> 20))
     # (self-launched ranks get the command line through the environment: torch.distributed.run's own parser trips over script options
     # that are prefixes of its own, e.g. --m)
     args = ap.parse_args(json.loads(os.environ["MOGP_BENCH_ARGV"]) if "MOGP_BENCH_ARGV" in os.environ and "WORLD_SIZE" in os.environ else None)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     # `python bench.py --gpus N` outside a launcher: start the N ranks ourselves (one process per GPU, the launch line the
     # driver documents), rank 0 of the children prints the JSON line.  Under torch.distributed.run WORLD_SIZE is set and
@@ -469,9 +522,17 @@ def main():
             s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
             cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
                    "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__), "--gpus", str(args.gpus)]
-            os.environ["MOGP_BENCH_ARGV"] = json.dumps(sys.argv[1:])
+            # (a child process, not exec: this process never touches the GPU and only waits for the launcher.  A signal that ends
+            # this process is passed on to the launcher, which ends the ranks; the launcher also gets SIGTERM if this process dies.)
+            import signal
+            import subprocess
+            env = dict(os.environ, MOGP_BENCH_ARGV=json.dumps(sys.argv[1:]))
             sys.stdout.flush()
-            os.execv(sys.executable, cmd)
+            pdeathsig = lambda: ctypes.CDLL(None).prctl(1, signal.SIGTERM)       # PR_SET_PDEATHSIG
+            launcher = subprocess.Popen(cmd, env=env, preexec_fn=pdeathsig)
+            for sig in (signal.SIGTERM, signal.SIGINT, signal.SIGHUP):
+                signal.signal(sig, lambda s, _: launcher.send_signal(s))
+            raise SystemExit(launcher.wait())
     elif int(os.environ["WORLD_SIZE"]) != args.gpus:
         raise SystemExit("bench.py: --gpus %d but WORLD_SIZE=%s (launch with --nproc-per-node equal to --gpus)" % (
             args.gpus, os.environ["WORLD_SIZE"]))
@@ -566,7 +627,7 @@ def main():
         assert ok.all() and ok2.all() and np.all(np.isfinite(g))
         if timed:
             phase["fit"] += t1 - t0; phase["fitgrad"] += t2 - t1; phase["predict"] += t3 - t2; phase["gather"] += t4 - t3
-        return f
+        return f, f2, g
 
     def barrier():
         if world > 1:
@@ -581,10 +642,12 @@ def main():
     barrier()
     t_start = time.perf_counter()
     for it in range(args.steps):
-        f_last = step(args.warmup + it, True)
+        f_last, f2_last, g_last = step(args.warmup + it, True)
     barrier()
     elapsed = time.perf_counter() - t_start
     lib.mogp_profile_enable(0)
+    # taken now: the untimed passes below reuse the device buffers of the last step
+    dump = last_step_outputs(f_last, f2_last, g_last, d_mean, d_var, gathered, world, per_rank, dist) if args.dump_outputs else None
 
     # outside the timed region: the reference-style host-buffer predict (H2D of X*, D2H of mean/var over PCIe)
     # and one end-to-end MAP fit (lock-step L-BFGS, theta0 given, 1 start) for orientation
@@ -831,6 +894,8 @@ def main():
             out["cpu_baseline"], values = cpu_baseline(X, T_all if args.scaling == "strong" else T, Xs, theta, nugget)
             out["parity_in_bench"] = parity_in_bench(mo, values, theta, Xs)
         nest_summaries(out, n, total_emus, world)
+        if dump is not None:
+            out["dumped_outputs"] = write_dump(args.dump_outputs, dump)
         os.write(json_fd, (json.dumps(out) + "\n").encode())
     if world > 1:
         dist.barrier()

@@ -8,6 +8,7 @@ import socket
 
 import numpy as np
 import pytest
+from numpy.testing import assert_allclose
 
 pytestmark = pytest.mark.gpu
 
@@ -231,12 +232,50 @@ def test_bench_gpus_flag_launches_that_many_ranks():
     assert cb["kind"] == "port" and cb["value"] > 0 and cb["cores"] >= 1 and cb["parity_in_bench"]["passed"] is True
 
 
-def test_bench_eight_ranks_control_flow_on_one_gpu():
-    """The driver's N = 8 line (8 emulators per rank: the chain-bound regime of the one-launch Cholesky), all eight ranks on the one
-    device of this box over gloo: shard bounds, the padded gather, the max-over-ranks reductions and the line's shape."""
-    out = _bench_line(8, ["--no-cpu-baseline", "--m", "2000"])
-    assert out["n_gpus"] == 8 and out["rccl_ranks"] == 8
-    assert out["config"]["outputs_per_gpu"] == 8 and out["config"]["outputs_total"] == 64 and out["scaling"] == "strong"
+def test_bench_four_ranks_control_flow_on_one_gpu(tmp_path):
+    """The N > 1 line with four ranks on the one device of this box over gloo (eight would put more processes on one GPU than a
+    shared machine allows), 62 emulators so that the last shard is short (16 / 16 / 16 / 14): shard bounds, the padded gather,
+    the max-over-ranks reductions and the line's shape; --dump-outputs takes the job's predictions out of that gather, so they
+    hold every emulator once, in order, without the padding rows."""
+    out = _bench_line(4, ["--no-cpu-baseline", "--m", "2000", "--outputs", "62", "--dump-outputs", str(tmp_path)])
+    assert out["n_gpus"] == 4 and out["rccl_ranks"] == 4
+    assert out["config"]["outputs_per_gpu"] == 16 and out["config"]["outputs_total"] == 62 and out["scaling"] == "strong"
     assert np.isfinite(out["value"]) and out["value"] > 0 and np.isfinite(out["logpost_checksum"])
-    assert out["roofline"]["headline_kernel"]["flops_per_launch"] == 8 * 2000. ** 3 / 3.
+    assert out["roofline"]["headline_kernel"]["flops_per_launch"] == 16 * 2000. ** 3 / 3.
     assert "cpu_baseline" not in out
+    d = {k: np.load(str(tmp_path / (k + ".npy"))) for k in ("logpost", "fit_grad_logpost", "fit_grad_gradient", "predict_mean", "predict_var")}
+    assert all(v.dtype == np.float64 and np.all(np.isfinite(v)) for v in d.values())
+    assert d["logpost"].shape == (62,) and d["fit_grad_gradient"].shape == (62, 11)
+    assert d["predict_mean"].shape == d["predict_var"].shape == (62, 2000)
+    assert np.sum(d["logpost"][:16]) == out["logpost_checksum"]          # rank 0's shard leads
+    assert_allclose(d["fit_grad_logpost"], d["logpost"], rtol=1e-9)
+    assert np.all(d["predict_var"] > 0.) and np.all(np.abs(d["predict_mean"]).max(axis=1) > 0.)   # no padding row
+
+
+def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
+    """`--dump-outputs DIR` writes what the timed path returned in its LAST timed step: the emulators' log-posteriors, gradients,
+    predictive means and variances (without the nugget, as the timed predict returns them) at that step's theta, against the oracle
+    for the first and the last emulator with the stated tolerances (as bench.py's parity_in_bench)."""
+    import bench
+    from oracle import cpu_ref as R
+    n, d, B, m, steps, warmup = 2000, 10, 4, 700, 2, 1
+    out = _bench_line(1, ["--n", str(n), "--d", str(d), "--outputs", str(B), "--m", str(m), "--steps", str(steps), "--warmup", str(warmup),
+                          "--no-cpu-baseline", "--no-other-configs", "--no-extras", "--no-shard-sweep", "--dump-outputs", str(tmp_path)])
+    assert out["steps"] == steps and out["ms_per_step"] > 0
+    assert sorted(out["dumped_outputs"]["files"]) == ["fit_grad_gradient", "fit_grad_logpost", "logpost", "predict_mean", "predict_var"]
+    g = {k: np.load(str(tmp_path / (k + ".npy"))) for k in out["dumped_outputs"]["files"]}
+    assert all(v.dtype == np.float64 for v in g.values())
+    assert g["logpost"].shape == (B,) and g["fit_grad_gradient"].shape == (B, d + 1) and g["predict_mean"].shape == (B, m)
+    assert np.sum(g["logpost"]) == out["logpost_checksum"]
+    X, T, Xs = bench.synth(2, n, d, B, m)
+    theta = np.array([-2. * np.log(0.3 * np.sqrt(d))] * d + [0.])
+    last = theta + 1e-3 * np.sin(warmup + steps - 1 + np.arange(B))[:, None]      # bench.py's step(): a new theta every step
+    for k in (0, B - 1):
+        ref = R.GPRef(X, T[k], nugget=1e-6)
+        assert_allclose(g["logpost"][k], ref.fit(last[k]), rtol=1e-10)
+        assert_allclose(g["fit_grad_logpost"][k], g["logpost"][k], rtol=1e-10)
+        grad = ref.logpost_deriv(last[k])
+        assert np.max(np.abs(g["fit_grad_gradient"][k] - grad)) <= 1e-7 * np.max(np.abs(grad))
+        mu, var, _ = ref.predict(Xs, include_nugget=False)
+        assert_allclose(g["predict_mean"][k], mu, rtol=1e-7, atol=1e-8)
+        assert_allclose(g["predict_var"][k], var, atol=1e-7)

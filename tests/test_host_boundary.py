@@ -360,6 +360,45 @@ def test_bench_refuses_a_world_size_that_disagrees_with_gpus():
     assert res.returncode != 0 and "WORLD_SIZE=3" in res.stderr
 
 
+def test_bench_refuses_zero_steps():
+    """--steps is the number of timed steps and ms_per_step is divided by it: zero is refused before torch is imported."""
+    import subprocess
+    import sys
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=60)
+    assert res.returncode != 0 and "--steps" in res.stderr
+
+
+def test_bench_dump_writer_keeps_to_its_budget(tmp_path):
+    """bench.py --dump-outputs: every array as float64 DIR/<name>.npy; predictions larger than the budget are cut to a fixed seeded
+    sample of the prediction points, the same for every emulator and from run to run; small ones are written whole."""
+    import bench
+    rng = np.random.default_rng(3)
+    n_emu, m = 64, 80000                                   # 2 x 41 MB of predictions: over the 64 MB budget
+    arrays = {"logpost": rng.normal(size=n_emu), "fit_grad_logpost": rng.normal(size=n_emu), "fit_grad_gradient": rng.normal(size=(n_emu, 11)),
+              "predict_mean": rng.normal(size=(n_emu, m)), "predict_var": rng.random((n_emu, m))}
+    info = bench.write_dump(str(tmp_path / "a"), arrays)
+    files = sorted((tmp_path / "a").iterdir())
+    assert [f.name for f in files] == sorted(k + ".npy" for k in arrays)
+    assert sum(f.stat().st_size for f in files) <= bench.DUMP_BUDGET_BYTES
+    got = {f.name[:-4]: np.load(str(f)) for f in files}
+    assert all(v.dtype == np.float64 for v in got.values())
+    keep = got["predict_mean"].shape[1]
+    assert got["predict_mean"].shape == got["predict_var"].shape == (n_emu, keep) and m // 2 < keep < m
+    assert info["files"]["predict_var"] == [n_emu, keep]
+    cols = [int(np.flatnonzero(arrays["predict_mean"][0] == v)[0]) for v in got["predict_mean"][0]]
+    assert cols == sorted(set(cols))
+    assert np.array_equal(got["predict_mean"], arrays["predict_mean"][:, cols]) and np.array_equal(got["predict_var"], arrays["predict_var"][:, cols])
+    for k in ("logpost", "fit_grad_logpost", "fit_grad_gradient"):
+        assert np.array_equal(got[k], arrays[k])
+    bench.write_dump(str(tmp_path / "b"), arrays)
+    assert np.array_equal(np.load(str(tmp_path / "b" / "predict_var.npy")), got["predict_var"])
+    small = dict(arrays, predict_mean=arrays["predict_mean"][:, :100].astype(np.float32), predict_var=arrays["predict_var"][:, :100])
+    info = bench.write_dump(str(tmp_path / "c"), small)
+    assert info["predict_points"] == "all 100"
+    mean = np.load(str(tmp_path / "c" / "predict_mean.npy"))
+    assert mean.dtype == np.float64 and np.array_equal(mean, small["predict_mean"])
+
+
 def test_one_hip_runtime_per_process_after_loading_the_library():
     """_capi.load() must leave ONE libamdhip64 in the process -- the copy bundled with an installed PyTorch-ROCm wheel when there is one,
     so that torch (imported later, or earlier) and the library share a runtime (round 4: with two runtimes torch.cuda found no device

@@ -1,5 +1,5 @@
-import sys, numpy as np
-sys.path.insert(0, "/root/repo")
+import os, sys, numpy as np
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import mogp_emulator_amd as M
 from mogp_emulator_amd.Priors import GPPriors
 from oracle import cpu_ref as R
