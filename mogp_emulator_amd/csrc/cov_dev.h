@@ -1,6 +1,5 @@
-// Device helpers shared by the covariance kernels (kernels_cov.hip) and the pivoted Cholesky (kernels_pivot.hip): kernel
-// functions with their exponential, LDS staging of input rows, and the rule for the entries of the augmented matrix
-// (targets / design rows / padding).
+// Device helpers of the covariance kernels (kernels_cov.hip): kernel functions with their exponential, LDS staging of input
+// rows, and the rule for the entries of the augmented matrix (targets / design rows / padding).
 #pragma once
 #include "launch.h"
 #include "exp_dev.h"

@@ -153,7 +153,7 @@ class Engine {
   bool mc_used = false;          // the last factorisation of this engine went through the one-launch kernel (its abort word is live)
   bool mc_force_legacy = false;  // transient: repeat a factorisation with a multi-launch schedule after an abort
   int n_cu = 256;
-  int* dBsFlags = nullptr;       // hand-off flags of the one-launch back substitution (B x ceil(n/128)), compared with bs_epoch
+  int* dBsStatus = nullptr;      // time-out words of the one-launch back substitution (one per emulator), compared with bs_epoch
   int bs_epoch = 0;
   double *dRes = nullptr, *hRes = nullptr;   // per emulator [log-det, status, Gram matrix]: device buffer and its pinned host mirror
   double *dGradOut = nullptr, *dGradPartial = nullptr;

@@ -236,7 +236,7 @@ Engine::~Engine() {
     if (p) hipFree(p);
   if (hRes) hipHostFree(hRes);
   if (hP) hipHostFree(hP);
-  if (dBsFlags) hipFree(dBsFlags);
+  if (dBsStatus) hipFree(dBsStatus);
   for (void* p : {(void*)dMcTable, (void*)dMcCtrl, (void*)dMcPacks})
     if (p) hipFree(p);
   if (sigU1) hipFree(sigU1);
@@ -411,7 +411,7 @@ void Engine::factorize_pivot(const std::vector<int>& ids, std::vector<int>& info
   if (!stopped.empty()) {
     upload_idx(stopped);
     BatchView t = view((int)stopped.size());
-    launch_pstrf_tail(t, dPerm, dRank, dX, nullptr, stream);
+    launch_pstrf_tail(t, dPerm, dRank, stream);
   }
   upload_idx(ids);
   v = view(nb);
@@ -468,13 +468,15 @@ void Engine::factorize_blocked(const std::vector<int>& ids, std::vector<int>& in
   upload_idx(ids);
   upload_params(ids);
   BatchView v = view(nb);
-  // schedule: 4 = one launch / task queue (default, kernels_mchol.hip); the multi-launch schedules (fall-back, > 2048 tiles per step):
-  // 3 = left-looking with look-ahead, 0 = left-looking in two emulator groups, 1 = right-looking + look-ahead
+  // schedule: 4 = one launch / task queue (default, kernels_mchol.hip); the multi-launch schedules (fall-back, >= 16384 tiles per step):
+  // 3 = left-looking with look-ahead, 0 = left-looking in two emulator groups, 1 = right-looking + look-ahead; 5 = the multi-launch
+  // schedule of the regime.  MOGP_CHOL forces one: mchol (4), la (3), left (0), right (1), multi (5)
   static const int forced = [] {
     const char* e = getenv("MOGP_CHOL");
     if (!e) return -1;
     if (e[0] == 'r') return 1;
     if (std::string(e) == "mchol") return 4;
+    if (std::string(e) == "multi") return 5;
     return (std::string(e) == "left") ? 0 : 3;
   }();
   // Measured (fit, ms; look-ahead / two groups / right-looking): 8 x n=2000 1.75 / 1.97 / 1.89, 16 x 2.21 / 2.38 / 2.44,
@@ -483,20 +485,20 @@ void Engine::factorize_blocked(const std::vector<int>& ids, std::vector<int>& in
   // a large batch fills the machine with the update of ONE emulator group while the other factors its panels.
   const long tiles64 = (long)nb * (NP / 64), tiles128 = (long)nb * (NP / TILE);
   const ScheduleOverride& ovr = schedule_override();
-  // Default: the ONE-LAUNCH task-queue kernel (schedule 4) up to 2048 128-tiles per block-column step.  Fit, ms, one launch /
+  // Default: the ONE-LAUNCH task-queue kernel (schedule 4) below 16384 128-tiles per block-column step.  Fit, ms, one launch /
   // best multi-launch schedule: 8 x n=2000 1.12 / 1.60, 16 x 1.54 / 1.98, 32 x 2.58 / 3.05, 64 x 4.73 - 4.84 / 5.06, 120 x 8.46 /
   // 8.83, 2 x n=5000 2.86 / 5.27, 16 x n=5000 14.4 / 17.5, n=16000 26.3 / 34.5, 3 x n=700 0.40 / 0.54, 64 x n=1000 1.04 / 1.06.
-  // Beyond that (the replica engines of a multi-start fit: 240 x n=2000 17.3 / 16.8) and for thousands of single-block
-  // matrices (2000 x n=100: 0.62 / 0.57, one task each) the two-group multi-launch schedule stays.
+  // Beyond that and for more than 512 single-block matrices (2000 x n=100: 0.62 / 0.57, one task each) the two-group multi-launch
+  // schedule stays.
   const int legacy = tiles64 < 256 ? 1 : (tiles128 >= 1024 ? 0 : 3);
-  static const bool mc_default = [] { const char* e = getenv("MOGP_MCHOL"); return !e || atoi(e) != 0; }();
   // Round 6: re-measured on the round-5 kernels, the one-launch kernel wins at every batch size -- 128 / 256 / 512 x n=2000: 7.71 / 15.24 /
   // 30.68 ms against 8.87 / 17.54 / 33.70 with the two-group schedule, 1024 x n=1000 11.19 / 11.73, 2048 x n=500 4.50 / 4.91, 4096 x n=250
   // 2.34 / 2.75, 64 x n=5000 52.2 / 56.9 (profiles/r06_big_batch.txt) -- so the bound is now the pack memory alone (147 KB per emulator and
   // block column: 16384 tiles = 2.4 GB); rounds 2-5 stopped at 2048 tiles (measured on the round-2 kernel: 240 x n=2000 17.3 / 16.8).
   const bool mc_regime = tiles128 < 16384 && (NP > TILE || nb <= 512);
-  int schedule = ovr.schedule >= 0 ? ovr.schedule : (forced >= 0 ? forced : ((mc_default && mc_regime) ? 4 : legacy));
-  if (schedule == 5) schedule = legacy;            // (mogp_profile_schedule(5, ..): the multi-launch schedule of this regime)
+  // precedence: the hook (mogp_profile_schedule), then MOGP_CHOL, then the regime
+  int schedule = ovr.schedule >= 0 ? ovr.schedule : forced >= 0 ? forced : mc_regime ? 4 : legacy;
+  if (schedule == 5) schedule = legacy;
   // the one-launch kernel addresses an emulator's matrix through a 32-bit buffer offset; after an abort the multi-launch
   // schedule of the same regime takes over
   if (schedule == 4 && (mc_force_legacy || MS * sizeof(double) >= (size_t)1 << 32)) schedule = legacy;
@@ -513,7 +515,7 @@ void Engine::factorize_blocked(const std::vector<int>& ids, std::vector<int>& in
     }
     if (nb > mc_slots) {
       // control rows and packs are per batch SLOT of a launch, sized for the largest launch seen so far -- not for the engine's B: a
-      // few-emulator retry on an engine whose full batch stays on the multi-launch schedules (B * NP / 128 >= 2048) would otherwise
+      // few-emulator retry on an engine whose full batch stays on the multi-launch schedules (B * NP / 128 >= 16384) would otherwise
       // allocate B packs per block column (4.7 GB at B = 2000, n = 2000)
       HIPCK(hipStreamSynchronize(stream));
       if (dMcCtrl) HIPCK(hipFree(dMcCtrl));
@@ -725,18 +727,16 @@ void Engine::eval(const std::vector<int>& ids, const std::vector<const double*>&
       upload_idx(todo);
       BatchView v = view((int)todo.size());
       bool chained = false, res_done = false;
-      // single right-hand side: the one-launch chain (MOGP_BACKSOLVE=1: per-block launches, the path a timed-out chain falls back to)
-      static const bool chain = [] { const char* e = getenv("MOGP_BACKSOLVE"); return !e; }();
-      const bool use_chain = chain && R == 1 && pass == 0;
-      // the chain on stream `st` (flags and sentinel rows prepared on the same stream, in front of it)
+      // single right-hand side: the one-launch chain; the per-block launches (launch_backsolve) serve R > 1 and the repeat of a timed-out chain
+      const bool use_chain = R == 1 && pass == 0;
+      // the chain on stream `st` (status words and sentinel rows prepared on the same stream, in front of it)
       auto launch_chain = [&](hipStream_t st) {
-        const size_t nfl = (size_t)B * ((n + 127) / 128);
-        if (!dBsFlags) {
-          dBsFlags = dalloc<int>(nfl + B);                 // flags, then one status word per emulator
-          HIPCK(hipMemsetAsync(dBsFlags, 0, (nfl + B) * sizeof(int), st));
+        if (!dBsStatus) {
+          dBsStatus = dalloc<int>(B);
+          HIPCK(hipMemsetAsync(dBsStatus, 0, B * sizeof(int), st));
         }
-        if (bs_epoch > 0x7FFFFF00) {                       // flags and status are compared with the epoch: start over before it wraps
-          HIPCK(hipMemsetAsync(dBsFlags, 0, (nfl + B) * sizeof(int), st));
+        if (bs_epoch > 0x7FFFFF00) {                       // the status words are compared with the epoch: start over before it wraps
+          HIPCK(hipMemsetAsync(dBsStatus, 0, B * sizeof(int), st));
           bs_epoch = 0;
         }
         if (z_armed.size() != (size_t)B) z_armed.assign(B, 0);
@@ -744,7 +744,7 @@ void Engine::eval(const std::vector<int>& ids, const std::vector<const double*>&
           if (!z_armed[i]) HIPCK(hipMemsetAsync(dAlpha + (size_t)i * RA * LD, 0xFF, (size_t)LD * sizeof(double), st));
           z_armed[i] = 0;                                  // consumed by this solve
         }
-        res_done = launch_backsolve_chain(v, dBsFlags, ++bs_epoch, dBsFlags + nfl, n_cu, st, dInfo, dRes, mc_used ? dMcCtrl : nullptr);
+        res_done = launch_backsolve_chain(v, ++bs_epoch, dBsStatus, n_cu, st, dInfo, dRes, mc_used ? dMcCtrl : nullptr);
         chained = true;
       };
       if (want_grad) {
@@ -772,7 +772,7 @@ void Engine::eval(const std::vector<int>& ids, const std::vector<const double*>&
         launch_backsolve(v, stream);
       }
       // (after the solves: it also collects the status words)
-      if (!res_done) launch_logdet(v, dInfo, dRes, stream, chained ? dBsFlags + (size_t)B * ((n + 127) / 128) : nullptr, bs_epoch, mc_used ? dMcCtrl : nullptr);
+      if (!res_done) launch_logdet(v, dInfo, dRes, stream, chained ? dBsStatus : nullptr, bs_epoch, mc_used ? dMcCtrl : nullptr);
       // status words, log-determinants and Gram matrices come back in ONE copy into pinned host memory
       HIPCK(hipMemcpyAsync(hRes, dRes, (size_t)B * RES_STRIDE * sizeof(double), hipMemcpyDeviceToHost, stream));
       HIPCK(hipStreamSynchronize(stream));
@@ -1455,14 +1455,12 @@ void Engine::pivot_cholesky(const double* Ain, int n, double* L_out, int* P_out,
     else hA[(size_t)i * NPp + i] = 1.0;
   }
   double* dA_ = dalloc<double>(hA.size());
-  double* dA0 = dalloc<double>((size_t)n * n);
   double* dW = dalloc<double>(pstrf_work_doubles(NPp));
   int* dI = dalloc<int>((size_t)n + 2);
   BatchView v{};
   v.n = n; v.D = 1; v.NP = NPp; v.LD = NPp; v.MS = (size_t)NPp * NPp; v.PS = 0; v.kernel_type = 0;
   v.A = dA_; v.R = 0; v.RA = 0; v.idx = nullptr; v.nb = 1;
   HIPCK(hipMemcpy(dA_, hA.data(), hA.size() * sizeof(double), hipMemcpyHostToDevice));
-  HIPCK(hipMemcpy(dA0, Ain, (size_t)n * n * sizeof(double), hipMemcpyHostToDevice));
   launch_pstrf_begin(v, dI, dI + n, dI + n + 1, dW, nullptr);
   int rk = -1;
   for (int k0 = 0; k0 < n; k0 += NBI) {
@@ -1473,11 +1471,11 @@ void Engine::pivot_cholesky(const double* Ain, int n, double* L_out, int* P_out,
     if (first_half) launch_update_narrow(v, k0 + NBI, k0, k0 + NBI, nullptr);
     launch_update_trailing(v, first_half ? k0 + TILE : k0 + NBI, k0, k0 + NBI, nullptr);
   }
-  launch_pstrf_tail(v, dI, dI + n, nullptr, dA0, nullptr);
+  launch_pstrf_tail(v, dI, dI + n, nullptr);
   std::vector<int> hi((size_t)n + 2);
   HIPCK(hipMemcpy(hi.data(), dI, hi.size() * sizeof(int), hipMemcpyDeviceToHost));
   HIPCK(hipMemcpy(hA.data(), dA_, hA.size() * sizeof(double), hipMemcpyDeviceToHost));
-  hipFree(dA_); hipFree(dA0); hipFree(dW); hipFree(dI);
+  hipFree(dA_); hipFree(dW); hipFree(dI);
   for (int i = 0; i < n; ++i) std::memcpy(L_out + (size_t)i * n, hA.data() + (size_t)i * NPp, (size_t)n * sizeof(double));
   if (hi[n + 1] != 0) throw std::runtime_error("not pd: no positive pivot");
   for (int i = 0; i < n; ++i) {

@@ -185,8 +185,8 @@ __device__ __forceinline__ void mainloop_w(const double* __restrict__ Ag, int ld
 template <int BM, int BN, int WR, int WC, int PD>
 __device__ __forceinline__ void mainloop_pf(const double* __restrict__ Ag, int lda, const double* __restrict__ Bg, int ldb, int nk,
                                             v4d (&acc)[WCfg<BM, BN, WR, WC>::TI][WCfg<BM, BN, WR, WC>::TJ], double* smem, int kmask = -1) {
-  // kmask (measurement only, MOGP_MC_NOTRAFFIC): k-step kt reads the operand columns of step kt & kmask -- with kmask = 3 every task
-  // re-reads its first 64 columns from the caches: the same instruction stream without the memory traffic (results are garbage)
+  // kmask (-1 at run time in every caller): k-step kt reads the operand columns of step kt & kmask -- with kmask = 3 every task re-read its first 64
+  // columns from the caches, the traffic measurement of round 5 (the same instruction stream without the memory traffic; results garbage)
   using C = WCfg<BM, BN, WR, WC>;
   const int t = mogp_tid(), lane = t & 63, wave = t >> 6;
   const int wr = wave / WC, wc = wave % WC;

@@ -231,29 +231,27 @@ __global__ __launch_bounds__(256) void backsolve_gemv4_kernel(BatchView v, int k
 // held in LDS) and publishes.  Chunks are dispatched right to left (the rightmost chunk has no dependencies), so a
 // workgroup only ever waits for workgroups with a smaller block index: no deadlock however many are resident.
 // Hand-off (MI355X_MICROARCH.md, inter-workgroup visibility, valid form "8-byte agent atomics on both sides";
-// cdna_hip_programming.md guideline 16, recipe R1): the payload is written with agent-scope atomic stores (sc1: through to
-// L2), EVERY storing wave drains them (inline-asm s_waitcnt: the compiler may drop a builtin wait in front of a flag store),
-// a barrier, then one lane stores the flag; the consumer polls the flag relaxed and reads the payload with agent-scope
-// atomic loads (sc1: past its own L1), so no cached copy of another workgroup's alpha is ever read.
+// cdna_hip_programming.md guideline 16, recipe R1): the solution vector is preset to all-ones bit patterns by the K build, a
+// chunk's entries are published by their own agent-scope stores (sc1: through to L2), and a consumer's lanes poll the 128
+// VALUES they need with agent-scope atomic loads (sc1: past their own L1) until they are no longer that pattern -- no flag, no
+// second round trip, and the lower half of a chunk (solved first) is folded while its producer still solves the upper half.
+// (Round 4; the flag + payload form it replaced cost a drain, a barrier and a flag store per chain step, ~2.5 of 7 us.)
 // Forward progress is NOT assumed: in-order dispatch makes a wait short, but HIP does not promise it, so every wait is
-// bounded and a workgroup that gives up records status[emu] = epoch (a word of its own -- not the factorisation's info,
-// which would start the jitter ladder) and still publishes, so nobody behind it hangs; the engine then repeats the solve
-// of that emulator with the multi-launch path (Engine::eval, after_factor).
+// bounded and a lane that gives up records status[emu] = epoch (a word of its own -- not the factorisation's info,
+// which would start the jitter ladder) and takes 0.0 (never the pattern, which an fma would propagate into its own results
+// and make every chunk behind it time out too), so nobody behind it hangs; the engine then repeats the solve of that
+// emulator with the multi-launch path (Engine::eval, after_factor).
 // Replaces 32 launches of ~6 us each at n = 2000 (0.2 ms of a 1.7 ms fit for 8 emulators, 0.43 of 5.3 ms for 64).
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ double ld_agent(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void st_agent(double* p, double x) { __hip_atomic_store(p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-// SENT (round 4, the default; MOGP_BS_SENTINEL=0 keeps the flag form): no flag and no second round trip -- the solution vector was
-// preset to all-ones bit patterns by the K build, a chunk's entries are published by their own agent-scope stores, and a consumer's
-// lanes poll the 128 VALUES they need until they are no longer that pattern.  Per chain step this removes the producer's drain +
-// barrier + flag store and the consumer's payload load behind its flag poll (~2.5 of 7 us), and the lower half of a chunk (solved
-// first) is folded while its producer still solves the upper half.  A lane that gives up stores the emulator's status word, takes 0.0 (never the
-// pattern, which an fma would propagate into its own results and make every chunk behind it time out too) and the emulator is re-solved by the engine.
-// HOIST (launches with at most one workgroup per CU -- the chain-bound ones; needs SENT): see preload_diag below; the one-per-CU build has the
+// HOIST (launches with at most one workgroup per CU -- the chain-bound ones): see preload_diag below; the one-per-CU build has the
 // registers for it (with two per CU the 128 extra live registers spilled into the solve they were meant to shorten).
-template <bool SENT, bool HOIST = false>
-__global__ __launch_bounds__(256, HOIST ? 1 : 2) void backsolve_chain_kernel(BatchView v, int* __restrict__ flags, int epoch, int nch, int* __restrict__ status, int spin_limit,
+// `unused` (the caller passes null) holds the place of the flag form's hand-off words (round 4, retired in round 7): the argument layout, and
+// with it the kernel's code, stays as it was measured.
+template <bool HOIST>
+__global__ __launch_bounds__(256, HOIST ? 1 : 2) void backsolve_chain_kernel(BatchView v, int* __restrict__ unused, int epoch, int nch, int* __restrict__ status, int spin_limit,
                                                                  const int* __restrict__ info, double* __restrict__ res, const unsigned* __restrict__ mc_abort) {
   __shared__ double Ld[2][64 * 65];        // the two diagonal blocks of this chunk: [row][column], row stride 65
   __shared__ double w[128], xs[128];
@@ -269,7 +267,6 @@ __global__ __launch_bounds__(256, HOIST ? 1 : 2) void backsolve_chain_kernel(Bat
   const int ld = v.LD, n = v.n;
   const double* A = v.A + (size_t)emu * v.MS;
   double* alpha = v.Z + (size_t)emu * ld;
-  int* fl = flags + (size_t)emu * nch;
   const int t = threadIdx.x, lane = t & 63, rg = __builtin_amdgcn_readfirstlane(t >> 6);      // (wave-uniform: row addresses are scalar)
   const int j0 = 128 * c;
   if (t == 0) timed_out = 0;
@@ -285,17 +282,16 @@ __global__ __launch_bounds__(256, HOIST ? 1 : 2) void backsolve_chain_kernel(Bat
   }
   // tile of 64 rows [k0, k0+64) x columns [j0, j0+128): lane -> two columns, wave -> 16 of the rows.  TWO register sets: both tiles of
   // the chunk that is folded next (and, last, the chunk's own off-diagonal tile) are requested a whole step before they are used --
-  // the loads do not depend on alpha, so their latency sits under the wait for the flag instead of on the chain (with one set the
+  // the loads do not depend on alpha, so their latency sits under the wait for the values instead of on the chain (with one set the
   // second tile of every chunk and the own tile were requested when they were needed: ~1.5 us each per chain step)
   v2d tA[16], tB[16];
   auto load_tile = [&](v2d (&tv)[16], int k0) {
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       const int row = k0 + 16 * rg + i;
-      // (SENT: unpredicated -- rows n .. NP-1 exist, hold finite values (forward-solved targets, identity padding) and meet x = 0; with the
-      // predicate every row became a basic block of its own in that form and the register allocator spilled 500 bytes per lane)
-      if (SENT) tv[i] = *reinterpret_cast<const v2d*>(A + (size_t)row * ld + j0 + 2 * lane);
-      else tv[i] = (row < n) ? *reinterpret_cast<const v2d*>(A + (size_t)row * ld + j0 + 2 * lane) : (v2d){0., 0.};
+      // (unpredicated -- rows n .. NP-1 exist, hold finite values (forward-solved targets, identity padding) and meet x = 0; with a
+      // predicate every row became a basic block of its own and the register allocator spilled 500 bytes per lane)
+      tv[i] = *reinterpret_cast<const v2d*>(A + (size_t)row * ld + j0 + 2 * lane);
     }
   };
   // w[cols] -= tile^T x, x = xs[xoff .. xoff+64); ncols = 128 (a block below the chunk) or 64 (inside the chunk)
@@ -318,14 +314,14 @@ __global__ __launch_bounds__(256, HOIST ? 1 : 2) void backsolve_chain_kernel(Bat
     }
     __syncthreads();
   };
-  // SENT: the lane's 64 scaled column entries of a diagonal block, -L[j][lane] / L_ll, in REGISTERS, held by the wave that solves the block: wave 0
+  // the lane's 64 scaled column entries of a diagonal block, -L[j][lane] / L_ll, in REGISTERS, held by the wave that solves the block: wave 0
   // the lower block (rows j0+64.., solved first), wave 1 the upper one.  HOIST (round 5): fetched at the START of the kernel, before the chunk's
   // dependencies arrive (they depend on L only); otherwise inside each solve -- 64 LDS reads + 64 multiplies in front of the 64-step substitution,
   // ~1 of the 2.3 us of a block, twice per step of the launch's dependent chain.
   double Lc[64], rdgw = 0.0;
   const int myblk = rg == 0 ? 1 : 0;           // (waves 2, 3: unused)
   auto preload_diag = [&]() {
-    if (SENT && rg < 2) {
+    if (rg < 2) {
       const double* Lb = Ld[myblk];
       const double dg = Lb[lane * 65 + lane];
       rdgw = (j0 + 64 * myblk + lane < n) ? 1.0 / dg : 0.0;
@@ -339,44 +335,30 @@ __global__ __launch_bounds__(256, HOIST ? 1 : 2) void backsolve_chain_kernel(Bat
   // x = L_kk^-T w[woff .. woff+64) for diagonal block blk (one wave; lane t holds column t of the block), into xs and alpha
   auto solve_diag = [&](int blk) {
     const int k0 = j0 + 64 * blk;
-    if (SENT ? rg == (blk ? 0 : 1) : rg == 0) {
-      const double* Lb = Ld[blk];
-      double xout = 0.0;
-      if (SENT) {
-        if (!HOIST) preload_diag();
-        // the lane carries b / L_ll instead of b: per step readlane -> fma (the multiply by 1 / L_ll left the chain; the scaled column
-        // entries L[j][lane] / L_ll do not depend on the right-hand side)
-        double bs = w[64 * blk + lane] * rdgw;
-        __builtin_amdgcn_sched_barrier(0);
-        int xlo = 0, xhi = 0;
-#pragma unroll
-        for (int j = 63; j >= 0; --j) {
-          // x_j: lane j's value, to every lane through two scalar registers -- and back into lane j of the result with v_writelane
-          // (a compare + selects per step were five of the eight instructions of a step)
-          const int lo = __builtin_amdgcn_readlane(__double2loint(bs), j), hi = __builtin_amdgcn_readlane(__double2hiint(bs), j);
-          asm("v_writelane_b32 %0, %1, %2" : "+v"(xlo) : "s"(lo), "n"(j));
-          asm("v_writelane_b32 %0, %1, %2" : "+v"(xhi) : "s"(hi), "n"(j));
-          bs = __builtin_fma(Lc[j], __hiloint2double(hi, lo), bs);      // rows >= n: rdg = 0 -> x_j = 0 (identity padding, right-hand-side rows)
-        }
-        xout = __hiloint2double(xhi, xlo);
-      } else {
-      const double dg = Lb[lane * 65 + lane];
-      const double rdg = (k0 + lane < n) ? 1.0 / dg : 0.0;
-      double b = w[64 * blk + lane];
+    if (rg == (blk ? 0 : 1)) {
+      if (!HOIST) preload_diag();
+      // the lane carries b / L_ll instead of b: per step readlane -> fma (the multiply by 1 / L_ll left the chain; the scaled column
+      // entries L[j][lane] / L_ll do not depend on the right-hand side)
+      double bs = w[64 * blk + lane] * rdgw;
+      __builtin_amdgcn_sched_barrier(0);
+      int xlo = 0, xhi = 0;
 #pragma unroll
       for (int j = 63; j >= 0; --j) {
-        const double xj = readlane_f64(b * rdg, j);       // rows >= n: rdg = 0 -> xj = 0 (identity padding, right-hand-side rows)
-        if (lane == j) xout = xj;
-        b = __builtin_fma(-Lb[j * 65 + lane], xj, b);      // L[k0+j][k0+lane]; only lanes < j use it afterwards
+        // x_j: lane j's value, to every lane through two scalar registers -- and back into lane j of the result with v_writelane
+        // (a compare + selects per step were five of the eight instructions of a step)
+        const int lo = __builtin_amdgcn_readlane(__double2loint(bs), j), hi = __builtin_amdgcn_readlane(__double2hiint(bs), j);
+        asm("v_writelane_b32 %0, %1, %2" : "+v"(xlo) : "s"(lo), "n"(j));
+        asm("v_writelane_b32 %0, %1, %2" : "+v"(xhi) : "s"(hi), "n"(j));
+        bs = __builtin_fma(Lc[j], __hiloint2double(hi, lo), bs);      // rows >= n: rdg = 0 -> x_j = 0 (identity padding, right-hand-side rows)
       }
-      }
+      double xout = __hiloint2double(xhi, xlo);
       xs[64 * blk + lane] = xout;
-      if (SENT && __double_as_longlong(xout) == -1ll) xout = __builtin_nan("");      // (only garbage can be the "not there yet" pattern)
+      if (__double_as_longlong(xout) == -1ll) xout = __builtin_nan("");      // (only garbage can be the "not there yet" pattern)
       st_agent(alpha + k0 + lane, xout);
     }
     __syncthreads();
   };
-  // SENT: lanes [lo, lo + 64) of the workgroup fetch entries lo .. lo+63 of chunk cc into xs, each polling its own value
+  // lanes [lo, lo + 64) of the workgroup fetch entries lo .. lo+63 of chunk cc into xs, each polling its own value
   auto poll_values = [&](int cc, int lo) {
     if (t >= lo && t < lo + 64) {
       const double* p = alpha + 128 * cc + t;
@@ -405,7 +387,7 @@ __global__ __launch_bounds__(256, HOIST ? 1 : 2) void backsolve_chain_kernel(Bat
   if (HOIST) preload_diag();
   // res != nullptr (round 5): the leftmost chunk -- last in the chain, idle until it is reached -- also forms the emulator's log-determinant and
   // Gram entry (the work of logdet_kernel: one launch and its 6 us gap less per evaluation) and, at its end, the status word
-  if (SENT && res && c == 0) logdet_gram_dev<1>(v, emu, res, red);
+  if (res && c == 0) logdet_gram_dev<1>(v, emu, res, red);
   // blocks below the chunk, from the bottom up: chunk cc' = nch-1 .. c+1, each with two 64-row blocks
   if (nch - 1 > c) {
     load_tile(tA, 128 * (nch - 1) + 64);
@@ -414,54 +396,27 @@ __global__ __launch_bounds__(256, HOIST ? 1 : 2) void backsolve_chain_kernel(Bat
     load_tile(tA, j0 + 64);                    // rightmost chunk: only its own off-diagonal tile
   }
   for (int cc = nch - 1; cc > c; --cc) {
-    if (SENT) {
-      poll_values(cc, 64);                     // the lower half of chunk cc is solved (and stored) first
-      apply_tile(tA, 64, 128);                 // rows 128cc+64 ..
-      if (cc - 1 > c) load_tile(tA, 128 * (cc - 1) + 64);
-      else load_tile(tA, j0 + 64);
-      poll_values(cc, 0);
-      apply_tile(tB, 0, 128);                  // rows 128cc ..
-      if (cc - 1 > c) load_tile(tB, 128 * (cc - 1));
-      continue;
-    }
-    if (t == 0) {
-      int spins = 0;
-      bool seen = false;
-      while (!(seen = __hip_atomic_load(fl + cc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == epoch) && spins++ < spin_limit) __builtin_amdgcn_s_sleep(2);
-      if (!seen) timed_out = 1;
-    }
-    __syncthreads();
-    if (t < 128) xs[t] = ld_agent(alpha + 128 * cc + t);
-    __syncthreads();
+    poll_values(cc, 64);                       // the lower half of chunk cc is solved (and stored) first
     apply_tile(tA, 64, 128);                   // rows 128cc+64 ..
     if (cc - 1 > c) load_tile(tA, 128 * (cc - 1) + 64);
     else load_tile(tA, j0 + 64);               // own rows j0+64 .. x columns j0 .. (only the first 64 columns are used)
+    poll_values(cc, 0);
     apply_tile(tB, 0, 128);                    // rows 128cc ..
     if (cc - 1 > c) load_tile(tB, 128 * (cc - 1));
   }
   // own rows: upper diagonal block, the 64 x 64 block between the two, lower diagonal block
   solve_diag(1);
   apply_tile(tA, 64, 64);
-  solve_diag(0);
-  if (SENT) {                                  // (the stores of solve_diag are the publication)
-    if (res && c == 0 && t == 0) {
-      // every chunk's values have been polled by this one: a wait that gave up anywhere in the chain stored the emulator's status word
-      // before that chunk published (poll_values), so it is visible here.  A NaN in the result is NOT a time-out: it surfaces with the
-      // factorisation's own status (non-finite log-posterior -> ok = 0) and is not re-solved.
-      const int st = info[emu];
-      const bool gave_up = timed_out || __hip_atomic_load(status + emu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == epoch;
-      int rep = (st == 0 && gave_up) ? BACKSOLVE_TIMEOUT : st;
-      if (mc_abort && *mc_abort != 0u) rep = MCHOL_ABORTED;
-      res[(size_t)emu * RES_STRIDE + 1] = (double)rep;
-    }
-    return;
-  }
-  // publish: payload drained, then the flag
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (t == 0) {
-    __hip_atomic_store(fl + c, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (timed_out) __hip_atomic_store(status + emu, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  solve_diag(0);                               // (its stores are the publication)
+  if (res && c == 0 && t == 0) {
+    // every chunk's values have been polled by this one: a wait that gave up anywhere in the chain stored the emulator's status word
+    // before that chunk published (poll_values), so it is visible here.  A NaN in the result is NOT a time-out: it surfaces with the
+    // factorisation's own status (non-finite log-posterior -> ok = 0) and is not re-solved.
+    const int st = info[emu];
+    const bool gave_up = timed_out || __hip_atomic_load(status + emu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == epoch;
+    int rep = (st == 0 && gave_up) ? BACKSOLVE_TIMEOUT : st;
+    if (mc_abort && *mc_abort != 0u) rep = MCHOL_ABORTED;
+    res[(size_t)emu * RES_STRIDE + 1] = (double)rep;
   }
 }
 
@@ -721,23 +676,19 @@ void launch_combine_rows(const BatchView& v, const double* M, hipStream_t s) {
   hipLaunchKernelGGL(combine_rows_kernel, dim3((v.LD + 255) / 256, v.nb), dim3(256), 0, s, v, M);
 }
 
-bool launch_backsolve_chain(const BatchView& v, int* flags, int epoch, int* status, int n_cu, hipStream_t s, const int* info, double* res, const unsigned* mc_abort) {
+bool launch_backsolve_chain(const BatchView& v, int epoch, int* status, int n_cu, hipStream_t s, const int* info, double* res, const unsigned* mc_abort) {
   const int nch = (v.n + 127) / 128;
   // MOGP_BS_SPIN: polls before a wait gives up (default 2^20, about a second); 0 makes every unsatisfied wait a timeout,
   // which is how the GPU suite exercises the fallback
   static const int spin_limit = [] { const char* e = getenv("MOGP_BS_SPIN"); return e ? atoi(e) : (1 << 20); }();
-  static const int sent = [] { const char* e = getenv("MOGP_BS_SENTINEL"); return e ? atoi(e) : 1; }();
   prof_begin("backsolve", s);
-  // MOGP_BS_HOIST=0: the chain-bound launches (at most one workgroup per CU) also run the two-per-CU build
-  static const int hoist = [] { const char* e = getenv("MOGP_BS_HOIST"); return e ? atoi(e) : 1; }();
-  // MOGP_BS_LOGDET=0: log-determinant and status by logdet_kernel behind the chain, as before round 5
-  static const int fuse = [] { const char* e = getenv("MOGP_BS_LOGDET"); return e ? atoi(e) : 1; }();
-  // (chain-bound launches only: with more workgroups than CUs the leftmost chunks, which stream the most rows of L, are the launch's stragglers)
-  double* r = (sent && fuse && v.R == 1 && v.nb * nch <= n_cu) ? res : nullptr;
-  if (sent && hoist && v.nb * nch <= n_cu)
-    hipLaunchKernelGGL((backsolve_chain_kernel<true, true>), dim3(v.nb * nch), dim3(256), 0, s, v, flags, epoch, nch, status, spin_limit, info, r, mc_abort);
-  else if (sent) hipLaunchKernelGGL(backsolve_chain_kernel<true>, dim3(v.nb * nch), dim3(256), 0, s, v, flags, epoch, nch, status, spin_limit, info, r, mc_abort);
-  else hipLaunchKernelGGL(backsolve_chain_kernel<false>, dim3(v.nb * nch), dim3(256), 0, s, v, flags, epoch, nch, status, spin_limit, info, r, mc_abort);
+  // Chain-bound launches (at most one workgroup per CU) run the hoisted build, and their leftmost chunks also form the log-determinant and
+  // the status word (R == 1).  With more workgroups than CUs the leftmost chunks, which stream the most rows of L, are the launch's
+  // stragglers: log-determinant and status then come from logdet_kernel behind the chain.
+  const bool bound = v.nb * nch <= n_cu;
+  double* r = (v.R == 1 && bound) ? res : nullptr;
+  if (bound) hipLaunchKernelGGL(backsolve_chain_kernel<true>, dim3(v.nb * nch), dim3(256), 0, s, v, nullptr, epoch, nch, status, spin_limit, info, r, mc_abort);
+  else hipLaunchKernelGGL(backsolve_chain_kernel<false>, dim3(v.nb * nch), dim3(256), 0, s, v, nullptr, epoch, nch, status, spin_limit, info, r, mc_abort);
   prof_end("backsolve", s, 0., (double)v.nb * 4.0 * (double)v.n * (double)v.n);      // algorithmic: the lower triangle of L read once
   return r != nullptr;
 }

@@ -20,7 +20,6 @@
 // (densegp_gpu.hpp:451-474), the explicit inverse via potrs (densegp_gpu.hpp:576-582) and the
 // predictive-variance gemm + batched dot (densegp_gpu.hpp:374-396).
 #include <algorithm>
-#include <cstdlib>
 #include <type_traits>
 #include "launch.h"
 #include "trsm_dev.h"
@@ -540,16 +539,15 @@ __global__ __launch_bounds__(512, 4) void update_tri8_kernel(BatchView v, int c0
 // k-steps: 3.4 x less L2-miss traffic, 1 - 7 % slower -- and the downward walk of the short row tile, MOGP_PV_DESC, are gone; their
 // measurements are in HISTORY.md.)
 constexpr bool PV_SWZ = true;      // swizzled ds_read_b128 fragments (mainloop_w<.., SWZ>; round 5: 65.2 -> 66.5 TFLOP/s, profiles/r05_predict_swz_ab.txt)
+// super-tile = 2^PVW_LGC column tiles x 64 / 2^PVW_LGC row-tile pairs (see launch_predict_var)
+constexpr int PVW_LGC = 3, PVW_SC = 1 << PVW_LGC, PVW_SR = 64 >> PVW_LGC;
 template <int WR, int WC, bool TRI>
 __global__ __launch_bounds__(64 * WR * WC, (WR * WC >= 8 ? 4 : 2)) void predict_var_w_kernel(
-    BatchView v, const double* __restrict__ Ks, int MP, int nti, int ntj, double* __restrict__ partial, int lgc, int single) {
+    BatchView v, const double* __restrict__ Ks, int MP, int nti, int ntj, double* __restrict__ partial) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   using C = WCfg<128, 128, WR, WC>;
-  // single (launches of fewer than a few rounds of workgroups, e.g. ONE emulator): a workgroup takes one row tile instead of a complementary
-  // pair, longest tiles first in dispatch order -- equally long pair tasks that fill the device 1.23 times cost two full rounds (C2,
-  // m = 10^4: 632 tasks on 512 slots), unequal single tiles dealt longest-first pack to within a tile of the average
-  const int npairs = single ? nti : (nti + 1) / 2;
-  const int SC = 1 << lgc, SR = 64 >> lgc;           // super-tile = SR pairs x SC column tiles
+  const int npairs = (nti + 1) / 2;
+  constexpr int lgc = PVW_LGC, SC = PVW_SC, SR = PVW_SR;
   const int nsr = (npairs + SR - 1) / SR, nsc = (ntj + SC - 1) / SC;
   const int t = threadIdx.x, lane = t & 63, wave = TRI ? __builtin_amdgcn_readfirstlane(t >> 6) : (t >> 6);
   const int wr = wave / WC, wc = wave % WC;
@@ -564,7 +562,7 @@ __global__ __launch_bounds__(64 * WR * WC, (WR * WC >= 8 ? 4 : 2)) void predict_
   const double* Li = v.Linv + (size_t)emu * v.MS;
   const double* K = Ks + (size_t)z * MP * ld;
   const int j0 = tj * 128;
-  const int ti_long = nti - 1 - pr, ti_short = single ? ti_long : pr;
+  const int ti_long = nti - 1 - pr, ti_short = pr;
   // both row tiles of a pair walk k upward (free-running workgroups: the order changes neither time nor traffic, round 3)
   for (int pass = 0; pass < 2; ++pass) {
     if (pass == 1 && ti_short == ti_long) break;
@@ -693,8 +691,7 @@ void launch_trtri_merges(const BatchView& v, hipStream_t s) {
   // sub-tile (merge_mainloop) the wide tile no longer pays for them.  Measured, fit + gradient, ms (64 x 64 everywhere / 128 x 128 from
   // h = 1024 / 512 / 256 / 128; before the round: 12.56): 64 x n=2000 12.10 / 11.82 / 11.94 / 11.98 / 11.85; 16 x n=5000 37.83 / 37.30 / 37.51 /
   // 37.44 (38.24); n=16000 70.95 / - / 68.16 / 68.02 (70.85); 8 x n=2000 2.006 / - / 2.083 / 2.094 (2.057): wide tiles where a level has
-  // thousands of them.  MOGP_TRTRI_WT4_FROM=<h> forces 128 x 128 tiles from level h on (a huge value: never).
-  static const int wt4_from = [] { const char* e = getenv("MOGP_TRTRI_WT4_FROM"); return e ? atoi(e) : -1; }();
+  // thousands of them.
   const double alg = ((double)v.n / v.NP) * ((double)v.n / v.NP) * ((double)v.n / v.NP);
   for (int h = 64; h < v.NP; h *= 2) {
     const int nodes = (v.NP + 2 * h - 1) / (2 * h);
@@ -707,7 +704,7 @@ void launch_trtri_merges(const BatchView& v, hipStream_t s) {
     }
     if (h > 64) prof_begin("trtri_merge", s);
     const long wide_tiles = (long)v.nb * nodes * (h / 128) * (h / 128);
-    if (wt4_from >= 0 ? (h >= wt4_from && h >= 128) : (h >= 512 && wide_tiles >= 3000)) {
+    if (h >= 512 && wide_tiles >= 3000) {
       const int tpd = h / 128;
       hipLaunchKernelGGL((trtri_merge_kernel<4, 0>), dim3(padded_grid(v.nb, tpd * tpd * nodes)), dim3(256), smem_bytes<4>(), s, v, h, tpd, nodes);
       hipLaunchKernelGGL((trtri_merge_kernel<4, 1>), dim3(padded_grid(v.nb, tpd * tpd * nodes)), dim3(256), smem_bytes<4>(), s, v, h, tpd, nodes);
@@ -720,20 +717,25 @@ void launch_trtri_merges(const BatchView& v, hipStream_t s) {
   }
 }
 
-// predict_var_q_kernel (round 5): the same task -- a pair of 128-row tiles of L^-1 against one column tile of K*, column sums of squares -- on
+// predict_var_q_kernel (round 5): the same task for ONE 128-row tile of L^-1 against one column tile of K*, column sums of squares -- on
 // the k-step of the one-launch Cholesky's GEMM tasks (mainloop_qt: three swizzled LDS stages, the next fragments requested before the barrier,
 // the step's instruction order prescribed).  256 threads (2 x 2 waves) per 128 x 64 tile, two workgroups per CU: alone in the probe that loop
 // reaches 0.91 of the fp64 MFMA peak with two waves per SIMD, where the 8-wave 128 x 128 form above (four waves per SIMD, 128 registers, two
 // stages, fragments read in front of the MFMAs that need them) stands at 0.83 - 0.85.  Column tiles are 64 points wide: K* is read as often as
 // before (half as wide a panel, twice as many of them), L^-1 twice as often.
+// Single row tiles (launches of fewer than a few rounds of workgroups, e.g. ONE emulator): a workgroup takes one row tile instead of a
+// complementary pair, longest tiles first in dispatch order -- equally long pair tasks that fill the device 1.23 times cost two full rounds
+// (C2, m = 10^4: 632 tasks on 512 slots), unequal single tiles dealt longest-first pack to within a tile of the average.
+// super-tile = 2^PVQ_LGC 64-point column tiles x 64 / 2^PVQ_LGC row tiles: sixteen of them, the 1024 points of eight 128-point tiles (one matrix
+// 52.5 -> 57.1 TFLOP/s against eight)
+constexpr int PVQ_LGC = 4, PVQ_SC = 1 << PVQ_LGC, PVQ_SR = 64 >> PVQ_LGC;
 template <bool TRI>
 __global__ __launch_bounds__(256, 2) void predict_var_q_kernel(BatchView v, const double* __restrict__ Ks, int MP, int nti, int ntj,
-                                                               double* __restrict__ partial, int lgc, int single) {
+                                                               double* __restrict__ partial) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   using C = WCfg<128, 64, 2, 2>;
-  const int npairs = single ? nti : (nti + 1) / 2;
-  const int SC = 1 << lgc, SR = 64 >> lgc;           // super-tile = SR pairs x SC column tiles
-  const int nsr = (npairs + SR - 1) / SR, nsc = (ntj + SC - 1) / SC;
+  constexpr int lgc = PVQ_LGC, SC = PVQ_SC, SR = PVQ_SR;
+  const int nsr = (nti + SR - 1) / SR, nsc = (ntj + SC - 1) / SC;
   const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int wr = wave / 2, wc = wave % 2;
   int z, tile;
@@ -741,46 +743,40 @@ __global__ __launch_bounds__(256, 2) void predict_var_q_kernel(BatchView v, cons
   if (z >= v.nb) return;
   const int st = tile >> 6, w = tile & 63;
   const int pr = (st / nsc) * SR + (w >> lgc), tj = (st % nsc) * SC + (w & (SC - 1));
-  if (pr >= npairs || tj >= ntj) return;
+  if (pr >= nti || tj >= ntj) return;
   const int emu = slot_to_emu(v.idx, z);
   const int ld = v.LD;
   const double* Li = v.Linv + (size_t)emu * v.MS;
   const double* K = Ks + (size_t)z * MP * ld;
   const int j0 = tj * 64;
-  const int ti_long = nti - 1 - pr, ti_short = single ? ti_long : pr;
-  for (int pass = 0; pass < 2; ++pass) {
-    if (pass == 1 && ti_short == ti_long) break;
-    const int ti = pass == 0 ? ti_long : ti_short;
-    const int i0 = ti * 128;
-    v4d acc[C::TI][C::TJ];
-    const int nk = min(i0 + 128, (v.n + 15) & ~15) / BK;
-    mainloop_qt<128, 64, 2, 2>(Li + (size_t)i0 * ld, ld, K + (size_t)j0 * ld, ld, nk, acc, smem, TRI ? i0 / BK : nk, TRI ? v.n - i0 : 128);
-    // column sums of squares over the tile's 128 rows: red[wr][64]
-    double* red = smem;
+  const int ti = nti - 1 - pr;                  // longest first
+  const int i0 = ti * 128;
+  v4d acc[C::TI][C::TJ];
+  const int nk = min(i0 + 128, (v.n + 15) & ~15) / BK;
+  mainloop_qt<128, 64, 2, 2>(Li + (size_t)i0 * ld, ld, K + (size_t)j0 * ld, ld, nk, acc, smem, TRI ? i0 / BK : nk, TRI ? v.n - i0 : 128);
+  // column sums of squares over the tile's 128 rows: red[wr][64]
+  double* red = smem;
 #pragma unroll
-    for (int j = 0; j < C::TJ; ++j) {
-      double s = 0.;
+  for (int j = 0; j < C::TJ; ++j) {
+    double s = 0.;
 #pragma unroll
-      for (int i = 0; i < C::TI; ++i)
+    for (int i = 0; i < C::TI; ++i)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) s += acc[i][j][r] * acc[i][j][r];
-      s += __shfl_xor(s, 16);
-      s += __shfl_xor(s, 32);
-      if (lane < 16) red[wr * 64 + wc * 16 * C::TJ + j * 16 + lane] = s;
-    }
-    __syncthreads();
-    if (t < 64) partial[((size_t)z * nti + ti) * MP + j0 + t] = red[t] + red[64 + t];
-    __syncthreads();                 // red aliases the operand buffers of the next pass
+      for (int r = 0; r < 4; ++r) s += acc[i][j][r] * acc[i][j][r];
+    s += __shfl_xor(s, 16);
+    s += __shfl_xor(s, 32);
+    if (lane < 16) red[wr * 64 + wc * 16 * C::TJ + j * 16 + lane] = s;
   }
+  __syncthreads();
+  if (t < 64) partial[((size_t)z * nti + ti) * MP + j0 + t] = red[t] + red[64 + t];
 }
 
 void launch_kinv(const BatchView& v, int n_cu, hipStream_t s) {
   const int kend = ((v.n + 15) / 16) * 16;
   const int nt = (v.n + 127) / 128;      // tiles that contain real rows
   const int ntiles = nt * (nt + 1) / 2;
-  // 64 x 64 tiles when the 128 x 128 ones would fill the device less than twice (MOGP_KINV_WT = 2 / 4 forces either)
-  static const int force_wt = [] { const char* e = getenv("MOGP_KINV_WT"); return e ? atoi(e) : 0; }();
-  const bool small = force_wt ? force_wt == 2 : ((long)v.nb * ntiles < 2L * 2 * n_cu);
+  // 64 x 64 tiles when the 128 x 128 ones would fill the device less than twice
+  const bool small = (long)v.nb * ntiles < 2L * 2 * n_cu;
   prof_begin("kinv", s);
   if (small) {
     const int nt2 = (v.n + 63) / 64;
@@ -798,38 +794,21 @@ void launch_predict_var(const BatchView& v, const double* Ks, int m, int MP, dou
   // super-tile = 2^lgc column tiles x 64/2^lgc row-tile pairs.  Measured at nti = 16 (8 pairs), m = 5632, L2-miss bytes per launch /
   // TFLOP/s: 8x8 37 GB / 62.3, 4 pairs x 16 44 GB / 61.9, 2 x 32 53 GB / 60.4, 1 x 64 54 GB / 60.4; without the XCD-aware
   // block decode (workgroups of a super-tile spread over all eight L2s) 47 GB but only 52.1 TFLOP/s
-  static const int lgc_env = [] { const char* e = getenv("MOGP_PV_LGC"); return e ? atoi(e) : -1; }();
-  const int lgc = lgc_env >= 0 ? lgc_env : 3;
-  // MOGP_PV_SINGLE = 0 / 1 forces pairs / single row tiles; default: single row tiles when the pair tasks fill the device fewer than twice.
-  // Measured (predict incl. host copies, m = 10^4, ms, pairs / single): 1 x n=2000 1.080 / 1.031, 2 x 1.82 / 1.84, 3 x 2.44 / 2.50, 4 x 3.05 /
-  // 3.27, 1 x n=5000 5.36 / 4.86, 1 x n=700 (m = 3000) 0.213 / 0.187; bit-identical
-  static const int force_single = [] { const char* e = getenv("MOGP_PV_SINGLE"); return e ? atoi(e) : -1; }();
-  {
-    const int SC = 1 << lgc, SR = 64 >> lgc;
-    const int nst = (((nti + 1) / 2 + SR - 1) / SR) * ((ntj + SC - 1) / SC);
-    const long pair_tasks = (long)v.nb * ((nti + 1) / 2) * ntj;
-    const bool single = force_single >= 0 ? force_single != 0 : pair_tasks < 2L * 2 * n_cu;
-    // predict_var_q_kernel for launches of single row tiles (one n = 2000 matrix, 10^4 points: 0.82 -> 0.70 ms); MOGP_PV_Q = 0 / 1 forces either
-    // kernel.  For full launches the two are level -- 64 x n=2000 66.5 / 66.4 TFLOP/s, n=16000 68.2 / 68.2, 16 x n=5000 66.3 / 65.3 -- two kernels
-    // that share nothing but the MFMA instruction end at the same rate: the part is at its power limit there (1.31 kW, 2.28 - 2.30 GHz under
-    // either; profiles/r05_predict_q_ab.txt)
-    static const int force_q = [] { const char* e = getenv("MOGP_PV_Q"); return e ? atoi(e) : -1; }();
-    const bool use_q = force_q >= 0 ? force_q != 0 : single;
-    if (use_q) {
-      // (64-point column tiles: sixteen of them per super-tile -- the 1024 points of eight 128-point tiles -- for single row tiles: one matrix
-      // 52.5 -> 57.1 TFLOP/s; full launches are fastest with eight)
-      const int lgq = lgc_env >= 0 ? lgc_env : (single ? 4 : 3);
-      const int SC = 1 << lgq, SR = 64 >> lgq;
-      const int ntq = MP / 64;
-      constexpr size_t lds_q = (size_t)QCfg<128, 64>::SMEM_DOUBLES * sizeof(double);
-      const int nsq = ((((single ? nti : (nti + 1) / 2)) + SR - 1) / SR) * ((ntq + SC - 1) / SC);
-      hipLaunchKernelGGL((predict_var_q_kernel<true>), dim3(padded_grid(v.nb, nsq * 64)), dim3(256), lds_q, s, v, Ks, MP,
-                         nti, ntq, partial, lgq, single ? 1 : 0);
-    } else if (single) {
-      const int nst1 = ((nti + SR - 1) / SR) * ((ntj + SC - 1) / SC);
-      hipLaunchKernelGGL((predict_var_w_kernel<2, 4, true>), dim3(padded_grid(v.nb, nst1 * 64)), dim3(512), smem_bytes<4>(), s, v, Ks, MP, nti, ntj, partial, lgc, 1);
-    } else
-      hipLaunchKernelGGL((predict_var_w_kernel<2, 4, true>), dim3(padded_grid(v.nb, nst * 64)), dim3(512), smem_bytes<4>(), s, v, Ks, MP, nti, ntj, partial, lgc, 0);
+  // Single row tiles when the pair tasks fill the device fewer than twice.  Measured (predict incl. host copies, m = 10^4, ms, pairs / single):
+  // 1 x n=2000 1.080 / 1.031, 2 x 1.82 / 1.84, 3 x 2.44 / 2.50, 4 x 3.05 / 3.27, 1 x n=5000 5.36 / 4.86, 1 x n=700 (m = 3000) 0.213 / 0.187;
+  // bit-identical
+  const long pair_tasks = (long)v.nb * ((nti + 1) / 2) * ntj;
+  if (pair_tasks < 2L * 2 * n_cu) {
+    // single row tiles on predict_var_q_kernel (one n = 2000 matrix, 10^4 points: 0.82 -> 0.70 ms).  For full launches the two kernels are
+    // level -- 64 x n=2000 66.5 / 66.4 TFLOP/s, n=16000 68.2 / 68.2, 16 x n=5000 66.3 / 65.3 -- two kernels that share nothing but the MFMA
+    // instruction end at the same rate: the part is at its power limit there (1.31 kW, 2.28 - 2.30 GHz under either; profiles/r05_predict_q_ab.txt)
+    const int ntq = MP / 64;
+    constexpr size_t lds_q = (size_t)QCfg<128, 64>::SMEM_DOUBLES * sizeof(double);
+    const int nsq = ((nti + PVQ_SR - 1) / PVQ_SR) * ((ntq + PVQ_SC - 1) / PVQ_SC);
+    hipLaunchKernelGGL((predict_var_q_kernel<true>), dim3(padded_grid(v.nb, nsq * 64)), dim3(256), lds_q, s, v, Ks, MP, nti, ntq, partial);
+  } else {
+    const int nst = (((nti + 1) / 2 + PVW_SR - 1) / PVW_SR) * ((ntj + PVW_SC - 1) / PVW_SC);
+    hipLaunchKernelGGL((predict_var_w_kernel<2, 4, true>), dim3(padded_grid(v.nb, nst * 64)), dim3(512), smem_bytes<4>(), s, v, Ks, MP, nti, ntj, partial);
   }
   prof_end("predict_var", s, (double)v.nb * (double)m * v.n * v.n, 0.);
   hipLaunchKernelGGL(predict_var_finish_kernel, dim3((m + 255) / 256, v.nb), dim3(256), 0, s, v, partial, m, MP, nti, var, var_ld);

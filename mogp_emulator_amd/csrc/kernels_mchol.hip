@@ -164,7 +164,7 @@ struct PieceWait {
 template <bool TRACE, bool SOLO = false>
 __global__ __launch_bounds__(256, SOLO ? 1 : 2) void mchol_kernel(BatchView v, unsigned* __restrict__ ctrl, const int* __restrict__ table, int ntasks,
                                                        int emu_stride, double* __restrict__ packs, int* __restrict__ info, int nq, int spin_limit,
-                                                       unsigned long long* __restrict__ trace, int tile_solve) {
+                                                       unsigned long long* __restrict__ trace, int opts) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   int* shi = reinterpret_cast<int*>(smem);
   double* lds = smem + MC_LDS_HDR;
@@ -175,7 +175,8 @@ __global__ __launch_bounds__(256, SOLO ? 1 : 2) void mchol_kernel(BatchView v, u
   const int home = (int)blockIdx.x & (nq - 1);          // observed: block b runs on XCD b % 8 (for speed only)
   const int emus_q = v.nb / nq;
   const int total = ntasks * emus_q;
-  const int gs = ((tile_solve >> 12) & 0xff) ? ((tile_solve >> 12) & 0xff) : emus_q;
+  // opts: bits 8, 9 = extra chain row pairs (see urgent below); bits 12 .. 19 = emulators per ticket group (0: all of the queue's)
+  const int gs = ((opts >> 12) & 0xff) ? ((opts >> 12) & 0xff) : emus_q;
   for (int qi = 0; qi < nq; ++qi) {
     const int q = (home + qi) & (nq - 1);                 // own queue first, then help the others
     unsigned* head = ctrl + MC_HEADS + q * MC_LINE;
@@ -300,8 +301,8 @@ __global__ __launch_bounds__(256, SOLO ? 1 : 2) void mchol_kernel(BatchView v, u
       const int r0 = 64 * r;
       // tasks of the dependent chain (diagonal tiles, the two row blocks of the next diagonal block) issue ahead of the
       // workgroup they share the CU with
-      // (tile_solve bits 8, 9: 4 + 2 x rows below the diagonal block are chain tasks -- chain-bound launches take three pairs)
-      const bool urgent = r < 2 * c + 4 + 2 * ((tile_solve >> 8) & 3);
+      // (opts bits 8, 9: 4 + 2 x rows below the diagonal block are chain tasks -- chain-bound launches take three pairs)
+      const bool urgent = r < 2 * c + 4 + 2 * ((opts >> 8) & 3);
       if (urgent) __builtin_amdgcn_s_setprio(2);
       const int kend = c;
       if (kend > 0) {
@@ -354,8 +355,11 @@ __global__ __launch_bounds__(256, SOLO ? 1 : 2) void mchol_kernel(BatchView v, u
             if (have < 0) return;
             mc_stamp<TRACE>(tr, 2);
             have = (have < kse ? have : kse) & ~(MC_PD - 1);
+            // (opts bit 1 is never set: the launcher lost its traffic-measurement switch, MOGP_MC_NOTRAFFIC, in round 7.  The operand stays
+            // because without it the register allocation of this kernel changes -- two-per-CU build: 65 -> 157 SGPR spills, +572
+            // instructions; SOLO build: one more VGPR.  The planned rewrite of the Cholesky chain can drop it.)
             MC_GEMM<64, 128>(A + (size_t)r0 * ld + 16 * ks, ld, A + (size_t)c0 * ld + 16 * ks, ld, have - ks, acc, lds,
-                             (tile_solve & 2) ? 3 : -1);
+                             (opts & 2) ? 3 : -1);
             ks = have;
           }
         }
@@ -544,23 +548,15 @@ void launch_mchol(const BatchView& v, unsigned* ctrl, size_t ctrl_ints, const in
   // column).  Chain-bound batches run ONE workgroup per CU, so that a diagonal-block task never shares its CU's matrix pipes; beyond that two
   // per CU.  Before the interleaved k-step the crossover was rho = 1 (mchol ms one / two per CU, profiles/r05_regime_sweep.txt: 4 x n=2000
   // 0.48 / 0.58, 8 x 0.71 / 0.73, 12 x 0.92 / 0.91 - 0.93, 16 x 1.17 / 1.15, 24 x 1.68 / 1.56, 32 x 2.13 / 1.97, 2 x n=5000 2.10 / 2.14, 4 x n=5000
-  // 3.73 / 3.61); now see below (profiles/r05_regime_sweep2.txt).  MOGP_MC_WGS = 1 / 2 forces either.  (Rounds 2 - 4: for 1 <= rho < 2 the workgroup sharing a CU with a
+  // 3.73 / 3.61); now see below (profiles/r05_regime_sweep2.txt).  (Rounds 2 - 4: for 1 <= rho < 2 the workgroup sharing a CU with a
   // diagonal-block task PARKED, MOGP_MC_PARK; on the round-5 kernels parking is level to 2 % slower in every regime and is gone.)
-  static const int force_wgs = [] { const char* e = getenv("MOGP_MC_WGS"); return e ? std::max(1, atoi(e)) : 0; }();
   const double rho = mchol_rho(v.nb, v.NP);
   // (with the interleaved k-step a lone workgroup's GEMM runs at 0.974 us per step, a pair at 1.873 for two: one per CU gives up 4 % of GEMM
   // throughput and keeps the chain free -- it now wins up to 14 x n=2000 (equal at 16; 20 x 1.34 / 1.29, 32 x 2.04 / 1.94, 64 x 3.96 / 3.66),
   // up to 4 x n=5000 (3 x 2.65 / 2.86, 4 x 3.43 / 3.58; equal at 6 - 8; 16 x 12.95 / 12.76) and for one n=16000 matrix (24.39 / 24.80): the
   // threshold grows with the depth of the matrix, whose share of GEMM work it follows)
   const double K16 = std::max(1.0, (v.NP / 128) / 16.0);
-  const int per_cu = force_wgs ? force_wgs : (rho < 1.2 * std::pow(K16, 0.7) ? 1 : 2);
-  // bit 1: MOGP_MC_NOTRAFFIC=1 (measurement only, garbage results): the bulk GEMM tasks re-read their first 64 operand columns -- the traffic A/B
-  static const int tile_solve = [] {
-    const char* f = getenv("MOGP_MC_NOTRAFFIC");
-    return (f && atoi(f)) ? 2 : 0;
-  }();
-  // MOGP_MC_URG = 0 / 1 / 2: two, four or six row tiles below the diagonal block are chain tasks (pipelined solve, pieces published)
-  static const int force_urg = [] { const char* e = getenv("MOGP_MC_URG"); return e ? atoi(e) & 3 : -1; }();
+  const int per_cu = rho < 1.2 * std::pow(K16, 0.7) ? 1 : 2;
 
   if (!ctrl_zeroed) (void)hipMemsetAsync(ctrl, 0, ctrl_ints * sizeof(unsigned), s);
   const int nq = (v.nb % 8 == 0) ? 8 : 1;
@@ -569,12 +565,10 @@ void launch_mchol(const BatchView& v, unsigned* ctrl, size_t ctrl_ints, const in
   const size_t lds_doubles = per_cu == 1 ? std::max<size_t>(lds_need, 10 * 1024 + 64) : lds_need;
   const int total = ntasks * v.nb;
   const int grid = std::min(per_cu * n_cu, total);
-  // the band-ahead order (mchol_task_table) needs more workgroups per queue than tickets that can wait in front of one diagonal block;
-  // MOGP_MC_AHEAD=0: always the in-order table
-  static const bool ahead_on = [] { const char* e = getenv("MOGP_MC_AHEAD"); return !e || atoi(e) != 0; }();
+  // the band-ahead order (mchol_task_table) needs more workgroups per queue than tickets that can wait in front of one diagonal block
   // (measured, mchol ms in-order / band-ahead: 4 x n=2000 0.485 / 0.477, 8 x 0.700 / 0.676, 12 x 0.923 / 0.905, 16 x 1.122 / 1.106, 24 x 1.556 / 1.534,
   // 32 x level, 64 x 3.69 / 3.77, one matrix 0.460 / 0.463, n=5000 and n=16000 level: profiles/r05_band_ahead_ab.txt -- so: 0.2 <= rho < 2)
-  const bool ahead = ahead_on && rho >= 0.2 && rho < 2.0 && 8 * (v.nb / nq) <= grid / nq;
+  const bool ahead = rho >= 0.2 && rho < 2.0 && 8 * (v.nb / nq) <= grid / nq;
   const int* table = tables + (ahead ? ntasks : 0);
   // MOGP_MC_TRACE=<file>: per-task time stamps of EVERY launch are appended to the file (analysis only: synchronises)
   static const char* trace_file = getenv("MOGP_MC_TRACE");
@@ -583,19 +577,18 @@ void launch_mchol(const BatchView& v, unsigned* ctrl, size_t ctrl_ints, const in
   // Emulators per ticket GROUP inside a queue (round 5): a queue hands out the tasks of gs of its emulators, interleaved, before the next gs -- the
   // next group starts in the tail of the one before, and fewer matrices are in flight per XCD.  The smallest divisor of the queue's emulators
   // that still offers 1.25 x as many row tiles as the queue has workgroups.  mchol ms, all / groups: 64 x n=2000 (8 per queue) 3.54 / 3.47 in
-  // fours (twos 3.61, ones 3.98), 16 x n=5000 (2 per queue) 12.48 / 12.32 in ones; bit-identical.  MOGP_MC_EGRP: 0 = no groups, n = groups of n.
-  static const int egrp = [] { const char* e = getenv("MOGP_MC_EGRP"); return e ? atoi(e) : -1; }();
+  // fours (twos 3.61, ones 3.98), 16 x n=5000 (2 per queue) 12.48 / 12.32 in ones; bit-identical.
   const int emus_q = v.nb / nq, wg_q = std::max(1, grid / nq);
   int gsz = 0;
-  if (egrp > 0) gsz = (emus_q % egrp == 0) ? egrp : 0;
-  else if (egrp < 0 && v.NP >= 2048)           // (128 x n=1000, sixteen per queue: groups of eight 1.222 against 1.198 ms undivided -- short matrices stay undivided;
-                                               //  96 x n=2000 5.43 -> 5.20, 120 x 6.77 -> 6.40, 32 x n=5000 24.9 -> 24.5)
+  if (v.NP >= 2048)           // (128 x n=1000, sixteen per queue: groups of eight 1.222 against 1.198 ms undivided -- short matrices stay undivided;
+                              //  96 x n=2000 5.43 -> 5.20, 120 x 6.77 -> 6.40, 32 x n=5000 24.9 -> 24.5)
     for (int g = 1; g < emus_q; ++g)
       if (emus_q % g == 0 && 4 * g * (v.NP / 64) >= 5 * wg_q) {
         gsz = g;
         break;
       }
-  const int ts = tile_solve | ((force_urg >= 0 ? force_urg : (rho < 1.0 ? 2 : 0)) << 8) | (gsz << 12);
+  // chain-bound launches (rho < 1): six, not two, row tiles below the diagonal block are chain tasks (pipelined solve, pieces published)
+  const int opts = ((rho < 1.0 ? 2 : 0) << 8) | (gsz << 12);
   if (trace_file) {
     if (hipMalloc(reinterpret_cast<void**>(&dtr), words * 8) != hipSuccess) {
       dtr = nullptr;                                        // no room for the stamps: factorise untraced, and say so
@@ -605,7 +598,7 @@ void launch_mchol(const BatchView& v, unsigned* ctrl, size_t ctrl_ints, const in
   if (trace_file && dtr) {
     (void)hipMemsetAsync(dtr, 0, words * 8, s);
     hipLaunchKernelGGL(mchol_kernel<true>, dim3(grid), dim3(256), lds_doubles * sizeof(double), s, v, ctrl, table, ntasks, mchol_emu_stride(v.NP), packs,
-                       info, nq, spin_limit, dtr, ts);
+                       info, nq, spin_limit, dtr, opts);
     std::vector<unsigned long long> h(words);
     (void)hipStreamSynchronize(s);
     (void)hipMemcpy(h.data(), dtr, words * 8, hipMemcpyDeviceToHost);
@@ -619,13 +612,12 @@ void launch_mchol(const BatchView& v, unsigned* ctrl, size_t ctrl_ints, const in
     return;
   }
   prof_begin("mchol", s);
-  static const int solo_ok = [] { const char* e = getenv("MOGP_MC_SOLO"); return e ? atoi(e) : 1; }();
-  if (per_cu == 1 && solo_ok)
+  if (per_cu == 1)
     hipLaunchKernelGGL((mchol_kernel<false, true>), dim3(grid), dim3(256), lds_doubles * sizeof(double), s, v, ctrl, table, ntasks, mchol_emu_stride(v.NP), packs,
-                     info, nq, spin_limit, (unsigned long long*)nullptr, ts);
+                     info, nq, spin_limit, (unsigned long long*)nullptr, opts);
   else
     hipLaunchKernelGGL(mchol_kernel<false>, dim3(grid), dim3(256), lds_doubles * sizeof(double), s, v, ctrl, table, ntasks, mchol_emu_stride(v.NP), packs,
-                     info, nq, spin_limit, (unsigned long long*)nullptr, ts);
+                     info, nq, spin_limit, (unsigned long long*)nullptr, opts);
   const double n = v.n;                 // ALGORITHMIC work (n^3 / 3 per emulator), not the padded NP the tiles cover
   prof_end("mchol", s, (double)v.nb * n * n * n / 3.0, (double)v.nb * 8.0 * n * n);
 }

@@ -20,9 +20,7 @@
 // that block so that rows n.. of A hold L^-1 [t, H] for the complete factor (pstrf_tail_kernel, HISTORY.md section 3d).
 #include <cfloat>
 #include <cmath>
-#include <cstdlib>
 #include "launch.h"
-#include "cov_dev.h"
 
 namespace mogp {
 
@@ -246,42 +244,14 @@ __global__ __launch_bounds__(PSTRF_THREADS) void pstrf_panel_kernel(BatchView v,
   }
 }
 
-// sigma^2 k(x_a, x_b) with the operation order of the covariance build (kernels_cov.hip micro_k)
-__device__ __forceinline__ double cov_pair_global(const BatchView& v, const double* __restrict__ X, const double* __restrict__ P, int a, int b) {
-  const int D = v.D;
-  const double* xa = X + (size_t)a * D;
-  const double* xb = X + (size_t)b * D;
-  if (v.kernel_type < 2) {
-    double r2 = 0.0;
-    for (int d = 0; d < D; ++d) {
-      const double sc = sqrt(P[d]);          // (the K build stages its inputs multiplied by sqrt(e_d): stage_rows<true>, micro_r2<.., true>)
-      const double df = xa[d] * sc - xb[d] * sc;
-      r2 = __builtin_fma(df, df, r2);
-    }
-    return P[D] * (v.kernel_type == 0 ? kern_val<0>(r2, EXP_TAB_G) : kern_val<1>(r2, EXP_TAB_G));
-  }
-  double k = 1.0, ssum = 0.0;
-  for (int d = 0; d < D; ++d) {
-    const double df = xa[d] - xb[d];
-    const double r2 = P[d] * df * df;
-    const double sd = sqrt(5.0 * r2);
-    k *= 1.0 + sd + (5.0 / 3.0) * r2;
-    ssum += sd;
-  }
-  return P[D] * (k * lean_exp_neg<false>(ssum, EXP_TAB_G));
-}
-
 // Emulators whose factorisation stopped at rank r < n: set the replacement diagonal of the block that was skipped and take the
-// right-hand-side rows through it (regen: first put the INPUT entries back into that block -- A0 != null: from the input matrix
-// (n x n, row-major) instead of the kernel function).
-__global__ __launch_bounds__(PSTRF_THREADS) void pstrf_tail_kernel(BatchView v, const int* __restrict__ perm, const int* __restrict__ rank,
-                                                                    const double* __restrict__ X0, const double* __restrict__ A0, int regen) {
+// right-hand-side rows through it.
+__global__ __launch_bounds__(PSTRF_THREADS) void pstrf_tail_kernel(BatchView v, const int* __restrict__ perm, const int* __restrict__ rank) {
   const int emu = v.idx ? v.idx[blockIdx.x] : blockIdx.x;
   const int n = v.n, ld = v.LD, r = rank[emu];
   if (r <= 0 || r >= n) return;
   double* A = v.A + (size_t)emu * v.MS;
   const int* P = perm + (size_t)emu * n;
-  const double* prm = v.P ? v.P + (size_t)emu * v.PS : nullptr;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int m = n - r;
   // The block that was skipped keeps what the factorisation left in it, as with LAPACK's blocked dpstrf (64-column blocks, as here):
@@ -290,14 +260,7 @@ __global__ __launch_bounds__(PSTRF_THREADS) void pstrf_tail_kernel(BatchView v, 
   // rows skipped as repeats of earlier pivots is rounding residue.  (Rounds 1-3 put the input entries back for every n, the
   // semantics of the unblocked dpstf2: with two skipped rows the forward substitution then multiplies the first one's amplified
   // rounding residue by an O(1) entry and divides by a replacement diagonal ~1e-8 -- log-posteriors off by up to 0.11 relative
-  // against scipy's dpstrf in the randomised test, n = 400, two repeated points.)  MOGP_PIVOT_TAIL=input restores that.
-  if (regen) {
-    for (long e = tid; e < (long)m * m; e += PSTRF_THREADS) {
-      const int i = r + (int)(e / m), j = r + (int)(e % m);
-      if (j >= i) continue;
-      A[(size_t)i * ld + j] = A0 ? A0[(size_t)P[i] * n + P[j]] : cov_pair_global(v, X0, prm, P[i], P[j]);
-    }
-  }
+  // against scipy's dpstrf in the randomised test, n = 400, two repeated points.)
   for (int e = tid; e < v.R * m; e += PSTRF_THREADS) {
     const int c = e / m, j = r + e % m;
     A[(size_t)(n + c) * ld + j] = (c == 0) ? v.T[(size_t)emu * n + P[j]] : v.H[(size_t)(c - 1) * n + P[j]];
@@ -355,9 +318,8 @@ void launch_pstrf_panel(const BatchView& v, int k0, int jb, int* perm, int* rank
   hipLaunchKernelGGL(pstrf_panel_kernel, dim3(v.nb), dim3(PSTRF_THREADS), 0, s, v, k0, jb, perm, rank, work);
 }
 
-void launch_pstrf_tail(const BatchView& v, const int* perm, const int* rank, const double* X0, const double* A0, hipStream_t s) {
-  static const int regen = [] { const char* e = getenv("MOGP_PIVOT_TAIL"); return (e && e[0] == 'i') ? 1 : 0; }();
-  hipLaunchKernelGGL(pstrf_tail_kernel, dim3(v.nb), dim3(PSTRF_THREADS), 0, s, v, perm, rank, X0, A0, regen);
+void launch_pstrf_tail(const BatchView& v, const int* perm, const int* rank, hipStream_t s) {
+  hipLaunchKernelGGL(pstrf_tail_kernel, dim3(v.nb), dim3(PSTRF_THREADS), 0, s, v, perm, rank);
 }
 
 void launch_pstrf_end(const BatchView& v, hipStream_t s) {

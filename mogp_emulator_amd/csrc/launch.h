@@ -127,11 +127,11 @@ void launch_logdet(const BatchView& v, const int* info, double* res, hipStream_t
 void launch_combine_rows(const BatchView& v, const double* M, hipStream_t s);
 // alpha = L^-T y (y = row n of A)
 void launch_backsolve(const BatchView& v, hipStream_t s);
-// the same in one launch (R == 1): flags = B * ceil(n/128) ints indexed by emulator, all != epoch on entry; status[emu] = epoch
-// when a wait of that emulator's chain timed out (alpha is then unusable: repeat with launch_backsolve)
+// the same in one launch (R == 1), with alpha preset to all-ones bit patterns: status = B ints indexed by emulator, all != epoch on entry;
+// status[emu] = epoch when a wait of that emulator's chain timed out (alpha is then unusable: repeat with launch_backsolve)
 // info / res / mc_abort: as launch_logdet's -- the chain's leftmost chunk then writes res (log-determinant, Gram entry, status word) itself;
-// returns whether it does (single right-hand side, sentinel form): the caller launches launch_logdet otherwise.
-bool launch_backsolve_chain(const BatchView& v, int* flags, int epoch, int* status, int n_cu, hipStream_t s, const int* info = nullptr,
+// returns whether it does (chain-bound launches): the caller launches launch_logdet otherwise.
+bool launch_backsolve_chain(const BatchView& v, int epoch, int* status, int n_cu, hipStream_t s, const int* info = nullptr,
                             double* res = nullptr, const unsigned* mc_abort = nullptr);
 // Pivoted Cholesky with LAPACK dpstrf semantics (nugget="pivot", linalg/cholesky.py:284-327), see kernels_pivot.hip.
 // A (K without nugget, and the right-hand-side rows) is factored in place with symmetric row/column interchanges:
@@ -142,9 +142,8 @@ bool launch_backsolve_chain(const BatchView& v, int* flags, int epoch, int* stat
 __host__ __device__ inline size_t pstrf_work_doubles(int NP) { return 2 * (size_t)NP + 8; }
 void launch_pstrf_begin(const BatchView& v, int* perm, int* rank, int* info, double* work, hipStream_t s);
 void launch_pstrf_panel(const BatchView& v, int k0, int jb, int* perm, int* rank, double* work, hipStream_t s);   // jb <= 64
-// emulators of the launch with 0 < rank < n: restore the skipped block from the kernel function on X0 (training order) or
-// from the input matrix A0 (n x n), replacement diagonal, right-hand-side rows through the skipped block
-void launch_pstrf_tail(const BatchView& v, const int* perm, const int* rank, const double* X0, const double* A0, hipStream_t s);
+// emulators of the launch with 0 < rank < n: replacement diagonal, right-hand-side rows through the skipped block
+void launch_pstrf_tail(const BatchView& v, const int* perm, const int* rank, hipStream_t s);
 void launch_pstrf_end(const BatchView& v, hipStream_t s);
 // Xp[emu] (n, D) <- X[perm[emu]] for the slots of the launch
 void launch_permute_rows(const BatchView& v, const double* X, const int* perm, double* Xp, hipStream_t s);

@@ -10,7 +10,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.mark.parametrize("seed, env", [(11, {}), (12, {}), (13, {"MOGP_MCHOL": "0"})], ids=["11", "12", "13-multi-launch-schedules"])
+@pytest.mark.parametrize("seed, env", [(11, {}), (12, {}), (13, {"MOGP_CHOL": "multi"})], ids=["11", "12", "13-multi-launch-schedules"])
 def test_random_configurations_match_the_oracle(seed, env):
     # (the default Cholesky of these sizes is the one-launch task-queue kernel; the third run keeps the multi-launch
     # schedules it falls back to under the same test)

@@ -665,25 +665,47 @@ solo = make_gp(X, T[2], nugget=eta); solo.fit(theta)
 if %(bitwise)r:      # one schedule for every batch size: an emulator inside a batch equals the same emulator alone, bit for bit
     assert solo.current_logpost == mo.emulators[2].current_logpost
     assert np.array_equal(solo.Kinv_t, mo.emulators[2].Kinv_t)
-print("SWITCH-OK", repr(float(f[0])))
+import hashlib
+digest = hashlib.sha256(b"".join(np.ascontiguousarray(a).tobytes() for a in (f, g, mean, unc, solo.Kinv_t, mo.emulators[2].Kinv_t))).hexdigest()
+print("SWITCH-OK", repr(float(f[0])), "DIGEST", digest)
 """
 
+# Switches the library no longer reads (retired in round 7 with the kernel paths only they reached, HISTORY.md).  A process that still sets one
+# computes what the default computes, bit for bit; the branches they used to force, where they still exist, are reached by the default-path
+# tests (test_c3_full_batch_64_default_schedule_vs_oracle, test_c2_single_output_fit_and_predict_at_all_10k_points_vs_oracle, the C2 script here).
+_RETIRED_SWITCHES = [{"MOGP_CHOL": "mchol", "MOGP_MC_WGS": "2"}, {"MOGP_MCHOL": "0"}, {"MOGP_CHOL": "mchol", "MOGP_MC_SOLO": "0"},
+                     {"MOGP_TRTRI_WT4_FROM": "128"}, {"MOGP_TRTRI_WT4_FROM": "100000"}, {"MOGP_KINV_WT": "2"}, {"MOGP_KINV_WT": "4"},
+                     {"MOGP_CHOL": "mchol", "MOGP_MC_AHEAD": "0"}, {"MOGP_CHOL": "mchol", "MOGP_MC_EGRP": "0"},
+                     {"MOGP_CHOL": "mchol", "MOGP_MC_EGRP": "1", "MOGP_MC_WGS": "2"}, {"MOGP_BS_HOIST": "0"}, {"MOGP_BS_LOGDET": "0"},
+                     {"MOGP_CHOL": "mchol", "MOGP_MC_URG": "0"}, {"MOGP_CHOL": "mchol", "MOGP_MC_URG": "1", "MOGP_MC_WGS": "2"},
+                     {"MOGP_PV_SINGLE": "1"}, {"MOGP_PV_SINGLE": "0"}, {"MOGP_PV_Q": "0"}, {"MOGP_PV_Q": "1", "MOGP_PV_SINGLE": "0"},
+                     {"MOGP_BACKSOLVE": "1"}, {"MOGP_BS_SENTINEL": "0"}]
+_SWITCH_DEFAULT = {}
 
-@pytest.mark.parametrize("env", [{"MOGP_CHOL": "mchol"}, {"MOGP_CHOL": "mchol", "MOGP_MC_WGS": "2"}, {"MOGP_MCHOL": "0"}, {"MOGP_CHOL": "mchol", "MOGP_MC_SOLO": "0"},
-                                 {"MOGP_TRTRI_WT4_FROM": "128"}, {"MOGP_TRTRI_WT4_FROM": "100000"}, {"MOGP_KINV_WT": "2"}, {"MOGP_KINV_WT": "4"},
-                                 {"MOGP_CHOL": "mchol", "MOGP_MC_AHEAD": "0"}, {"MOGP_CHOL": "mchol", "MOGP_MC_EGRP": "0"}, {"MOGP_CHOL": "mchol", "MOGP_MC_EGRP": "1", "MOGP_MC_WGS": "2"}, {"MOGP_BS_HOIST": "0"}, {"MOGP_BS_LOGDET": "0"},
-                                 {"MOGP_CHOL": "mchol", "MOGP_MC_URG": "0"}, {"MOGP_CHOL": "mchol", "MOGP_MC_URG": "1", "MOGP_MC_WGS": "2"}, {"MOGP_PV_SINGLE": "1"}, {"MOGP_PV_SINGLE": "0"}, {"MOGP_PV_Q": "0"}, {"MOGP_PV_Q": "1", "MOGP_PV_SINGLE": "0"},
-                                 {"MOGP_CHOL": "la"}, {"MOGP_CHOL": "left"}, {"MOGP_CHOL": "right"},
-                                 {"MOGP_BACKSOLVE": "1"}, {"MOGP_BS_SENTINEL": "0"}, {"MOGP_KS_BUDGET_GB": "0.05"}],
-                         ids=lambda e: ",".join(k + "=" + v for k, v in e.items()))
-def test_cholesky_schedules_and_switches(env):
-    """Every A/B switch libmogp_hip.so still reads (HISTORY.md section 5) goes through the C2 full-size parity check in its own
-    process (the library reads its environment once); with the Cholesky schedule forced, batching is bit-invisible."""
+
+def _run_switch_script(env):
     import subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    script = _SWITCH_SCRIPT % {"root": root, "tests": os.path.join(root, "tests"), "bitwise": "MOGP_CHOL" in env}
+    bitwise = env.get("MOGP_CHOL") in ("mchol", "la", "left", "right")
+    script = _SWITCH_SCRIPT % {"root": root, "tests": os.path.join(root, "tests"), "bitwise": bitwise}
     out = subprocess.run([sys.executable, "-c", script], env=dict(os.environ, **env), capture_output=True, text=True, timeout=600)
     assert out.returncode == 0 and "SWITCH-OK" in out.stdout, out.stdout[-2000:] + out.stderr[-4000:]
+    return out.stdout.split("DIGEST")[-1].split()[0]
+
+
+@pytest.mark.parametrize("env", [{"MOGP_CHOL": "mchol"}, {"MOGP_CHOL": "la"}, {"MOGP_CHOL": "left"}, {"MOGP_CHOL": "right"}, {"MOGP_CHOL": "multi"},
+                                 {"MOGP_KS_BUDGET_GB": "0.05"}] + _RETIRED_SWITCHES,
+                         ids=lambda e: ",".join(k + "=" + v for k, v in e.items()))
+def test_cholesky_schedules_and_switches(env):
+    """Every forced Cholesky schedule and the cross-covariance chunking switch libmogp_hip.so reads go through the C2
+    full-size parity check in its own process (the library reads its environment once); with ONE schedule forced, batching is bit-invisible
+    (multi: the multi-launch schedule of each regime -- the batch and the solo fit take different ones).  A retired switch passes the same
+    check and changes no bit of the default's results."""
+    digest = _run_switch_script(env)
+    if env in _RETIRED_SWITCHES:
+        if "default" not in _SWITCH_DEFAULT:
+            _SWITCH_DEFAULT["default"] = _run_switch_script({})
+        assert digest == _SWITCH_DEFAULT["default"], "a retired switch changed the results: %r" % env
 
 
 def test_diagonal_block_grouped_columns_vs_column_at_a_time(tmp_path):

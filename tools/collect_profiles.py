@@ -42,8 +42,6 @@ for c in ("C2", "S8", "C4", "C5"):
 for t in ("1_2000_10", "8_2000_10", "64_2000_10", "1_16000_8"):
     wr("mchol_trace_%s.txt" % t, "# MOGP_MC_TRACE=... CONFIGS=%s python tools/mchol_check.py; python tools/mchol_trace.py (per-task time stamps of the one-launch Cholesky)\n" % t.replace("_", ":")
        + rd("mchol_trace_%s.txt" % t))
-wr("mchol_notraffic.txt", "# the one-launch Cholesky at 64 x n=2000 with its GEMM tasks re-reading their first 64 operand columns from the caches (MOGP_MC_NOTRAFFIC=1: same\n"
-   "# instruction stream, no fabric traffic, garbage results) against the real thing: python tools/mchol_time.py\n" + rd("mchol_notraffic.txt"))
 # FETCH / WRITE
 per_launch = None
 for suffix, what in (("", "64 x n=2000 x d=10, m=10000"), ("_S8", "the 8-emulator shard: 8 x n=2000, m=10000"), ("_C2", "C2: one n=2000 emulator, m=10000")):
