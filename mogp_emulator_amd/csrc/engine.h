@@ -109,6 +109,9 @@ class Engine {
                 const std::function<void(int, double, const std::vector<double>&)>& done);
   // slot `slot` of this (replica) engine takes targets, nugget type and priors of emulator i of `src`
   void retarget(int slot, const Engine& src, int i);
+  // new training inputs of the same shape (a cached replica engine taken by another fit): X, the analytic mean's design
+  // matrix and every slot's pivot-ordered copy of the inputs
+  void reset_inputs(const std::vector<double>& X);
 
   hipStream_t stream = nullptr;      // main stream: covariance build, trailing updates, everything else
   hipStream_t pstream = nullptr;     // look-ahead stream: panel factorisations
@@ -129,6 +132,7 @@ class Engine {
   void factorize_pivot(const std::vector<int>& ids, std::vector<int>& info);
   void ensure_pivot_buffers();
   void unpermute(int i, double* vec) const;          // vec (n) from pivoted to training order, in place
+  void restore_order(int i);                         // emulator i's inputs back to training order (after a pivoted fit)
   void panel(const BatchView& v, int o, int w, hipStream_t st);
   void ensure_linv(const std::vector<int>& ids);
   void ensure_kinv(const std::vector<int>& ids, bool for_gradient = false);

@@ -74,6 +74,7 @@ struct FlagGuard {
 };
 static std::atomic<long long> g_bs_timeouts{0}, g_obj_evals{0}, g_grad_evals{0}, g_mc_aborts{0};
 static std::atomic<long long> g_lb_iters{0}, g_ls_short{0}, g_ls_long{0}, g_lb_runs{0}, g_pool_rounds{0}, g_pool_slot_rounds{0}, g_rep_build_us{0}, g_rep_pool_us{0}, g_retarget_us{0}, g_retargets{0}, g_rep_reused{0};
+static std::atomic<long long> g_inputs_restored{0};
 long long prof_counter(const char* name) {
   const std::string s(name ? name : "");
   if (s == "backsolve_timeouts") return g_bs_timeouts.load();
@@ -93,6 +94,8 @@ long long prof_counter(const char* name) {
   if (s == "retarget_us") return g_retarget_us.load();                   // host time inside Engine::retarget (slot takes another emulator's targets)
   if (s == "retargets") return g_retargets.load();
   if (s == "replica_engines_reused") return g_rep_reused.load();          // multi-start fits that took the cached replica engine
+  // replica slots whose inputs went from pivot order back to training order when they took another run's emulator or another fit
+  if (s == "replica_inputs_restored") return g_inputs_restored.load();
   if (s == "replica_pool_us") return g_rep_pool_us.load();               // ... from there to the end of fit_map's replica block (pool + its destruction excluded)
   return -1;
 }
@@ -430,18 +433,21 @@ void Engine::factorize_pivot(const std::vector<int>& ids, std::vector<int>& info
   }
 }
 
+// (asynchronous on `stream`: every later kernel that reads the inputs runs behind it on that stream or on one that waits for it)
+void Engine::restore_order(int i) {
+  HIPCK(hipMemcpyAsync(dXp + (size_t)i * n * D, dX, (size_t)n * D * sizeof(double), hipMemcpyDeviceToDevice, stream));
+  for (int k = 0; k < n; ++k) hPerm[(size_t)i * n + k] = k;
+  gp[i].permuted = false;
+  gp[i].rank = 0;
+}
+
 void Engine::factorize(const std::vector<int>& ids, std::vector<int>& info, bool defer_info) {
   std::vector<int> piv, rest;
   for (int i : ids) (gp[i].nug_type == NUG_PIVOT ? piv : rest).push_back(i);
   if (piv.empty()) {
     // an emulator that was pivoted earlier goes back to training order
     for (int i : rest)
-      if (gp[i].permuted) {
-        HIPCK(hipMemcpyAsync(dXp + (size_t)i * n * D, dX, (size_t)n * D * sizeof(double), hipMemcpyDeviceToDevice, stream));
-        for (int k = 0; k < n; ++k) hPerm[(size_t)i * n + k] = k;
-        gp[i].permuted = false;
-        gp[i].rank = 0;
-      }
+      if (gp[i].permuted) restore_order(i);
     factorize_blocked(rest, info, defer_info);
     return;
   }
@@ -1741,6 +1747,13 @@ void Engine::retarget(int slot, const Engine& src, int i) {
   if (!analytic && mean.n_params() == 0 && mean.kind == 1)
     for (auto& x : res) x -= mean.value;
   HIPCK(hipMemcpyAsync(dT + (size_t)slot * n, res.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, stream));
+  // the fresh state below is not permuted, so the slot's inputs have to be in training order again: the next run's kernels read
+  // dXp[slot] whatever its nugget type.  (The pool hands out runs between evaluations, after the synchronisation of `stream` that
+  // every side stream has joined: nothing in flight still reads the slot.)
+  if (dXp && gp[slot].permuted) {
+    restore_order(slot);
+    g_inputs_restored += 1;
+  }
   HIPCK(hipStreamSynchronize(stream));          // `res` is a temporary
   const GPState& s = src.gp[i];
   GPState d;
@@ -1753,6 +1766,26 @@ void Engine::retarget(int slot, const Engine& src, int i) {
   d.beta.assign(q, 0.);
   drop_w2(slot);
   gp[slot] = std::move(d);
+}
+
+// The inputs of a cached replica engine taken by a fit with other inputs of the same shape: everything the engine derived from X
+// is rebuilt -- the host and device copies, the analytic mean's design matrix H(X), and every slot's copy in pivot order (put back
+// into training order: the slots' states are replaced by retarget before a run, and a state that is not permuted reads that copy).
+void Engine::reset_inputs(const std::vector<double>& X) {
+  hX = X;
+  HIPCK(hipMemcpy(dX, hX.data(), hX.size() * sizeof(double), hipMemcpyHostToDevice));
+  if (R > 1) {
+    std::vector<double> dummy(q, 0.);
+    mean.mean_deriv(hX.data(), n, D, dummy.data(), q, hH.data());
+    HIPCK(hipMemcpy(dH, hH.data(), hH.size() * sizeof(double), hipMemcpyHostToDevice));
+  }
+  if (dXp) {
+    for (int i = 0; i < B; ++i) {
+      if (gp[i].permuted) g_inputs_restored += 1;
+      restore_order(i);
+    }
+    HIPCK(hipStreamSynchronize(stream));
+  }
 }
 
 // Multi-start MAP fit (fitting.hpp:61-128, fitting.py:219-266): n_tries L-BFGS runs per emulator, the best end point wins.
@@ -1844,8 +1877,7 @@ void Engine::fit_map(const std::vector<int>& ids_in, int n_tries, const double* 
           slot->testing_size == testing_size && slot->device == dev && slot->mean.kind == mean.kind && slot->mean.value == mean.value &&
           slot->mean.dims == mean.dims && slot->mean.powers == mean.powers) {
         rep = std::move(slot);
-        rep->hX = hX;
-        HIPCK(hipMemcpy(rep->dX, hX.data(), hX.size() * sizeof(double), hipMemcpyHostToDevice));
+        rep->reset_inputs(hX);
         g_rep_reused += 1;
       } else {
         slot.reset();                                   // (frees the old one BEFORE the new one is allocated)
