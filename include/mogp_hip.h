@@ -244,6 +244,13 @@ int mogp_mchol_task_table_ahead(int n_plus_rhs, int* out, int capacity);
    "replica_engine_build_us" / "replica_pool_us" = host time constructing (or re-taking) the replica engine / inside the pool,
    "replica_engines_reused" = multi-start fits that ran on the replica engine the previous one left behind (MOGP_REPLICA_CACHE) */
 int mogp_profile_counter(const char* name, long long* out);
+/* gKDR dimension reduction (mogp_emulator/DimensionReduction.py:132-236) over a grid of kernel scales, in one call.  X (n, m) and y (n)
+   row-major; sgx2 (nx) / sgy2 (ny): the squared input / output kernel scales SGX^2, SGY^2 (positive); eps: the regularisation EPS >= 0
+   (A = Kx + n eps I).  R_out (nx * ny, m, m): R of every pair (sgx2[i], sgy2[j]) at index i * ny + j.  info_out (nx): non-zero when A of
+   input scale i is not positive definite (the R of its pairs are NaN).  max_pairs_per_pass: pairs per device pass, 0 = sized by the free
+   device memory; R does not depend on it, bit for bit. */
+int mogp_gkdr_R(const double* X, int n, int m, const double* y, int nx, const double* sgx2, int ny, const double* sgy2, double eps,
+                int max_pairs_per_pass, double* R_out, int* info_out);
 /* device memory helpers so a host program can hand device-resident buffers to the *_dev calls */
 void* mogp_dev_malloc(unsigned long long bytes);
 int mogp_dev_free(void* d_ptr);

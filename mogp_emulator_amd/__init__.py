@@ -8,9 +8,12 @@ mogp_emulator_amd -- MI355X (gfx950) native fit + predict backend for mogp_emula
                    host-side mirrors of the reference's GPU-facing Python interface
   HistoryMatching.py, SequentialDesign.py, validation.py
                    consumers of the batched prediction (implausibility, MICE scoring, validation errors)
+  DimensionReduction.py
+                   gKDR dimension reduction; R of a whole (X_scale, Y_scale) grid in one device call
   dist.py          one-process-per-GPU sharding of emulators + single gather (torch.distributed/RCCL)
 """
 from .LibGPGPU import HAVE_LIBGPGPU, gpu_usable            # noqa: F401
+from .DimensionReduction import gKDR                        # noqa: F401
 
 if HAVE_LIBGPGPU:
     from .GaussianProcessGPU import GaussianProcessGPU, PredictResult   # noqa: F401

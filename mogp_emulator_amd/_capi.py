@@ -125,6 +125,8 @@ SIGNATURES = {
     "mogp_fit_GP_MAP": (c_int, [c_void_p, c_int, c_double_p, c_int]),
     "mogp_set_fit_options": (c_int, [c_int, c_double, c_double, c_ulonglong]),
     "mogp_kernel_eval": (c_int, [c_int, c_int, c_double_p, c_int, c_double_p, c_int, c_int, c_double_p, c_int, c_double_p]),
+    "mogp_gkdr_R": (c_int, [c_double_p, c_int, c_int, c_double_p, c_int, c_double_p, c_int, c_double_p, c_double, c_int, c_double_p,
+                            c_int_p]),
     "mogp_profile_enable": (c_int, [c_int]),
     "mogp_profile_reset": (c_int, []),
     "mogp_profile_schedule": (c_int, [c_int, c_int]),

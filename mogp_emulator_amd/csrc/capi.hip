@@ -625,6 +625,11 @@ int mogp_kernel_eval(int kernel_type, int what, const double* x1, int n1, const 
   GUARD(kernel_eval_impl(kernel_type, what, x1, n1, x2, n2, D, params, n_params, out));
 }
 
+int mogp_gkdr_R(const double* X, int n, int m, const double* y, int nx, const double* sgx2, int ny, const double* sgy2, double eps,
+                int max_pairs_per_pass, double* R_out, int* info_out) {
+  GUARD(gkdr_R(X, n, m, y, nx, sgx2, ny, sgy2, eps, max_pairs_per_pass, R_out, info_out));
+}
+
 // ---- measurement hooks ----------------------------------------------------------------------------
 int mogp_profile_enable(int on) { prof_enable(on != 0); return 0; }
 int mogp_profile_reset(void) { prof_reset(); return 0; }

@@ -112,6 +112,11 @@ class Engine {
   // new training inputs of the same shape (a cached replica engine taken by another fit): X, the analytic mean's design
   // matrix and every slot's pivot-ordered copy of the inputs
   void reset_inputs(const std::vector<double>& X);
+  // gKDR (kernels_gkdr.hip): every slot's matrix is written into the factor buffer by `fill` -- the launch of the covariance build,
+  // with the same layout (launch.h) -- and factored with the schedule of the regime; info (indexed by slot) as factorize.  The
+  // slots that factor form L^-1 (linv_buffer(), lower triangle).  Needs nugget type "fixed" on every slot.
+  void factor_prebuilt(const std::function<void(const BatchView&)>& fill, std::vector<int>& info);
+  const double* linv_buffer() const { return dLinv; }
 
   hipStream_t stream = nullptr;      // main stream: covariance build, trailing updates, everything else
   hipStream_t pstream = nullptr;     // look-ahead stream: panel factorisations
@@ -138,6 +143,7 @@ class Engine {
   void ensure_kinv(const std::vector<int>& ids, bool for_gradient = false);
   BatchView view(int nb) const;
   void build_cov(const BatchView& v, const ZeroRanges& zero = ZeroRanges());
+  const std::function<void(const BatchView&)>* prebuilt = nullptr;   // factor_prebuilt: build_cov runs this instead
   std::vector<char> z_armed;     // per emulator: its solution row holds the sentinel pattern of the one-launch back substitution
   void set_theta(int i, const double* theta);
   void ensure_predict_scratch(int nb, int MC);
@@ -188,6 +194,11 @@ struct FitOptions {
   unsigned long long seed = 0;
 };
 FitOptions& fit_options();
+
+// gKDR (kernels_gkdr.hip): R of every (input scale, output scale) pair, row-major, into R_out (nx * ny * m * m); info_out[i] != 0 when
+// A = Kx + n eps I of input scale i is not positive definite (its R are NaN).  max_pairs_per_pass = 0: sized by free device memory.
+void gkdr_R(const double* X, int n, int m, const double* y, int nx, const double* sgx2, int ny, const double* sgy2, double eps,
+            int max_pairs_per_pass, double* R_out, int* info_out);
 
 // measurement hooks (mogp_profile_schedule): force the Cholesky schedule / serialise it onto one stream so that the
 // HIP-event time of a kernel is its time alone on the device; -1 / false = the library's own choice.

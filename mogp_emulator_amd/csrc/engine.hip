@@ -263,6 +263,14 @@ double Engine::nugget_size(int i) const {
 // back substitution polls for (backsolve_chain_kernel<SENT>); `z_armed` records that, so that a chain launched on a row that has
 // not been preset since its last solve arms it itself instead of reading stale values as "already there".
 void Engine::build_cov(const BatchView& v, const ZeroRanges& zero) {
+  if (prebuilt) {
+    for (int r = 0; r < 2; ++r)
+      if (zero.p[r] && zero.n[r]) HIPCK(hipMemsetAsync(zero.p[r], 0, zero.n[r] * sizeof(unsigned), stream));
+    (*prebuilt)(v);
+    if (z_armed.size() != (size_t)B) z_armed.assign(B, 0);
+    for (int i : idx_on_device) z_armed[i] = 0;
+    return;
+  }
   launch_cov_build(v, stream, zero);
   if (z_armed.size() != (size_t)B) z_armed.assign(B, 0);
   for (int i : idx_on_device) z_armed[i] = (R == 1 && v.Z != nullptr) ? 1 : 0;
@@ -1766,6 +1774,30 @@ void Engine::retarget(int slot, const Engine& src, int i) {
   d.beta.assign(q, 0.);
   drop_w2(slot);
   gp[slot] = std::move(d);
+}
+
+void Engine::factor_prebuilt(const std::function<void(const BatchView&)>& fill, std::vector<int>& info) {
+  std::vector<int> ids(B);
+  for (int i = 0; i < B; ++i) {
+    if (gp[i].nug_type != NUG_FIXED || gp[i].permuted) throw std::runtime_error("factor_prebuilt: every slot needs nugget type fixed");
+    ids[i] = i;
+    gp[i].nugget_used = gp[i].nug_size;
+  }
+  struct Reset {      // build_cov is the covariance build again when this returns or throws
+    const std::function<void(const BatchView&)>*& p;
+    ~Reset() { p = nullptr; }
+  } reset{prebuilt};
+  prebuilt = &fill;
+  factorize_blocked(ids, info, false);
+  std::vector<int> ok;
+  for (int i : ids) {
+    GPState& g = gp[i];
+    g.has_data = false;
+    g.factored = info[i] == 0;
+    g.linv = g.kinv = false;
+    if (g.factored) ok.push_back(i);
+  }
+  if (!ok.empty()) ensure_linv(ok);
 }
 
 // The inputs of a cached replica engine taken by a fit with other inputs of the same shape: everything the engine derived from X

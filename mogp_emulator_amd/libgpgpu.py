@@ -26,6 +26,7 @@ __all__ = [
     "WeakPrior", "InvGammaPrior", "GammaPrior", "LogNormalPrior",
     "BaseTransform", "CovTransform", "CorrTransform",
     "SquaredExponentialKernel", "Matern52Kernel", "MeanPriors", "set_fit_options", "set_device", "device_count", "pivot_cholesky",
+    "gkdr_R",
 ]
 
 
@@ -1015,6 +1016,23 @@ def pivot_cholesky(A):
     rank = ctypes.c_int(0)
     check(_lib.mogp_pivot_cholesky(dptr(A), n, dptr(L), iptr(P), ctypes.byref(rank)))
     return L, P, rank.value
+
+
+def gkdr_R(X, y, sgx2, sgy2, eps, max_pairs_per_pass=0):
+    """(R, info) of gKDR (DimensionReduction.py:132-236) for every pair of squared kernel scales, in one device call:
+    R (len(sgx2), len(sgy2), M, M), info (len(sgx2)) non-zero where Kx + N eps I is not positive definite (those R are NaN)."""
+    X = _f64(X, 2, "X")
+    n, m = X.shape
+    y = _f64(np.reshape(y, (-1,)), 1, "y")
+    if y.shape[0] != n:
+        raise ValueError("y must have one entry per row of X")
+    sx = _f64(np.atleast_1d(sgx2), 1, "sgx2")
+    sy = _f64(np.atleast_1d(sgy2), 1, "sgy2")
+    R = np.empty((sx.size, sy.size, m, m))
+    info = np.zeros(sx.size, dtype=np.int32)
+    check(_lib.mogp_gkdr_R(dptr(X), n, m, dptr(y), sx.size, dptr(sx), sy.size, dptr(sy), float(eps), int(max_pairs_per_pass),
+                           dptr(R), iptr(info)))
+    return R, info
 
 
 # --------------------------------------------------------------------------------------
