@@ -18,6 +18,12 @@ fit+grad/s and predict pts/s are reported next to it from the same timed steps; 
 phase), fit_grad_logpost and fit_grad_gradient (fit+grad phase), predict_mean and predict_var (predict phase; a fixed seeded sample
 of the prediction points when all of them would exceed 64 MB).  The inputs are seeded, so the same arguments give the same inputs.
 
+A plain run does only that: set-up, warm-up, the timed steps, --dump-outputs and the result line, whose `kernels` and `roofline` are
+read off the HIP events of the timed steps.  `--full` adds, after the timed region, the blocks below that take runs of their own:
+shard_sweep with fit_GP_MAP and projected_scaling, other_configs, the untimed extras (host-buffer predict, deriv, implausibility,
+full_cov, pivot, tsunami), predict_first_call_ms, kernels_fit_single_stream, nccl_world1, cpu_baseline and parity_in_bench; the
+`--no-*` options and --cpu-budget-s trim that.  The timed steps are the same in both modes.
+
 other_configs (N = 1): BASELINE's C2 (one n=2000 emulator, predict m=10^4), C4 (16 x n=5000, Matern-5/2, fitted nugget) and
 C5 (n=16000) timed on this GPU with their tagged kernels, each with the CPU oracle beside it (`cpu_baseline`: one / two / one of its outputs fitted
 on the host, outside every timed region, within --cpu-budget-s) and its own `parity` block from the values that run produces;
@@ -27,7 +33,8 @@ multi-GPU measurement can be made on a one-GPU box); roofline.traffic_source: wh
 times fit_GP_MAP with 15 concurrent starts per emulator (the workload users run at shard size).
 roofline: for the kernel with the largest share of device time; `achieved` = algorithmic flops (n^3/3 per
 Cholesky, m n^2 per predictive variance, ...) of all its launches in the timed steps / their total duration measured with
-HIP events recorded on the launch stream inside libmogp_hip.so (mogp_profile_*).  fit_roofline: the whole fit phase
+HIP events recorded on the launch stream inside libmogp_hip.so (mogp_profile_*); with --full at N = 1 the `achieved` of the
+Cholesky kernels comes from a single-stream pass of their own (kernels_fit_single_stream).  fit_roofline: the whole fit phase
 against the fp64 MFMA peak (n^3/3 flops per emulator / phase time).  shard_sweep (N = 1): the per-GPU shard regime of the
 multi-GPU runs (8 / 16 / 32 emulators, and 2 x n=5000 of C4) timed on this GPU.  cpu_baseline: the oracle (NumPy/LAPACK
 restatement of the reference CPU path) timed on this host on a bounded sample of the same workload; parity_in_bench: the
@@ -35,7 +42,7 @@ device results for the emulators the CPU baseline evaluates anyway, compared wit
 Round 6: compact copies of the blocks above are NESTED in `roofline` (headline_kernel = the one-launch Cholesky behind `value`, fit_phase,
 kernels, other_configs, shard_sweep, projected_scaling, fit_GP_MAP) and in `cpu_baseline` (parity_in_bench), because the driver's record
 keeps nested values of those two objects but only the names of other top-level keys; for N > 1 kernel times are maxima over the ranks,
-`traffic` is null, and rank 0 still times the CPU baseline after the timed region.
+`traffic` is null, and with --full rank 0 still times the CPU baseline after the timed region.
 """
 import argparse
 import ctypes
@@ -492,16 +499,20 @@ def main():
     ap.add_argument("--outputs", type=int, default=64, help="emulators: in total (strong scaling) / per GPU (weak scaling)")
     ap.add_argument("--scaling", choices=["strong", "weak"], default="strong",
                     help="strong: BASELINE's C3, the 64 outputs are sharded over the GPUs; weak: 64 outputs on every GPU")
-    ap.add_argument("--no-shard-sweep", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beyond the headline: CPU baseline and parity, other "
+                         "configurations, shard sweep, fit_GP_MAP, untimed extras, single-stream kernel pass, RCCL world-1 "
+                         "(without it: set-up, warm-up, timed steps, --dump-outputs, the result line)")
+    ap.add_argument("--no-shard-sweep", action="store_true", help="with --full: skip shard_sweep and the 64-emulator fit_GP_MAP")
     ap.add_argument("--m", type=int, default=10000, help="prediction points per emulator")
     ap.add_argument("--kernel", default="SquaredExponential")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip every CPU oracle run (cpu_baseline, parity)")
     ap.add_argument("--cpu-budget-s", type=float, default=240.,
-                    help="host seconds the CPU oracle may spend beside the other configurations (C2 / C4 / C5); what does not fit is reported as skipped")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the C2 / C4 / C5 block (other_configs)")
+                    help="with --full: host seconds the CPU oracle may spend beside the other configurations (C2 / C4 / C5); what does not "
+                         "fit is reported as skipped")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the C2 / C4 / C5 block (other_configs)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="only the timed steps (+ the single-stream pass): none of the untimed extras (host-buffer predict, deriv, full_cov, "
-                         "fit_GP_MAP, pivot, tsunami) -- for kernel traces whose per-kernel averages should be those of the timed steps")
+                    help="with --full: none of the untimed extras (host-buffer predict, deriv, full_cov, fit_GP_MAP, pivot, tsunami)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned (log-posteriors, gradient, predictive mean "
                          "and variance of every emulator) as DIR/<name>.npy, float64, at most %d MB in all" % (DUMP_BUDGET_BYTES >> 20))
@@ -649,10 +660,12 @@ def main():
     # taken now: the untimed passes below reuse the device buffers of the last step
     dump = last_step_outputs(f_last, f2_last, g_last, d_mean, d_var, gathered, world, per_rank, dist) if args.dump_outputs else None
 
+    # Every measurement or check below that is not read off the timed steps runs with --full only: a plain run reports what the
+    # timed steps measured (phase times, HIP-event kernel times) and nothing else.
     # outside the timed region: the reference-style host-buffer predict (H2D of X*, D2H of mean/var over PCIe)
     # and one end-to-end MAP fit (lock-step L-BFGS, theta0 given, 1 start) for orientation
     extras = {}
-    if rank == 0 and world == 1 and not args.no_shard_sweep and (n, d, B) == (2000, 10, 64):
+    if args.full and rank == 0 and world == 1 and not args.no_shard_sweep and (n, d, B) == (2000, 10, 64):
         # the per-GPU shards of the 2 / 4 / 8-GPU runs of THIS workload, and of C4 (16 x n=5000 over 8 GPUs), on one GPU
         # (+ what users run at shard size: fit_GP_MAP with 15 concurrent starts and a fixed cap of 10 iterations)
         sweep = [time_shard(M, GPPriors, 2, n, d, b, m, args.kernel, nugget, theta, 7, map_starts=15) for b in (1, 8, 16, 32)]
@@ -660,7 +673,7 @@ def main():
                                 np.array([-2. * np.log(0.3 * np.sqrt(20))] * 20 + [0., np.log(1e-4)]), 3))
         extras["shard_sweep"] = sweep
         extras["fit_GP_MAP_15_starts_64_emulators"] = time_fit_map(M, X, T, args.kernel, nugget, 15, 10)
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         means_h = np.zeros((B, m)); vars_h = np.zeros((B, m))
         mo.predict_variance_batch(Xs, means_h, vars_h)
         t0 = time.perf_counter()
@@ -719,7 +732,7 @@ def main():
 
     # The timed predict follows eval(grad=True), i.e. L^-1 exists (steady state: many predictions per fit).  The FIRST predict after a
     # plain fit also builds L^-1 (the reference pays its invQ inside fit, densegp_gpu.hpp:576-582): reported next to it.
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         first, steady = [], []
         for it in range(3):
             mo.eval(thetas + 1e-3 * (it + 11), grad=False)
@@ -768,9 +781,9 @@ def main():
                 kv["note"] = "time = max over the %d ranks; work = one rank's shard" % world
     # The factorisation overlaps kernels of two streams, so the event time of a Cholesky kernel above includes the share
     # of the device it did NOT have.  Its time alone: the same evaluation serialised onto one stream (outside the timed
-    # region, N = 1 only); `achieved` of the chol_* kernels is taken from this pass.
+    # region, N = 1 only, --full); `achieved` of the chol_* kernels is taken from this pass.
     kern_serial = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         lib.mogp_profile_reset()
         lib.mogp_profile_schedule(-1, 1)
         mo.eval(thetas, grad=False)
@@ -888,7 +901,7 @@ def main():
                                     "predict_efficiency": (t_pr / K * 1e3 / N) / e["predict_ms"]}
             out["projected_scaling"] = {"basis": "one-GPU time of the per-rank shard (shard_sweep) -- a projection, not a multi-GPU measurement",
                                         "n_gpus": proj}
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # rank 0, after the timed region, for every N ("in the same run"); the pool fits all outputs of the
             # workload (strong scaling: the 64 of C3), the device side of the parity block is rank 0's shard
             out["cpu_baseline"], values = cpu_baseline(X, T_all if args.scaling == "strong" else T, Xs, theta, nugget)

@@ -216,8 +216,8 @@ def test_bench_gpus_flag_launches_that_many_ranks():
     """`python bench.py --gpus 2` (no launcher around it) must start two ranks itself (--gpus was parsed and
     ignored).  gloo + both ranks on device 0, as the one GPU of this box allows; the command shape is the driver's.  Round 6: an
     N > 1 line carries `cpu_baseline` (rank 0, after the timed region) and, nested in `roofline`, the headline kernel's fraction with
-    the kernel times taken as maxima over the ranks; `traffic` is null and says why."""
-    out = _bench_line(2, [])
+    the kernel times taken as maxima over the ranks; `traffic` is null and says why.  The CPU baseline comes with --full."""
+    out = _bench_line(2, ["--full"])
     assert out["n_gpus"] == 2 and out["rccl_ranks"] == 2 and out["collective_backend"] == "gloo"
     assert out["config"]["outputs_per_gpu"] == 32 and out["config"]["outputs_total"] == 64
     assert np.isfinite(out["value"]) and out["value"] > 0 and np.isfinite(out["predict_pts_per_s"])
@@ -279,3 +279,24 @@ def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
         mu, var, _ = ref.predict(Xs, include_nugget=False)
         assert_allclose(g["predict_mean"][k], mu, rtol=1e-7, atol=1e-8)
         assert_allclose(g["predict_var"][k], var, atol=1e-7)
+
+
+def test_bench_plain_run_reports_the_timed_steps_and_full_adds_the_rest():
+    """A plain run sets up, warms up, times its steps and prints the line: nothing that takes a run of its own.  --full adds the
+    untimed extras, the first-call predict, the single-stream kernel pass, RCCL at world size 1, the CPU baseline and its parity
+    check, on the same timed steps (a small workload: the shard sweep and the other configurations belong to the default one)."""
+    args = ["--n", "2000", "--d", "10", "--outputs", "4", "--m", "700", "--steps", "2", "--warmup", "1"]
+    plain = _bench_line(1, args)
+    full = _bench_line(1, args + ["--full"])
+    moved = ("cpu_baseline", "parity_in_bench", "predict_first_call_ms", "predict_pts_per_s_host_buffers", "pivot_fits_per_s",
+             "tsunami_benchmark", "nccl_world1")
+    assert [k for k in moved if k in plain] == [] and plain["kernels_fit_single_stream"] is None
+    assert [k for k in moved if k not in full] == [] and full["kernels_fit_single_stream"]["fit_ms_single_stream"] > 0
+    assert "shard_sweep" not in full and "other_configs" not in full
+    assert full["parity_in_bench"]["passed"] is True and full["cpu_baseline"]["parity_in_bench"]["passed"] is True
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup", "config"):
+        assert plain[k] == full[k], k
+    for out in (plain, full):
+        assert np.isfinite(out["value"]) and out["value"] > 0 and out["ms_per_step"] > 0
+        assert out["kernels"] and out["roofline"]["achieved"] > 0
+    assert_allclose(plain["logpost_checksum"], full["logpost_checksum"], rtol=1e-12)

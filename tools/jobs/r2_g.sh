@@ -1,10 +1,11 @@
 #!/bin/bash
 export TMPDIR=/tmp
-python bench.py --steps 10 --warmup 2 > gpurun_out/r2g_bench.json 2> gpurun_out/r2g_bench.err
-tail -3 gpurun_out/r2g_bench.err
+export OUT=${OUT:-.}                                                  # where the bench line and its log go
+python bench.py --steps 10 --warmup 2 --full > $OUT/r2g_bench.json 2> $OUT/r2g_bench.err
+tail -3 $OUT/r2g_bench.err
 python - <<'PY'
-import json
-d = json.loads(open("gpurun_out/r2g_bench.json").read().strip().splitlines()[-1])
+import json, os
+d = json.loads(open(os.path.join(os.environ["OUT"], "r2g_bench.json")).read().strip().splitlines()[-1])
 for k in ("value", "fit_grad_per_s", "predict_pts_per_s", "phase_ms_per_step", "roofline", "fit_roofline", "parity_in_bench", "shard_sweep"):
     print(k, json.dumps(d.get(k))[:900])
 for k, v in d["kernels"].items():

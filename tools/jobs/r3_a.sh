@@ -5,12 +5,13 @@ R=/root/repo
 cd $R
 timeout 1700 python -m pytest tests -m gpu -x -q --durations=25 2>&1 | tail -45 > gpurun_out/r3a_tests.txt
 tail -8 gpurun_out/r3a_tests.txt
-( time python bench.py ) > gpurun_out/r3a_bench.json 2> gpurun_out/r3a_bench.err
-tail -5 gpurun_out/r3a_bench.err
+export OUT=${OUT:-.}                                                  # where the bench line and its log go
+( time python bench.py --full ) > $OUT/r3a_bench.json 2> $OUT/r3a_bench.err
+tail -5 $OUT/r3a_bench.err
 python - <<'PY'
-import json
+import json, os
 try:
-    d = json.loads(open("gpurun_out/r3a_bench.json").read().strip().splitlines()[-1])
+    d = json.loads(open(os.path.join(os.environ["OUT"], "r3a_bench.json")).read().strip().splitlines()[-1])
     for k in ("value", "fit_grad_per_s", "predict_pts_per_s", "phase_ms_per_step", "roofline", "fit_roofline", "parity_in_bench", "nccl_world1", "cpu_baseline", "fit_GP_MAP_15_starts_64_emulators"):
         print(k, json.dumps(d.get(k))[:1200])
     for e in d.get("shard_sweep", []):

@@ -11,7 +11,7 @@ cd $R
 timeout 1700 python -m pytest tests -m gpu -x -q --durations=10 2>&1 | tail -22 > $O/gpu_tests.txt
 tail -3 $O/gpu_tests.txt
 # 2. the bench line the driver will also produce
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 # 3. kernel stats of the default bench workload
 cd /tmp
 CMD="python bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-shard-sweep --no-other-configs"

@@ -5,7 +5,7 @@ cd /root/repo
 O=gpurun_out/suite_${TAG:-head}; rm -rf $O; mkdir -p $O
 timeout 2700 python -m pytest tests -m gpu -x -q --durations=12 2>&1 | tail -26 > $O/gpu_tests.txt; tail -4 $O/gpu_tests.txt
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 | tee $O/smoke.txt
-python bench.py > $O/bench.json 2> $O/bench.err; python - <<PY
+python bench.py --full > $O/bench.json 2> $O/bench.err; python - <<PY
 import json
 l=[x for x in open('$O/bench.json').read().splitlines() if x.startswith('{')][-1]; d=json.loads(l)
 print({k:d[k] for k in ('value','ms_per_step')}, d['phase_ms_per_step'], d['roofline']['frac'])

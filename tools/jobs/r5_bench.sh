@@ -4,7 +4,7 @@ export TMPDIR=/tmp
 cd /root/repo
 O=gpurun_out/r5bench_${TAG:-head}; rm -rf $O; mkdir -p $O
 cp mogp_emulator_amd/libmogp_hip.build $O/build_commit.txt
-python bench.py > $O/bench.json 2> $O/bench.err; echo "rc=$?"
+python bench.py --full > $O/bench.json 2> $O/bench.err; echo "rc=$?"
 tail -5 $O/bench.err
 python - <<PY
 import json

@@ -14,7 +14,7 @@ timeout 2400 python -m pytest tests -m gpu -x -q --durations=10 2>&1 | tail -22 
 tail -3 $O/gpu_tests.txt
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 >> $O/gpu_tests.txt
 # 2. the bench line the driver will also produce
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 # 3. kernel stats of the default bench workload: ONLY the timed steps (+ the single-stream pass), no extras
 cd /tmp
 CMD="python bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-shard-sweep --no-other-configs --no-extras"

@@ -6,4 +6,4 @@ for c in default mchol left la right; do
   if [ $c = default ]; then timeout 300 python tools/adaptive_edge.py; else MOGP_CHOL=$c timeout 300 python tools/adaptive_edge.py; fi
 done > $O/adaptive_edge.txt 2>&1
 cat $O/adaptive_edge.txt | cut -c1-400
-python bench.py > $O/bench.json 2> $O/bench.err; cut -c1-1500 $O/bench.json
+python bench.py --full > $O/bench.json 2> $O/bench.err; cut -c1-1500 $O/bench.json

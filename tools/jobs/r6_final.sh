@@ -10,7 +10,7 @@ rm -rf $O; mkdir -p $O
 cd $R
 cp mogp_emulator_amd/libmogp_hip.build $O/build_commit.txt; cat $O/build_commit.txt        # written by the Makefile next to the library
 # 1. the bench line the driver will also produce (first: on the fresh box, as the driver runs it)
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 # 2. the GPU suite + smoke
 timeout 2400 python -m pytest tests -m gpu -x -q --durations=10 2>&1 | tail -22 > $O/gpu_tests.txt
 tail -3 $O/gpu_tests.txt

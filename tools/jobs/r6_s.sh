@@ -1,7 +1,7 @@
 #!/bin/bash
 export TMPDIR=/tmp
 R=/root/repo; O=$R/gpurun_out/r6_s; rm -rf $O; mkdir -p $O; cd $R
-python bench.py --no-cpu-baseline --no-other-configs > $O/bench.json 2> $O/bench.err
+python bench.py --full --no-cpu-baseline --no-other-configs > $O/bench.json 2> $O/bench.err
 python - <<'PY'
 import json
 b=json.loads([l for l in open("/root/repo/gpurun_out/r6_s/bench.json") if l.startswith("{")][-1])
