@@ -157,7 +157,17 @@ mogp_mogp* mogp_mogp_create(const double* inputs, int n, int D, const double* ta
                             const mogp_meanfunc* mean, int kernel_type, int nugget_type, double nugget_size);
 mogp_mogp* mogp_mogp_create_analytic_mean(const double* inputs, int n, int D, const double* targets, int n_out, unsigned testing_size,
                                           const mogp_meanfunc* mean, int kernel_type, int nugget_type, double nugget_size);
+/* The same model spread over several devices in one process: the emulators are split into contiguous blocks of ceil(n_out / n_devices)
+ * (dist.shard_bounds), empty blocks are dropped, and part k holds one engine on devices[k] for its block.  A device may be repeated
+ * (parts on one device run one after the other); an ordinal outside [0, device count) is refused.  analytic_mean as
+ * mogp_mogp_create_analytic_mean.  Every mogp_mogp_* entry works on the result; each call runs the parts on one host thread each. */
+mogp_mogp* mogp_mogp_create_on_devices(const double* inputs, int n, int D, const double* targets, int n_out, unsigned testing_size,
+                                       const mogp_meanfunc* mean, int kernel_type, int nugget_type, double nugget_size, int analytic_mean,
+                                       const int* devices, int n_devices);
 void mogp_mogp_destroy(mogp_mogp*);
+/* number of parts (1 for a handle created without a device list); part k: its device and emulator block [lo, hi) */
+int mogp_mogp_n_parts(const mogp_mogp*);
+int mogp_mogp_part(const mogp_mogp*, int k, int* device, int* lo, int* hi);
 int mogp_mogp_n(const mogp_mogp*);
 int mogp_mogp_D(const mogp_mogp*);
 int mogp_mogp_n_emulators(const mogp_mogp*);

@@ -3,7 +3,9 @@
 
 All emulators share the inputs and live in ONE native engine; ``fit``, ``predict`` and
 ``fit_GP_MAP`` are single batched device passes over every emulator (the reference loops over
-per-emulator objects with OpenMP on one stream, multioutputgp_gpu.hpp:156-228).
+per-emulator objects with OpenMP on one stream, multioutputgp_gpu.hpp:156-228).  With ``devices=``
+(or ``MOGP_DEVICES``) the emulators are split into contiguous blocks, one engine per block on its GPU,
+driven concurrently from this process.
 
 Fixes relative to the reference wrapper: priors given as a list/dict are
 honoured (the reference passes an unknown keyword), ``__call__`` works, test points are not
@@ -12,6 +14,7 @@ limited to batch_size / n_emulators.
 import numpy as np
 
 from . import LibGPGPU
+from .devices import parse_devices
 from .GaussianProcessGPU import (GaussianProcessGPU, PredictResult, _resolve_kernel, _resolve_mean,
                                  apply_mean_priors, create_prior_params)
 from .Priors import GPPriors
@@ -19,7 +22,9 @@ from .Priors import GPPriors
 
 class MultiOutputGP_GPU(object):
     def __init__(self, inputs, targets, mean=None, kernel="SquaredExponential", priors=None, nugget="adaptive",
-                 inputdict={}, use_patsy=True, batch_size=16000, analytic_mean=False):
+                 inputdict={}, use_patsy=True, batch_size=16000, analytic_mean=False, devices=None):
+        """devices: None (read MOGP_DEVICES; unset: one engine on the current device), "all" or a list of device ordinals --
+        the emulators are then split into contiguous blocks, one engine per block on its device, all driven from this process"""
         if not LibGPGPU.gpu_usable():
             raise RuntimeError("Cannot construct MultiOutputGP_GPU: the GPU library or a compatible GPU is unavailable")
         inputs = np.array(inputs, dtype=np.float64)
@@ -52,8 +57,9 @@ class MultiOutputGP_GPU(object):
         # analytic_mean=True: mean coefficients integrated out with weak priors (the CPU class's
         # treatment, GaussianProcess.py:640-700) rather than optimised inside theta (the reference GPU class)
         self._analytic_mean = bool(analytic_mean)
+        devlist = parse_devices(devices, LibGPGPU.device_count())
         self._mogp_gpu = LibGPGPU.MultiOutputGP_GPU(inputs, targets, batch_size, _resolve_mean(mean), ktype, nugtype, nugsize,
-                                                    analytic_mean=bool(analytic_mean))
+                                                    analytic_mean=bool(analytic_mean), devices=devlist)
 
         if isinstance(priors, (GPPriors, dict)) or priors is None:
             priorslist = [priors] * self.n_emulators
@@ -83,6 +89,8 @@ class MultiOutputGP_GPU(object):
     n_params = property(lambda self: self._mogp_gpu.n_data_params())
     n_emulators = property(lambda self: self._mogp_gpu.n_emulators())
     n_corr = property(lambda self: self._mogp_gpu.n_corr_params())
+    # the device of every part, in emulator order (one entry without a device list; blocks left empty by the split are dropped)
+    devices = property(lambda self: [d for d, _, _ in self._mogp_gpu.parts()])
 
     @property
     def emulators(self):

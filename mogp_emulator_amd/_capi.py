@@ -99,7 +99,11 @@ SIGNATURES = {
     "mogp_fit_single_GP_MAP": (c_int, [c_void_p, c_int, c_double_p, c_int]),
     "mogp_mogp_create": (c_void_p, [c_double_p, c_int, c_int, c_double_p, c_int, c_uint, c_void_p, c_int, c_int, c_double]),
     "mogp_mogp_create_analytic_mean": (c_void_p, [c_double_p, c_int, c_int, c_double_p, c_int, c_uint, c_void_p, c_int, c_int, c_double]),
+    "mogp_mogp_create_on_devices": (c_void_p, [c_double_p, c_int, c_int, c_double_p, c_int, c_uint, c_void_p, c_int, c_int, c_double, c_int,
+                                               c_int_p, c_int]),
     "mogp_mogp_destroy": (None, [c_void_p]),
+    "mogp_mogp_n_parts": (c_int, [c_void_p]),
+    "mogp_mogp_part": (c_int, [c_void_p, c_int, c_int_p, c_int_p, c_int_p]),
     "mogp_mogp_n": (c_int, [c_void_p]),
     "mogp_mogp_D": (c_int, [c_void_p]),
     "mogp_mogp_n_emulators": (c_int, [c_void_p]),

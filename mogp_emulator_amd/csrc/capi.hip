@@ -3,8 +3,13 @@
 // with that message, matching the std::runtime_error -> RuntimeError mapping of pybind11 in the
 // reference (bindings.cu).
 #include <cstring>
+#include <exception>
+#include <functional>
 #include <limits>
+#include <map>
 #include <memory>
+#include <mutex>
+#include <thread>
 
 #include "../../include/mogp_hip.h"
 #include "engine.h"
@@ -15,7 +20,28 @@ static thread_local std::string g_err;
 
 struct mogp_meanfunc { MeanFunc mf; };
 struct mogp_densegp { Engine* eng; int idx; bool owns; };
-struct mogp_mogp { std::unique_ptr<Engine> eng; std::vector<mogp_densegp> views; double nug_size0; int nug_type0; };
+// One part of a MultiOutputGP_GPU: the engine of emulators [lo, hi) on `device`.  A handle created without a device list has one
+// part on the current device; mogp_mogp_create_on_devices splits the emulators into contiguous blocks, one part per non-empty block.
+struct mogp_part { std::unique_ptr<Engine> eng; int device = 0; int lo = 0, hi = 0; };
+struct mogp_mogp {
+  std::vector<mogp_part> parts;
+  Engine* eng = nullptr;                 // part 0's engine: the whole model when there is one part
+  std::vector<mogp_densegp> views;       // emulator i: borrowed view into its part's engine at index i - lo
+  double nug_size0;
+  int nug_type0;
+  bool multi() const { return parts.size() > 1; }
+  ~mogp_mogp() {
+    for (auto& p : parts) {
+      if (!p.eng) continue;
+      try {
+        DeviceGuard g(p.device);
+        p.eng.reset();
+      } catch (...) {
+        p.eng.reset();
+      }
+    }
+  }
+};
 
 #define GUARD(body)                      \
   try {                                  \
@@ -28,6 +54,8 @@ struct mogp_mogp { std::unique_ptr<Engine> eng; std::vector<mogp_densegp> views;
     g_err = "unknown error";             \
     return 1;                            \
   }
+// the same with the work of a DenseGP handle (own or borrowed) on its engine's device
+#define DGUARD(h, body) GUARD({ DeviceGuard dguard_((h)->eng->device_id()); body; })
 
 static void set_priors(Engine* eng, int i, int n_corr, const int* ct, const double* cp, int covt, const double* covp, int nugt,
                        const double* nugp) {
@@ -164,7 +192,7 @@ mogp_densegp* mogp_densegp_create_analytic_mean(const double* inputs, int n, int
   return densegp_create(inputs, n, D, targets, testing_size, mean, kernel_type, nugget_type, nugget_size, true);
 }
 int mogp_densegp_set_mean_priors(mogp_densegp* h, int q, const double* b, const double* Binv, const double* Binv_b, double logdetB) {
-  GUARD(h->eng->set_mean_priors(h->idx, q, b, Binv, Binv_b, logdetB));
+  DGUARD(h, h->eng->set_mean_priors(h->idx, q, b, Binv, Binv_b, logdetB));
 }
 int mogp_densegp_n_beta(const mogp_densegp* h) { return h->eng->q; }
 int mogp_densegp_get_beta(const mogp_densegp* h, double* out) {
@@ -174,7 +202,11 @@ int mogp_densegp_get_beta(const mogp_densegp* h, double* out) {
 }
 void mogp_densegp_destroy(mogp_densegp* h) {
   if (!h || !h->owns) return;
-  delete h->eng;
+  try {
+    DeviceGuard g(h->eng->device_id());
+    delete h->eng;
+  } catch (...) {
+  }
   delete h;
 }
 int mogp_densegp_n(const mogp_densegp* h) { return h->eng->n; }
@@ -208,33 +240,33 @@ int mogp_densegp_get_theta(const mogp_densegp* h, double* data_out, double* mean
 }
 int mogp_densegp_create_gppriors(mogp_densegp* h, int n_corr, const int* ct, const double* cp, int covt, const double* covp, int nugt,
                                  const double* nugp) {
-  GUARD(set_priors(h->eng, h->idx, n_corr, ct, cp, covt, covp, nugt, nugp));
+  DGUARD(h, set_priors(h->eng, h->idx, n_corr, ct, cp, covt, covp, nugt, nugp));
 }
 int mogp_densegp_priors_logp(const mogp_densegp* h, const double* th, int len, double* out) {
-  GUARD({
+  DGUARD(h, {
     if (len != h->eng->n_data(h->idx)) throw std::runtime_error("Shape of new GPParams object does not match existing one");
     std::vector<double> v(th, th + len);
     *out = h->eng->gp[h->idx].pri.logp(v, h->eng->NC, h->eng->gp[h->idx].nug_type);
   });
 }
 int mogp_densegp_priors_dlogpdtheta(const mogp_densegp* h, const double* th, int len, double* out) {
-  GUARD({
+  DGUARD(h, {
     if (len != h->eng->n_data(h->idx)) throw std::runtime_error("Shape of new GPParams object does not match existing one");
     std::vector<double> v(th, th + len);
     h->eng->gp[h->idx].pri.dlogpdtheta(v, h->eng->NC, h->eng->gp[h->idx].nug_type, out);
   });
 }
 int mogp_densegp_priors_sample(mogp_densegp* h, double* out) {
-  GUARD({
+  DGUARD(h, {
     static std::mt19937_64 r(std::random_device{}());
     const int nm = h->eng->n_mean();
     for (int k = 0; k < nm; ++k) out[k] = 0.;
     h->eng->gp[h->idx].pri.sample(r, h->eng->NC, h->eng->gp[h->idx].nug_type, out + nm);
   });
 }
-int mogp_densegp_fit(mogp_densegp* h, const double* theta, int len) { GUARD(h->eng->fit_one(h->idx, theta, len)); }
+int mogp_densegp_fit(mogp_densegp* h, const double* theta, int len) { DGUARD(h, h->eng->fit_one(h->idx, theta, len)); }
 int mogp_densegp_get_logpost(mogp_densegp* h, const double* theta, int len, double* out) {
-  GUARD({
+  DGUARD(h, {
     Engine* e = h->eng;
     const int i = h->idx;
     if (len != e->n_theta(i)) throw std::runtime_error("Shape of new GPParams object does not match existing one");
@@ -252,7 +284,7 @@ int mogp_densegp_get_logpost(mogp_densegp* h, const double* theta, int len, doub
   });
 }
 int mogp_densegp_logpost_deriv(mogp_densegp* h, double* out, int len) {
-  GUARD({
+  DGUARD(h, {
     Engine* e = h->eng;
     if (len < e->n_theta(h->idx)) throw std::runtime_error("logpost_deriv: the result buffer passed was too small");
     if (!e->gp[h->idx].factored) throw std::runtime_error("logpost_deriv: hyperparameters have not been fit");
@@ -267,35 +299,35 @@ static void check_batch(const mogp_densegp* h, int m, int D, int out_len, const 
     throw std::runtime_error("predict_variance_batch: More test points were passed than the maximum batch size");
 }
 int mogp_densegp_predict(mogp_densegp* h, const double* testing, int D, double* mean_out) {
-  GUARD({
+  DGUARD(h, {
     if (D != h->eng->D) throw std::runtime_error("testing point must have D entries");
     std::vector<int> ids{h->idx};
     h->eng->predict(ids, testing, 1, false, mean_out, nullptr, 1, false, nullptr);
   });
 }
 int mogp_densegp_predict_variance(mogp_densegp* h, const double* testing, int D, double* mean_out, double* var_out) {
-  GUARD({
+  DGUARD(h, {
     if (D != h->eng->D) throw std::runtime_error("testing point must have D entries");
     std::vector<int> ids{h->idx};
     h->eng->predict(ids, testing, 1, false, mean_out, var_out, 1, false, nullptr);
   });
 }
 int mogp_densegp_predict_batch(mogp_densegp* h, const double* testing, int m, int D, double* mean_out, int out_len) {
-  GUARD({
+  DGUARD(h, {
     check_batch(h, m, D, out_len, "predict_batch: the result buffer passed was too small to hold the result");
     std::vector<int> ids{h->idx};
     h->eng->predict(ids, testing, m, false, mean_out, nullptr, m, false, nullptr);
   });
 }
 int mogp_densegp_predict_variance_batch(mogp_densegp* h, const double* testing, int m, int D, double* mean_out, double* var_out, int out_len) {
-  GUARD({
+  DGUARD(h, {
     check_batch(h, m, D, out_len, "predict_variance_batch: The result buffer passed was too small to hold the variance");
     std::vector<int> ids{h->idx};
     h->eng->predict(ids, testing, m, false, mean_out, var_out, m, false, nullptr);
   });
 }
 int mogp_densegp_predict_deriv(mogp_densegp* h, const double* testing, int m, int D, double* out, int out_rows, int out_cols) {
-  GUARD({
+  DGUARD(h, {
     if (out_rows < m || out_cols != h->eng->D)
       throw std::runtime_error("predict_deriv: the result buffer passed was the wrong shape to hold the result");
     check_batch(h, m, D, m, "");
@@ -304,7 +336,7 @@ int mogp_densegp_predict_deriv(mogp_densegp* h, const double* testing, int m, in
   });
 }
 int mogp_densegp_predict_full_cov(mogp_densegp* h, const double* testing, int m, int D, double* mean_out, double* cov_out) {
-  GUARD({
+  DGUARD(h, {
     if (D != h->eng->D) throw std::runtime_error("testing points must have D columns");
     std::vector<int> ids{h->idx};
     h->eng->predict_full_cov(ids, testing, m, mean_out, cov_out);
@@ -312,18 +344,18 @@ int mogp_densegp_predict_full_cov(mogp_densegp* h, const double* testing, int m,
 }
 int mogp_densegp_implausibility(mogp_densegp* h, const double* testing, int m, int D, double obs, double obs_var, double discrepancy,
                                 int include_nugget, double* out) {
-  GUARD({
+  DGUARD(h, {
     if (D != h->eng->D) throw std::runtime_error("testing points must have D columns");
     std::vector<int> ids{h->idx};
     h->eng->implausibility(ids, testing, m, &obs, &obs_var, &discrepancy, include_nugget != 0, 0, out);
   });
 }
-int mogp_densegp_loo_variance(mogp_densegp* h, double* out) { GUARD(h->eng->loo_variance(h->idx, out)); }
-int mogp_densegp_get_K(mogp_densegp* h, double* out) { GUARD(h->eng->get_K(h->idx, out)); }
-int mogp_densegp_get_invQ(mogp_densegp* h, double* out) { GUARD(h->eng->get_invQ(h->idx, out)); }
-int mogp_densegp_get_invQt(mogp_densegp* h, double* out) { GUARD(h->eng->get_invQt(h->idx, out)); }
-int mogp_densegp_get_cholesky_lower(mogp_densegp* h, double* out) { GUARD(h->eng->get_chol(h->idx, out)); }
-int mogp_densegp_get_pivot(mogp_densegp* h, int* P_out, int* rank_out) { GUARD(h->eng->get_pivot(h->idx, P_out, rank_out)); }
+int mogp_densegp_loo_variance(mogp_densegp* h, double* out) { DGUARD(h, h->eng->loo_variance(h->idx, out)); }
+int mogp_densegp_get_K(mogp_densegp* h, double* out) { DGUARD(h, h->eng->get_K(h->idx, out)); }
+int mogp_densegp_get_invQ(mogp_densegp* h, double* out) { DGUARD(h, h->eng->get_invQ(h->idx, out)); }
+int mogp_densegp_get_invQt(mogp_densegp* h, double* out) { DGUARD(h, h->eng->get_invQt(h->idx, out)); }
+int mogp_densegp_get_cholesky_lower(mogp_densegp* h, double* out) { DGUARD(h, h->eng->get_chol(h->idx, out)); }
+int mogp_densegp_get_pivot(mogp_densegp* h, int* P_out, int* rank_out) { DGUARD(h, h->eng->get_pivot(h->idx, P_out, rank_out)); }
 int mogp_pivot_cholesky(const double* A, int n, double* L_out, int* P_out, int* rank_out) {
   GUARD(Engine::pivot_cholesky(A, n, L_out, P_out, rank_out));
 }
@@ -342,7 +374,7 @@ int mogp_densegp_set_nugget_size(mogp_densegp* h, double v) {
 }
 int mogp_densegp_get_nugget_type(const mogp_densegp* h) { return h->eng->gp[h->idx].nug_type; }
 int mogp_densegp_set_nugget_type(mogp_densegp* h, int t) {
-  GUARD({
+  DGUARD(h, {
     if (t < 0 || t > 3) throw std::runtime_error("Unrecognized nugget_type");
     GPState& g = h->eng->gp[h->idx];
     if (t != g.nug_type) {
@@ -355,7 +387,7 @@ int mogp_densegp_set_nugget_type(mogp_densegp* h, int t) {
 }
 int mogp_densegp_get_kernel_type(const mogp_densegp* h) { return h->eng->kernel_type; }
 int mogp_fit_single_GP_MAP(mogp_densegp* h, int n_tries, const double* theta0, int theta0_len) {
-  GUARD({
+  DGUARD(h, {
     std::vector<int> ids{h->idx};
     h->eng->fit_map(ids, n_tries, theta0, theta0_len);
   });
@@ -363,46 +395,159 @@ int mogp_fit_single_GP_MAP(mogp_densegp* h, int n_tries, const double* theta0, i
 
 // ---- MultiOutputGP_GPU ---------------------------------------------------------------------------
 static mogp_mogp* mogp_create(const double* inputs, int n, int D, const double* targets, int n_out, unsigned testing_size,
-                              const mogp_meanfunc* mean, int kernel_type, int nugget_type, double nugget_size, bool analytic);
+                              const mogp_meanfunc* mean, int kernel_type, int nugget_type, double nugget_size, bool analytic,
+                              const int* devices, int n_devices);
 mogp_mogp* mogp_mogp_create(const double* inputs, int n, int D, const double* targets, int n_out, unsigned testing_size,
                             const mogp_meanfunc* mean, int kernel_type, int nugget_type, double nugget_size) {
-  return mogp_create(inputs, n, D, targets, n_out, testing_size, mean, kernel_type, nugget_type, nugget_size, false);
+  return mogp_create(inputs, n, D, targets, n_out, testing_size, mean, kernel_type, nugget_type, nugget_size, false, nullptr, 0);
 }
 mogp_mogp* mogp_mogp_create_analytic_mean(const double* inputs, int n, int D, const double* targets, int n_out, unsigned testing_size,
                                           const mogp_meanfunc* mean, int kernel_type, int nugget_type, double nugget_size) {
-  return mogp_create(inputs, n, D, targets, n_out, testing_size, mean, kernel_type, nugget_type, nugget_size, true);
+  return mogp_create(inputs, n, D, targets, n_out, testing_size, mean, kernel_type, nugget_type, nugget_size, true, nullptr, 0);
+}
+mogp_mogp* mogp_mogp_create_on_devices(const double* inputs, int n, int D, const double* targets, int n_out, unsigned testing_size,
+                                       const mogp_meanfunc* mean, int kernel_type, int nugget_type, double nugget_size, int analytic_mean,
+                                       const int* devices, int n_devices) {
+  if (!devices || n_devices < 1) {
+    g_err = "create_on_devices: at least one device is needed";
+    return nullptr;
+  }
+  return mogp_create(inputs, n, D, targets, n_out, testing_size, mean, kernel_type, nugget_type, nugget_size, analytic_mean != 0, devices,
+                     n_devices);
 }
 static mogp_mogp* mogp_create(const double* inputs, int n, int D, const double* targets, int n_out, unsigned testing_size,
-                              const mogp_meanfunc* mean, int kernel_type, int nugget_type, double nugget_size, bool analytic) {
+                              const mogp_meanfunc* mean, int kernel_type, int nugget_type, double nugget_size, bool analytic,
+                              const int* devices, int n_devices) {
   try {
     MeanFunc mf;
     if (mean) mf = mean->mf;
-    auto* h = new mogp_mogp;
-    h->eng.reset(new Engine(inputs, n, D, targets, n_out, testing_size, mf, kernel_type, nugget_type, nugget_size, analytic));
+    std::unique_ptr<mogp_mogp> h(new mogp_mogp);
+    if (!devices) {
+      // no device list: one engine on the current device
+      h->parts.resize(1);
+      mogp_part& p = h->parts[0];
+      p.eng.reset(new Engine(inputs, n, D, targets, n_out, testing_size, mf, kernel_type, nugget_type, nugget_size, analytic));
+      p.device = p.eng->device_id();
+      p.lo = 0;
+      p.hi = n_out;
+    } else {
+      if (n_out < 1) throw std::runtime_error("inputs must have shape (n, D) with n, D >= 1");
+      const int count = mogp_device_count();
+      for (int k = 0; k < n_devices; ++k)
+        if (devices[k] < 0 || devices[k] >= count)
+          throw std::runtime_error("device ordinal " + std::to_string(devices[k]) + " is out of range [0, " + std::to_string(count) + ")");
+      // contiguous blocks of ceil(n_out / n_devices) emulators (dist.shard_bounds); empty blocks are dropped
+      const int per = (n_out + n_devices - 1) / n_devices;
+      for (int k = 0; k < n_devices; ++k) {
+        const int lo = std::min(k * per, n_out), hi = std::min(lo + per, n_out);
+        if (lo >= hi) continue;
+        h->parts.emplace_back();
+        mogp_part& p = h->parts.back();
+        p.device = devices[k];
+        p.lo = lo;
+        p.hi = hi;
+        DeviceGuard g(p.device);
+        p.eng.reset(new Engine(inputs, n, D, targets + (size_t)lo * n, hi - lo, testing_size, mf, kernel_type, nugget_type, nugget_size,
+                               analytic));
+      }
+    }
+    h->eng = h->parts[0].eng.get();
     h->views.resize(n_out);
-    for (int i = 0; i < n_out; ++i) h->views[i] = mogp_densegp{h->eng.get(), i, false};
+    for (auto& p : h->parts)
+      for (int i = p.lo; i < p.hi; ++i) h->views[i] = mogp_densegp{p.eng.get(), i - p.lo, false};
     h->nug_size0 = nugget_size;
     h->nug_type0 = nugget_type;
-    return h;
+    return h.release();
   } catch (const std::exception& e) {
     g_err = e.what();
     return nullptr;
   }
 }
 void mogp_mogp_destroy(mogp_mogp* h) { delete h; }
+int mogp_mogp_n_parts(const mogp_mogp* h) { return (int)h->parts.size(); }
+int mogp_mogp_part(const mogp_mogp* h, int k, int* device, int* lo, int* hi) {
+  if (k < 0 || k >= (int)h->parts.size()) {
+    g_err = "Invalid part index";
+    return 1;
+  }
+  const mogp_part& p = h->parts[k];
+  if (device) *device = p.device;
+  if (lo) *lo = p.lo;
+  if (hi) *hi = p.hi;
+  return 0;
+}
+
+// ---- running the parts of a multi-part handle ------------------------------------------------------
+// One mutex per device: the parts that share a device take it for the whole operation, so that two parts never have kernels in
+// flight on one device at once (the one-launch Cholesky and the back-substitution chain spin-wait on the device and assume
+// they are not co-resident with another such launch).  Never destroyed (threads of other handles may still hold one at exit).
+static std::mutex& device_mutex(int device) {
+  static std::mutex* reg = new std::mutex();
+  static std::map<int, std::unique_ptr<std::mutex>>* mus = new std::map<int, std::unique_ptr<std::mutex>>();
+  std::lock_guard<std::mutex> lk(*reg);
+  std::unique_ptr<std::mutex>& m = (*mus)[device];
+  if (!m) m.reset(new std::mutex());
+  return *m;
+}
+static std::string part_tag(const mogp_part& p) {
+  return " [part on device " + std::to_string(p.device) + ", emulators [" + std::to_string(p.lo) + ", " + std::to_string(p.hi) + ")]";
+}
+// f(part, k) for every part, one host thread per part, each under its device's mutex and a DeviceGuard.  The first failure in part order
+// is rethrown on the calling thread once every part has finished, its message naming the part.
+static void for_parts(mogp_mogp* h, const std::function<void(mogp_part&, int)>& f) {
+  const int np = (int)h->parts.size();
+  std::vector<std::exception_ptr> err(np);
+  std::vector<std::thread> th;
+  th.reserve(np);
+  try {
+    for (int k = 0; k < np; ++k)
+      th.emplace_back([&, k] {
+        mogp_part& p = h->parts[k];
+        try {
+          std::lock_guard<std::mutex> lk(device_mutex(p.device));
+          DeviceGuard g(p.device);
+          f(p, k);
+        } catch (...) {
+          err[k] = std::current_exception();
+        }
+      });
+  } catch (...) {
+    for (auto& t : th) t.join();
+    throw;
+  }
+  for (auto& t : th) t.join();
+  for (int k = 0; k < np; ++k) {
+    if (!err[k]) continue;
+    try {
+      std::rethrow_exception(err[k]);
+    } catch (const std::exception& e) {
+      throw std::runtime_error(std::string(e.what()) + part_tag(h->parts[k]));
+    } catch (...) {
+      throw std::runtime_error("unknown error" + part_tag(h->parts[k]));
+    }
+  }
+}
+// work on the part that holds emulator i, on the calling thread
+static mogp_part& part_of(mogp_mogp* h, int i) {
+  for (auto& p : h->parts)
+    if (i >= p.lo && i < p.hi) return p;
+  throw std::runtime_error("Invalid emulator index");
+}
+
 int mogp_mogp_n(const mogp_mogp* h) { return h->eng->n; }
 int mogp_mogp_D(const mogp_mogp* h) { return h->eng->D; }
-int mogp_mogp_n_emulators(const mogp_mogp* h) { return h->eng->B; }
+int mogp_mogp_n_emulators(const mogp_mogp* h) { return (int)h->views.size(); }
 int mogp_mogp_inputs(const mogp_mogp* h, double* out) {
   std::memcpy(out, h->eng->hX.data(), h->eng->hX.size() * sizeof(double));
   return 0;
 }
 int mogp_mogp_targets(const mogp_mogp* h, double* out) {
-  std::memcpy(out, h->eng->hT.data(), h->eng->hT.size() * sizeof(double));
+  for (const auto& p : h->parts)
+    std::memcpy(out + (size_t)p.lo * h->eng->n, p.eng->hT.data(), p.eng->hT.size() * sizeof(double));
   return 0;
 }
 mogp_densegp* mogp_mogp_emulator(mogp_mogp* h, int index) {
-  if (index < 0 || index >= h->eng->B) {
+  if (index < 0 || index >= (int)h->views.size()) {
     g_err = "Invalid emulator index";
     return nullptr;
   }
@@ -412,74 +557,104 @@ int mogp_mogp_get_nugget_type(const mogp_mogp* h) { return h->nug_type0; }
 double mogp_mogp_get_nugget_size(const mogp_mogp* h) { return h->nug_size0; }
 int mogp_mogp_get_fitted_indices(const mogp_mogp* h, int* out) {
   int c = 0;
-  for (int i = 0; i < h->eng->B; ++i)
-    if (h->eng->gp[i].has_data) out[c++] = i;
+  for (int i = 0; i < (int)h->views.size(); ++i)
+    if (h->views[i].eng->gp[h->views[i].idx].has_data) out[c++] = i;
   return c;
 }
 int mogp_mogp_get_unfitted_indices(const mogp_mogp* h, int* out) {
   int c = 0;
-  for (int i = 0; i < h->eng->B; ++i)
-    if (!h->eng->gp[i].has_data) out[c++] = i;
+  for (int i = 0; i < (int)h->views.size(); ++i)
+    if (!h->views[i].eng->gp[h->views[i].idx].has_data) out[c++] = i;
   return c;
 }
 int mogp_mogp_reset_fit_status(mogp_mogp* h) {
-  for (int i = 0; i < h->eng->B; ++i) mogp_densegp_reset_theta_fit_status(&h->views[i]);
+  for (auto& v : h->views) mogp_densegp_reset_theta_fit_status(&v);
   return 0;
 }
 int mogp_mogp_create_priors_for_emulator(mogp_mogp* h, int index, int n_corr, const int* ct, const double* cp, int covt, const double* covp,
                                          int nugt, const double* nugp) {
   GUARD({
-    if (index < 0 || index >= h->eng->B) throw std::runtime_error("Invalid emulator index for setting priors");
-    set_priors(h->eng.get(), index, n_corr, ct, cp, covt, covp, nugt, nugp);
+    if (index < 0 || index >= (int)h->views.size()) throw std::runtime_error("Invalid emulator index for setting priors");
+    set_priors(h->views[index].eng, h->views[index].idx, n_corr, ct, cp, covt, covp, nugt, nugp);
   });
 }
 int mogp_mogp_eval(mogp_mogp* h, const double* thetas, int n_rows, int n_cols, double* logpost_out, double* grad_out, int* ok_out) {
   GUARD({
-    Engine* e = h->eng.get();
-    if (n_rows != e->B) throw std::runtime_error("thetas must have one row per emulator");
-    std::vector<int> ids(e->B);
-    std::vector<const double*> th(e->B);
-    for (int i = 0; i < e->B; ++i) {
-      if (n_cols != e->n_theta(i)) throw std::runtime_error("Shape of new GPParams object does not match existing one");
-      ids[i] = i;
-      th[i] = thetas + (size_t)i * n_cols;
+    if (!h->multi()) {
+      Engine* e = h->eng;
+      DeviceGuard g(e->device_id());
+      if (n_rows != e->B) throw std::runtime_error("thetas must have one row per emulator");
+      std::vector<int> ids(e->B);
+      std::vector<const double*> th(e->B);
+      for (int i = 0; i < e->B; ++i) {
+        if (n_cols != e->n_theta(i)) throw std::runtime_error("Shape of new GPParams object does not match existing one");
+        ids[i] = i;
+        th[i] = thetas + (size_t)i * n_cols;
+      }
+      std::vector<double> f(e->B);
+      std::vector<int> ok(e->B);
+      e->eval(ids, th, grad_out != nullptr, f.data(), grad_out, n_cols, ok.data());
+      if (logpost_out) std::memcpy(logpost_out, f.data(), sizeof(double) * e->B);
+      if (ok_out) std::memcpy(ok_out, ok.data(), sizeof(int) * e->B);
+      return 0;
     }
-    std::vector<double> f(e->B);
-    std::vector<int> ok(e->B);
-    e->eval(ids, th, grad_out != nullptr, f.data(), grad_out, n_cols, ok.data());
-    if (logpost_out) std::memcpy(logpost_out, f.data(), sizeof(double) * e->B);
-    if (ok_out) std::memcpy(ok_out, ok.data(), sizeof(int) * e->B);
+    if (n_rows != (int)h->views.size()) throw std::runtime_error("thetas must have one row per emulator");
+    for (const auto& v : h->views)
+      if (n_cols != v.eng->n_theta(v.idx)) throw std::runtime_error("Shape of new GPParams object does not match existing one");
+    for_parts(h, [&](mogp_part& p, int) {
+      const int nb = p.hi - p.lo;
+      std::vector<int> ids(nb);
+      std::vector<const double*> th(nb);
+      for (int i = 0; i < nb; ++i) {
+        ids[i] = i;
+        th[i] = thetas + (size_t)(p.lo + i) * n_cols;
+      }
+      std::vector<double> f(nb);
+      std::vector<int> ok(nb);
+      p.eng->eval(ids, th, grad_out != nullptr, f.data(), grad_out ? grad_out + (size_t)p.lo * n_cols : nullptr, n_cols, ok.data());
+      if (logpost_out) std::memcpy(logpost_out + p.lo, f.data(), sizeof(double) * nb);
+      if (ok_out) std::memcpy(ok_out + p.lo, ok.data(), sizeof(int) * nb);
+    });
   });
 }
 int mogp_mogp_fit(mogp_mogp* h, const double* thetas, int n_rows, int n_cols) {
   GUARD({
-    Engine* e = h->eng.get();
-    std::vector<int> ok(e->B);
+    const int B = (int)h->views.size();
+    std::vector<int> ok(B);
     if (mogp_mogp_eval(h, thetas, n_rows, n_cols, nullptr, nullptr, ok.data())) throw std::runtime_error(g_err);
-    for (int i = 0; i < e->B; ++i)
-      if (!ok[i] && !(e->gp[i].nug_type == NUG_PIVOT && e->gp[i].factored)) {
-        if (e->gp[i].nug_type == NUG_ADAPTIVE) throw std::runtime_error("All attempts at factorization failed. Last return code 1");
+    for (int i = 0; i < B; ++i) {
+      const GPState& g = h->views[i].eng->gp[h->views[i].idx];
+      if (!ok[i] && !(g.nug_type == NUG_PIVOT && g.factored)) {
+        if (g.nug_type == NUG_ADAPTIVE) throw std::runtime_error("All attempts at factorization failed. Last return code 1");
         throw std::runtime_error("Unable to factorize matrix using selected nugget type");
       }
+    }
   });
 }
 int mogp_mogp_fit_emulator(mogp_mogp* h, int index, const double* theta, int len) {
   GUARD({
-    if (index < 0 || index >= h->eng->B) throw std::runtime_error("Invalid emulator index");
-    h->eng->fit_one(index, theta, len);
+    if (index < 0 || index >= (int)h->views.size()) throw std::runtime_error("Invalid emulator index");
+    if (!h->multi()) {
+      DeviceGuard g(h->eng->device_id());
+      h->eng->fit_one(index, theta, len);
+      return 0;
+    }
+    mogp_part& p = part_of(h, index);
+    std::lock_guard<std::mutex> lk(device_mutex(p.device));
+    DeviceGuard g(p.device);
+    p.eng->fit_one(index - p.lo, theta, len);
   });
 }
-static std::vector<int> fitted_ids(const mogp_mogp* h) {
+static std::vector<int> fitted_ids(const Engine* e) {
   std::vector<int> ids;
-  for (int i = 0; i < h->eng->B; ++i)
-    if (h->eng->gp[i].has_data && h->eng->gp[i].factored) ids.push_back(i);
+  for (int i = 0; i < e->B; ++i)
+    if (e->gp[i].has_data && e->gp[i].factored) ids.push_back(i);
   return ids;
 }
 // results of fitted emulators go to their own rows; rows of unfitted emulators are untouched
-static void mogp_predict_common(mogp_mogp* h, const double* testing, int m, int D, double* means, double* vars, double* derivs) {
-  Engine* e = h->eng.get();
+static void engine_predict_common(Engine* e, const double* testing, int m, int D, double* means, double* vars, double* derivs) {
   if (D != e->D) throw std::runtime_error("testing points must have D columns");
-  std::vector<int> ids = fitted_ids(h);
+  std::vector<int> ids = fitted_ids(e);
   if (ids.empty()) return;
   const size_t nf = ids.size();
   if ((int)nf == e->B) {             // every emulator fitted: results go straight into the caller's arrays (means == null: derivatives only)
@@ -494,6 +669,20 @@ static void mogp_predict_common(mogp_mogp* h, const double* testing, int m, int 
     if (derivs) std::memcpy(derivs + (size_t)ids[k] * m * D, dd.data() + k * m * D, (size_t)m * D * sizeof(double));
   }
 }
+// each part writes its own rows of the caller's (n_emulators, ...) arrays
+static void mogp_predict_common(mogp_mogp* h, const double* testing, int m, int D, double* means, double* vars, double* derivs) {
+  if (!h->multi()) {
+    DeviceGuard g(h->eng->device_id());
+    engine_predict_common(h->eng, testing, m, D, means, vars, derivs);
+    return;
+  }
+  if (D != h->eng->D) throw std::runtime_error("testing points must have D columns");
+  for_parts(h, [&](mogp_part& p, int) {
+    const size_t lo = p.lo;
+    engine_predict_common(p.eng.get(), testing, m, D, means ? means + lo * m : nullptr, vars ? vars + lo * m : nullptr,
+                          derivs ? derivs + lo * m * D : nullptr);
+  });
+}
 int mogp_mogp_predict_batch(mogp_mogp* h, const double* testing, int m, int D, double* means) {
   GUARD(mogp_predict_common(h, testing, m, D, means, nullptr, nullptr));
 }
@@ -503,49 +692,107 @@ int mogp_mogp_predict_variance_batch(mogp_mogp* h, const double* testing, int m,
 int mogp_mogp_predict_deriv(mogp_mogp* h, const double* testing, int m, int D, double* derivs) {
   GUARD(mogp_predict_common(h, testing, m, D, nullptr, nullptr, derivs));
 }
+static void engine_predict_full_cov(Engine* e, const double* testing, int m, int D, double* means, double* covs) {
+  if (D != e->D) throw std::runtime_error("testing points must have D columns");
+  std::vector<int> ids = fitted_ids(e);
+  if (ids.empty()) return;
+  if ((int)ids.size() == e->B) {
+    e->predict_full_cov(ids, testing, m, means, covs);
+  } else {
+    const size_t nf = ids.size();
+    const size_t mm = (size_t)m * m;
+    std::vector<double> mu(nf * m);
+    std::vector<double> cc(nf * mm);
+    e->predict_full_cov(ids, testing, m, mu.data(), cc.data());
+    for (size_t k = 0; k < nf; ++k) {
+      std::memcpy(means + (size_t)ids[k] * m, mu.data() + k * m, m * sizeof(double));
+      std::memcpy(covs + (size_t)ids[k] * mm, cc.data() + k * mm, mm * sizeof(double));
+    }
+  }
+}
 int mogp_mogp_predict_full_cov(mogp_mogp* h, const double* testing, int m, int D, double* means, double* covs) {
   GUARD({
-    Engine* e = h->eng.get();
-    if (D != e->D) throw std::runtime_error("testing points must have D columns");
-    std::vector<int> ids = fitted_ids(h);
-    if (ids.empty()) return 0;
-    if ((int)ids.size() == e->B) {
-      e->predict_full_cov(ids, testing, m, means, covs);
-    } else {
-      const size_t nf = ids.size();
-      const size_t mm = (size_t)m * m;
-      std::vector<double> mu(nf * m);
-      std::vector<double> cc(nf * mm);
-      e->predict_full_cov(ids, testing, m, mu.data(), cc.data());
-      for (size_t k = 0; k < nf; ++k) {
-        std::memcpy(means + (size_t)ids[k] * m, mu.data() + k * m, m * sizeof(double));
-        std::memcpy(covs + (size_t)ids[k] * mm, cc.data() + k * mm, mm * sizeof(double));
-      }
+    if (!h->multi()) {
+      DeviceGuard g(h->eng->device_id());
+      engine_predict_full_cov(h->eng, testing, m, D, means, covs);
+      return 0;
     }
+    if (D != h->eng->D) throw std::runtime_error("testing points must have D columns");
+    for_parts(h, [&](mogp_part& p, int) {
+      const size_t lo = p.lo;
+      engine_predict_full_cov(p.eng.get(), testing, m, D, means + lo * m, covs + lo * (size_t)m * m);
+    });
   });
+}
+// Several parts: every part writes the (rank+1) largest implausibilities of its own emulators per query point into one block of a
+// device buffer on part 0's device (implausibility_top); implausibility_merge_kernel reduces them there.  The query points go in outer
+// chunks of at most 2^18, so that the lists of one chunk stay small next to the engines' own scratch.
+static void mogp_implausibility_parts(mogp_mogp* h, const double* testing, int m, const double* obs, const double* obs_var,
+                                      const double* discrepancy, bool include_nugget, int rank, double* out) {
+  const int B = (int)h->views.size();
+  if (B == 1) rank = 0;                                       // HistoryMatching.py:254-255
+  if (rank < 0) throw std::runtime_error("rank must be a non-negative integer");
+  if (rank >= B) throw std::runtime_error("rank must be less than the number of observations");
+  if (rank > IMPLAUS_MAX_RANK) throw std::runtime_error("rank above " + std::to_string(IMPLAUS_MAX_RANK) + " is not supported on the device");
+  if (m <= 0) return;
+  const int np = (int)h->parts.size(), keep = rank + 1, dev0 = h->parts[0].device;
+  const long OC = std::min<long>(m, 1L << 18);
+  double *dLists = nullptr, *dOut = nullptr;
+  auto release = [&] {
+    DeviceGuard g(dev0);
+    if (dLists) hipFree(dLists);
+    if (dOut) hipFree(dOut);
+  };
+  try {
+    {
+      DeviceGuard g(dev0);
+      hip_check(hipMalloc(reinterpret_cast<void**>(&dLists), (size_t)np * keep * OC * sizeof(double)), "hipMalloc");
+      hip_check(hipMalloc(reinterpret_cast<void**>(&dOut), (size_t)OC * sizeof(double)), "hipMalloc");
+    }
+    for (long c0 = 0; c0 < m; c0 += OC) {
+      const int mc = (int)std::min<long>(OC, m - c0);
+      for_parts(h, [&](mogp_part& p, int k) {
+        std::vector<int> ids(p.hi - p.lo);
+        for (int i = 0; i < (int)ids.size(); ++i) ids[i] = i;
+        p.eng->implausibility_top(ids, testing + (size_t)c0 * h->eng->D, mc, obs + p.lo, obs_var + p.lo, discrepancy + p.lo, include_nugget,
+                                  keep, dLists + (size_t)k * keep * OC, OC, dev0);
+      });
+      mogp_part& p0 = h->parts[0];
+      std::lock_guard<std::mutex> lk(device_mutex(dev0));
+      DeviceGuard g(dev0);
+      launch_implausibility_merge(np, dLists, OC, mc, rank, dOut, p0.eng->stream);
+      hip_check(hipMemcpyAsync(out + c0, dOut, (size_t)mc * sizeof(double), hipMemcpyDeviceToHost, p0.eng->stream), "hipMemcpyAsync");
+      hip_check(hipStreamSynchronize(p0.eng->stream), "hipStreamSynchronize");
+    }
+    hip_check(hipGetLastError(), "implausibility_merge_kernel");
+  } catch (...) {
+    release();
+    throw;
+  }
+  release();
 }
 int mogp_mogp_implausibility(mogp_mogp* h, const double* testing, int m, int D, const double* obs, const double* obs_var,
                              const double* discrepancy, int include_nugget, int rank, double* out) {
   GUARD({
-    Engine* e = h->eng.get();
-    if (D != e->D) throw std::runtime_error("testing points must have D columns");
-    std::vector<int> ids = fitted_ids(h);
-    if ((int)ids.size() != e->B) throw std::runtime_error("Hyperparameters have not been fit for this Gaussian Process");
-    e->implausibility(ids, testing, m, obs, obs_var, discrepancy, include_nugget != 0, rank, out);
+    if (D != h->eng->D) throw std::runtime_error("testing points must have D columns");
+    for (const auto& v : h->views)
+      if (!(v.eng->gp[v.idx].has_data && v.eng->gp[v.idx].factored))
+        throw std::runtime_error("Hyperparameters have not been fit for this Gaussian Process");
+    if (!h->multi()) {
+      Engine* e = h->eng;
+      DeviceGuard g(e->device_id());
+      std::vector<int> ids = fitted_ids(e);
+      e->implausibility(ids, testing, m, obs, obs_var, discrepancy, include_nugget != 0, rank, out);
+      return 0;
+    }
+    mogp_implausibility_parts(h, testing, m, obs, obs_var, discrepancy, include_nugget != 0, rank, out);
   });
 }
 // device-resident prediction: d_means / d_vars (n_emulators, m) and d_derivs (n_emulators, m, D) are device buffers (d_vars, d_derivs may be
 // null); rows of emulators that are not fit are filled with NaN (MultiOutputGP_GPU.py:288-296)
 #define HIPCK(x) hip_check((x), #x)
-static void mogp_predict_dev_common(mogp_mogp* h, const double* d_testing, int m, int D, double* d_means, double* d_vars, double* d_derivs) {
-  Engine* e = h->eng.get();
-  if (D != e->D) throw std::runtime_error("testing points must have D columns");
-  if (m <= 0) return;
-  // the same contract whatever the fit status is (ADVICE r5): the test points are required, any of the three outputs may be null
-  // (Engine::predict: means == nullptr = derivatives only), but not all of them
-  if (!d_testing) throw std::runtime_error("device-resident predict: the test points pointer is null");
-  if (!d_means && !d_vars && !d_derivs) throw std::runtime_error("device-resident predict: no output buffer given");
-  std::vector<int> ids = fitted_ids(h);
+static void engine_predict_dev(Engine* e, const double* d_testing, int m, int D, double* d_means, double* d_vars, double* d_derivs) {
+  std::vector<int> ids = fitted_ids(e);
   if ((int)ids.size() == e->B) {
     e->predict(ids, d_testing, m, true, d_means, d_vars, m, true, d_derivs);
     return;
@@ -593,6 +840,62 @@ static void mogp_predict_dev_common(mogp_mogp* h, const double* d_testing, int m
   }
   release();
 }
+// Several parts: a part on the device of the caller's buffers predicts straight into its rows; a part on another device copies the test points
+// to its own device, predicts into scratch there and copies its rows back with peer copies on its stream.
+static void mogp_predict_dev_parts(mogp_mogp* h, const double* d_testing, int m, int D, double* d_means, double* d_vars, double* d_derivs) {
+  int caller = -1;
+  hipPointerAttribute_t attr;
+  if (hipPointerGetAttributes(&attr, d_testing) == hipSuccess && attr.device >= 0) caller = attr.device;
+  else HIPCK(hipGetDevice(&caller));
+  for_parts(h, [&](mogp_part& p, int) {
+    Engine* e = p.eng.get();
+    const size_t rows = p.hi - p.lo, lo = p.lo, row = (size_t)m, drow = (size_t)m * D;
+    double* om = d_means ? d_means + lo * row : nullptr;
+    double* ov = d_vars ? d_vars + lo * row : nullptr;
+    double* od = d_derivs ? d_derivs + lo * drow : nullptr;
+    if (p.device == caller) {
+      engine_predict_dev(e, d_testing, m, D, om, ov, od);
+      return;
+    }
+    double *xs = nullptr, *tm = nullptr, *tv = nullptr, *td = nullptr;
+    hipStream_t st = e->stream;
+    auto release = [&] {
+      for (double* q : {xs, tm, tv, td})
+        if (q) hipFree(q);
+    };
+    try {
+      HIPCK(hipMalloc((void**)&xs, drow * sizeof(double)));
+      if (om) HIPCK(hipMalloc((void**)&tm, rows * row * sizeof(double)));
+      if (ov) HIPCK(hipMalloc((void**)&tv, rows * row * sizeof(double)));
+      if (od) HIPCK(hipMalloc((void**)&td, rows * drow * sizeof(double)));
+      HIPCK(hipMemcpyPeerAsync(xs, p.device, d_testing, caller, drow * sizeof(double), st));
+      engine_predict_dev(e, xs, m, D, tm, tv, td);
+      if (om) HIPCK(hipMemcpyPeerAsync(om, caller, tm, p.device, rows * row * sizeof(double), st));
+      if (ov) HIPCK(hipMemcpyPeerAsync(ov, caller, tv, p.device, rows * row * sizeof(double), st));
+      if (od) HIPCK(hipMemcpyPeerAsync(od, caller, td, p.device, rows * drow * sizeof(double), st));
+      HIPCK(hipStreamSynchronize(st));
+    } catch (...) {
+      hipStreamSynchronize(st);
+      release();
+      throw;
+    }
+    release();
+  });
+}
+static void mogp_predict_dev_common(mogp_mogp* h, const double* d_testing, int m, int D, double* d_means, double* d_vars, double* d_derivs) {
+  if (D != h->eng->D) throw std::runtime_error("testing points must have D columns");
+  if (m <= 0) return;
+  // the same contract whatever the fit status is (ADVICE r5): the test points are required, any of the three outputs may be null
+  // (Engine::predict: means == nullptr = derivatives only), but not all of them
+  if (!d_testing) throw std::runtime_error("device-resident predict: the test points pointer is null");
+  if (!d_means && !d_vars && !d_derivs) throw std::runtime_error("device-resident predict: no output buffer given");
+  if (!h->multi()) {
+    DeviceGuard g(h->eng->device_id());
+    engine_predict_dev(h->eng, d_testing, m, D, d_means, d_vars, d_derivs);
+    return;
+  }
+  mogp_predict_dev_parts(h, d_testing, m, D, d_means, d_vars, d_derivs);
+}
 #undef HIPCK
 int mogp_mogp_predict_variance_batch_dev(mogp_mogp* h, const double* d_testing, int m, int D, double* d_means, double* d_vars) {
   GUARD(mogp_predict_dev_common(h, d_testing, m, D, d_means, d_vars, nullptr));
@@ -600,11 +903,35 @@ int mogp_mogp_predict_variance_batch_dev(mogp_mogp* h, const double* d_testing, 
 int mogp_mogp_predict_dev(mogp_mogp* h, const double* d_testing, int m, int D, double* d_means, double* d_vars, double* d_derivs) {
   GUARD(mogp_predict_dev_common(h, d_testing, m, D, d_means, d_vars, d_derivs));
 }
+using EmuRef = std::pair<const Engine*, int>;      // (a comma inside GUARD's argument would split it)
 int mogp_fit_GP_MAP(mogp_mogp* h, int n_tries, const double* theta0, int theta0_len) {
   GUARD({
-    std::vector<int> ids(h->eng->B);
-    for (int i = 0; i < h->eng->B; ++i) ids[i] = i;
-    h->eng->fit_map(ids, n_tries, theta0, theta0_len);
+    if (!h->multi()) {
+      DeviceGuard g(h->eng->device_id());
+      std::vector<int> ids(h->eng->B);
+      for (int i = 0; i < h->eng->B; ++i) ids[i] = i;
+      h->eng->fit_map(ids, n_tries, theta0, theta0_len);
+      return 0;
+    }
+    // every starting point is drawn here, in the order of the unsharded model (start-major), from part 0's rng -- seeded as a single
+    // engine's is -- with each emulator's own priors; each part then runs its block.  The end point of a run does not depend on the
+    // batch it ran in (Engine::run_pool), so the result is the single-engine one whatever the split.
+    if (n_tries < 1) throw std::runtime_error("number of attempts must be positive");
+    std::vector<EmuRef> emus;
+    for (const auto& v : h->views) {
+      if (theta0_len > 0 && theta0_len != v.eng->n_theta(v.idx)) throw std::runtime_error("length of theta0 must equal n_params of GP.");
+      emus.emplace_back(v.eng, v.idx);
+    }
+    const Engine::Starts x0 = Engine::draw_starts(h->eng->random(), emus, n_tries, theta0, theta0_len);
+    for_parts(h, [&](mogp_part& p, int) {
+      const int nb = p.hi - p.lo;
+      std::vector<int> ids(nb);
+      for (int i = 0; i < nb; ++i) ids[i] = i;
+      Engine::Starts sub(n_tries, std::vector<std::vector<double>>(nb));
+      for (int s = 0; s < n_tries; ++s)
+        for (int i = 0; i < nb; ++i) sub[s][i] = x0[s][p.lo + i];
+      p.eng->fit_map_from(ids, sub);
+    });
   });
 }
 int mogp_set_fit_options(int max_iter, double ftol, double gtol, unsigned long long seed) {

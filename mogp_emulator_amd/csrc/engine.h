@@ -16,6 +16,24 @@
 
 namespace mogp {
 
+void hip_check(hipError_t e, const char* what);
+
+// Makes `device` the calling thread's current HIP device and gives the caller's back when it goes out of scope.  HIP's current
+// device belongs to each host thread, so every entry that touches an engine runs under one for the engine's device.
+struct DeviceGuard {
+  int prev = -1;
+  explicit DeviceGuard(int device) {
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    if (prev != device) hip_check(hipSetDevice(device), "hipSetDevice");
+  }
+  ~DeviceGuard() {
+    int cur = -1;
+    if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
+  }
+  DeviceGuard(const DeviceGuard&) = delete;
+  DeviceGuard& operator=(const DeviceGuard&) = delete;
+};
+
 struct GPState {
   std::vector<double> data;      // n_data: corr_raw (NC), log sigma^2, [log nugget]
   std::vector<double> meanp;     // n_mean
@@ -89,6 +107,10 @@ class Engine {
   // obs / obs_var / discrepancy per entry of ids; out (m) host.  Query points are processed in device chunks.
   void implausibility(const std::vector<int>& ids, const double* Xs, int m, const double* obs, const double* obs_var,
                       const double* discrepancy, bool include_nugget, int rank, double* out);
+  // the same for one part of a multi-part model: per query point the `keep` largest implausibilities of emulators `ids`, list r at
+  // out[r * out_ld + j] in device memory of device `out_device` (-inf where there are fewer); no rank checks (the caller's)
+  void implausibility_top(const std::vector<int>& ids, const double* Xs, int m, const double* obs, const double* obs_var,
+                          const double* discrepancy, bool include_nugget, int keep, double* out, long out_ld, int out_device);
   // leave-one-out predictive variance of emulator i at its own training inputs (MICEFastGP.fast_predict for every index)
   void loo_variance(int i, double* out);
   // predict(full_cov=True), GaussianProcess.py:899-911: means (nb, m), covs (nb, m, m) host buffers, nugget NOT included
@@ -103,6 +125,15 @@ class Engine {
 
   // multi-start MAP fit of emulators `ids` (fitting.hpp:61-128): all (emulator, start) runs through one slot pool
   void fit_map(const std::vector<int>& ids, int n_tries, const double* theta0, int theta0_len);
+  // starting points x0[s][e] of a multi-start fit of emulators `emus` (engine, index): start 0 = theta0 if given, every other one
+  // drawn from the emulator's priors with `rng`, in (start, emulator) order -- what fit_map draws from the engine's own rng
+  using Starts = std::vector<std::vector<std::vector<double>>>;
+  static Starts draw_starts(std::mt19937_64& rng, const std::vector<std::pair<const Engine*, int>>& emus, int n_tries, const double* theta0,
+                            int theta0_len);
+  // fit_map from given starting points x0[s][e] of emulator ids[e] (n_tries = x0.size())
+  void fit_map_from(const std::vector<int>& ids, const Starts& x0);
+  std::mt19937_64& random() { return rng; }
+  int device_id() const { return device; }
   // the optimiser runs as a slot pool on emulators `slots` of this engine: next(pos, x0, tag) hands slot `pos` its next run (false: none
   // left), done(tag, f, x) receives a run's end point (f = +inf, x empty: failed)
   void run_pool(const std::vector<int>& slots, const std::function<bool(int, std::vector<double>&, int&)>& next,
@@ -146,6 +177,10 @@ class Engine {
   const std::function<void(const BatchView&)>* prebuilt = nullptr;   // factor_prebuilt: build_cov runs this instead
   std::vector<char> z_armed;     // per emulator: its solution row holds the sentinel pattern of the one-launch back substitution
   void set_theta(int i, const double* theta);
+  // implausibility / implausibility_top: validation, then per chunk of query points the means and variances in dMean / dVar (nb, MC);
+  // tail(dPrm, c0, mc, MC) consumes them (the stream is synchronised after it: the next chunk reuses the buffers)
+  void implausibility_chunks(const std::vector<int>& ids, const double* Xs, int m, const double* obs, const double* obs_var,
+                             const double* discrepancy, bool include_nugget, const std::function<void(const double*, int, int, int)>& tail);
   void ensure_predict_scratch(int nb, int MC);
 
   double *dX = nullptr, *dP = nullptr, *dT = nullptr, *dA = nullptr, *dLinv = nullptr, *dKinv = nullptr, *dAlpha = nullptr;
@@ -210,7 +245,6 @@ struct ScheduleOverride {
 };
 ScheduleOverride& schedule_override();
 
-void hip_check(hipError_t e, const char* what);
 void prof_enable(bool on);
 void prof_reset();
 bool prof_get(const char* tag, double* ms, long long* launches, double* flops, double* bytes);

@@ -1335,18 +1335,10 @@ void Engine::predict_full_cov(const std::vector<int>& ids, const double* Xs, int
   for (double* p : {dXf, dKf, dV, dC, dDots}) if (p) hipFree(p);
 }
 
-void Engine::implausibility(const std::vector<int>& ids, const double* Xs, int m, const double* obs, const double* obs_var,
-                            const double* discrepancy, bool include_nugget, int rank, double* out) {
+void Engine::implausibility_chunks(const std::vector<int>& ids, const double* Xs, int m, const double* obs, const double* obs_var,
+                                   const double* discrepancy, bool include_nugget,
+                                   const std::function<void(const double*, int, int, int)>& tail) {
   const int nb = (int)ids.size();
-  if (nb == 0 || m == 0) return;
-  for (int i : ids)
-    if (!gp[i].factored) throw std::runtime_error("emulator has not been fit");
-  if (R > 1 || n_mean() > 0)
-    throw std::runtime_error("implausibility: the fused device path supports zero / fixed mean functions only");
-  if (nb == 1) rank = 0;                                       // HistoryMatching.py:254-255
-  if (rank < 0) throw std::runtime_error("rank must be a non-negative integer");
-  if (rank >= nb) throw std::runtime_error("rank must be less than the number of observations");
-  if (rank > IMPLAUS_MAX_RANK) throw std::runtime_error("rank above " + std::to_string(IMPLAUS_MAX_RANK) + " is not supported on the device");
   std::vector<double> prm((size_t)nb * 3);
   for (int k = 0; k < nb; ++k) {
     if (discrepancy[k] < 0.) throw std::runtime_error("Model discrepancy variance cannot be negative");
@@ -1366,7 +1358,6 @@ void Engine::implausibility(const std::vector<int>& ids, const double* Xs, int m
   grow(dMean, capMean, (size_t)nb * MC);
   grow(dVar, capVar, (size_t)nb * MC);
   double* dPrm = dalloc<double>(prm.size());
-  double* dOut = dalloc<double>((size_t)MC);
   try {
     HIPCK(hipMemcpyAsync(dPrm, prm.data(), prm.size() * sizeof(double), hipMemcpyHostToDevice, stream));
     for (int c0 = 0; c0 < m; c0 += (int)MC) {
@@ -1375,18 +1366,76 @@ void Engine::implausibility(const std::vector<int>& ids, const double* Xs, int m
       HIPCK(hipMemcpyAsync(dXs, Xs + (size_t)c0 * D, (size_t)mc * D * sizeof(double), hipMemcpyHostToDevice, stream));
       launch_cross_cov_mean(v, dXs, mc, MPc, dKs, dMean, (int)MC, stream);
       launch_predict_var(v, dKs, mc, MPc, dVarPartial, dVar, (int)MC, n_cu, stream);
-      launch_implausibility(nb, dMean, dVar, (int)MC, mc, dPrm, rank, dOut, stream);
-      HIPCK(hipMemcpyAsync(out + c0, dOut, (size_t)mc * sizeof(double), hipMemcpyDeviceToHost, stream));
+      tail(dPrm, c0, mc, (int)MC);
       HIPCK(hipStreamSynchronize(stream));      // dXs is re-used by the next chunk
     }
     HIPCK(hipGetLastError());
   } catch (...) {
+    hipStreamSynchronize(stream);
     hipFree(dPrm);
-    hipFree(dOut);
     throw;
   }
   hipFree(dPrm);
+}
+
+void Engine::implausibility(const std::vector<int>& ids, const double* Xs, int m, const double* obs, const double* obs_var,
+                            const double* discrepancy, bool include_nugget, int rank, double* out) {
+  const int nb = (int)ids.size();
+  if (nb == 0 || m == 0) return;
+  for (int i : ids)
+    if (!gp[i].factored) throw std::runtime_error("emulator has not been fit");
+  if (R > 1 || n_mean() > 0)
+    throw std::runtime_error("implausibility: the fused device path supports zero / fixed mean functions only");
+  if (nb == 1) rank = 0;                                       // HistoryMatching.py:254-255
+  if (rank < 0) throw std::runtime_error("rank must be a non-negative integer");
+  if (rank >= nb) throw std::runtime_error("rank must be less than the number of observations");
+  if (rank > IMPLAUS_MAX_RANK) throw std::runtime_error("rank above " + std::to_string(IMPLAUS_MAX_RANK) + " is not supported on the device");
+  const int MPtot = roundup(m, 128);
+  long MC = (long)(6.0e9 / ((double)nb * LD * 8.0)) / 128 * 128;
+  MC = std::max<long>(128, std::min<long>(MC, MPtot));
+  double* dOut = dalloc<double>((size_t)MC);
+  try {
+    implausibility_chunks(ids, Xs, m, obs, obs_var, discrepancy, include_nugget, [&](const double* dPrm, int c0, int mc, int ld) {
+      launch_implausibility(nb, dMean, dVar, ld, mc, dPrm, rank, dOut, stream);
+      HIPCK(hipMemcpyAsync(out + c0, dOut, (size_t)mc * sizeof(double), hipMemcpyDeviceToHost, stream));
+    });
+  } catch (...) {
+    hipFree(dOut);
+    throw;
+  }
   hipFree(dOut);
+}
+
+void Engine::implausibility_top(const std::vector<int>& ids, const double* Xs, int m, const double* obs, const double* obs_var,
+                                const double* discrepancy, bool include_nugget, int keep, double* out, long out_ld, int out_device) {
+  const int nb = (int)ids.size();
+  if (nb == 0 || m == 0) return;
+  for (int i : ids)
+    if (!gp[i].factored) throw std::runtime_error("emulator has not been fit");
+  if (R > 1 || n_mean() > 0)
+    throw std::runtime_error("implausibility: the fused device path supports zero / fixed mean functions only");
+  if (keep < 1 || keep > IMPLAUS_MAX_RANK + 1) throw std::runtime_error("implausibility: bad number of largest values to keep");
+  // the lists go straight into `out` when it lives on this engine's device, else through a scratch block and a peer copy
+  const bool local = out_device == device;
+  const int MPtot = roundup(m, 128);
+  long MC = (long)(6.0e9 / ((double)nb * LD * 8.0)) / 128 * 128;
+  MC = std::max<long>(128, std::min<long>(MC, MPtot));
+  double* dTop = local ? nullptr : dalloc<double>((size_t)keep * MC);
+  try {
+    implausibility_chunks(ids, Xs, m, obs, obs_var, discrepancy, include_nugget, [&](const double* dPrm, int c0, int mc, int ld) {
+      if (local) {
+        launch_implausibility_top(nb, dMean, dVar, ld, mc, dPrm, keep, out + c0, out_ld, stream);
+        return;
+      }
+      launch_implausibility_top(nb, dMean, dVar, ld, mc, dPrm, keep, dTop, MC, stream);
+      for (int r = 0; r < keep; ++r)
+        HIPCK(hipMemcpyPeerAsync(out + (size_t)r * out_ld + c0, out_device, dTop + (size_t)r * MC, device, (size_t)mc * sizeof(double), stream));
+    });
+  } catch (...) {
+    if (dTop) hipFree(dTop);
+    throw;
+  }
+  if (dTop) hipFree(dTop);
 }
 
 void Engine::loo_variance(int i, double* out) {
@@ -1564,10 +1613,11 @@ struct Lbfgs {
 };
 }  // namespace
 
-// the process-wide replica engine kept between multi-start fits (never destroyed at exit: the HIP runtime may be gone by then)
-static std::unique_ptr<Engine>& replica_cache() {
-  static std::unique_ptr<Engine>* p = new std::unique_ptr<Engine>();
-  return *p;
+// the replica engine kept between multi-start fits, one per device (never destroyed at exit: the HIP runtime may be gone by then);
+// the slots of different devices are independent, so the parts of a multi-part model on different GPUs do not evict each other's
+static std::unique_ptr<Engine>& replica_cache(int device) {
+  static std::map<int, std::unique_ptr<Engine>>* p = new std::map<int, std::unique_ptr<Engine>>();
+  return (*p)[device];
 }
 static std::mutex& replica_cache_mutex() {
   static std::mutex* m = new std::mutex();
@@ -1826,22 +1876,40 @@ void Engine::reset_inputs(const std::vector<double>& X) {
 // problems, whose batches do not fill the GPU, then cost about one start instead of n_tries, and large ones keep every batched
 // evaluation full until the queue of runs drains.  MOGP_PARALLEL_STARTS=0: no replica engine -- the slots are this engine's own
 // emulators, each working through its own starts one after the other (still without waiting for its neighbours).
-void Engine::fit_map(const std::vector<int>& ids_in, int n_tries, const double* theta0, int theta0_len) {
-  std::vector<int> ids(ids_in);
+Engine::Starts Engine::draw_starts(std::mt19937_64& rng, const std::vector<std::pair<const Engine*, int>>& emus, int n_tries,
+                                   const double* theta0, int theta0_len) {
+  const int ne = (int)emus.size();
+  // starting points: start 0 = theta0 if given, everything else drawn from the priors (Priors.py:394-418)
+  Starts x0(n_tries, std::vector<std::vector<double>>(ne));
+  for (int s = 0; s < n_tries; ++s)
+    for (int e = 0; e < ne; ++e) {
+      const Engine& g = *emus[e].first;
+      const int i = emus[e].second;
+      std::vector<double>& x = x0[s][e];
+      x.assign(g.n_theta(i), 0.);
+      if (s == 0 && theta0_len > 0) x.assign(theta0, theta0 + theta0_len);
+      else g.gp[i].pri.sample(rng, g.NC, g.gp[i].nug_type, x.data() + g.n_mean());
+    }
+  return x0;
+}
+
+void Engine::fit_map(const std::vector<int>& ids, int n_tries, const double* theta0, int theta0_len) {
   if (ids.empty()) return;
   if (n_tries < 1) throw std::runtime_error("number of attempts must be positive");
   for (int i : ids)
     if (theta0_len > 0 && theta0_len != n_theta(i)) throw std::runtime_error("length of theta0 must equal n_params of GP.");
+  std::vector<std::pair<const Engine*, int>> emus;
+  for (int i : ids) emus.emplace_back(this, i);
+  fit_map_from(ids, draw_starts(rng, emus, n_tries, theta0, theta0_len));
+}
+
+void Engine::fit_map_from(const std::vector<int>& ids, const Starts& x0) {
+  if (ids.empty()) return;
+  const int n_tries = (int)x0.size();
+  if (n_tries < 1) throw std::runtime_error("number of attempts must be positive");
   const int ne = (int)ids.size();
-  // starting points: start 0 = theta0 if given, everything else drawn from the priors (Priors.py:394-418)
-  std::vector<std::vector<std::vector<double>>> x0(n_tries, std::vector<std::vector<double>>(ne));
-  for (int s = 0; s < n_tries; ++s)
-    for (int e = 0; e < ne; ++e) {
-      std::vector<double>& x = x0[s][e];
-      x.assign(n_theta(ids[e]), 0.);
-      if (s == 0 && theta0_len > 0) x.assign(theta0, theta0 + theta0_len);
-      else gp[ids[e]].pri.sample(rng, NC, gp[ids[e]].nug_type, x.data() + n_mean());
-    }
+  for (const auto& row : x0)
+    if ((int)row.size() != ne) throw std::runtime_error("fit_map: one starting point per emulator and start is needed");
   std::vector<double> best_f(ne, std::numeric_limits<double>::infinity());
   std::vector<int> best_s(ne, -1);
   std::vector<std::vector<double>> best_x(ne);
@@ -1902,9 +1970,9 @@ void Engine::fit_map(const std::vector<int>& ids_in, int n_tries, const double* 
     std::unique_ptr<Engine> rep;
     {
       std::lock_guard<std::mutex> lk(replica_cache_mutex());
-      std::unique_ptr<Engine>& slot = replica_cache();
       int dev = -1;
       (void)hipGetDevice(&dev);
+      std::unique_ptr<Engine>& slot = replica_cache(dev);
       if (slot && cache_on && slot->n == n && slot->D == D && slot->B == (int)slots_n && slot->kernel_type == kernel_type && slot->analytic == analytic &&
           slot->testing_size == testing_size && slot->device == dev && slot->mean.kind == mean.kind && slot->mean.value == mean.value &&
           slot->mean.dims == mean.dims && slot->mean.powers == mean.powers) {
@@ -1923,8 +1991,9 @@ void Engine::fit_map(const std::vector<int>& ids_in, int n_tries, const double* 
       bool on;
       ~Keep() {
         if (!on || !rep || std::uncaught_exceptions() > 0) return;
+        const int dev = rep->device;
         std::lock_guard<std::mutex> lk(replica_cache_mutex());
-        replica_cache() = std::move(rep);
+        replica_cache(dev) = std::move(rep);
       }
     } keep{rep, cache_on};
     g_rep_build_us += std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - tc0).count();

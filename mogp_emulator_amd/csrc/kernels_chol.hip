@@ -533,6 +533,63 @@ __global__ __launch_bounds__(256) void implausibility_kernel(int nb, const doubl
   out[j] = res;
 }
 
+// The same score over emulators spread across several engines (one per part of a multi-part model): each part writes, per
+// query point, its own `keep` (= rank+1) largest implausibilities in descending order, list r at out[r * out_ld + j] (-inf where
+// the part has fewer emulators); implausibility_merge_kernel reduces the lists of all parts.  The insertion is the one of
+// implausibility_kernel, so the (rank+1)-th largest over the union is the value the single-engine kernel returns.
+__global__ __launch_bounds__(256) void implausibility_top_kernel(int nb, const double* __restrict__ mean, const double* __restrict__ var, int ld,
+                                                                 int m, const double* __restrict__ prm, int keep, double* __restrict__ out,
+                                                                 long out_ld) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= m) return;
+  double top[IMPL_MAXRANK];
+#pragma unroll
+  for (int r = 0; r < IMPL_MAXRANK; ++r) top[r] = -INFINITY;
+  for (int k = 0; k < nb; ++k) {
+    const double mu = mean[(size_t)k * ld + j] + prm[3 * k + 2];
+    const double vv = fmax(var[(size_t)k * ld + j], 0.0) + prm[3 * k + 1];
+    double I = fabs(prm[3 * k] - mu) / sqrt(vv);
+#pragma unroll
+    for (int r = 0; r < IMPL_MAXRANK; ++r)
+      if (r < keep && I > top[r]) {
+        const double t = top[r];
+        top[r] = I;
+        I = t;
+      }
+  }
+#pragma unroll
+  for (int r = 0; r < IMPL_MAXRANK; ++r)
+    if (r < keep) out[(size_t)r * out_ld + j] = top[r];
+}
+
+// lists (nparts * (rank+1), ld): list r of part p at row p * (rank+1) + r.  The running list starts at -1 like
+// implausibility_kernel's, so a padding entry (-inf) or a NaN never enters it and ties resolve to the same value.
+__global__ __launch_bounds__(256) void implausibility_merge_kernel(int nparts, const double* __restrict__ lists, long ld, int m, int rank,
+                                                                  double* __restrict__ out) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= m) return;
+  double top[IMPL_MAXRANK];
+#pragma unroll
+  for (int r = 0; r < IMPL_MAXRANK; ++r) top[r] = -1.0;
+  const int keep = rank + 1;
+  for (int p = 0; p < nparts; ++p)
+    for (int q = 0; q < keep; ++q) {
+      double I = lists[((size_t)p * keep + q) * ld + j];
+#pragma unroll
+      for (int r = 0; r < IMPL_MAXRANK; ++r)
+        if (r <= rank && I > top[r]) {
+          const double t = top[r];
+          top[r] = I;
+          I = t;
+        }
+    }
+  double res = top[0];
+#pragma unroll
+  for (int r = 1; r < IMPL_MAXRANK; ++r)
+    if (r == rank) res = top[r];
+  out[j] = res;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Mean-function terms of a batched prediction, on the device (densegp_gpu.hpp:334-337, 402-405, 443-447; analytic mean:
 // GaussianProcess.py:906-935), so that predictions of models with a mean function can stay in HBM (the sharded predict gathers
@@ -720,6 +777,15 @@ void launch_loo_variance(const BatchView& v, double* out, int out_ld, hipStream_
 void launch_implausibility(int nb, const double* mean, const double* var, int ld, int m, const double* prm, int rank, double* out,
                            hipStream_t s) {
   hipLaunchKernelGGL(implausibility_kernel, dim3((m + 255) / 256), dim3(256), 0, s, nb, mean, var, ld, m, prm, rank, out);
+}
+
+void launch_implausibility_top(int nb, const double* mean, const double* var, int ld, int m, const double* prm, int keep, double* out,
+                               long out_ld, hipStream_t s) {
+  hipLaunchKernelGGL(implausibility_top_kernel, dim3((m + 255) / 256), dim3(256), 0, s, nb, mean, var, ld, m, prm, keep, out, out_ld);
+}
+
+void launch_implausibility_merge(int nparts, const double* lists, long ld, int m, int rank, double* out, hipStream_t s) {
+  hipLaunchKernelGGL(implausibility_merge_kernel, dim3((m + 255) / 256), dim3(256), 0, s, nparts, lists, ld, m, rank, out);
 }
 
 // basis (1 + nterm, m) and dbasis (nterm, m) of a polynomial mean function at device-resident test points (round 6, ADVICE r5: the host used to

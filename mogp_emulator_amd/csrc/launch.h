@@ -82,6 +82,11 @@ void launch_loo_variance(const BatchView& v, double* out, int out_ld, hipStream_
 constexpr int IMPLAUS_MAX_RANK = 15;
 void launch_implausibility(int nb, const double* mean, const double* var, int ld, int m, const double* prm, int rank, double* out,
                            hipStream_t s);
+// the same over the emulators of one part of a multi-part model: out[r * out_ld + j] = the (r+1)-th largest of its own, r < keep
+// (-inf where it has fewer); merge: lists (nparts * (rank+1), ld) of every part -> out[j] = (rank+1)-th largest overall
+void launch_implausibility_top(int nb, const double* mean, const double* var, int ld, int m, const double* prm, int keep, double* out,
+                               long out_ld, hipStream_t s);
+void launch_implausibility_merge(int nparts, const double* lists, long ld, int m, int rank, double* out, hipStream_t s);
 // out (nb, m, m) = sigma^2 k(Xs, Xs) per slot (no nugget)
 void launch_cov_self_batch(const BatchView& v, const double* Xs, int m, double* out, hipStream_t s);
 // full predictive covariance: cov (nb, m, m) holds K** on entry, K** - Ks K^-1 Ks^T on return; V: nb*NP*MP scratch

@@ -9,7 +9,7 @@ from . import LibGPGPU
 from .GaussianProcessGPU import GaussianProcessGPU
 from .MultiOutputGP_GPU import MultiOutputGP_GPU
 
-_GP_KWARGS = ("mean", "kernel", "priors", "nugget", "inputdict", "use_patsy")
+_GP_KWARGS = ("mean", "kernel", "priors", "nugget", "inputdict", "use_patsy", "devices")
 
 
 def _check_common(n_tries, method):

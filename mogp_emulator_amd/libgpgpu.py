@@ -821,7 +821,9 @@ class DenseGP_GPU(object):
 # --------------------------------------------------------------------------------------
 class MultiOutputGP_GPU(object):
     def __init__(self, inputs, targets, testing_size, meanfunc=None, kern=kernel_type.SquaredExponential,
-                 nugtype=nugget_type.adaptive, nugsize=0., analytic_mean=False):
+                 nugtype=nugget_type.adaptive, nugsize=0., analytic_mean=False, devices=None):
+        """devices: None -- one engine on the current device; a list of ordinals -- the emulators split into contiguous blocks,
+        one engine per non-empty block on devices[k] (mogp_mogp_create_on_devices; a device may be repeated)"""
         X = _f64(inputs, 2, "inputs")
         T = np.ascontiguousarray(np.array([np.asarray(t, dtype=np.float64) for t in targets]))
         if T.ndim != 2 or T.shape[1] != X.shape[0]:
@@ -829,9 +831,15 @@ class MultiOutputGP_GPU(object):
         if meanfunc is None:
             meanfunc = ZeroMeanFunc()
         self._meanfunc = meanfunc
-        create = _lib.mogp_mogp_create_analytic_mean if analytic_mean else _lib.mogp_mogp_create
-        self._h = create(dptr(X), X.shape[0], X.shape[1], dptr(T), T.shape[0], int(testing_size), meanfunc._h,
-                         int(kernel_type(kern)), int(nugget_type(nugtype)), float(nugsize))
+        if devices is None:
+            create = _lib.mogp_mogp_create_analytic_mean if analytic_mean else _lib.mogp_mogp_create
+            self._h = create(dptr(X), X.shape[0], X.shape[1], dptr(T), T.shape[0], int(testing_size), meanfunc._h,
+                             int(kernel_type(kern)), int(nugget_type(nugtype)), float(nugsize))
+        else:
+            dev = np.ascontiguousarray(np.asarray(list(devices), dtype=np.int32).reshape(-1))
+            self._h = _lib.mogp_mogp_create_on_devices(dptr(X), X.shape[0], X.shape[1], dptr(T), T.shape[0], int(testing_size),
+                                                       meanfunc._h, int(kernel_type(kern)), int(nugget_type(nugtype)), float(nugsize),
+                                                       int(bool(analytic_mean)), iptr(dev), int(dev.size))
         if not self._h:
             raise RuntimeError(_capi.last_error())
 
@@ -848,6 +856,18 @@ class MultiOutputGP_GPU(object):
 
     def n_emulators(self):
         return int(_lib.mogp_mogp_n_emulators(self._h))
+
+    def n_parts(self):
+        return int(_lib.mogp_mogp_n_parts(self._h))
+
+    def parts(self):
+        """[(device, lo, hi)] of every part: the engine on `device` holds emulators [lo, hi)"""
+        out = []
+        for k in range(self.n_parts()):
+            d, lo, hi = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+            check(_lib.mogp_mogp_part(self._h, k, ctypes.byref(d), ctypes.byref(lo), ctypes.byref(hi)))
+            out.append((d.value, lo.value, hi.value))
+        return out
 
     def inputs(self):
         out = np.zeros((self.n(), self.D()))
