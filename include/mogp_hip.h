@@ -261,6 +261,13 @@ int mogp_profile_counter(const char* name, long long* out);
    device memory; R does not depend on it, bit for bit. */
 int mogp_gkdr_R(const double* X, int n, int m, const double* y, int nx, const double* sgx2, int ny, const double* sgy2, double eps,
                 int max_pairs_per_pass, double* R_out, int* info_out);
+/* Maximin design scoring (mogp_emulator/ExperimentalDesign.py:663-668): designs (T, n, D) row-major, T >= 1 designs of n >= 2 points in
+   1 <= D <= 80 dimensions; out (T): out[t] = min over i < j of the Euclidean distance of points i and j of design t (the squared
+   differences summed in ascending d without fused multiply-add; one square root, of the minimum).  The designs pass through the device
+   64 MiB at a time, so T is not bounded by device memory; the result does not depend on the split.  n <= 370688.  The designs must be
+   finite and their squared distances must not overflow: a NaN coordinate is NOT reported (the minimum skips it), and out[t] is
+   +infinity when every squared distance of design t overflows.  (The Python shim rejects non-finite designs before the call.) */
+int mogp_design_min_pdist(const double* designs, int T, int n, int D, double* out);
 /* device memory helpers so a host program can hand device-resident buffers to the *_dev calls */
 void* mogp_dev_malloc(unsigned long long bytes);
 int mogp_dev_free(void* d_ptr);

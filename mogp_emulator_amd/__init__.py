@@ -7,13 +7,16 @@ mogp_emulator_amd -- MI355X (gfx950) native fit + predict backend for mogp_emula
   LibGPGPU.py, GaussianProcessGPU.py, MultiOutputGP_GPU.py, fitting.py, Priors.py, Kernel.py
                    host-side mirrors of the reference's GPU-facing Python interface
   HistoryMatching.py, SequentialDesign.py, validation.py
-                   consumers of the batched prediction (implausibility, MICE scoring, validation errors)
+                   consumers of the batched prediction (implausibility, MICE scoring and the sequential-design drivers, validation errors)
+  ExperimentalDesign.py
+                   one-shot designs (Monte Carlo, Latin hypercube on the host; maximin LHC scored on the device)
   DimensionReduction.py
                    gKDR dimension reduction; R of a whole (X_scale, Y_scale) grid in one device call
   dist.py          one-process-per-GPU sharding of emulators + single gather (torch.distributed/RCCL)
 """
 from .LibGPGPU import HAVE_LIBGPGPU, gpu_usable            # noqa: F401
 from .DimensionReduction import gKDR                        # noqa: F401
+from .ExperimentalDesign import ExperimentalDesign, MonteCarloDesign, LatinHypercubeDesign, MaxiMinLHC   # noqa: F401
 
 if HAVE_LIBGPGPU:
     from .GaussianProcessGPU import GaussianProcessGPU, PredictResult   # noqa: F401
@@ -22,7 +25,7 @@ if HAVE_LIBGPGPU:
     from .Kernel import SquaredExponential, Matern52, ProductMat52, UniformSqExp, UniformMat52   # noqa: F401
     from .Priors import GPPriors, MeanPriors, InvGammaPrior, GammaPrior, LogNormalPrior, WeakPrior   # noqa: F401
     from .HistoryMatching import HistoryMatching                           # noqa: F401
-    from .SequentialDesign import MICEFastGP, mice_criterion               # noqa: F401
+    from .SequentialDesign import MICEFastGP, mice_criterion, SequentialDesign, MICEDesign   # noqa: F401
     from . import validation                                                # noqa: F401
 
 __version__ = "0.1.0"

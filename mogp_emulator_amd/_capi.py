@@ -131,6 +131,7 @@ SIGNATURES = {
     "mogp_kernel_eval": (c_int, [c_int, c_int, c_double_p, c_int, c_double_p, c_int, c_int, c_double_p, c_int, c_double_p]),
     "mogp_gkdr_R": (c_int, [c_double_p, c_int, c_int, c_double_p, c_int, c_double_p, c_int, c_double_p, c_double, c_int, c_double_p,
                             c_int_p]),
+    "mogp_design_min_pdist": (c_int, [c_double_p, c_int, c_int, c_int, c_double_p]),
     "mogp_profile_enable": (c_int, [c_int]),
     "mogp_profile_reset": (c_int, []),
     "mogp_profile_schedule": (c_int, [c_int, c_int]),

@@ -957,6 +957,10 @@ int mogp_gkdr_R(const double* X, int n, int m, const double* y, int nx, const do
   GUARD(gkdr_R(X, n, m, y, nx, sgx2, ny, sgy2, eps, max_pairs_per_pass, R_out, info_out));
 }
 
+int mogp_design_min_pdist(const double* designs, int T, int n, int D, double* out) {
+  GUARD(design_min_pdist(designs, T, n, D, out));
+}
+
 // ---- measurement hooks ----------------------------------------------------------------------------
 int mogp_profile_enable(int on) { prof_enable(on != 0); return 0; }
 int mogp_profile_reset(void) { prof_reset(); return 0; }

@@ -235,6 +235,13 @@ FitOptions& fit_options();
 void gkdr_R(const double* X, int n, int m, const double* y, int nx, const double* sgx2, int ny, const double* sgy2, double eps,
             int max_pairs_per_pass, double* R_out, int* info_out);
 
+// Maximin design scoring (kernels_design.hip): out[t] = the smallest pairwise Euclidean distance of design t of `designs` (T, n, D), host
+// pointers.  The designs pass through the device DESIGN_SCRATCH_BYTES at a time (one design where a single one is larger), so T is unbounded.
+constexpr size_t DESIGN_SCRATCH_BYTES = (size_t)64 << 20;
+constexpr int DESIGN_MAX_PASS = 32768;      // designs per pass (the second grid dimension)
+constexpr int DESIGN_MAX_N = 370688;        // points per design: 64 x 64 tiles of the lower triangle x 256 threads < 2^32 work-items
+void design_min_pdist(const double* designs, int T, int n, int D, double* out);
+
 // measurement hooks (mogp_profile_schedule): force the Cholesky schedule / serialise it onto one stream so that the
 // HIP-event time of a kernel is its time alone on the device; -1 / false = the library's own choice.
 // FOR MEASUREMENT ONLY: process-global, read by every engine at the start of a factorisation and not synchronised --

@@ -26,7 +26,7 @@ __all__ = [
     "WeakPrior", "InvGammaPrior", "GammaPrior", "LogNormalPrior",
     "BaseTransform", "CovTransform", "CorrTransform",
     "SquaredExponentialKernel", "Matern52Kernel", "MeanPriors", "set_fit_options", "set_device", "device_count", "pivot_cholesky",
-    "gkdr_R",
+    "gkdr_R", "design_min_pdist",
 ]
 
 
@@ -1053,6 +1053,26 @@ def gkdr_R(X, y, sgx2, sgy2, eps, max_pairs_per_pass=0):
     check(_lib.mogp_gkdr_R(dptr(X), n, m, dptr(y), sx.size, dptr(sx), sy.size, dptr(sy), float(eps), int(max_pairs_per_pass),
                            dptr(R), iptr(info)))
     return R, info
+
+
+def design_min_pdist(designs):
+    """Smallest pairwise Euclidean distance of every design of ``designs`` (T, n, D) -- ``pdist(d).min()`` of
+    ExperimentalDesign.py:665 for all tries of a maximin search in one device call; returns an array (T,).  A single design (n, D)
+    counts as T = 1.  n = 1 has no pair: ValueError, as ``np.min`` of the empty ``pdist`` raises."""
+    designs = _f64(designs)
+    if designs.ndim == 2:
+        designs = designs[None]
+    if designs.ndim != 3:
+        raise TypeError("designs must be a (T, n, D) float64 array")
+    T, n, D = designs.shape
+    if n < 2:
+        raise ValueError("zero-size array to reduction operation minimum which has no identity")
+    if not np.all(np.isfinite(designs)):
+        raise ValueError("designs must be finite")
+    out = np.empty(T)
+    if T:
+        check(_lib.mogp_design_min_pdist(dptr(designs), T, n, D, dptr(out)))
+    return out
 
 
 # --------------------------------------------------------------------------------------
