@@ -131,6 +131,17 @@ int mogp_densegp_predict_full_cov(mogp_densegp*, const double* testing, int m, i
 int mogp_densegp_implausibility(mogp_densegp*, const double* testing, int m, int D, double obs, double obs_var, double discrepancy,
                                 int include_nugget, double* out /* m */);
 int mogp_densegp_loo_variance(mogp_densegp*, double* out /* n */);
+/* Variance-based sensitivity analysis of the predictive mean f (mean function included), fused behind the batched prediction: A, B are
+ * two independent host (N, D) sample matrices of the input distribution, AB_i is A with column i of B (built on the device, a chunk
+ * at a time).  With f0 = mean(fA | fB): variance_out = mean((fA | fB - f0)^2), mean_out = f0,
+ *   S[i]  = mean((fB - f0)(fAB_i - fA)) / variance       first order (Saltelli 2010)
+ *   ST[i] = mean((fA - fAB_i)^2) / (2 variance)           total effect (Jansen)
+ * and, with unc != 0, emulator_variance_out = the mean over A and B of the predictive variance as predict() reports it (nugget added
+ * when include_nugget != 0, clipped at zero); it may be NULL otherwise.  A constant emulator (variance 0) gives NaN indices.
+ * Refused: N < 2, samples that are not finite, a D that is not the model's, an emulator that is not fit, and an N whose means do not
+ * fit half of the free device memory.  The same inputs give the same bits in every call. */
+int mogp_densegp_sobol(mogp_densegp*, const double* A, const double* B, int N, int D, int unc, int include_nugget, double* S /* D */,
+                       double* ST /* D */, double* mean_out, double* variance_out, double* emulator_variance_out);
 int mogp_densegp_get_K(mogp_densegp*, double* out /* n*n */);
 int mogp_densegp_get_invQ(mogp_densegp*, double* out /* n*n */);
 int mogp_densegp_get_invQt(mogp_densegp*, double* out /* n */);
@@ -201,6 +212,10 @@ int mogp_mogp_predict_deriv(mogp_mogp*, const double* testing, int m, int D, dou
 int mogp_mogp_implausibility(mogp_mogp*, const double* testing, int m, int D, const double* obs, const double* obs_var,
                              const double* discrepancy, int include_nugget, int rank, double* out /* m */);
 int mogp_mogp_predict_full_cov(mogp_mogp*, const double* testing, int m, int D, double* means, double* covs);
+/* mogp_densegp_sobol for every emulator in one batched pass per part: S, ST (n_out, D), mean_out, variance_out and
+ * emulator_variance_out (n_out).  Rows of emulators that are not fit are filled with NaN. */
+int mogp_mogp_sobol(mogp_mogp*, const double* A, const double* B, int N, int D, int unc, int include_nugget, double* S, double* ST,
+                    double* mean_out, double* variance_out, double* emulator_variance_out);
 /* predict_variance_batch (multioutputgp_gpu.hpp:182-192) with DEVICE pointers: inputs already resident in HBM, results stay in HBM
  * (every mean function; rows of emulators that are not fit are filled with NaN, MultiOutputGP_GPU.py:288-296) */
 int mogp_mogp_predict_variance_batch_dev(mogp_mogp*, const double* d_testing, int m, int D, double* d_means, double* d_vars);

@@ -8,6 +8,8 @@ mogp_emulator_amd -- MI355X (gfx950) native fit + predict backend for mogp_emula
                    host-side mirrors of the reference's GPU-facing Python interface
   HistoryMatching.py, SequentialDesign.py, validation.py
                    consumers of the batched prediction (implausibility, MICE scoring and the sequential-design drivers, validation errors)
+  SensitivityAnalysis.py
+                   first-order and total-effect Sobol indices of the predictive mean, fused behind the batched prediction
   ExperimentalDesign.py
                    one-shot designs (Monte Carlo, Latin hypercube on the host; maximin LHC scored on the device)
   DimensionReduction.py
@@ -26,6 +28,7 @@ if HAVE_LIBGPGPU:
     from .Priors import GPPriors, MeanPriors, InvGammaPrior, GammaPrior, LogNormalPrior, WeakPrior   # noqa: F401
     from .HistoryMatching import HistoryMatching                           # noqa: F401
     from .SequentialDesign import MICEFastGP, mice_criterion, SequentialDesign, MICEDesign   # noqa: F401
+    from .SensitivityAnalysis import sobol_indices, SobolResult          # noqa: F401
     from . import validation                                                # noqa: F401
 
 __version__ = "0.1.0"

@@ -350,6 +350,16 @@ int mogp_densegp_implausibility(mogp_densegp* h, const double* testing, int m, i
     h->eng->implausibility(ids, testing, m, &obs, &obs_var, &discrepancy, include_nugget != 0, 0, out);
   });
 }
+int mogp_densegp_sobol(mogp_densegp* h, const double* A, const double* B, int N, int D, int unc, int include_nugget, double* S, double* ST,
+                       double* mean_out, double* variance_out, double* emulator_variance_out) {
+  DGUARD(h, {
+    if (D != h->eng->D) throw std::runtime_error("sobol: the sample matrices must have D columns");
+    if (!S || !ST || !mean_out || !variance_out) throw std::runtime_error("sobol: null result buffer");
+    if (unc && !emulator_variance_out) throw std::runtime_error("sobol: unc needs a buffer for the emulator variance");
+    std::vector<int> ids{h->idx};
+    h->eng->sobol(ids, A, B, N, unc != 0, include_nugget != 0, S, ST, mean_out, variance_out, unc ? emulator_variance_out : nullptr);
+  });
+}
 int mogp_densegp_loo_variance(mogp_densegp* h, double* out) { DGUARD(h, h->eng->loo_variance(h->idx, out)); }
 int mogp_densegp_get_K(mogp_densegp* h, double* out) { DGUARD(h, h->eng->get_K(h->idx, out)); }
 int mogp_densegp_get_invQ(mogp_densegp* h, double* out) { DGUARD(h, h->eng->get_invQ(h->idx, out)); }
@@ -786,6 +796,53 @@ int mogp_mogp_implausibility(mogp_mogp* h, const double* testing, int m, int D, 
       return 0;
     }
     mogp_implausibility_parts(h, testing, m, obs, obs_var, discrepancy, include_nugget != 0, rank, out);
+  });
+}
+// the fitted emulators of one engine into their own rows of the caller's arrays; rows of unfitted emulators become NaN
+static void engine_sobol(Engine* e, const double* A, const double* B, int N, bool unc, bool include_nugget, double* S, double* ST,
+                         double* mean_out, double* variance_out, double* emvar_out) {
+  const int D = e->D;
+  std::vector<int> ids = fitted_ids(e);
+  const size_t nf = ids.size();
+  if ((int)nf == e->B) {
+    e->sobol(ids, A, B, N, unc, include_nugget, S, ST, mean_out, variance_out, emvar_out);
+    return;
+  }
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  for (int i = 0; i < e->B; ++i) {
+    for (int d = 0; d < D; ++d) S[(size_t)i * D + d] = ST[(size_t)i * D + d] = nan;
+    mean_out[i] = variance_out[i] = nan;
+    if (emvar_out) emvar_out[i] = nan;
+  }
+  if (nf == 0) return;
+  std::vector<double> s(nf * D), st(nf * D), mu(nf), va(nf), ev(nf);
+  e->sobol(ids, A, B, N, unc, include_nugget, s.data(), st.data(), mu.data(), va.data(), emvar_out ? ev.data() : nullptr);
+  for (size_t k = 0; k < nf; ++k) {
+    std::memcpy(S + (size_t)ids[k] * D, s.data() + k * D, D * sizeof(double));
+    std::memcpy(ST + (size_t)ids[k] * D, st.data() + k * D, D * sizeof(double));
+    mean_out[ids[k]] = mu[k];
+    variance_out[ids[k]] = va[k];
+    if (emvar_out) emvar_out[ids[k]] = ev[k];
+  }
+}
+// Emulators are independent: every part runs its own block on its own engine and writes its own rows (no cross-device reduction)
+int mogp_mogp_sobol(mogp_mogp* h, const double* A, const double* B, int N, int D, int unc, int include_nugget, double* S, double* ST,
+                    double* mean_out, double* variance_out, double* emulator_variance_out) {
+  GUARD({
+    if (D != h->eng->D) throw std::runtime_error("sobol: the sample matrices must have D columns");
+    if (!S || !ST || !mean_out || !variance_out) throw std::runtime_error("sobol: null result buffer");
+    if (unc && !emulator_variance_out) throw std::runtime_error("sobol: unc needs a buffer for the emulator variance");
+    double* ev = unc ? emulator_variance_out : nullptr;
+    if (!h->multi()) {
+      DeviceGuard g(h->eng->device_id());
+      engine_sobol(h->eng, A, B, N, unc != 0, include_nugget != 0, S, ST, mean_out, variance_out, ev);
+      return 0;
+    }
+    for_parts(h, [&](mogp_part& p, int) {
+      const size_t lo = p.lo;
+      engine_sobol(p.eng.get(), A, B, N, unc != 0, include_nugget != 0, S + lo * D, ST + lo * D, mean_out + lo, variance_out + lo,
+                   ev ? ev + lo : nullptr);
+    });
   });
 }
 // device-resident prediction: d_means / d_vars (n_emulators, m) and d_derivs (n_emulators, m, D) are device buffers (d_vars, d_derivs may be

@@ -111,6 +111,11 @@ class Engine {
   // out[r * out_ld + j] in device memory of device `out_device` (-inf where there are fewer); no rank checks (the caller's)
   void implausibility_top(const std::vector<int>& ids, const double* Xs, int m, const double* obs, const double* obs_var,
                           const double* discrepancy, bool include_nugget, int keep, double* out, long out_ld, int out_device);
+  // Sobol sensitivity indices of the predictive means of emulators `ids` (kernels_sobol.hip): A, B host (N, D) sample matrices;
+  // S, ST (ids.size(), D), mean / variance (ids.size()) and -- with unc -- emulator_variance (ids.size(), the mean predictive variance
+  // over A and B, as predict() reports it) are host buffers.  AB_i exists only as one chunk in device memory.
+  void sobol(const std::vector<int>& ids, const double* A, const double* B, long N, bool unc, bool include_nugget, double* S, double* ST,
+             double* mean_out, double* var_out, double* emvar_out);
   // leave-one-out predictive variance of emulator i at its own training inputs (MICEFastGP.fast_predict for every index)
   void loo_variance(int i, double* out);
   // predict(full_cov=True), GaussianProcess.py:899-911: means (nb, m), covs (nb, m, m) host buffers, nugget NOT included

@@ -1146,6 +1146,12 @@ void Engine::grad_current(const std::vector<int>& ids, double* grad, int grad_ld
   }
 }
 
+// bytes one chunk of a prediction may take (12 GB: one cross-covariance chunk for 64 x n=2000 x m=10^4)
+static double ks_budget_bytes() {
+  static const double budget = [] { const char* e = getenv("MOGP_KS_BUDGET_GB"); return (e ? atof(e) : 12.0) * 1e9; }();
+  return budget;
+}
+
 void Engine::ensure_predict_scratch(int nb, int MC) {
   grow(dKs, capKs, (size_t)nb * MC * LD);
   // partial sums per row tile
@@ -1198,7 +1204,7 @@ void Engine::predict(const std::vector<int>& ids, const double* Xs, int m, bool 
     dots_ld = m;
   }
   const int MPtot = roundup(m, 128);
-  static const double budget = [] { const char* e = getenv("MOGP_KS_BUDGET_GB"); return (e ? atof(e) : 12.0) * 1e9; }();  // cross-covariance chunk (12 GB: one chunk for 64 x n=2000 x m=10^4)
+  const double budget = ks_budget_bytes();
   // never more than half of what the device has free right now (several engines / ranks per GPU, smaller devices);
   // what is already allocated for the chunk counts as free
   double cap = budget;
@@ -1436,6 +1442,103 @@ void Engine::implausibility_top(const std::vector<int>& ids, const double* Xs, i
     throw;
   }
   if (dTop) hipFree(dTop);
+}
+
+// First-order and total-effect Sobol indices of the predictive means (kernels_sobol.hip has the estimators).  Pass 1 predicts A and B
+// (one resident (2N, D) block) through predict()'s device-to-device path and keeps the means; pass 2 goes over the inputs and chunks of
+// base rows: pick-freeze into dPick, the same mean path, the two sums into per-workgroup slots.  Only SOBOL_STATS + 2 D numbers per
+// emulator come back.  Everything runs on the main stream; predict() synchronises it at the end of every call.
+void Engine::sobol(const std::vector<int>& ids, const double* A, const double* Bs, long N, bool unc, bool include_nugget, double* S,
+                   double* ST, double* mean_out, double* var_out, double* emvar_out) {
+  const int nb = (int)ids.size();
+  if (nb == 0) return;
+  if (!A || !Bs) throw std::runtime_error("sobol: null sample matrix");
+  if (N < 2) throw std::runtime_error("sobol: at least two base samples are needed (N = " + std::to_string(N) + ")");
+  if (N > (1L << 28)) throw std::runtime_error("sobol: at most 2^28 base samples are supported");
+  for (int i : ids)
+    if (!gp[i].factored) throw std::runtime_error("emulator has not been fit");
+  for (size_t e = 0; e < (size_t)N * D; ++e)
+    if (!std::isfinite(A[e]) || !std::isfinite(Bs[e])) throw std::runtime_error("sobol: the sample matrices must be finite");
+  const long M2 = 2 * N;
+  // resident for the whole call: the samples, fA | fB (and their variances); refused beyond half of the free memory
+  const double resident = 8.0 * ((double)M2 * D + (double)nb * M2 * (unc ? 2.0 : 1.0));
+  size_t free_b = 0, total_b = 0;
+  const bool have_free = hipMemGetInfo(&free_b, &total_b) == hipSuccess;
+  if (have_free && resident > 0.5 * (double)free_b)
+    throw std::runtime_error("sobol: the means of " + std::to_string(N) + " base samples x " + std::to_string(nb) +
+                             " emulators do not fit half of the free device memory; use fewer base samples");
+  // rows per chunk of pass 2: the chunk of AB_i, its means and predict()'s dot-product rows within predict()'s own budget
+  double cap = ks_budget_bytes();
+  if (have_free) cap = std::min(cap, 0.5 * ((double)free_b - resident));
+  const double per_row = 8.0 * ((double)D + (double)nb * (1.0 + (R > 1 ? R : 0)) + (mean.kind == 3 ? 2.0 * mean.dims.size() + 1.0 : 1.0));
+  long CH = (long)(cap / per_row) / 128 * 128;
+  CH = std::min<long>(std::max<long>(128, CH), N);
+  const long nchunks = (N + CH - 1) / CH;
+  const int groups = sobol_groups(CH);
+  const long nslot = nchunks * groups;
+  const size_t n_part = std::max<size_t>((size_t)nb * SOBOL_MAX_GROUPS, (size_t)nb * D * nslot * 2);
+  double *dS = nullptr, *dF = nullptr, *dV = nullptr, *dPick = nullptr, *dFab = nullptr, *dPart = nullptr, *dStats = nullptr, *dSums = nullptr;
+  auto release = [&] {
+    for (double* p : {dS, dF, dV, dPick, dFab, dPart, dStats, dSums})
+      if (p) hipFree(p);
+  };
+  try {
+    dS = dalloc<double>((size_t)M2 * D);
+    dF = dalloc<double>((size_t)nb * M2);
+    if (unc) dV = dalloc<double>((size_t)nb * M2);
+    dPick = dalloc<double>((size_t)CH * D);
+    dFab = dalloc<double>((size_t)nb * CH);
+    dPart = dalloc<double>(n_part);
+    dStats = dalloc<double>((size_t)nb * SOBOL_STATS);
+    dSums = dalloc<double>((size_t)nb * D * 2);
+    std::vector<double> stats((size_t)nb * SOBOL_STATS, 0.);
+    // the nugget predict() adds to the variances on the host (not with nugget="pivot", GaussianProcess.py:915)
+    for (int k = 0; k < nb; ++k)
+      stats[(size_t)k * SOBOL_STATS + 3] = (include_nugget && gp[ids[k]].nug_type != NUG_PIVOT) ? nugget_size(ids[k]) : 0.;
+    HIPCK(hipMemcpyAsync(dStats, stats.data(), stats.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+    HIPCK(hipMemcpyAsync(dS, A, (size_t)N * D * sizeof(double), hipMemcpyHostToDevice, stream));
+    HIPCK(hipMemcpyAsync(dS + (size_t)N * D, Bs, (size_t)N * D * sizeof(double), hipMemcpyHostToDevice, stream));
+    // pass 1: fA | fB, then f0 and V (two passes over the resident means), and the mean predictive variance
+    predict(ids, dS, (int)M2, true, dF, dV, M2, true, nullptr);
+    launch_sobol_row_mean(nb, 0, dF, M2, M2, nullptr, 0, dPart, dStats + 0, SOBOL_STATS, stream);
+    launch_sobol_row_mean(nb, 1, dF, M2, M2, dStats + 0, SOBOL_STATS, dPart, dStats + 1, SOBOL_STATS, stream);
+    if (unc) launch_sobol_row_mean(nb, 2, dV, M2, M2, dStats + 3, SOBOL_STATS, dPart, dStats + 2, SOBOL_STATS, stream);
+    // pass 2
+    for (int col = 0; col < D; ++col) {
+      for (long c = 0; c < nchunks; ++c) {
+        const long r0 = c * CH;
+        const int rows = (int)std::min<long>(CH, N - r0);
+        launch_sobol_pick_freeze(dS, dS + (size_t)N * D, r0, rows, D, col, dPick, stream);
+        predict(ids, dPick, rows, true, dFab, nullptr, CH, true, nullptr);
+        launch_sobol_pair_sum(nb, dF + r0, dF + N + r0, M2, dFab, CH, rows, dStats, SOBOL_STATS, dPart, D, col, nslot, c * groups, groups,
+                              stream);
+      }
+    }
+    launch_sobol_pair_final(nb * D, dPart, nslot, 1.0 / (double)N, dSums, stream);
+    std::vector<double> sums((size_t)nb * D * 2);
+    HIPCK(hipMemcpyAsync(stats.data(), dStats, stats.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIPCK(hipMemcpyAsync(sums.data(), dSums, sums.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIPCK(hipStreamSynchronize(stream));
+    HIPCK(hipGetLastError());
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (int k = 0; k < nb; ++k) {
+      const double* st = stats.data() + (size_t)k * SOBOL_STATS;
+      const double V = st[1];
+      mean_out[k] = st[0];
+      var_out[k] = V;
+      if (emvar_out) emvar_out[k] = unc ? st[2] : nan;
+      for (int d = 0; d < D; ++d) {
+        // a constant emulator (V == 0) has no indices: NaN, not an error
+        S[(size_t)k * D + d] = V > 0. ? sums[((size_t)k * D + d) * 2] / V : nan;
+        ST[(size_t)k * D + d] = V > 0. ? sums[((size_t)k * D + d) * 2 + 1] / (2. * V) : nan;
+      }
+    }
+  } catch (...) {
+    hipStreamSynchronize(stream);
+    release();
+    throw;
+  }
+  release();
 }
 
 void Engine::loo_variance(int i, double* out) {

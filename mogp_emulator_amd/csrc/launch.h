@@ -185,6 +185,25 @@ void launch_predict_mean_finish(int nb, int m, int D, int R, int nbasis, const d
                                 const double* LA, double* mean, double* var, long ld, int nterm, const double* dbasis, const int* ddims,
                                 const int* dpowers, double* deriv, hipStream_t s);
 
+// --- sensitivity (kernels_sobol.hip) -----------------------------------------------------------
+// Every reduction: wave shuffles, LDS, one partial per workgroup in a scratch slot, a final pass in a fixed order (no atomics).
+constexpr int SOBOL_MAX_GROUPS = 256;   // workgroups of one row reduction
+constexpr int SOBOL_STATS = 4;          // per emulator [f0, V, mean predictive variance, nugget added to the variances]
+int sobol_groups(long m);               // workgroups a reduction over m elements is launched with (<= SOBOL_MAX_GROUPS)
+// out (rows, D) = rows [r0, r0 + rows) of A (N, D) with column col taken from B
+void launch_sobol_pick_freeze(const double* A, const double* B, long r0, int rows, int D, int col, double* out, hipStream_t s);
+// out[k * ostride] = mean over j < m of  x[k][j] (mode 0),  (x[k][j] - prm[k * pstride])^2 (mode 1),  max(x[k][j] + prm[k * pstride], 0)
+// (mode 2);  x (nb, ld); partial: nb * sobol_groups(m) doubles scratch
+void launch_sobol_row_mean(int nb, int mode, const double* x, long ld, long m, const double* prm, int pstride, double* partial, double* out,
+                           int ostride, hipStream_t s);
+// one chunk of `rows` base rows of input col: fA, fB (nb, ld) and fAB (nb, ldab) point at the chunk's first row, f0 = stats[k * sstride];
+// partial[((k * D + col) * nslot + slot0 + w) * 2 + {0, 1}] = sum (fB - f0)(fAB - fA), sum (fA - fAB)^2 of workgroup w < groups
+void launch_sobol_pair_sum(int nb, const double* fA, const double* fB, long ld, const double* fAB, long ldab, int rows,
+                           const double* stats, int sstride, double* partial, int D, int col, long nslot, long slot0, int groups,
+                           hipStream_t s);
+// out[q * 2 + {0, 1}] = scale * sum of the nslot partials of quantity q < nq, in a fixed order
+void launch_sobol_pair_final(int nq, const double* partial, long nslot, double scale, double* out, hipStream_t s);
+
 // --- utilities -------------------------------------------------------------------------------
 // out (n,n) <- tile of src (NP,NP): mode 0 copy, mode 1 transpose, mode 2 symmetrise from lower
 void launch_extract(const double* src, int NP, int n, double* out, int mode, hipStream_t s);

@@ -109,6 +109,21 @@ def _outbuf(a, name):
     return a
 
 
+def _sobol_call(fn, handle, D, n_out, A, B, unc, include_nugget):
+    """shared by DenseGP_GPU.sobol and MultiOutputGP_GPU.sobol: (S, ST, mean, variance, emulator_variance or None), one row per output"""
+    a, b = _f64(A, 2, "A"), _f64(B, 2, "B")
+    if a.shape != b.shape:
+        raise ValueError("sobol: A and B must have the same shape, got %s and %s" % (a.shape, b.shape))
+    if a.shape[1] != D:
+        raise ValueError("sobol: the sample matrices must have %d columns, got %d" % (D, a.shape[1]))
+    S, ST = np.zeros((n_out, D)), np.zeros((n_out, D))
+    mean, var = np.zeros(n_out), np.zeros(n_out)
+    ev = np.zeros(n_out) if unc else None
+    check(fn(handle, dptr(a), dptr(b), a.shape[0], a.shape[1], int(bool(unc)), int(bool(include_nugget)), dptr(S), dptr(ST),
+             dptr(mean), dptr(var), dptr(ev)))
+    return S, ST, mean, var, ev
+
+
 # --------------------------------------------------------------------------------------
 # mean functions (bindings.cu:365-413)
 # --------------------------------------------------------------------------------------
@@ -779,6 +794,12 @@ class DenseGP_GPU(object):
                                                float(discrepancy), int(bool(include_nugget)), dptr(out)))
         return out
 
+    def sobol(self, A, B, unc=False, include_nugget=True):
+        """first-order and total-effect Sobol indices of the predictive mean from the sample matrices A, B (N, D), computed on the
+        device behind the prediction: (S (D,), ST (D,), mean, variance, emulator_variance or None)"""
+        S, ST, mean, var, ev = _sobol_call(_lib.mogp_densegp_sobol, self._h, self.D(), 1, A, B, unc, include_nugget)
+        return S[0], ST[0], float(mean[0]), float(var[0]), (float(ev[0]) if unc else None)
+
     def loo_variance(self):
         """leave-one-out predictive variance 1/[K^-1]_ii at every training input (MICEFastGP.fast_predict for all indices)"""
         out = np.zeros(self.n())
@@ -999,6 +1020,11 @@ class MultiOutputGP_GPU(object):
         check(_lib.mogp_mogp_implausibility(self._h, dptr(x), x.shape[0], x.shape[1], dptr(z), dptr(ov), dptr(dc),
                                             int(bool(include_nugget)), int(rank), dptr(out)))
         return out
+
+    def sobol(self, A, B, unc=False, include_nugget=True):
+        """Sobol indices of every emulator in one batched pass per part: (S, ST (n_emulators, D), mean, variance, emulator_variance
+        or None (n_emulators,)); rows of emulators that are not fit are NaN"""
+        return _sobol_call(_lib.mogp_mogp_sobol, self._h, self.D(), self.n_emulators(), A, B, unc, include_nugget)
 
     def predict_variance_batch_dev(self, d_testing, m, d_means, d_vars):
         """Device-pointer variant: inputs already resident in HBM, results stay in HBM."""
