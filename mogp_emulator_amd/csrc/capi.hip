@@ -89,37 +89,26 @@ static void kernel_eval_impl(int kernel_type, int what, const double* x1, int n1
     P[D] = std::exp(params[nc]);
     const size_t planes = what == 0 ? 1 : (what == 1 ? (size_t)D + 1 : (size_t)D);
     const size_t cnt = planes * (size_t)n1 * n2;
-    double *d1 = nullptr, *d2 = nullptr, *dP = nullptr, *dO = nullptr;
-    auto cleanup = [&]() { for (double* p : {d1, d2, dP, dO}) if (p) hipFree(p); };
-    try {
-      hip_check(hipMalloc(reinterpret_cast<void**>(&d1), (size_t)n1 * D * 8), "hipMalloc");
-      hip_check(hipMalloc(reinterpret_cast<void**>(&d2), (size_t)n2 * D * 8), "hipMalloc");
-      hip_check(hipMalloc(reinterpret_cast<void**>(&dP), P.size() * 8), "hipMalloc");
-      hip_check(hipMalloc(reinterpret_cast<void**>(&dO), cnt * 8), "hipMalloc");
-      hip_check(hipMemcpy(d1, x1, (size_t)n1 * D * 8, hipMemcpyHostToDevice), "hipMemcpy");
-      hip_check(hipMemcpy(d2, x2, (size_t)n2 * D * 8, hipMemcpyHostToDevice), "hipMemcpy");
-      hip_check(hipMemcpy(dP, P.data(), P.size() * 8, hipMemcpyHostToDevice), "hipMemcpy");
-      launch_kernel_object(dk, d1, n1, d2, n2, D, dP, what, dO, nullptr);
-      std::vector<double> tmp(cnt);
-      hip_check(hipMemcpy(tmp.data(), dO, cnt * 8, hipMemcpyDeviceToHost), "hipMemcpy");
-      hip_check(hipGetLastError(), "kernel_object_kernel");
-      if (what == 1 && uniform) {
-        // one shared length scale: d/dtheta_0 = sum of the per-dimension planes (Kernel.py:338-376); then the sigma^2 plane
-        const size_t pl = (size_t)n1 * n2;
-        for (size_t e = 0; e < pl; ++e) {
-          double s = 0.;
-          for (int d = 0; d < D; ++d) s += tmp[(size_t)d * pl + e];
-          out[e] = s;
-          out[pl + e] = tmp[(size_t)D * pl + e];
-        }
-      } else {
-        std::memcpy(out, tmp.data(), cnt * 8);
+    DevBuf<double> d1((size_t)n1 * D), d2((size_t)n2 * D), dP(P.size()), dO(cnt);
+    hip_check(hipMemcpy(d1, x1, (size_t)n1 * D * 8, hipMemcpyHostToDevice), "hipMemcpy");
+    hip_check(hipMemcpy(d2, x2, (size_t)n2 * D * 8, hipMemcpyHostToDevice), "hipMemcpy");
+    hip_check(hipMemcpy(dP, P.data(), P.size() * 8, hipMemcpyHostToDevice), "hipMemcpy");
+    launch_kernel_object(dk, d1, n1, d2, n2, D, dP, what, dO, nullptr);
+    std::vector<double> tmp(cnt);
+    hip_check(hipMemcpy(tmp.data(), dO, cnt * 8, hipMemcpyDeviceToHost), "hipMemcpy");
+    hip_check(hipGetLastError(), "kernel_object_kernel");
+    if (what == 1 && uniform) {
+      // one shared length scale: d/dtheta_0 = sum of the per-dimension planes (Kernel.py:338-376); then the sigma^2 plane
+      const size_t pl = (size_t)n1 * n2;
+      for (size_t e = 0; e < pl; ++e) {
+        double s = 0.;
+        for (int d = 0; d < D; ++d) s += tmp[(size_t)d * pl + e];
+        out[e] = s;
+        out[pl + e] = tmp[(size_t)D * pl + e];
       }
-    } catch (...) {
-      cleanup();
-      throw;
+    } else {
+      std::memcpy(out, tmp.data(), cnt * 8);
     }
-    cleanup();
   }
 }
 
@@ -173,11 +162,8 @@ static mogp_densegp* densegp_create(const double* inputs, int n, int D, const do
   try {
     MeanFunc mf;
     if (mean) mf = mean->mf;
-    auto* h = new mogp_densegp;
-    h->eng = new Engine(inputs, n, D, targets, 1, testing_size, mf, kernel_type, nugget_type, nugget_size, analytic);
-    h->idx = 0;
-    h->owns = true;
-    return h;
+    std::unique_ptr<Engine> e(new Engine(inputs, n, D, targets, 1, testing_size, mf, kernel_type, nugget_type, nugget_size, analytic));
+    return new mogp_densegp{e.release(), 0, true};
   } catch (const std::exception& e) {
     g_err = e.what();
     return nullptr;
@@ -503,9 +489,15 @@ static std::string part_tag(const mogp_part& p) {
   return " [part on device " + std::to_string(p.device) + ", emulators [" + std::to_string(p.lo) + ", " + std::to_string(p.hi) + ")]";
 }
 // f(part, k) for every part, one host thread per part, each under its device's mutex and a DeviceGuard.  The first failure in part order
-// is rethrown on the calling thread once every part has finished, its message naming the part.
+// is rethrown on the calling thread once every part has finished, its message naming the part.  A handle with ONE part is the plain
+// single-engine model: f runs on the calling thread under a DeviceGuard -- no thread, no mutex, the message as it was thrown.
 static void for_parts(mogp_mogp* h, const std::function<void(mogp_part&, int)>& f) {
   const int np = (int)h->parts.size();
+  if (np == 1) {
+    DeviceGuard g(h->parts[0].device);
+    f(h->parts[0], 0);
+    return;
+  }
   std::vector<std::exception_ptr> err(np);
   std::vector<std::thread> th;
   th.reserve(np);
@@ -590,24 +582,6 @@ int mogp_mogp_create_priors_for_emulator(mogp_mogp* h, int index, int n_corr, co
 }
 int mogp_mogp_eval(mogp_mogp* h, const double* thetas, int n_rows, int n_cols, double* logpost_out, double* grad_out, int* ok_out) {
   GUARD({
-    if (!h->multi()) {
-      Engine* e = h->eng;
-      DeviceGuard g(e->device_id());
-      if (n_rows != e->B) throw std::runtime_error("thetas must have one row per emulator");
-      std::vector<int> ids(e->B);
-      std::vector<const double*> th(e->B);
-      for (int i = 0; i < e->B; ++i) {
-        if (n_cols != e->n_theta(i)) throw std::runtime_error("Shape of new GPParams object does not match existing one");
-        ids[i] = i;
-        th[i] = thetas + (size_t)i * n_cols;
-      }
-      std::vector<double> f(e->B);
-      std::vector<int> ok(e->B);
-      e->eval(ids, th, grad_out != nullptr, f.data(), grad_out, n_cols, ok.data());
-      if (logpost_out) std::memcpy(logpost_out, f.data(), sizeof(double) * e->B);
-      if (ok_out) std::memcpy(ok_out, ok.data(), sizeof(int) * e->B);
-      return 0;
-    }
     if (n_rows != (int)h->views.size()) throw std::runtime_error("thetas must have one row per emulator");
     for (const auto& v : h->views)
       if (n_cols != v.eng->n_theta(v.idx)) throw std::runtime_error("Shape of new GPParams object does not match existing one");
@@ -644,13 +618,9 @@ int mogp_mogp_fit(mogp_mogp* h, const double* thetas, int n_rows, int n_cols) {
 int mogp_mogp_fit_emulator(mogp_mogp* h, int index, const double* theta, int len) {
   GUARD({
     if (index < 0 || index >= (int)h->views.size()) throw std::runtime_error("Invalid emulator index");
-    if (!h->multi()) {
-      DeviceGuard g(h->eng->device_id());
-      h->eng->fit_one(index, theta, len);
-      return 0;
-    }
     mogp_part& p = part_of(h, index);
-    std::lock_guard<std::mutex> lk(device_mutex(p.device));
+    std::unique_lock<std::mutex> lk;      // (parts that share a device take turns; a single part has nobody to wait for)
+    if (h->multi()) lk = std::unique_lock<std::mutex>(device_mutex(p.device));
     DeviceGuard g(p.device);
     p.eng->fit_one(index - p.lo, theta, len);
   });
@@ -661,31 +631,43 @@ static std::vector<int> fitted_ids(const Engine* e) {
     if (e->gp[i].has_data && e->gp[i].factored) ids.push_back(i);
   return ids;
 }
-// results of fitted emulators go to their own rows; rows of unfitted emulators are untouched
-static void engine_predict_common(Engine* e, const double* testing, int m, int D, double* means, double* vars, double* derivs) {
-  if (D != e->D) throw std::runtime_error("testing points must have D columns");
-  std::vector<int> ids = fitted_ids(e);
-  if (ids.empty()) return;
-  const size_t nf = ids.size();
-  if ((int)nf == e->B) {             // every emulator fitted: results go straight into the caller's arrays (means == null: derivatives only)
-    e->predict(ids, testing, m, false, means, vars, m, false, derivs);
+// The fitted emulators of one engine, computed on compact scratch and scattered to their rows.  out[a] is the caller's array a with one
+// row of row[a] doubles per emulator of the engine (null: not asked for); run(ids, buf) fills buf[a] -- (ids.size(), row[a]), null where
+// out[a] is -- and row k of it goes to row ids[k] of out[a].  With every emulator fitted, run writes the caller's arrays themselves.
+// Rows of unfitted emulators are left untouched, or become NaN with nan_unfitted.
+using RowRun = std::function<void(const std::vector<int>&, const std::vector<double*>&)>;
+static void with_fitted_rows(Engine* e, const std::vector<double*>& out, const std::vector<size_t>& row, bool nan_unfitted, const RowRun& run) {
+  const std::vector<int> ids = fitted_ids(e);
+  const size_t nf = ids.size(), na = out.size();
+  if ((int)nf == e->B) {
+    run(ids, out);
     return;
   }
-  std::vector<double> mm(means ? nf * m : 0), vv(vars ? nf * m : 0), dd(derivs ? nf * m * D : 0);
-  e->predict(ids, testing, m, false, means ? mm.data() : nullptr, vars ? vv.data() : nullptr, m, false, derivs ? dd.data() : nullptr);
-  for (size_t k = 0; k < nf; ++k) {
-    if (means) std::memcpy(means + (size_t)ids[k] * m, mm.data() + k * m, m * sizeof(double));
-    if (vars) std::memcpy(vars + (size_t)ids[k] * m, vv.data() + k * m, m * sizeof(double));
-    if (derivs) std::memcpy(derivs + (size_t)ids[k] * m * D, dd.data() + k * m * D, (size_t)m * D * sizeof(double));
-  }
+  if (nan_unfitted)
+    for (size_t a = 0; a < na; ++a)
+      if (out[a]) std::fill(out[a], out[a] + (size_t)e->B * row[a], std::numeric_limits<double>::quiet_NaN());
+  if (nf == 0) return;
+  std::vector<std::vector<double>> tmp(na);
+  std::vector<double*> buf(na, nullptr);
+  for (size_t a = 0; a < na; ++a)
+    if (out[a]) {
+      tmp[a].resize(nf * row[a]);
+      buf[a] = tmp[a].data();
+    }
+  run(ids, buf);
+  for (size_t k = 0; k < nf; ++k)
+    for (size_t a = 0; a < na; ++a)
+      if (out[a]) std::memcpy(out[a] + (size_t)ids[k] * row[a], buf[a] + k * row[a], row[a] * sizeof(double));
+}
+// results of fitted emulators go to their own rows; rows of unfitted emulators are untouched (means == null: derivatives only)
+static void engine_predict_common(Engine* e, const double* testing, int m, int D, double* means, double* vars, double* derivs) {
+  if (D != e->D) throw std::runtime_error("testing points must have D columns");
+  with_fitted_rows(e, {means, vars, derivs}, {(size_t)m, (size_t)m, (size_t)m * D}, false, [&](const std::vector<int>& ids, const std::vector<double*>& o) {
+    e->predict(ids, testing, m, false, o[0], o[1], m, false, o[2]);
+  });
 }
 // each part writes its own rows of the caller's (n_emulators, ...) arrays
 static void mogp_predict_common(mogp_mogp* h, const double* testing, int m, int D, double* means, double* vars, double* derivs) {
-  if (!h->multi()) {
-    DeviceGuard g(h->eng->device_id());
-    engine_predict_common(h->eng, testing, m, D, means, vars, derivs);
-    return;
-  }
   if (D != h->eng->D) throw std::runtime_error("testing points must have D columns");
   for_parts(h, [&](mogp_part& p, int) {
     const size_t lo = p.lo;
@@ -704,29 +686,12 @@ int mogp_mogp_predict_deriv(mogp_mogp* h, const double* testing, int m, int D, d
 }
 static void engine_predict_full_cov(Engine* e, const double* testing, int m, int D, double* means, double* covs) {
   if (D != e->D) throw std::runtime_error("testing points must have D columns");
-  std::vector<int> ids = fitted_ids(e);
-  if (ids.empty()) return;
-  if ((int)ids.size() == e->B) {
-    e->predict_full_cov(ids, testing, m, means, covs);
-  } else {
-    const size_t nf = ids.size();
-    const size_t mm = (size_t)m * m;
-    std::vector<double> mu(nf * m);
-    std::vector<double> cc(nf * mm);
-    e->predict_full_cov(ids, testing, m, mu.data(), cc.data());
-    for (size_t k = 0; k < nf; ++k) {
-      std::memcpy(means + (size_t)ids[k] * m, mu.data() + k * m, m * sizeof(double));
-      std::memcpy(covs + (size_t)ids[k] * mm, cc.data() + k * mm, mm * sizeof(double));
-    }
-  }
+  with_fitted_rows(e, {means, covs}, {(size_t)m, (size_t)m * m}, false, [&](const std::vector<int>& ids, const std::vector<double*>& o) {
+    e->predict_full_cov(ids, testing, m, o[0], o[1]);
+  });
 }
 int mogp_mogp_predict_full_cov(mogp_mogp* h, const double* testing, int m, int D, double* means, double* covs) {
   GUARD({
-    if (!h->multi()) {
-      DeviceGuard g(h->eng->device_id());
-      engine_predict_full_cov(h->eng, testing, m, D, means, covs);
-      return 0;
-    }
     if (D != h->eng->D) throw std::runtime_error("testing points must have D columns");
     for_parts(h, [&](mogp_part& p, int) {
       const size_t lo = p.lo;
@@ -747,39 +712,24 @@ static void mogp_implausibility_parts(mogp_mogp* h, const double* testing, int m
   if (m <= 0) return;
   const int np = (int)h->parts.size(), keep = rank + 1, dev0 = h->parts[0].device;
   const long OC = std::min<long>(m, 1L << 18);
-  double *dLists = nullptr, *dOut = nullptr;
-  auto release = [&] {
-    DeviceGuard g(dev0);
-    if (dLists) hipFree(dLists);
-    if (dOut) hipFree(dOut);
-  };
-  try {
-    {
-      DeviceGuard g(dev0);
-      hip_check(hipMalloc(reinterpret_cast<void**>(&dLists), (size_t)np * keep * OC * sizeof(double)), "hipMalloc");
-      hip_check(hipMalloc(reinterpret_cast<void**>(&dOut), (size_t)OC * sizeof(double)), "hipMalloc");
-    }
-    for (long c0 = 0; c0 < m; c0 += OC) {
-      const int mc = (int)std::min<long>(OC, m - c0);
-      for_parts(h, [&](mogp_part& p, int k) {
-        std::vector<int> ids(p.hi - p.lo);
-        for (int i = 0; i < (int)ids.size(); ++i) ids[i] = i;
-        p.eng->implausibility_top(ids, testing + (size_t)c0 * h->eng->D, mc, obs + p.lo, obs_var + p.lo, discrepancy + p.lo, include_nugget,
-                                  keep, dLists + (size_t)k * keep * OC, OC, dev0);
-      });
-      mogp_part& p0 = h->parts[0];
-      std::lock_guard<std::mutex> lk(device_mutex(dev0));
-      DeviceGuard g(dev0);
-      launch_implausibility_merge(np, dLists, OC, mc, rank, dOut, p0.eng->stream);
-      hip_check(hipMemcpyAsync(out + c0, dOut, (size_t)mc * sizeof(double), hipMemcpyDeviceToHost, p0.eng->stream), "hipMemcpyAsync");
-      hip_check(hipStreamSynchronize(p0.eng->stream), "hipStreamSynchronize");
-    }
-    hip_check(hipGetLastError(), "implausibility_merge_kernel");
-  } catch (...) {
-    release();
-    throw;
+  // the two buffers live on part 0's device: the calling thread stays on it for the whole function (the threads of for_parts set their own)
+  DeviceGuard g(dev0);
+  DevBuf<double> dLists((size_t)np * keep * OC), dOut((size_t)OC);
+  for (long c0 = 0; c0 < m; c0 += OC) {
+    const int mc = (int)std::min<long>(OC, m - c0);
+    for_parts(h, [&](mogp_part& p, int k) {
+      std::vector<int> ids(p.hi - p.lo);
+      for (int i = 0; i < (int)ids.size(); ++i) ids[i] = i;
+      p.eng->implausibility_top(ids, testing + (size_t)c0 * h->eng->D, mc, obs + p.lo, obs_var + p.lo, discrepancy + p.lo, include_nugget,
+                                keep, dLists + (size_t)k * keep * OC, OC, dev0);
+    });
+    mogp_part& p0 = h->parts[0];
+    std::lock_guard<std::mutex> lk(device_mutex(dev0));
+    launch_implausibility_merge(np, dLists, OC, mc, rank, dOut, p0.eng->stream);
+    hip_check(hipMemcpyAsync(out + c0, dOut, (size_t)mc * sizeof(double), hipMemcpyDeviceToHost, p0.eng->stream), "hipMemcpyAsync");
+    hip_check(hipStreamSynchronize(p0.eng->stream), "hipStreamSynchronize");
   }
-  release();
+  hip_check(hipGetLastError(), "implausibility_merge_kernel");
 }
 int mogp_mogp_implausibility(mogp_mogp* h, const double* testing, int m, int D, const double* obs, const double* obs_var,
                              const double* discrepancy, int include_nugget, int rank, double* out) {
@@ -801,29 +751,10 @@ int mogp_mogp_implausibility(mogp_mogp* h, const double* testing, int m, int D, 
 // the fitted emulators of one engine into their own rows of the caller's arrays; rows of unfitted emulators become NaN
 static void engine_sobol(Engine* e, const double* A, const double* B, int N, bool unc, bool include_nugget, double* S, double* ST,
                          double* mean_out, double* variance_out, double* emvar_out) {
-  const int D = e->D;
-  std::vector<int> ids = fitted_ids(e);
-  const size_t nf = ids.size();
-  if ((int)nf == e->B) {
-    e->sobol(ids, A, B, N, unc, include_nugget, S, ST, mean_out, variance_out, emvar_out);
-    return;
-  }
-  const double nan = std::numeric_limits<double>::quiet_NaN();
-  for (int i = 0; i < e->B; ++i) {
-    for (int d = 0; d < D; ++d) S[(size_t)i * D + d] = ST[(size_t)i * D + d] = nan;
-    mean_out[i] = variance_out[i] = nan;
-    if (emvar_out) emvar_out[i] = nan;
-  }
-  if (nf == 0) return;
-  std::vector<double> s(nf * D), st(nf * D), mu(nf), va(nf), ev(nf);
-  e->sobol(ids, A, B, N, unc, include_nugget, s.data(), st.data(), mu.data(), va.data(), emvar_out ? ev.data() : nullptr);
-  for (size_t k = 0; k < nf; ++k) {
-    std::memcpy(S + (size_t)ids[k] * D, s.data() + k * D, D * sizeof(double));
-    std::memcpy(ST + (size_t)ids[k] * D, st.data() + k * D, D * sizeof(double));
-    mean_out[ids[k]] = mu[k];
-    variance_out[ids[k]] = va[k];
-    if (emvar_out) emvar_out[ids[k]] = ev[k];
-  }
+  const size_t D = e->D;
+  with_fitted_rows(e, {S, ST, mean_out, variance_out, emvar_out}, {D, D, 1, 1, 1}, true, [&](const std::vector<int>& ids, const std::vector<double*>& o) {
+    e->sobol(ids, A, B, N, unc, include_nugget, o[0], o[1], o[2], o[3], o[4]);
+  });
 }
 // Emulators are independent: every part runs its own block on its own engine and writes its own rows (no cross-device reduction)
 int mogp_mogp_sobol(mogp_mogp* h, const double* A, const double* B, int N, int D, int unc, int include_nugget, double* S, double* ST,
@@ -833,11 +764,6 @@ int mogp_mogp_sobol(mogp_mogp* h, const double* A, const double* B, int N, int D
     if (!S || !ST || !mean_out || !variance_out) throw std::runtime_error("sobol: null result buffer");
     if (unc && !emulator_variance_out) throw std::runtime_error("sobol: unc needs a buffer for the emulator variance");
     double* ev = unc ? emulator_variance_out : nullptr;
-    if (!h->multi()) {
-      DeviceGuard g(h->eng->device_id());
-      engine_sobol(h->eng, A, B, N, unc != 0, include_nugget != 0, S, ST, mean_out, variance_out, ev);
-      return 0;
-    }
     for_parts(h, [&](mogp_part& p, int) {
       const size_t lo = p.lo;
       engine_sobol(p.eng.get(), A, B, N, unc != 0, include_nugget != 0, S + lo * D, ST + lo * D, mean_out + lo, variance_out + lo,
@@ -870,32 +796,22 @@ static void engine_predict_dev(Engine* e, const double* d_testing, int m, int D,
     HIPCK(hipStreamSynchronize(st));
     return;
   }
-  double *tm = nullptr, *tv = nullptr, *td = nullptr;
-  auto release = [&] {
-    for (double* p : {tm, tv, td})
-      if (p) hipFree(p);
-  };
-  try {
-    if (d_means) HIPCK(hipMalloc((void**)&tm, nf * row * sizeof(double)));
-    if (d_vars) HIPCK(hipMalloc((void**)&tv, nf * row * sizeof(double)));
-    if (d_derivs) HIPCK(hipMalloc((void**)&td, nf * drow * sizeof(double)));
-    e->predict(ids, d_testing, m, true, tm, tv, m, true, td);
-    // runs of consecutive fitted emulators go in one copy each
-    for (size_t k = 0; k < nf;) {
-      size_t len = 1;
-      while (k + len < nf && ids[k + len] == ids[k] + (int)len) ++len;
-      if (d_means) HIPCK(hipMemcpyAsync(d_means + (size_t)ids[k] * row, tm + k * row, len * row * sizeof(double), hipMemcpyDeviceToDevice, st));
-      if (d_vars) HIPCK(hipMemcpyAsync(d_vars + (size_t)ids[k] * row, tv + k * row, len * row * sizeof(double), hipMemcpyDeviceToDevice, st));
-      if (d_derivs) HIPCK(hipMemcpyAsync(d_derivs + (size_t)ids[k] * drow, td + k * drow, len * drow * sizeof(double), hipMemcpyDeviceToDevice, st));
-      k += len;
-    }
-    HIPCK(hipStreamSynchronize(st));
-  } catch (...) {
-    hipStreamSynchronize(st);
-    release();
-    throw;
+  DevBuf<double> tm, tv, td;
+  SyncOnUnwind drained{st};
+  if (d_means) tm.reserve(nf * row);
+  if (d_vars) tv.reserve(nf * row);
+  if (d_derivs) td.reserve(nf * drow);
+  e->predict(ids, d_testing, m, true, tm, tv, m, true, td);
+  // runs of consecutive fitted emulators go in one copy each
+  for (size_t k = 0; k < nf;) {
+    size_t len = 1;
+    while (k + len < nf && ids[k + len] == ids[k] + (int)len) ++len;
+    if (d_means) HIPCK(hipMemcpyAsync(d_means + (size_t)ids[k] * row, tm + k * row, len * row * sizeof(double), hipMemcpyDeviceToDevice, st));
+    if (d_vars) HIPCK(hipMemcpyAsync(d_vars + (size_t)ids[k] * row, tv + k * row, len * row * sizeof(double), hipMemcpyDeviceToDevice, st));
+    if (d_derivs) HIPCK(hipMemcpyAsync(d_derivs + (size_t)ids[k] * drow, td + k * drow, len * drow * sizeof(double), hipMemcpyDeviceToDevice, st));
+    k += len;
   }
-  release();
+  HIPCK(hipStreamSynchronize(st));
 }
 // Several parts: a part on the device of the caller's buffers predicts straight into its rows; a part on another device copies the test points
 // to its own device, predicts into scratch there and copies its rows back with peer copies on its stream.
@@ -914,29 +830,18 @@ static void mogp_predict_dev_parts(mogp_mogp* h, const double* d_testing, int m,
       engine_predict_dev(e, d_testing, m, D, om, ov, od);
       return;
     }
-    double *xs = nullptr, *tm = nullptr, *tv = nullptr, *td = nullptr;
     hipStream_t st = e->stream;
-    auto release = [&] {
-      for (double* q : {xs, tm, tv, td})
-        if (q) hipFree(q);
-    };
-    try {
-      HIPCK(hipMalloc((void**)&xs, drow * sizeof(double)));
-      if (om) HIPCK(hipMalloc((void**)&tm, rows * row * sizeof(double)));
-      if (ov) HIPCK(hipMalloc((void**)&tv, rows * row * sizeof(double)));
-      if (od) HIPCK(hipMalloc((void**)&td, rows * drow * sizeof(double)));
-      HIPCK(hipMemcpyPeerAsync(xs, p.device, d_testing, caller, drow * sizeof(double), st));
-      engine_predict_dev(e, xs, m, D, tm, tv, td);
-      if (om) HIPCK(hipMemcpyPeerAsync(om, caller, tm, p.device, rows * row * sizeof(double), st));
-      if (ov) HIPCK(hipMemcpyPeerAsync(ov, caller, tv, p.device, rows * row * sizeof(double), st));
-      if (od) HIPCK(hipMemcpyPeerAsync(od, caller, td, p.device, rows * drow * sizeof(double), st));
-      HIPCK(hipStreamSynchronize(st));
-    } catch (...) {
-      hipStreamSynchronize(st);
-      release();
-      throw;
-    }
-    release();
+    DevBuf<double> xs(drow), tm, tv, td;
+    SyncOnUnwind drained{st};
+    if (om) tm.reserve(rows * row);
+    if (ov) tv.reserve(rows * row);
+    if (od) td.reserve(rows * drow);
+    HIPCK(hipMemcpyPeerAsync(xs, p.device, d_testing, caller, drow * sizeof(double), st));
+    engine_predict_dev(e, xs, m, D, tm, tv, td);
+    if (om) HIPCK(hipMemcpyPeerAsync(om, caller, tm, p.device, rows * row * sizeof(double), st));
+    if (ov) HIPCK(hipMemcpyPeerAsync(ov, caller, tv, p.device, rows * row * sizeof(double), st));
+    if (od) HIPCK(hipMemcpyPeerAsync(od, caller, td, p.device, rows * drow * sizeof(double), st));
+    HIPCK(hipStreamSynchronize(st));
   });
 }
 static void mogp_predict_dev_common(mogp_mogp* h, const double* d_testing, int m, int D, double* d_means, double* d_vars, double* d_derivs) {
@@ -963,16 +868,10 @@ int mogp_mogp_predict_dev(mogp_mogp* h, const double* d_testing, int m, int D, d
 using EmuRef = std::pair<const Engine*, int>;      // (a comma inside GUARD's argument would split it)
 int mogp_fit_GP_MAP(mogp_mogp* h, int n_tries, const double* theta0, int theta0_len) {
   GUARD({
-    if (!h->multi()) {
-      DeviceGuard g(h->eng->device_id());
-      std::vector<int> ids(h->eng->B);
-      for (int i = 0; i < h->eng->B; ++i) ids[i] = i;
-      h->eng->fit_map(ids, n_tries, theta0, theta0_len);
-      return 0;
-    }
     // every starting point is drawn here, in the order of the unsharded model (start-major), from part 0's rng -- seeded as a single
     // engine's is -- with each emulator's own priors; each part then runs its block.  The end point of a run does not depend on the
-    // batch it ran in (Engine::run_pool), so the result is the single-engine one whatever the split.
+    // batch it ran in (Engine::run_pool), so the result is the single-engine one whatever the split.  With one part this is
+    // Engine::fit_map: the same checks in the same order, the same draws from the same generator.
     if (n_tries < 1) throw std::runtime_error("number of attempts must be positive");
     std::vector<EmuRef> emus;
     for (const auto& v : h->views) {

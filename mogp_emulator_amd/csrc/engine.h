@@ -11,6 +11,7 @@
 #include <map>
 #include <vector>
 
+#include "devmem.h"
 #include "hostmath.h"
 #include "launch.h"
 
@@ -154,12 +155,13 @@ class Engine {
   void factor_prebuilt(const std::function<void(const BatchView&)>& fill, std::vector<int>& info);
   const double* linv_buffer() const { return dLinv; }
 
-  hipStream_t stream = nullptr;      // main stream: covariance build, trailing updates, everything else
-  hipStream_t pstream = nullptr;     // look-ahead stream: panel factorisations
-  std::vector<hipEvent_t> evPanel, evUpd;
-  std::vector<hipStream_t> gstreams;  // extra streams for independent emulator groups
-  hipEvent_t evReady = nullptr;
-  hipEvent_t evGroup[15] = {};
+  // (streams and events are declared in front of every buffer: members go in reverse order, so the streams are destroyed last)
+  Stream stream;                     // main stream: covariance build, trailing updates, everything else
+  Stream pstream;                    // look-ahead stream: panel factorisations
+  std::vector<Event> evPanel, evUpd;
+  std::vector<Stream> gstreams;      // extra streams for independent emulator groups
+  Event evReady;
+  Event evGroup[15];
 
  private:
   void upload_params(const std::vector<int>& ids);
@@ -188,41 +190,40 @@ class Engine {
                              const double* discrepancy, bool include_nugget, const std::function<void(const double*, int, int, int)>& tail);
   void ensure_predict_scratch(int nb, int MC);
 
-  double *dX = nullptr, *dP = nullptr, *dT = nullptr, *dA = nullptr, *dLinv = nullptr, *dKinv = nullptr, *dAlpha = nullptr;
-  uint32_t* sigU1 = nullptr;     // signal word of the stream memory operations of the look-ahead schedule (hipMallocSignalMemory)
+  DevBuf<double> dX, dP, dT, dA, dLinv, dKinv, dAlpha;
+  // signal word of the stream memory operations of the look-ahead schedule.  The one raw pointer of the engine: signal memory comes from
+  // hipExtMallocWithFlags(hipMallocSignalMemory), not from the allocator behind DevBuf, and is freed in ~Engine.
+  uint32_t* sigU1 = nullptr;
   uint32_t sig_epoch = 1;
   bool can_waitval = false;      // hipDeviceAttributeCanUseStreamWaitValue of the engine's device
   int device = 0;                // HIP device the engine was created on
   // one-launch Cholesky (kernels_mchol.hip): task table, control words, per-column packs
-  int* dMcTable = nullptr;       // the task order of one emulator (mchol_task_table)
+  DevBuf<int> dMcTable;          // the task order of one emulator (mchol_task_table)
   int mc_ntasks = 0;
-  unsigned* dMcCtrl = nullptr;
-  size_t mc_ctrl_ints = 0;
+  DevBuf<unsigned> dMcCtrl;
   int mc_slots = 0;              // batch slots dMcCtrl / dMcPacks are sized for (grown to the largest one-launch batch seen)
-  double* dMcPacks = nullptr;
+  DevBuf<double> dMcPacks;
   bool mc_used = false;          // the last factorisation of this engine went through the one-launch kernel (its abort word is live)
   bool mc_force_legacy = false;  // transient: repeat a factorisation with a multi-launch schedule after an abort
   int n_cu = 256;
-  int* dBsStatus = nullptr;      // time-out words of the one-launch back substitution (one per emulator), compared with bs_epoch
+  DevBuf<int> dBsStatus;         // time-out words of the one-launch back substitution (one per emulator), compared with bs_epoch
   int bs_epoch = 0;
-  double *dRes = nullptr, *hRes = nullptr;   // per emulator [log-det, status, Gram matrix]: device buffer and its pinned host mirror
-  double *dGradOut = nullptr, *dGradPartial = nullptr;
-  int *dInfo = nullptr, *dIdx = nullptr;
-  double* dLpack = nullptr;
-  double *dH = nullptr, *dZ = nullptr, *dM = nullptr;
+  DevBuf<double> dRes;           // per emulator [log-det, status, Gram matrix] ...
+  PinnedBuf<double> hRes;        // ... and its pinned host mirror
+  DevBuf<double> dGradOut, dGradPartial;
+  DevBuf<int> dInfo, dIdx;
+  DevBuf<double> dLpack;
+  DevBuf<double> dH, dZ, dM;
   // nugget="pivot": per-emulator inputs in pivot order (B*n*D), pivot order (B*n), rank (B), scratch (B*2*NP)
-  double *dXp = nullptr, *dPivWork = nullptr;
-  int *dPerm = nullptr, *dRank = nullptr;
+  DevBuf<double> dXp, dPivWork;
+  DevBuf<int> dPerm, dRank;
   std::vector<int> hPerm;
-  std::map<int, double*> w2;     // emulator -> (n - rank) x LD rows of L^-1 of the skipped pivots (gradient path)
-  void drop_w2(int i);
+  std::map<int, DevBuf<double>> w2;     // emulator -> (n - rank) x LD rows of L^-1 of the skipped pivots (gradient path)
   std::vector<double> hH;        // q x n design-matrix columns      // packed transposed diagonal block + reciprocal diagonal (potf2 -> trsm)
-  double* hP = nullptr;          // pinned host copy of the parameter blocks (B * PS doubles)
+  PinnedBuf<double> hP;          // pinned host copy of the parameter blocks (B * PS doubles)
   // predict scratch
-  double *dXs = nullptr, *dKs = nullptr, *dMean = nullptr, *dVar = nullptr, *dVarPartial = nullptr, *dDeriv = nullptr;
-  size_t capXs = 0, capKs = 0, capMean = 0, capVar = 0, capVarPartial = 0, capDeriv = 0;
-  double *dMeanFin = nullptr, *dMeanAux = nullptr;   // finished means when the dot products have their own rows; staging of the mean-function terms
-  size_t capMeanFin = 0, capMeanAux = 0;
+  DevBuf<double> dXs, dKs, dMean, dVar, dVarPartial, dDeriv;
+  DevBuf<double> dMeanFin, dMeanAux;   // finished means when the dot products have their own rows; staging of the mean-function terms
   std::mt19937_64 rng;
 };
 

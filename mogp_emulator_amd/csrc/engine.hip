@@ -32,13 +32,14 @@ ScheduleOverride& schedule_override() {
 // ---------------------------------------------------------------------------------------------
 namespace {
 struct ProfRec {
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
+  std::vector<std::pair<Event, Event>> ev;
   double flops = 0., bytes = 0., ms_done = 0.;
   long long launches = 0;
-  hipEvent_t pending = nullptr;
+  Event pending;
 };
 bool g_prof_on = false;
-std::map<std::string, ProfRec> g_prof;
+// (never destroyed: events that are still registered at exit must not be handed back to a runtime that is shutting down)
+std::map<std::string, ProfRec>& g_prof = *new std::map<std::string, ProfRec>();
 std::mutex g_prof_mu;
 }  // namespace
 
@@ -46,21 +47,20 @@ void prof_begin(const char* tag, hipStream_t s) {
   if (!g_prof_on) return;
   std::lock_guard<std::mutex> lk(g_prof_mu);
   ProfRec& r = g_prof[tag];
-  hipEvent_t e;
-  if (hipEventCreate(&e) != hipSuccess) return;
+  Event e = try_make_timing_event();
+  if (!e) return;
   hipEventRecord(e, s);
-  r.pending = e;
+  r.pending = std::move(e);
 }
 void prof_end(const char* tag, hipStream_t s, double flops, double bytes) {
   if (!g_prof_on) return;
   std::lock_guard<std::mutex> lk(g_prof_mu);
   ProfRec& r = g_prof[tag];
   if (!r.pending) return;
-  hipEvent_t e;
-  if (hipEventCreate(&e) != hipSuccess) return;
+  Event e = try_make_timing_event();
+  if (!e) return;
   hipEventRecord(e, s);
-  r.ev.emplace_back(r.pending, e);
-  r.pending = nullptr;
+  r.ev.emplace_back(std::move(r.pending), std::move(e));
   r.flops += flops;
   r.bytes += bytes;
   r.launches += 1;
@@ -96,18 +96,13 @@ long long prof_counter(const char* name) {
   if (s == "replica_engines_reused") return g_rep_reused.load();          // multi-start fits that took the cached replica engine
   // replica slots whose inputs went from pivot order back to training order when they took another run's emulator or another fit
   if (s == "replica_inputs_restored") return g_inputs_restored.load();
+  if (s == "device_bytes_live") return g_device_bytes_live.load();       // device bytes held by DevBuf objects right now (devmem.h)
   if (s == "replica_pool_us") return g_rep_pool_us.load();               // ... from there to the end of fit_map's replica block (pool + its destruction excluded)
   return -1;
 }
 bool prof_is_on() { return g_prof_on; }
 void prof_reset() {
   std::lock_guard<std::mutex> lk(g_prof_mu);
-  for (auto& kv : g_prof) {
-    for (auto& p : kv.second.ev) {
-      hipEventDestroy(p.first);
-      hipEventDestroy(p.second);
-    }
-  }
   g_prof.clear();
 }
 bool prof_get(const char* tag, double* ms, long long* launches, double* flops, double* bytes) {
@@ -120,8 +115,6 @@ bool prof_get(const char* tag, double* ms, long long* launches, double* flops, d
     float t = 0.f;
     hipEventElapsedTime(&t, p.first, p.second);
     r.ms_done += t;
-    hipEventDestroy(p.first);
-    hipEventDestroy(p.second);
   }
   r.ev.clear();
   *ms = r.ms_done;
@@ -133,20 +126,6 @@ bool prof_get(const char* tag, double* ms, long long* launches, double* flops, d
 
 // ---------------------------------------------------------------------------------------------
 static int roundup(int x, int m) { return (x + m - 1) / m * m; }
-
-template <class T>
-static T* dalloc(size_t count) {
-  T* p = nullptr;
-  HIPCK(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(count, 1) * sizeof(T)));
-  return p;
-}
-template <class T>
-static void grow(T*& p, size_t& cap, size_t need) {
-  if (need <= cap) return;
-  if (p) HIPCK(hipFree(p));
-  p = dalloc<T>(need);
-  cap = need;
-}
 
 Engine::Engine(const double* X, int n_, int D_, const double* targets, int B_, unsigned testing_size_, const MeanFunc& mean_,
                int kernel_type_, int nug_type, double nug_size, bool analytic_mean)
@@ -190,38 +169,39 @@ Engine::Engine(const double* X, int n_, int D_, const double* targets, int B_, u
     can_waitval = hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&ok, hipDeviceAttributeCanUseStreamWaitValue, dev) == hipSuccess && ok != 0;
     device = dev;
   }
-  HIPCK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-  HIPCK(hipEventCreateWithFlags(&evReady, hipEventDisableTiming));
-  for (auto& e : evGroup) HIPCK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  // (no try / catch: when one of these throws, the members built so far are destroyed by the language)
+  stream = make_stream(hipStreamNonBlocking);
+  evReady = make_event(hipEventDisableTiming);
+  for (auto& e : evGroup) e = make_event(hipEventDisableTiming);
   {
     int lo = 0, hi = 0;   // numerically lower = higher priority
     HIPCK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-    HIPCK(hipStreamCreateWithPriority(&pstream, hipStreamNonBlocking, hi));
+    pstream = make_stream(hipStreamNonBlocking, hi);
   }
-  dX = dalloc<double>((size_t)n * D);
-  dP = dalloc<double>((size_t)B * PS);
-  dT = dalloc<double>((size_t)B * n);
-  dA = dalloc<double>((size_t)B * MS);
+  dX.reserve((size_t)n * D);
+  dP.reserve((size_t)B * PS);
+  dT.reserve((size_t)B * n);
+  dA.reserve((size_t)B * MS);
   RA = (R > 1) ? R + 1 : 1;
-  dAlpha = dalloc<double>((size_t)B * RA * LD);
+  dAlpha.reserve((size_t)B * RA * LD);
   if (R > 1) {
-    dZ = dalloc<double>((size_t)B * R * LD);
-    dM = dalloc<double>((size_t)B * (RMAX + 1) * RMAX);
+    dZ.reserve((size_t)B * R * LD);
+    dM.reserve((size_t)B * (RMAX + 1) * RMAX);
     // design matrix columns: row c of mean_deriv = d mean / d beta_c = basis function c evaluated at X
     hH.assign((size_t)q * n, 0.);
     std::vector<double> dummy(q, 0.);
     mean.mean_deriv(X, n, D, dummy.data(), q, hH.data());
-    dH = dalloc<double>(hH.size());
+    dH.reserve(hH.size());
     HIPCK(hipMemcpy(dH, hH.data(), hH.size() * sizeof(double), hipMemcpyHostToDevice));
   }
-  dRes = dalloc<double>((size_t)B * RES_STRIDE);
-  HIPCK(hipHostMalloc(reinterpret_cast<void**>(&hRes), (size_t)B * RES_STRIDE * sizeof(double), hipHostMallocDefault));
-  dInfo = dalloc<int>(B);
-  dIdx = dalloc<int>(B);
-  dLpack = dalloc<double>((size_t)B * lpack128_doubles_per_emulator());
+  dRes.reserve((size_t)B * RES_STRIDE);
+  hRes = PinnedBuf<double>((size_t)B * RES_STRIDE);
+  dInfo.reserve(B);
+  dIdx.reserve(B);
+  dLpack.reserve((size_t)B * lpack128_doubles_per_emulator());
   // (pinned: the parameter block goes up in front of every evaluation, and an asynchronous copy from pageable memory is staged by the runtime)
-  HIPCK(hipHostMalloc(reinterpret_cast<void**>(&hP), (size_t)B * PS * sizeof(double), hipHostMallocDefault));
-  std::fill(hP, hP + (size_t)B * PS, 0.);
+  hP = PinnedBuf<double>((size_t)B * PS);
+  std::fill(hP.get(), hP.get() + (size_t)B * PS, 0.);
   HIPCK(hipMemcpy(dX, hX.data(), hX.size() * sizeof(double), hipMemcpyHostToDevice));
   // residual targets for parameter-free means are fixed once
   std::vector<double> res(hT);
@@ -231,26 +211,9 @@ Engine::Engine(const double* X, int n_, int D_, const double* targets, int B_, u
   rng.seed(fit_options().seed ? fit_options().seed : std::random_device{}());
 }
 
+// every buffer, stream and event is a member that releases itself; the signal word is the one exception (engine.h)
 Engine::~Engine() {
-  for (void* p : {(void*)dX, (void*)dP, (void*)dT, (void*)dA, (void*)dLinv, (void*)dKinv, (void*)dAlpha, (void*)dRes,
-                  (void*)dGradOut, (void*)dGradPartial, (void*)dInfo, (void*)dIdx, (void*)dXs, (void*)dKs, (void*)dMean, (void*)dVar,
-                  (void*)dVarPartial, (void*)dDeriv, (void*)dLpack, (void*)dH, (void*)dZ, (void*)dM, (void*)dXp, (void*)dPivWork,
-                  (void*)dPerm, (void*)dRank, (void*)dMeanFin, (void*)dMeanAux})
-    if (p) hipFree(p);
-  if (hRes) hipHostFree(hRes);
-  if (hP) hipHostFree(hP);
-  if (dBsStatus) hipFree(dBsStatus);
-  for (void* p : {(void*)dMcTable, (void*)dMcCtrl, (void*)dMcPacks})
-    if (p) hipFree(p);
   if (sigU1) hipFree(sigU1);
-  for (auto& kv : w2) hipFree(kv.second);
-  for (auto st : gstreams) hipStreamDestroy(st);
-  if (evReady) hipEventDestroy(evReady);
-  for (auto e : evGroup) if (e) hipEventDestroy(e);
-  for (auto e : evPanel) hipEventDestroy(e);
-  for (auto e : evUpd) hipEventDestroy(e);
-  if (pstream) hipStreamDestroy(pstream);
-  if (stream) hipStreamDestroy(stream);
 }
 
 double Engine::nugget_size(int i) const {
@@ -368,17 +331,17 @@ void Engine::panel(const BatchView& v, int o, int w, hipStream_t st) {
 // trailing update instead of in front of it.
 void Engine::ensure_pivot_buffers() {
   if (dXp) return;
-  dPerm = dalloc<int>((size_t)B * n);
-  dRank = dalloc<int>(B);
-  dPivWork = dalloc<double>((size_t)B * pstrf_work_doubles(NP));
+  dPerm.reserve((size_t)B * n);
+  dRank.reserve(B);
+  dPivWork.reserve((size_t)B * pstrf_work_doubles(NP));
   hPerm.resize((size_t)B * n);
   for (int i = 0; i < B; ++i)
     for (int k = 0; k < n; ++k) hPerm[(size_t)i * n + k] = k;
-  double* xp = dalloc<double>((size_t)B * n * D);
+  DevBuf<double> xp((size_t)B * n * D);
   for (int i = 0; i < B; ++i)
     HIPCK(hipMemcpyAsync(xp + (size_t)i * n * D, dX, (size_t)n * D * sizeof(double), hipMemcpyDeviceToDevice, stream));
   HIPCK(hipStreamSynchronize(stream));
-  dXp = xp;
+  dXp = std::move(xp);
 }
 
 // nugget="pivot" (cholesky_factor(K, nugget, "pivot"), linalg/cholesky.py:182-184): K without nugget, factored with
@@ -524,7 +487,7 @@ void Engine::factorize_blocked(const std::vector<int>& ids, std::vector<int>& in
       const std::vector<int> ta = mchol_task_table(NP, true);
       mc_ntasks = (int)tb.size();
       tb.insert(tb.end(), ta.begin(), ta.end());              // [in-order | band-ahead]: launch_mchol picks
-      dMcTable = dalloc<int>(tb.size());
+      dMcTable.reserve(tb.size());
       HIPCK(hipMemcpy(dMcTable, tb.data(), tb.size() * sizeof(int), hipMemcpyHostToDevice));
     }
     if (nb > mc_slots) {
@@ -532,18 +495,16 @@ void Engine::factorize_blocked(const std::vector<int>& ids, std::vector<int>& in
       // few-emulator retry on an engine whose full batch stays on the multi-launch schedules (B * NP / 128 >= 16384) would otherwise
       // allocate B packs per block column (4.7 GB at B = 2000, n = 2000)
       HIPCK(hipStreamSynchronize(stream));
-      if (dMcCtrl) HIPCK(hipFree(dMcCtrl));
-      if (dMcPacks) HIPCK(hipFree(dMcPacks));
-      dMcCtrl = nullptr;
-      dMcPacks = nullptr;
+      mc_slots = 0;                    // (both go before either comes back; a failed allocation leaves "sized for nothing")
+      dMcCtrl.reset();
+      dMcPacks.reset();
+      dMcCtrl.reserve(mchol_ctrl_ints(NP, nb));
+      dMcPacks.reserve(mchol_pack_doubles(NP, nb));
       mc_slots = nb;
-      mc_ctrl_ints = mchol_ctrl_ints(NP, mc_slots);
-      dMcCtrl = dalloc<unsigned>(mc_ctrl_ints);
-      dMcPacks = dalloc<double>(mchol_pack_doubles(NP, mc_slots));
     }
     // (the info words and the kernel's control words are cleared by the K build: two memset commands less in front of a small fit)
     ZeroRanges zr;
-    zr.p[0] = reinterpret_cast<unsigned*>(dInfo); zr.n[0] = (unsigned)B;
+    zr.p[0] = reinterpret_cast<unsigned*>(dInfo.get()); zr.n[0] = (unsigned)B;
     zr.p[1] = dMcCtrl; zr.n[1] = (unsigned)mchol_ctrl_ints(NP, nb);
     build_cov(v, zr);
     launch_mchol(v, dMcCtrl, mchol_ctrl_ints(NP, nb), dMcTable, mc_ntasks, dMcPacks, dInfo, n_cu, stream, true);
@@ -573,12 +534,9 @@ void Engine::factorize_blocked(const std::vector<int>& ids, std::vector<int>& in
     std::vector<int> cols;
     for (int o = 0; o < n + R; o += TILE) cols.push_back(o);
     const int K = (int)cols.size();
-    while ((int)evPanel.size() < K + 1) {
-      hipEvent_t a, b;
-      HIPCK(hipEventCreateWithFlags(&a, hipEventDisableTiming));
-      HIPCK(hipEventCreateWithFlags(&b, hipEventDisableTiming));
-      evPanel.push_back(a);
-      evUpd.push_back(b);
+    while ((int)evUpd.size() < K + 1) {
+      evPanel.push_back(make_event(hipEventDisableTiming));
+      evUpd.push_back(make_event(hipEventDisableTiming));
     }
     constexpr long tail_threshold = 1100L;
     auto long_update = [&](int o, int k1, hipStream_t st) {
@@ -641,9 +599,7 @@ void Engine::factorize_blocked(const std::vector<int>& ids, std::vector<int>& in
     constexpr long tail_threshold = 1100L;
     const int G = ovr.single_stream ? 1 : std::min(2, std::max(1, nb / 8));
     while ((int)gstreams.size() < G - 1) {
-      hipStream_t st;
-      HIPCK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-      gstreams.push_back(st);
+      gstreams.push_back(make_stream(hipStreamNonBlocking));
     }
     HIPCK(hipMemsetAsync(dInfo, 0, B * sizeof(int), stream));
     build_cov(v);
@@ -686,12 +642,9 @@ void Engine::factorize_blocked(const std::vector<int>& ids, std::vector<int>& in
   constexpr int OUTERW = 512;
   for (int o = 0; o < n + R; o += OUTERW) starts.push_back(o);
   const int K = (int)starts.size();
-  while ((int)evPanel.size() < K + 1) {
-    hipEvent_t a, b;
-    HIPCK(hipEventCreateWithFlags(&a, hipEventDisableTiming));
-    HIPCK(hipEventCreateWithFlags(&b, hipEventDisableTiming));
-    evPanel.push_back(a);
-    evUpd.push_back(b);
+  while ((int)evUpd.size() < K + 1) {
+    evPanel.push_back(make_event(hipEventDisableTiming));
+    evUpd.push_back(make_event(hipEventDisableTiming));
   }
   auto width = [&](int k) { return std::min(OUTERW, NP - starts[k]); };
   HIPCK(hipEventRecord(evUpd[K], stream));                 // K build done
@@ -746,7 +699,7 @@ void Engine::eval(const std::vector<int>& ids, const std::vector<const double*>&
       // the chain on stream `st` (status words and sentinel rows prepared on the same stream, in front of it)
       auto launch_chain = [&](hipStream_t st) {
         if (!dBsStatus) {
-          dBsStatus = dalloc<int>(B);
+          dBsStatus.reserve(B);
           HIPCK(hipMemsetAsync(dBsStatus, 0, B * sizeof(int), st));
         }
         if (bs_epoch > 0x7FFFFF00) {                       // the status words are compared with the epoch: start over before it wraps
@@ -1034,10 +987,10 @@ void Engine::ensure_linv(const std::vector<int>& ids) {
   }
   if (need.empty()) return;
   if (!dLinv) {
-    dLinv = dalloc<double>((size_t)B * MS);
-    dKinv = dalloc<double>((size_t)B * MS);
-    dGradOut = dalloc<double>((size_t)B * (D + 3));
-    dGradPartial = dalloc<double>((size_t)B * grad_num_tiles(n) * (D + 3));
+    dKinv.reserve((size_t)B * MS);
+    dGradOut.reserve((size_t)B * (D + 3));
+    dGradPartial.reserve((size_t)B * grad_num_tiles(n) * (D + 3));
+    dLinv.reserve((size_t)B * MS);      // (last: it is the one that says "all four are there")
   }
   upload_idx(need);
   BatchView v = view((int)need.size());
@@ -1046,13 +999,6 @@ void Engine::ensure_linv(const std::vector<int>& ids) {
     gp[i].linv = true;
     gp[i].kinv = false;   // trtri used Kinv as scratch
   }
-}
-
-void Engine::drop_w2(int i) {
-  auto it = w2.find(i);
-  if (it == w2.end()) return;
-  hipFree(it->second);
-  w2.erase(it);
 }
 
 // for_gradient: an emulator whose pivoted factorisation skipped rows gets K^-1 WITHOUT the rows of L^-1 of the skipped
@@ -1071,9 +1017,9 @@ void Engine::ensure_kinv(const std::vector<int>& ids, bool for_gradient) {
   for (int i : need)
     if (for_gradient && gp[i].permuted && gp[i].rank < n) {
       const int m = n - gp[i].rank;
-      drop_w2(i);
-      double* buf = dalloc<double>((size_t)m * LD);
-      w2[i] = buf;
+      w2.erase(i);                              // (first: the old rows go before the new ones come)
+      DevBuf<double>& buf = w2[i];
+      buf.reserve((size_t)m * LD);
       double* rows = dLinv + (size_t)i * MS + (size_t)gp[i].rank * LD;
       HIPCK(hipMemcpy2DAsync(buf, rowb, rows, rowb, wb, m, hipMemcpyDeviceToDevice, stream));
       HIPCK(hipMemset2DAsync(rows, rowb, 0, wb, m, stream));
@@ -1102,10 +1048,10 @@ void Engine::grad_current(const std::vector<int>& ids, double* grad, int grad_ld
   for (int i : ids)
     if (gp[i].kinv_split) {
       const int m = n - gp[i].rank;
-      double* part = dalloc<double>((size_t)m * ((n + 127) / 128) * (D + 1));
+      DevBuf<double> part((size_t)m * ((n + 127) / 128) * (D + 1));
+      SyncOnUnwind drained{stream};
       launch_grad_lowrank(v, i, w2.at(i), m, part, dGradOut, stream);
       HIPCK(hipStreamSynchronize(stream));
-      hipFree(part);
     }
   const int NQ = D + 3;
   std::vector<double> out((size_t)B * NQ);
@@ -1153,10 +1099,10 @@ static double ks_budget_bytes() {
 }
 
 void Engine::ensure_predict_scratch(int nb, int MC) {
-  grow(dKs, capKs, (size_t)nb * MC * LD);
+  dKs.reserve((size_t)nb * MC * LD);
   // partial sums per row tile
   const size_t nti = (n + 127) / 128;
-  grow(dVarPartial, capVarPartial, (size_t)nb * nti * MC);
+  dVarPartial.reserve((size_t)nb * nti * MC);
 }
 
 void Engine::predict(const std::vector<int>& ids, const double* Xs, int m, bool xs_on_device, double* means, double* vars, long out_ld,
@@ -1170,7 +1116,7 @@ void Engine::predict(const std::vector<int>& ids, const double* Xs, int m, bool 
   BatchView v = view(nb);
   const double* dXsrc = Xs;
   if (!xs_on_device) {
-    grow(dXs, capXs, (size_t)m * D);
+    dXs.reserve((size_t)m * D);
     HIPCK(hipMemcpyAsync(dXs, Xs, (size_t)m * D * sizeof(double), hipMemcpyHostToDevice, stream));
     dXsrc = dXs;
   }
@@ -1184,22 +1130,22 @@ void Engine::predict(const std::vector<int>& ids, const double* Xs, int m, bool 
   const bool want_mean = means != nullptr;       // derivatives only (mogp_*_predict_deriv): no cross covariance, no mean
   if (!want_mean && vars) throw std::runtime_error("predict: variances without means");
   if (!out_on_device && want_mean) {
-    grow(dMeanFin, capMeanFin, (size_t)nb * m);
+    dMeanFin.reserve((size_t)nb * m);
     fm = dMeanFin;
     ld = m;
     if (vars) {
-      grow(dVar, capVar, (size_t)nb * m);
+      dVar.reserve((size_t)nb * m);
       fv = dVar;
     }
   }
   if (!out_on_device && derivs) {
-    grow(dDeriv, capDeriv, (size_t)nb * m * D);
+    dDeriv.reserve((size_t)nb * m * D);
     fd = dDeriv;
   }
   double* dots = fm;
   long dots_ld = ld;
   if (R > 1 && want_mean) {
-    grow(dMean, capMean, (size_t)nb * R * m);
+    dMean.reserve((size_t)nb * R * m);
     dots = dMean;
     dots_ld = m;
   }
@@ -1210,7 +1156,7 @@ void Engine::predict(const std::vector<int>& ids, const double* Xs, int m, bool 
   double cap = budget;
   if (vars) {
     size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) cap = std::min(cap, 0.5 * ((double)free_b + (double)capKs * sizeof(double)));
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) cap = std::min(cap, 0.5 * ((double)free_b + (double)dKs.size() * sizeof(double)));
   }
   long MC = (long)(cap / ((double)nb * LD * 8.0)) / 128 * 128;
   MC = std::max<long>(128, std::min<long>(MC, MPtot));
@@ -1250,7 +1196,7 @@ void Engine::predict(const std::vector<int>& ids, const double* Xs, int m, bool 
       hi[nterm + t] = mean.powers[t];
     }
     std::memcpy(st.data() + (o_int - o_coef), hi.data(), 2 * (size_t)nterm * sizeof(int));
-    grow(dMeanAux, capMeanAux, total);
+    dMeanAux.reserve(total);
     HIPCK(hipMemcpyAsync(dMeanAux + o_coef, st.data(), st.size() * sizeof(double), hipMemcpyHostToDevice, stream));
     const int* di = reinterpret_cast<const int*>(dMeanAux + o_int);
     launch_mean_basis(dXsrc, m, D, nterm, di, di + nterm, dMeanAux + o_basis, dMeanAux + o_dbasis, stream);
@@ -1288,57 +1234,46 @@ void Engine::predict_full_cov(const std::vector<int>& ids, const double* Xs, int
   ensure_linv(ids);
   upload_idx(ids);
   BatchView v = view(nb);
-  double *dXf = nullptr, *dKf = nullptr, *dV = nullptr, *dC = nullptr, *dDots = nullptr;
-  try {
-    dXf = dalloc<double>((size_t)m * D);
-    dKf = dalloc<double>((size_t)nb * MP * LD);
-    dV = dalloc<double>((size_t)nb * NP * MP);
-    dC = dalloc<double>((size_t)nb * m * m);
-    dDots = dalloc<double>((size_t)nb * R * m);
-    HIPCK(hipMemcpyAsync(dXf, Xs, (size_t)m * D * sizeof(double), hipMemcpyHostToDevice, stream));
-    launch_cross_cov_mean(v, dXf, m, MP, dKf, dDots, m, stream);
-    launch_cov_self_batch(v, dXf, m, dC, stream);
-    launch_predict_fullcov(v, dKf, m, MP, dV, dC, stream);
-    std::vector<double> dots((size_t)nb * R * m);
-    HIPCK(hipMemcpyAsync(dots.data(), dDots, dots.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-    HIPCK(hipMemcpyAsync(covs, dC, (size_t)nb * m * m * sizeof(double), hipMemcpyDeviceToHost, stream));
-    HIPCK(hipStreamSynchronize(stream));
-    HIPCK(hipGetLastError());
-    std::vector<double> mv(m), Hs((size_t)q * m), rm((size_t)q * m), dummy(std::max(q, 1), 0.);
-    if (R > 1) mean.mean_deriv(Xs, m, D, dummy.data(), q, Hs.data());
-    for (int k = 0; k < nb; ++k) {
-      const GPState& g = gp[ids[k]];
-      const double* dk = dots.data() + (size_t)k * R * m;
-      double* mu = means + (size_t)k * m;
-      for (int j = 0; j < m; ++j) mu[j] = dk[j];
-      if (R > 1) {
-        // + h(x*)^T beta and + (LA^-1 R)^T (LA^-1 R), R = H*^T - H^T K^-1 k*   (calc_R, linalg_utils.py:123-168)
-        for (int j = 0; j < m; ++j) {
-          for (int c = 0; c < q; ++c) {
-            mu[j] += g.beta[c] * Hs[(size_t)c * m + j];
-            double s = Hs[(size_t)c * m + j] - dk[(size_t)(1 + c) * m + j];
-            for (int p = 0; p < c; ++p) s -= g.LA[c * q + p] * rm[(size_t)p * m + j];
-            rm[(size_t)c * m + j] = s / g.LA[c * q + c];
-          }
+  DevBuf<double> dXf((size_t)m * D), dKf((size_t)nb * MP * LD), dV((size_t)nb * NP * MP), dC((size_t)nb * m * m), dDots((size_t)nb * R * m);
+  HIPCK(hipMemcpyAsync(dXf, Xs, (size_t)m * D * sizeof(double), hipMemcpyHostToDevice, stream));
+  launch_cross_cov_mean(v, dXf, m, MP, dKf, dDots, m, stream);
+  launch_cov_self_batch(v, dXf, m, dC, stream);
+  launch_predict_fullcov(v, dKf, m, MP, dV, dC, stream);
+  std::vector<double> dots((size_t)nb * R * m);
+  HIPCK(hipMemcpyAsync(dots.data(), dDots, dots.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+  HIPCK(hipMemcpyAsync(covs, dC, (size_t)nb * m * m * sizeof(double), hipMemcpyDeviceToHost, stream));
+  HIPCK(hipStreamSynchronize(stream));
+  HIPCK(hipGetLastError());
+  std::vector<double> mv(m), Hs((size_t)q * m), rm((size_t)q * m), dummy(std::max(q, 1), 0.);
+  if (R > 1) mean.mean_deriv(Xs, m, D, dummy.data(), q, Hs.data());
+  for (int k = 0; k < nb; ++k) {
+    const GPState& g = gp[ids[k]];
+    const double* dk = dots.data() + (size_t)k * R * m;
+    double* mu = means + (size_t)k * m;
+    for (int j = 0; j < m; ++j) mu[j] = dk[j];
+    if (R > 1) {
+      // + h(x*)^T beta and + (LA^-1 R)^T (LA^-1 R), R = H*^T - H^T K^-1 k*   (calc_R, linalg_utils.py:123-168)
+      for (int j = 0; j < m; ++j) {
+        for (int c = 0; c < q; ++c) {
+          mu[j] += g.beta[c] * Hs[(size_t)c * m + j];
+          double s = Hs[(size_t)c * m + j] - dk[(size_t)(1 + c) * m + j];
+          for (int p = 0; p < c; ++p) s -= g.LA[c * q + p] * rm[(size_t)p * m + j];
+          rm[(size_t)c * m + j] = s / g.LA[c * q + c];
         }
-        double* Ck = covs + (size_t)k * m * m;
-        for (int i = 0; i < m; ++i)
-          for (int c = 0; c < q; ++c) {
-            const double ri = rm[(size_t)c * m + i];
-            const double* rc = rm.data() + (size_t)c * m;
-            double* row = Ck + (size_t)i * m;
-            for (int j = 0; j < m; ++j) row[j] += ri * rc[j];
-          }
-      } else if (mean.kind != 0) {
-        mean.mean_f(Xs, m, D, g.meanp.data(), n_mean(), mv.data());
-        for (int j = 0; j < m; ++j) mu[j] += mv[j];
       }
+      double* Ck = covs + (size_t)k * m * m;
+      for (int i = 0; i < m; ++i)
+        for (int c = 0; c < q; ++c) {
+          const double ri = rm[(size_t)c * m + i];
+          const double* rc = rm.data() + (size_t)c * m;
+          double* row = Ck + (size_t)i * m;
+          for (int j = 0; j < m; ++j) row[j] += ri * rc[j];
+        }
+    } else if (mean.kind != 0) {
+      mean.mean_f(Xs, m, D, g.meanp.data(), n_mean(), mv.data());
+      for (int j = 0; j < m; ++j) mu[j] += mv[j];
     }
-  } catch (...) {
-    for (double* p : {dXf, dKf, dV, dC, dDots}) if (p) hipFree(p);
-    throw;
   }
-  for (double* p : {dXf, dKf, dV, dC, dDots}) if (p) hipFree(p);
 }
 
 void Engine::implausibility_chunks(const std::vector<int>& ids, const double* Xs, int m, const double* obs, const double* obs_var,
@@ -1360,28 +1295,22 @@ void Engine::implausibility_chunks(const std::vector<int>& ids, const double* Xs
   long MC = (long)(6.0e9 / ((double)nb * LD * 8.0)) / 128 * 128;
   MC = std::max<long>(128, std::min<long>(MC, MPtot));
   ensure_predict_scratch(nb, (int)MC);
-  grow(dXs, capXs, (size_t)MC * D);
-  grow(dMean, capMean, (size_t)nb * MC);
-  grow(dVar, capVar, (size_t)nb * MC);
-  double* dPrm = dalloc<double>(prm.size());
-  try {
-    HIPCK(hipMemcpyAsync(dPrm, prm.data(), prm.size() * sizeof(double), hipMemcpyHostToDevice, stream));
-    for (int c0 = 0; c0 < m; c0 += (int)MC) {
-      const int mc = std::min<int>((int)MC, m - c0);
-      const int MPc = roundup(mc, 128);
-      HIPCK(hipMemcpyAsync(dXs, Xs + (size_t)c0 * D, (size_t)mc * D * sizeof(double), hipMemcpyHostToDevice, stream));
-      launch_cross_cov_mean(v, dXs, mc, MPc, dKs, dMean, (int)MC, stream);
-      launch_predict_var(v, dKs, mc, MPc, dVarPartial, dVar, (int)MC, n_cu, stream);
-      tail(dPrm, c0, mc, (int)MC);
-      HIPCK(hipStreamSynchronize(stream));      // dXs is re-used by the next chunk
-    }
-    HIPCK(hipGetLastError());
-  } catch (...) {
-    hipStreamSynchronize(stream);
-    hipFree(dPrm);
-    throw;
+  dXs.reserve((size_t)MC * D);
+  dMean.reserve((size_t)nb * MC);
+  dVar.reserve((size_t)nb * MC);
+  DevBuf<double> dPrm(prm.size());
+  SyncOnUnwind drained{stream};
+  HIPCK(hipMemcpyAsync(dPrm, prm.data(), prm.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+  for (int c0 = 0; c0 < m; c0 += (int)MC) {
+    const int mc = std::min<int>((int)MC, m - c0);
+    const int MPc = roundup(mc, 128);
+    HIPCK(hipMemcpyAsync(dXs, Xs + (size_t)c0 * D, (size_t)mc * D * sizeof(double), hipMemcpyHostToDevice, stream));
+    launch_cross_cov_mean(v, dXs, mc, MPc, dKs, dMean, (int)MC, stream);
+    launch_predict_var(v, dKs, mc, MPc, dVarPartial, dVar, (int)MC, n_cu, stream);
+    tail(dPrm, c0, mc, (int)MC);
+    HIPCK(hipStreamSynchronize(stream));      // dXs is re-used by the next chunk
   }
-  hipFree(dPrm);
+  HIPCK(hipGetLastError());
 }
 
 void Engine::implausibility(const std::vector<int>& ids, const double* Xs, int m, const double* obs, const double* obs_var,
@@ -1399,17 +1328,11 @@ void Engine::implausibility(const std::vector<int>& ids, const double* Xs, int m
   const int MPtot = roundup(m, 128);
   long MC = (long)(6.0e9 / ((double)nb * LD * 8.0)) / 128 * 128;
   MC = std::max<long>(128, std::min<long>(MC, MPtot));
-  double* dOut = dalloc<double>((size_t)MC);
-  try {
-    implausibility_chunks(ids, Xs, m, obs, obs_var, discrepancy, include_nugget, [&](const double* dPrm, int c0, int mc, int ld) {
-      launch_implausibility(nb, dMean, dVar, ld, mc, dPrm, rank, dOut, stream);
-      HIPCK(hipMemcpyAsync(out + c0, dOut, (size_t)mc * sizeof(double), hipMemcpyDeviceToHost, stream));
-    });
-  } catch (...) {
-    hipFree(dOut);
-    throw;
-  }
-  hipFree(dOut);
+  DevBuf<double> dOut((size_t)MC);
+  implausibility_chunks(ids, Xs, m, obs, obs_var, discrepancy, include_nugget, [&](const double* dPrm, int c0, int mc, int ld) {
+    launch_implausibility(nb, dMean, dVar, ld, mc, dPrm, rank, dOut, stream);
+    HIPCK(hipMemcpyAsync(out + c0, dOut, (size_t)mc * sizeof(double), hipMemcpyDeviceToHost, stream));
+  });
 }
 
 void Engine::implausibility_top(const std::vector<int>& ids, const double* Xs, int m, const double* obs, const double* obs_var,
@@ -1426,22 +1349,17 @@ void Engine::implausibility_top(const std::vector<int>& ids, const double* Xs, i
   const int MPtot = roundup(m, 128);
   long MC = (long)(6.0e9 / ((double)nb * LD * 8.0)) / 128 * 128;
   MC = std::max<long>(128, std::min<long>(MC, MPtot));
-  double* dTop = local ? nullptr : dalloc<double>((size_t)keep * MC);
-  try {
-    implausibility_chunks(ids, Xs, m, obs, obs_var, discrepancy, include_nugget, [&](const double* dPrm, int c0, int mc, int ld) {
-      if (local) {
-        launch_implausibility_top(nb, dMean, dVar, ld, mc, dPrm, keep, out + c0, out_ld, stream);
-        return;
-      }
-      launch_implausibility_top(nb, dMean, dVar, ld, mc, dPrm, keep, dTop, MC, stream);
-      for (int r = 0; r < keep; ++r)
-        HIPCK(hipMemcpyPeerAsync(out + (size_t)r * out_ld + c0, out_device, dTop + (size_t)r * MC, device, (size_t)mc * sizeof(double), stream));
-    });
-  } catch (...) {
-    if (dTop) hipFree(dTop);
-    throw;
-  }
-  if (dTop) hipFree(dTop);
+  DevBuf<double> dTop;
+  if (!local) dTop.reserve((size_t)keep * MC);
+  implausibility_chunks(ids, Xs, m, obs, obs_var, discrepancy, include_nugget, [&](const double* dPrm, int c0, int mc, int ld) {
+    if (local) {
+      launch_implausibility_top(nb, dMean, dVar, ld, mc, dPrm, keep, out + c0, out_ld, stream);
+      return;
+    }
+    launch_implausibility_top(nb, dMean, dVar, ld, mc, dPrm, keep, dTop, MC, stream);
+    for (int r = 0; r < keep; ++r)
+      HIPCK(hipMemcpyPeerAsync(out + (size_t)r * out_ld + c0, out_device, dTop + (size_t)r * MC, device, (size_t)mc * sizeof(double), stream));
+  });
 }
 
 // First-order and total-effect Sobol indices of the predictive means (kernels_sobol.hip has the estimators).  Pass 1 predicts A and B
@@ -1477,68 +1395,52 @@ void Engine::sobol(const std::vector<int>& ids, const double* A, const double* B
   const int groups = sobol_groups(CH);
   const long nslot = nchunks * groups;
   const size_t n_part = std::max<size_t>((size_t)nb * SOBOL_MAX_GROUPS, (size_t)nb * D * nslot * 2);
-  double *dS = nullptr, *dF = nullptr, *dV = nullptr, *dPick = nullptr, *dFab = nullptr, *dPart = nullptr, *dStats = nullptr, *dSums = nullptr;
-  auto release = [&] {
-    for (double* p : {dS, dF, dV, dPick, dFab, dPart, dStats, dSums})
-      if (p) hipFree(p);
-  };
-  try {
-    dS = dalloc<double>((size_t)M2 * D);
-    dF = dalloc<double>((size_t)nb * M2);
-    if (unc) dV = dalloc<double>((size_t)nb * M2);
-    dPick = dalloc<double>((size_t)CH * D);
-    dFab = dalloc<double>((size_t)nb * CH);
-    dPart = dalloc<double>(n_part);
-    dStats = dalloc<double>((size_t)nb * SOBOL_STATS);
-    dSums = dalloc<double>((size_t)nb * D * 2);
-    std::vector<double> stats((size_t)nb * SOBOL_STATS, 0.);
-    // the nugget predict() adds to the variances on the host (not with nugget="pivot", GaussianProcess.py:915)
-    for (int k = 0; k < nb; ++k)
-      stats[(size_t)k * SOBOL_STATS + 3] = (include_nugget && gp[ids[k]].nug_type != NUG_PIVOT) ? nugget_size(ids[k]) : 0.;
-    HIPCK(hipMemcpyAsync(dStats, stats.data(), stats.size() * sizeof(double), hipMemcpyHostToDevice, stream));
-    HIPCK(hipMemcpyAsync(dS, A, (size_t)N * D * sizeof(double), hipMemcpyHostToDevice, stream));
-    HIPCK(hipMemcpyAsync(dS + (size_t)N * D, Bs, (size_t)N * D * sizeof(double), hipMemcpyHostToDevice, stream));
-    // pass 1: fA | fB, then f0 and V (two passes over the resident means), and the mean predictive variance
-    predict(ids, dS, (int)M2, true, dF, dV, M2, true, nullptr);
-    launch_sobol_row_mean(nb, 0, dF, M2, M2, nullptr, 0, dPart, dStats + 0, SOBOL_STATS, stream);
-    launch_sobol_row_mean(nb, 1, dF, M2, M2, dStats + 0, SOBOL_STATS, dPart, dStats + 1, SOBOL_STATS, stream);
-    if (unc) launch_sobol_row_mean(nb, 2, dV, M2, M2, dStats + 3, SOBOL_STATS, dPart, dStats + 2, SOBOL_STATS, stream);
-    // pass 2
-    for (int col = 0; col < D; ++col) {
-      for (long c = 0; c < nchunks; ++c) {
-        const long r0 = c * CH;
-        const int rows = (int)std::min<long>(CH, N - r0);
-        launch_sobol_pick_freeze(dS, dS + (size_t)N * D, r0, rows, D, col, dPick, stream);
-        predict(ids, dPick, rows, true, dFab, nullptr, CH, true, nullptr);
-        launch_sobol_pair_sum(nb, dF + r0, dF + N + r0, M2, dFab, CH, rows, dStats, SOBOL_STATS, dPart, D, col, nslot, c * groups, groups,
-                              stream);
-      }
+  DevBuf<double> dS((size_t)M2 * D), dF((size_t)nb * M2), dV, dPick((size_t)CH * D), dFab((size_t)nb * CH), dPart(n_part),
+      dStats((size_t)nb * SOBOL_STATS), dSums((size_t)nb * D * 2);
+  if (unc) dV.reserve((size_t)nb * M2);
+  SyncOnUnwind drained{stream};
+  std::vector<double> stats((size_t)nb * SOBOL_STATS, 0.);
+  // the nugget predict() adds to the variances on the host (not with nugget="pivot", GaussianProcess.py:915)
+  for (int k = 0; k < nb; ++k)
+    stats[(size_t)k * SOBOL_STATS + 3] = (include_nugget && gp[ids[k]].nug_type != NUG_PIVOT) ? nugget_size(ids[k]) : 0.;
+  HIPCK(hipMemcpyAsync(dStats, stats.data(), stats.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+  HIPCK(hipMemcpyAsync(dS, A, (size_t)N * D * sizeof(double), hipMemcpyHostToDevice, stream));
+  HIPCK(hipMemcpyAsync(dS + (size_t)N * D, Bs, (size_t)N * D * sizeof(double), hipMemcpyHostToDevice, stream));
+  // pass 1: fA | fB, then f0 and V (two passes over the resident means), and the mean predictive variance
+  predict(ids, dS, (int)M2, true, dF, dV, M2, true, nullptr);
+  launch_sobol_row_mean(nb, 0, dF, M2, M2, nullptr, 0, dPart, dStats + 0, SOBOL_STATS, stream);
+  launch_sobol_row_mean(nb, 1, dF, M2, M2, dStats + 0, SOBOL_STATS, dPart, dStats + 1, SOBOL_STATS, stream);
+  if (unc) launch_sobol_row_mean(nb, 2, dV, M2, M2, dStats + 3, SOBOL_STATS, dPart, dStats + 2, SOBOL_STATS, stream);
+  // pass 2
+  for (int col = 0; col < D; ++col) {
+    for (long c = 0; c < nchunks; ++c) {
+      const long r0 = c * CH;
+      const int rows = (int)std::min<long>(CH, N - r0);
+      launch_sobol_pick_freeze(dS, dS + (size_t)N * D, r0, rows, D, col, dPick, stream);
+      predict(ids, dPick, rows, true, dFab, nullptr, CH, true, nullptr);
+      launch_sobol_pair_sum(nb, dF + r0, dF + N + r0, M2, dFab, CH, rows, dStats, SOBOL_STATS, dPart, D, col, nslot, c * groups, groups,
+                            stream);
     }
-    launch_sobol_pair_final(nb * D, dPart, nslot, 1.0 / (double)N, dSums, stream);
-    std::vector<double> sums((size_t)nb * D * 2);
-    HIPCK(hipMemcpyAsync(stats.data(), dStats, stats.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-    HIPCK(hipMemcpyAsync(sums.data(), dSums, sums.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-    HIPCK(hipStreamSynchronize(stream));
-    HIPCK(hipGetLastError());
-    const double nan = std::numeric_limits<double>::quiet_NaN();
-    for (int k = 0; k < nb; ++k) {
-      const double* st = stats.data() + (size_t)k * SOBOL_STATS;
-      const double V = st[1];
-      mean_out[k] = st[0];
-      var_out[k] = V;
-      if (emvar_out) emvar_out[k] = unc ? st[2] : nan;
-      for (int d = 0; d < D; ++d) {
-        // a constant emulator (V == 0) has no indices: NaN, not an error
-        S[(size_t)k * D + d] = V > 0. ? sums[((size_t)k * D + d) * 2] / V : nan;
-        ST[(size_t)k * D + d] = V > 0. ? sums[((size_t)k * D + d) * 2 + 1] / (2. * V) : nan;
-      }
-    }
-  } catch (...) {
-    hipStreamSynchronize(stream);
-    release();
-    throw;
   }
-  release();
+  launch_sobol_pair_final(nb * D, dPart, nslot, 1.0 / (double)N, dSums, stream);
+  std::vector<double> sums((size_t)nb * D * 2);
+  HIPCK(hipMemcpyAsync(stats.data(), dStats, stats.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+  HIPCK(hipMemcpyAsync(sums.data(), dSums, sums.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+  HIPCK(hipStreamSynchronize(stream));
+  HIPCK(hipGetLastError());
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  for (int k = 0; k < nb; ++k) {
+    const double* st = stats.data() + (size_t)k * SOBOL_STATS;
+    const double V = st[1];
+    mean_out[k] = st[0];
+    var_out[k] = V;
+    if (emvar_out) emvar_out[k] = unc ? st[2] : nan;
+    for (int d = 0; d < D; ++d) {
+      // a constant emulator (V == 0) has no indices: NaN, not an error
+      S[(size_t)k * D + d] = V > 0. ? sums[((size_t)k * D + d) * 2] / V : nan;
+      ST[(size_t)k * D + d] = V > 0. ? sums[((size_t)k * D + d) * 2 + 1] / (2. * V) : nan;
+    }
+  }
 }
 
 void Engine::loo_variance(int i, double* out) {
@@ -1546,11 +1448,10 @@ void Engine::loo_variance(int i, double* out) {
   std::vector<int> ids{i};
   ensure_linv(ids);
   upload_idx(ids);
-  double* tmp = dalloc<double>((size_t)n);
+  DevBuf<double> tmp((size_t)n);
   launch_loo_variance(view(1), tmp, n, stream);
   HIPCK(hipMemcpyAsync(out, tmp, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, stream));
   HIPCK(hipStreamSynchronize(stream));
-  hipFree(tmp);
   unpermute(i, out);
 }
 
@@ -1569,7 +1470,7 @@ void Engine::get_pivot(int i, int* perm_out, int* rank_out) {
 
 void Engine::get_K(int i, double* out) {
   if (!gp[i].has_data) throw std::runtime_error("emulator has not been fit");
-  double* tmp = dalloc<double>((size_t)n * n);
+  DevBuf<double> tmp((size_t)n * n);
   std::vector<int> ids{i};
   upload_params(ids);
   BatchView v = view(1);
@@ -1578,17 +1479,15 @@ void Engine::get_K(int i, double* out) {
   launch_cov_full(v, i, tmp, stream);
   HIPCK(hipMemcpyAsync(out, tmp, (size_t)n * n * sizeof(double), hipMemcpyDeviceToHost, stream));
   HIPCK(hipStreamSynchronize(stream));
-  hipFree(tmp);
 }
 
 void Engine::get_invQ(int i, double* out) {
   std::vector<int> ids{i};
   ensure_kinv(ids, false);
-  double* tmp = dalloc<double>((size_t)n * n);
+  DevBuf<double> tmp((size_t)n * n);
   launch_extract(dKinv + (size_t)i * MS, LD, n, tmp, 2, stream);
   HIPCK(hipMemcpyAsync(out, tmp, (size_t)n * n * sizeof(double), hipMemcpyDeviceToHost, stream));
   HIPCK(hipStreamSynchronize(stream));
-  hipFree(tmp);
   if (gp[i].permuted) {          // K^-1 of the pivoted matrix back to training order
     const int* P = hPerm.data() + (size_t)i * n;
     std::vector<double> t(out, out + (size_t)n * n);
@@ -1620,9 +1519,8 @@ void Engine::pivot_cholesky(const double* Ain, int n, double* L_out, int* P_out,
     if (i < n) std::memcpy(hA.data() + (size_t)i * NPp, Ain + (size_t)i * n, (size_t)n * sizeof(double));
     else hA[(size_t)i * NPp + i] = 1.0;
   }
-  double* dA_ = dalloc<double>(hA.size());
-  double* dW = dalloc<double>(pstrf_work_doubles(NPp));
-  int* dI = dalloc<int>((size_t)n + 2);
+  DevBuf<double> dA_(hA.size()), dW(pstrf_work_doubles(NPp));
+  DevBuf<int> dI((size_t)n + 2);
   BatchView v{};
   v.n = n; v.D = 1; v.NP = NPp; v.LD = NPp; v.MS = (size_t)NPp * NPp; v.PS = 0; v.kernel_type = 0;
   v.A = dA_; v.R = 0; v.RA = 0; v.idx = nullptr; v.nb = 1;
@@ -1641,7 +1539,6 @@ void Engine::pivot_cholesky(const double* Ain, int n, double* L_out, int* P_out,
   std::vector<int> hi((size_t)n + 2);
   HIPCK(hipMemcpy(hi.data(), dI, hi.size() * sizeof(int), hipMemcpyDeviceToHost));
   HIPCK(hipMemcpy(hA.data(), dA_, hA.size() * sizeof(double), hipMemcpyDeviceToHost));
-  hipFree(dA_); hipFree(dW); hipFree(dI);
   for (int i = 0; i < n; ++i) std::memcpy(L_out + (size_t)i * n, hA.data() + (size_t)i * NPp, (size_t)n * sizeof(double));
   if (hi[n + 1] != 0) throw std::runtime_error("not pd: no positive pivot");
   for (int i = 0; i < n; ++i) {
@@ -1653,11 +1550,10 @@ void Engine::pivot_cholesky(const double* Ain, int n, double* L_out, int* P_out,
 
 void Engine::get_chol(int i, double* out) {
   if (!gp[i].factored) throw std::runtime_error("emulator has not been fit");
-  double* tmp = dalloc<double>((size_t)n * n);
+  DevBuf<double> tmp((size_t)n * n);
   launch_extract(dA + (size_t)i * MS, LD, n, tmp, 1, stream);
   HIPCK(hipMemcpyAsync(out, tmp, (size_t)n * n * sizeof(double), hipMemcpyDeviceToHost, stream));
   HIPCK(hipStreamSynchronize(stream));
-  hipFree(tmp);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1925,7 +1821,7 @@ void Engine::retarget(int slot, const Engine& src, int i) {
   d.data.assign(s.data.size(), 0.);
   d.meanp.assign(n_mean(), 0.);
   d.beta.assign(q, 0.);
-  drop_w2(slot);
+  w2.erase(slot);
   gp[slot] = std::move(d);
 }
 

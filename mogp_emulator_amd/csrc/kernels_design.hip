@@ -100,14 +100,6 @@ __global__ __launch_bounds__(256) void design_finish_kernel(const unsigned long 
   if (t < T) out[t] = sqrt(__longlong_as_double((long long)best[t]));
 }
 
-struct DevBuf {
-  void* p = nullptr;
-  explicit DevBuf(size_t bytes) { HIPCK(hipMalloc(&p, bytes)); }
-  ~DevBuf() { (void)hipFree(p); }
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-};
-
 }  // namespace
 
 void design_min_pdist(const double* designs, int T, int n, int D, double* out) {
@@ -124,21 +116,22 @@ void design_min_pdist(const double* designs, int T, int n, int D, double* out) {
   const size_t per = (size_t)n * D * sizeof(double);
   // designs per pass: DESIGN_SCRATCH_BYTES of staged designs (one design where a single one is larger), at most DESIGN_MAX_PASS (grid.y)
   const int chunk = (int)std::max<size_t>(1, std::min<size_t>({(size_t)T, DESIGN_SCRATCH_BYTES / per, (size_t)DESIGN_MAX_PASS}));
-  DevBuf dX((size_t)chunk * per), dBest((size_t)chunk * sizeof(unsigned long long)), dOut((size_t)chunk * sizeof(double));
+  DevBuf<double> dX((size_t)chunk * n * D), dOut(chunk);
+  DevBuf<unsigned long long> dBest(chunk);
   hipStream_t st = nullptr;
   const size_t lds = (size_t)128 * D * sizeof(double);
   for (int t0 = 0; t0 < T; t0 += chunk) {
     const int nb = std::min(chunk, T - t0);
-    HIPCK(hipMemcpyAsync(dX.p, designs + (size_t)t0 * n * D, (size_t)nb * per, hipMemcpyHostToDevice, st));
+    HIPCK(hipMemcpyAsync(dX, designs + (size_t)t0 * n * D, (size_t)nb * per, hipMemcpyHostToDevice, st));
     prof_begin("design_min_pdist", st);
-    hipLaunchKernelGGL(design_init_kernel, dim3((nb + 255) / 256), dim3(256), 0, st, (unsigned long long*)dBest.p, nb);
-    hipLaunchKernelGGL(design_min_r2_kernel, dim3((unsigned)ntiles, nb), dim3(256), lds, st, (const double*)dX.p, n, D,
-                       (unsigned long long*)dBest.p);
-    hipLaunchKernelGGL(design_finish_kernel, dim3((nb + 255) / 256), dim3(256), 0, st, (const unsigned long long*)dBest.p, nb, (double*)dOut.p);
+    hipLaunchKernelGGL(design_init_kernel, dim3((nb + 255) / 256), dim3(256), 0, st, dBest.get(), nb);
+    hipLaunchKernelGGL(design_min_r2_kernel, dim3((unsigned)ntiles, nb), dim3(256), lds, st, (const double*)dX.get(), n, D,
+                       dBest.get());
+    hipLaunchKernelGGL(design_finish_kernel, dim3((nb + 255) / 256), dim3(256), 0, st, (const unsigned long long*)dBest.get(), nb, dOut.get());
     HIPCK(hipGetLastError());
     // algorithmic: a subtraction, a product and an addition per pair and dimension; every design read once
     prof_end("design_min_pdist", st, 1.5 * (double)nb * n * ((double)n - 1.0) * D, (double)nb * per);
-    HIPCK(hipMemcpyAsync(out + t0, dOut.p, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCK(hipMemcpyAsync(out + t0, dOut, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCK(hipStreamSynchronize(st));
   }
 }

@@ -184,20 +184,6 @@ void gemm(const GemmArgs& g, int rows, int cols, int nb, hipStream_t s) {
 
 unsigned elem_blocks(size_t total) { return (unsigned)std::min<size_t>((total + 255) / 256, 4096); }
 
-struct DevMem {
-  std::vector<void*> ptrs;
-  template <typename T>
-  T* get(size_t count) {
-    void* p = nullptr;
-    HIPCK(hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)));
-    ptrs.push_back(p);
-    return static_cast<T*>(p);
-  }
-  ~DevMem() {
-    for (void* p : ptrs) hipFree(p);
-  }
-};
-
 }  // namespace
 
 void gkdr_R(const double* X, int n, int m, const double* y, int nx, const double* sgx2, int ny, const double* sgy2, double eps,
@@ -217,13 +203,12 @@ void gkdr_R(const double* X, int n, int m, const double* y, int nx, const double
   const int NP = eng.NP;
   const int MP = (m + 127) / 128 * 128;
   const size_t MS = (size_t)NP * NP;
-  DevMem mem;
-  double* dX = mem.get<double>((size_t)n * m);
-  double* dY = mem.get<double>(n);
-  double* dXt = mem.get<double>((size_t)MP * NP);
-  double* dSx = mem.get<double>(nx);
-  double* dSy = mem.get<double>(ny);
-  double* dKx = mem.get<double>((size_t)nx * MS);
+  DevBuf<double> dX((size_t)n * m);
+  DevBuf<double> dY(n);
+  DevBuf<double> dXt((size_t)MP * NP);
+  DevBuf<double> dSx(nx);
+  DevBuf<double> dSy(ny);
+  DevBuf<double> dKx((size_t)nx * MS);
   HIPCK(hipMemcpyAsync(dX, X, (size_t)n * m * sizeof(double), hipMemcpyHostToDevice, st));
   HIPCK(hipMemcpyAsync(dY, y, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
   HIPCK(hipMemcpyAsync(dSx, sgx2, (size_t)nx * sizeof(double), hipMemcpyHostToDevice, st));
@@ -244,7 +229,7 @@ void gkdr_R(const double* X, int n, int m, const double* y, int nx, const double
   const int gt = NP / GT;
   const std::function<void(const BatchView&)> fill = [&](const BatchView& v) {
     if (v.nb != nx) throw std::runtime_error("gkdr: the factorisation must cover every input scale");
-    hipLaunchKernelGGL(gkdr_gram_kernel, dim3(gt, gt, nx), dim3(256), 0, eng.stream, dX, n, m, dSx, nullptr, dKx, NP, shift, v.A, v.MS);
+    hipLaunchKernelGGL(gkdr_gram_kernel, dim3(gt, gt, nx), dim3(256), 0, st, dX.get(), n, m, dSx.get(), nullptr, dKx.get(), NP, shift, v.A, v.MS);
     HIPCK(hipGetLastError());
   };
   std::vector<int> info;
@@ -260,10 +245,10 @@ void gkdr_R(const double* X, int n, int m, const double* y, int nx, const double
   if (okx.empty()) return;
   const int nz = (int)okx.size();
   // per factored input scale (position k of okx): L^-1 and L^-T (zero padding); per input scale Kx Kx
-  double* dLI = mem.get<double>((size_t)nz * MS);
-  double* dLT = mem.get<double>((size_t)nz * MS);
-  double* dKK = mem.get<double>((size_t)nx * MS);
-  int* dOk = mem.get<int>(nz);
+  DevBuf<double> dLI((size_t)nz * MS);
+  DevBuf<double> dLT((size_t)nz * MS);
+  DevBuf<double> dKK((size_t)nx * MS);
+  DevBuf<int> dOk(nz);
   HIPCK(hipMemcpyAsync(dOk, okx.data(), nz * sizeof(int), hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(gkdr_linv_kernel, dim3(elem_blocks(MS), nz), dim3(256), 0, st, eng.linv_buffer(), eng.MS, dOk, n, NP, dLI, dLT);
   HIPCK(hipGetLastError());
@@ -292,16 +277,16 @@ void gkdr_R(const double* X, int n, int m, const double* y, int nx, const double
     P = (int)std::max<size_t>(1, std::min<size_t>((size_t)npairs, fr / 2 / per_pair));
   }
   P = std::min(P, npairs);
-  double* dKy = mem.get<double>((size_t)P * MS);
-  double* dT = mem.get<double>((size_t)P * MS);
-  double* dF = mem.get<double>((size_t)P * MS);
-  double* dW = mem.get<double>((size_t)P * MS);
-  double* dYt = mem.get<double>((size_t)P * MP * NP);
-  double* dQ = mem.get<double>((size_t)P * MP * MP);
-  double* dR = mem.get<double>((size_t)P * RS);
-  int* dPz = mem.get<int>(P);
-  int* dPw = mem.get<int>(P);
-  int* dPk = mem.get<int>(P);
+  DevBuf<double> dKy((size_t)P * MS);
+  DevBuf<double> dT((size_t)P * MS);
+  DevBuf<double> dF((size_t)P * MS);
+  DevBuf<double> dW((size_t)P * MS);
+  DevBuf<double> dYt((size_t)P * MP * NP);
+  DevBuf<double> dQ((size_t)P * MP * MP);
+  DevBuf<double> dR((size_t)P * RS);
+  DevBuf<int> dPz(P);
+  DevBuf<int> dPw(P);
+  DevBuf<int> dPk(P);
   for (int p0 = 0; p0 < npairs; p0 += P) {
     const int nb = std::min(P, npairs - p0);
     HIPCK(hipMemcpyAsync(dPz, pz.data() + p0, nb * sizeof(int), hipMemcpyHostToDevice, st));

@@ -40,6 +40,7 @@
 #include <vector>
 #define MOGP_OPAQUE_TID 1
 #include "launch.h"
+#include "devmem.h"
 #include "chol128_dev.h"
 #include "trsm_dev.h"
 #include "gemm_dev.h"
@@ -573,7 +574,7 @@ void launch_mchol(const BatchView& v, unsigned* ctrl, size_t ctrl_ints, const in
   // MOGP_MC_TRACE=<file>: per-task time stamps of EVERY launch are appended to the file (analysis only: synchronises)
   static const char* trace_file = getenv("MOGP_MC_TRACE");
   const size_t words = (size_t)total * MC_TRW;
-  unsigned long long* dtr = nullptr;
+  DevBuf<unsigned long long> dtr;
   // Emulators per ticket GROUP inside a queue (round 5): a queue hands out the tasks of gs of its emulators, interleaved, before the next gs -- the
   // next group starts in the tail of the one before, and fewer matrices are in flight per XCD.  The smallest divisor of the queue's emulators
   // that still offers 1.25 x as many row tiles as the queue has workgroups.  mchol ms, all / groups: 64 x n=2000 (8 per queue) 3.54 / 3.47 in
@@ -590,19 +591,19 @@ void launch_mchol(const BatchView& v, unsigned* ctrl, size_t ctrl_ints, const in
   // chain-bound launches (rho < 1): six, not two, row tiles below the diagonal block are chain tasks (pipelined solve, pieces published)
   const int opts = ((rho < 1.0 ? 2 : 0) << 8) | (gsz << 12);
   if (trace_file) {
-    if (hipMalloc(reinterpret_cast<void**>(&dtr), words * 8) != hipSuccess) {
-      dtr = nullptr;                                        // no room for the stamps: factorise untraced, and say so
+    try {
+      dtr.reserve(words);
+    } catch (const std::exception&) {                       // no room for the stamps: factorise untraced, and say so
       fprintf(stderr, "libmogp_hip: MOGP_MC_TRACE: no device memory for %zu stamp words, this factorisation is not traced\n", words);
     }
   }
   if (trace_file && dtr) {
     (void)hipMemsetAsync(dtr, 0, words * 8, s);
     hipLaunchKernelGGL(mchol_kernel<true>, dim3(grid), dim3(256), lds_doubles * sizeof(double), s, v, ctrl, table, ntasks, mchol_emu_stride(v.NP), packs,
-                       info, nq, spin_limit, dtr, opts);
+                       info, nq, spin_limit, dtr.get(), opts);
     std::vector<unsigned long long> h(words);
     (void)hipStreamSynchronize(s);
     (void)hipMemcpy(h.data(), dtr, words * 8, hipMemcpyDeviceToHost);
-    (void)hipFree(dtr);
     if (FILE* f = fopen(trace_file, "ab")) {
       const long long hdr[4] = {v.nb, ntasks, v.NP, grid + 1000000LL * MC_TRW};
       fwrite(hdr, sizeof(hdr), 1, f);
