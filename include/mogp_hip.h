@@ -142,6 +142,13 @@ int mogp_densegp_loo_variance(mogp_densegp*, double* out /* n */);
  * fit half of the free device memory.  The same inputs give the same bits in every call. */
 int mogp_densegp_sobol(mogp_densegp*, const double* A, const double* B, int N, int D, int unc, int include_nugget, double* S /* D */,
                        double* ST /* D */, double* mean_out, double* variance_out, double* emulator_variance_out);
+/* Hessian of the negative log-posterior at theta = [corr_raw | log sigma^2 | log nugget (fit only)] (len = n_params), computed on the
+ * device from Q^-1, alpha and the planes Q^-1 dQ/dtheta_p: out (len, len) row-major, both triangles, exactly symmetric.  An adaptive or
+ * fixed nugget is a constant, as in the gradient.  The cached state of an emulator that is fit stays what it was (one fit at exactly theta is
+ * not evaluated again, one fit elsewhere is put back); an emulator that was not fit is left fit at theta.  The same inputs give the same
+ * bits in every call.  Refused: nugget type "pivot", the analytic mean, a mean function with parameters in theta, the ProductMat52
+ * kernel, and a theta at which the covariance matrix cannot be factorised. */
+int mogp_densegp_logpost_hessian(mogp_densegp*, const double* theta, int len, double* out /* len*len */);
 int mogp_densegp_get_K(mogp_densegp*, double* out /* n*n */);
 int mogp_densegp_get_invQ(mogp_densegp*, double* out /* n*n */);
 int mogp_densegp_get_invQt(mogp_densegp*, double* out /* n */);
@@ -216,6 +223,11 @@ int mogp_mogp_predict_full_cov(mogp_mogp*, const double* testing, int m, int D, 
  * emulator_variance_out (n_out).  Rows of emulators that are not fit are filled with NaN. */
 int mogp_mogp_sobol(mogp_mogp*, const double* A, const double* B, int N, int D, int unc, int include_nugget, double* S, double* ST,
                     double* mean_out, double* variance_out, double* emulator_variance_out);
+/* mogp_densegp_logpost_hessian for every emulator in one batched call per part: thetas (n_rows = n_emulators, n_cols = the largest
+ * n_params of the model), row i read up to emulator i's own n_params; hess_out (n_rows, n_cols, n_cols) with the leading block of every
+ * emulator filled and NaN elsewhere.  ok_out[i] = 0 and a NaN block where the factorisation fails at row i, or where the row starts
+ * with NaN (the emulator is then skipped); the other emulators are not affected. */
+int mogp_mogp_hessian(mogp_mogp*, const double* thetas, int n_rows, int n_cols, double* hess_out /* n_rows*n_cols*n_cols */, int* ok_out);
 /* predict_variance_batch (multioutputgp_gpu.hpp:182-192) with DEVICE pointers: inputs already resident in HBM, results stay in HBM
  * (every mean function; rows of emulators that are not fit are filled with NaN, MultiOutputGP_GPU.py:288-296) */
 int mogp_mogp_predict_variance_batch_dev(mogp_mogp*, const double* d_testing, int m, int D, double* d_means, double* d_vars);

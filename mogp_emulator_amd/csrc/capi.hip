@@ -346,6 +346,18 @@ int mogp_densegp_sobol(mogp_densegp* h, const double* A, const double* B, int N,
     h->eng->sobol(ids, A, B, N, unc != 0, include_nugget != 0, S, ST, mean_out, variance_out, unc ? emulator_variance_out : nullptr);
   });
 }
+int mogp_densegp_logpost_hessian(mogp_densegp* h, const double* theta, int len, double* out) {
+  DGUARD(h, {
+    Engine* e = h->eng;
+    if (len != e->n_theta(h->idx)) throw std::runtime_error("Shape of new GPParams object does not match existing one");
+    if (!theta || !out) throw std::runtime_error("logpost_hessian: null buffer");
+    std::vector<int> ids{h->idx};
+    std::vector<const double*> th{theta};
+    int ok = 0;
+    e->hessian(ids, th, out, len, &ok);
+    if (!ok) throw std::runtime_error("logpost_hessian: the covariance matrix could not be factorised at theta");
+  });
+}
 int mogp_densegp_loo_variance(mogp_densegp* h, double* out) { DGUARD(h, h->eng->loo_variance(h->idx, out)); }
 int mogp_densegp_get_K(mogp_densegp* h, double* out) { DGUARD(h, h->eng->get_K(h->idx, out)); }
 int mogp_densegp_get_invQ(mogp_densegp* h, double* out) { DGUARD(h, h->eng->get_invQ(h->idx, out)); }
@@ -768,6 +780,36 @@ int mogp_mogp_sobol(mogp_mogp* h, const double* A, const double* B, int N, int D
       const size_t lo = p.lo;
       engine_sobol(p.eng.get(), A, B, N, unc != 0, include_nugget != 0, S + lo * D, ST + lo * D, mean_out + lo, variance_out + lo,
                    ev ? ev + lo : nullptr);
+    });
+  });
+}
+int mogp_mogp_hessian(mogp_mogp* h, const double* thetas, int n_rows, int n_cols, double* hess_out, int* ok_out) {
+  GUARD({
+    if (n_rows != (int)h->views.size()) throw std::runtime_error("thetas must have one row per emulator");
+    if (!thetas || !hess_out) throw std::runtime_error("logpost_hessian: null buffer");
+    int widest = 0;
+    for (const auto& v : h->views) widest = std::max(widest, v.eng->n_theta(v.idx));
+    if (n_cols != widest) throw std::runtime_error("Shape of new GPParams object does not match existing one");
+    const size_t blk = (size_t)n_cols * n_cols;
+    std::fill(hess_out, hess_out + (size_t)n_rows * blk, std::numeric_limits<double>::quiet_NaN());
+    if (ok_out) std::fill(ok_out, ok_out + n_rows, 0);
+    for_parts(h, [&](mogp_part& p, int) {
+      std::vector<int> ids;
+      std::vector<const double*> th;
+      for (int i = 0; i < p.hi - p.lo; ++i) {
+        const double* row = thetas + (size_t)(p.lo + i) * n_cols;
+        if (std::isnan(row[0])) continue;
+        ids.push_back(i);
+        th.push_back(row);
+      }
+      if (ids.empty()) return;
+      std::vector<double> Hs(ids.size() * blk);
+      std::vector<int> ok(ids.size());
+      p.eng->hessian(ids, th, Hs.data(), n_cols, ok.data());
+      for (size_t k = 0; k < ids.size(); ++k) {
+        if (ok[k]) std::memcpy(hess_out + (size_t)(p.lo + ids[k]) * blk, Hs.data() + k * blk, blk * sizeof(double));
+        if (ok_out) ok_out[p.lo + ids[k]] = ok[k];
+      }
     });
   });
 }

@@ -117,6 +117,10 @@ class Engine {
   // over A and B, as predict() reports it) are host buffers.  AB_i exists only as one chunk in device memory.
   void sobol(const std::vector<int>& ids, const double* A, const double* B, long N, bool unc, bool include_nugget, double* S, double* ST,
              double* mean_out, double* var_out, double* emvar_out);
+  // Hessian of the negative log-posterior at thetas[k] of emulator ids[k] (kernels_hess.hip): H holds one ld x ld row-major block per
+  // entry, the leading n_theta x n_theta block filled; ok[k] = 0 and NaN where the factorisation fails.  Throws for what it does not
+  // cover (nugget="pivot", analytic mean, mean parameters in theta, ProductMat52).  The cached state of a fitted emulator is kept.
+  void hessian(const std::vector<int>& ids, const std::vector<const double*>& thetas, double* H, int ld, int* ok);
   // leave-one-out predictive variance of emulator i at its own training inputs (MICEFastGP.fast_predict for every index)
   void loo_variance(int i, double* out);
   // predict(full_cov=True), GaussianProcess.py:899-911: means (nb, m), covs (nb, m, m) host buffers, nugget NOT included

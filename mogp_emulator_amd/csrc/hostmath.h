@@ -36,6 +36,14 @@ struct Prior {
       default: return 0.;
     }
   }
+  double d2logpdx2(double x) const {
+    switch (type) {
+      case PRIOR_INVGAMMA: return (shape + 1.) / (x * x) - 2. * scale / (x * x * x);
+      case PRIOR_GAMMA: return -(shape - 1.) / (x * x);
+      case PRIOR_LOGNORMAL: return (-1. / (shape * shape) + std::log(x / scale) / (shape * shape) + 1.) / (x * x);
+      default: return 0.;
+    }
+  }
   // draw of the scaled variable (Priors.py sample_x); weak priors sample the RAW variable
   template <class RNG>
   double sample_x(RNG& rng) const {
@@ -75,6 +83,23 @@ struct Priors {
     if (nug_type == NUG_FIT) {
       const double eta = std::exp(th[D + 1]);
       out[D + 1] = nug.dlogpdx(eta) * eta;
+    }
+  }
+  // diagonal of the second derivative with respect to the raw parameters (Priors.py:356-391, 648-666): d2p/dx2 (dx/dtheta)^2 + dp/dx d2x/dtheta2
+  // with x = exp(-theta/2) for a correlation length (dx = -x/2, d2x = x/4) and x = exp(theta) for sigma^2 and the nugget (dx = d2x = x)
+  void d2logpdtheta2(const std::vector<double>& th, int D, int nug_type, double* out) const {
+    const int nd = D + 1 + (nug_type == NUG_FIT ? 1 : 0);
+    for (int i = 0; i < nd; ++i) out[i] = 0.;
+    if (!created) return;
+    for (int d = 0; d < D; ++d) {
+      const double l = std::exp(-0.5 * th[d]);
+      out[d] = corr[d].d2logpdx2(l) * (0.25 * l * l) + corr[d].dlogpdx(l) * (0.25 * l);
+    }
+    const double s2 = std::exp(th[D]);
+    out[D] = cov.d2logpdx2(s2) * (s2 * s2) + cov.dlogpdx(s2) * s2;
+    if (nug_type == NUG_FIT) {
+      const double eta = std::exp(th[D + 1]);
+      out[D + 1] = nug.d2logpdx2(eta) * (eta * eta) + nug.dlogpdx(eta) * eta;
     }
   }
   template <class RNG>

@@ -204,6 +204,23 @@ void launch_sobol_pair_sum(int nb, const double* fA, const double* fB, long ld, 
 // out[q * 2 + {0, 1}] = scale * sum of the nslot partials of quantity q < nq, in a fixed order
 void launch_sobol_pair_final(int nq, const double* partial, long nslot, double scale, double* out, hipStream_t s);
 
+// --- Hessian of the log-posterior (kernels_hess.hip) ----------------------------------------------
+// NPh = hess_np(n) = n rounded up to 64.  Per slot of the launch: Xs (NPh, D) scaled inputs; M (D, NPh, NPh) the planes Q^-1 Q_p;
+// needs Kinv (lower triangle) and alpha.  Reductions as the sensitivity kernels': per-workgroup slots, a fixed-order final sum.
+constexpr int HESS_MAX_GROUPS = 256;    // workgroups (= scratch slots) of one emulator's trace / pair reduction
+int hess_np(int n);
+int hess_trace_groups(int n);
+int hess_pair_groups(int n);
+void launch_hess_scale(const BatchView& v, double* Xs, hipStream_t s);
+void launch_hess_planes(const BatchView& v, const double* Xs, double* M, hipStream_t s);
+// out (nb, D + 1, D + 2): [p][q] = sum_ab P_p[a,b] P_q[b,a], planes P_p = M_p (p < D), P_D = Q^-1, P_{D+1} = I; valid for p < D, p <= q
+// and for [D][D]; partial: nb * hess_trace_groups(n) * (D + 1) * (D + 2) doubles
+void launch_hess_trace(const BatchView& v, const double* M, double* partial, double* out, hipStream_t s);
+// out (nb, D, D): [p][q] = sum_ab W[a,b] sigma^2 k''(r2) s_p s_q, p <= q; partial: nb * hess_pair_groups(n) * D * D doubles
+void launch_hess_pair(const BatchView& v, const double* Xs, double* partial, double* out, hipStream_t s);
+// V, U (nb, D, NPh): v_p = M_p^T t, u_p = M_p alpha;  Zv (nb, NPh) = Q^-1 alpha
+void launch_hess_vectors(const BatchView& v, const double* M, double* V, double* U, double* Zv, hipStream_t s);
+
 // --- utilities -------------------------------------------------------------------------------
 // out (n,n) <- tile of src (NP,NP): mode 0 copy, mode 1 transpose, mode 2 symmetrise from lower
 void launch_extract(const double* src, int NP, int n, double* out, int mode, hipStream_t s);

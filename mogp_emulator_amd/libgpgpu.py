@@ -733,6 +733,15 @@ class DenseGP_GPU(object):
         _outbuf(result, "result")
         check(_lib.mogp_densegp_logpost_deriv(self._h, dptr(result), int(result.size)))
 
+    def logpost_hessian(self, theta):
+        """Hessian of the negative log-posterior at theta, (n_params, n_params), computed on the device (both triangles, exactly
+        symmetric).  A fitted emulator keeps its cached state.  RuntimeError for nugget "pivot", the analytic mean, a mean function
+        with parameters in theta, ProductMat52, and a theta at which the covariance matrix cannot be factorised."""
+        th = self._theta_vec(theta)
+        out = np.zeros((th.size, th.size))
+        check(_lib.mogp_densegp_logpost_hessian(self._h, dptr(th), int(th.size), dptr(out)))
+        return out
+
     # -- predict ------------------------------------------------------------------------------
     def _testing(self, testing):
         x = _f64(testing)
@@ -959,6 +968,17 @@ class MultiOutputGP_GPU(object):
         ok = np.zeros(th.shape[0], dtype=np.int32)
         check(_lib.mogp_mogp_eval(self._h, dptr(th), th.shape[0], th.shape[1], dptr(f), dptr(g), iptr(ok)))
         return f, g, ok.astype(bool)
+
+    def hessian(self, thetas):
+        """Hessians of every emulator at its own row of thetas (n_emulators, widest n_params) in ONE batched device call per part:
+        (hess (n_emulators, P, P), ok (n_emulators,) bool).  A row that starts with NaN is skipped; its block, and that of a
+        row at which the factorisation fails, is NaN with ok False.  An emulator with fewer parameters than the widest fills the
+        leading block of its own size; the rest of its block is NaN."""
+        th = _f64(thetas, 2, "thetas")
+        hess = np.zeros((th.shape[0], th.shape[1], th.shape[1]))
+        ok = np.zeros(th.shape[0], dtype=np.int32)
+        check(_lib.mogp_mogp_hessian(self._h, dptr(th), th.shape[0], th.shape[1], dptr(hess), iptr(ok)))
+        return hess, ok.astype(bool)
 
     def _testing(self, testing):
         x = _f64(testing)
