@@ -71,7 +71,7 @@ static void set_priors(Engine* eng, int i, int n_corr, const int* ct, const doub
   pr.nug.type = nugt; pr.nug.shape = nugp[0]; pr.nug.scale = nugp[1];
   pr.created = true;
   eng->gp[i].pri = pr;
-  eng->gp[i].logpost_stale = true;      // the cached log-posterior was computed with the old priors
+  eng->gp[i].priors_changed();
 }
 
 static void kernel_eval_impl(int kernel_type, int what, const double* x1, int n1, const double* x2, int n2, int D, const double* params,
@@ -212,8 +212,7 @@ int mogp_densegp_targets(const mogp_densegp* h, double* out) {
 int mogp_densegp_theta_fit_status(const mogp_densegp* h) { return h->eng->gp[h->idx].has_data ? 1 : 0; }
 int mogp_densegp_reset_theta_fit_status(mogp_densegp* h) {
   GPState& g = h->eng->gp[h->idx];
-  g.has_data = false;
-  g.factored = g.linv = g.kinv = false;
+  g.unfit();
   std::fill(g.data.begin(), g.data.end(), 0.);
   std::fill(g.meanp.begin(), g.meanp.end(), 0.);
   return 0;
@@ -372,10 +371,7 @@ int mogp_densegp_set_nugget_size(mogp_densegp* h, double v) {
   GPState& g = h->eng->gp[h->idx];
   // a fixed nugget is part of the factored matrix: a new value invalidates the factor, alpha and the log-posterior
   // (the reference keeps serving the stale ones, densegp_gpu.hpp:125-135); the emulator has to be fit again
-  if (g.nug_type == NUG_FIXED && v != g.nug_size) {
-    g.has_data = false;
-    g.factored = g.linv = g.kinv = false;
-  }
+  if (g.nug_type == NUG_FIXED && v != g.nug_size) g.unfit();
   g.nug_size = v;
   if (g.nug_type == NUG_FIT && !g.data.empty()) g.data[g.data.size() - 1] = v;   // gpparams.hpp:167-172
   return 0;
@@ -388,8 +384,7 @@ int mogp_densegp_set_nugget_type(mogp_densegp* h, int t) {
     if (t != g.nug_type) {
       g.nug_type = t;
       g.data.assign(h->eng->NC + 1 + (t == NUG_FIT ? 1 : 0), 0.);
-      g.has_data = false;
-      g.factored = g.linv = g.kinv = false;
+      g.unfit();
     }
   });
 }

@@ -56,6 +56,12 @@ struct GPState {
   // informative mean priors beta ~ N(b, B) of the analytic mean (Priors.py:423-581); empty = weak
   std::vector<double> mp_b, mp_Binv, mp_Binvb;
   double mp_logdetB = 0.;
+
+  // The transitions of the cached state.  L^-1 and K^-1 belong to the factor: they are only read where `factored` holds.
+  void drop_factor() { factored = linv = kinv = false; }   // A no longer holds a usable factor (nor the buffers its inverses)
+  void unfit() { has_data = false; drop_factor(); }        // hyper-parameters, nugget or mean priors changed: fit again
+  void set_fit(bool ok) { has_data = factored = ok; }      // outcome of a fit (what was built from the factor since stays as it is)
+  void priors_changed() { logpost_stale = true; }          // `logpost` was computed with the old priors; the factor is still valid
 };
 
 class Engine {
@@ -174,7 +180,27 @@ class Engine {
   // synchronisation per evaluation instead of two)
   void factorize(const std::vector<int>& ids, std::vector<int>& info, bool defer_info = false);
   void factorize_blocked(const std::vector<int>& ids, std::vector<int>& info, bool defer_info);
+  // the schedules factorize_blocked chooses from (chol_schedule.h); every one leaves the status words in dInfo
+  void chol_one_launch(const std::vector<int>& ids, const BatchView& v, std::vector<int>& info, bool defer_info);
+  void chol_lookahead(const BatchView& v);
+  void chol_two_groups(const BatchView& v);
+  void chol_right_looking(const BatchView& v);
+  void begin_multi_launch(const BatchView& v);       // what the three multi-launch schedules start with: status words cleared, K built
+  void grow_step_events(int K);                      // evPanel / evUpd hold at least K + 1 events each
+  // the one-launch kernel aborted: count it and factorise again with the multi-launch schedule of the regime
+  void refactor_after_abort(const std::vector<int>& ids, std::vector<int>& info, bool defer_info);
   void read_info(std::vector<int>& info, bool defer_info);
+  // the steps of eval.  solve_and_collect: behind a factorisation of `list`, alpha (and L^-1 with want_grad), log-determinants and Gram
+  // matrices in ONE read-back; info_out (may be null) receives the status words the factorisation left on the device
+  void solve_and_collect(const std::vector<int>& list, std::vector<int>* info_out, bool want_grad, std::vector<double>& logdet,
+                         std::vector<double>& gram);
+  // the one-launch back substitution of `todo` on stream `st`; true: it also left log-det / status / Gram in dRes
+  bool launch_backsolve_chain_on(hipStream_t st, const BatchView& v, const std::vector<int>& todo);
+  // adaptive nugget: the emulators of `failed` with that nugget type are factored again with growing jitter; good[i] = 1 where it worked
+  void jitter_ladder(const std::vector<int>& failed, std::vector<int>& info, std::vector<char>& good, bool want_grad,
+                     std::vector<double>& logdet, std::vector<double>& gram);
+  // gradient rows of the emulators of ids that are still good, each into its own row of grad
+  void scatter_gradient(const std::vector<int>& ids, const std::vector<char>& good, double* grad, int grad_ld);
   std::vector<int> idx_on_device;          // what dIdx holds (upload_idx skips an identical list)
   void factorize_pivot(const std::vector<int>& ids, std::vector<int>& info);
   void ensure_pivot_buffers();

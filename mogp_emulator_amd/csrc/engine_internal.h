@@ -1,0 +1,32 @@
+// What engine.hip, engine_chol.hip and engine_fit.hip share and nobody else sees: the error-check macro, small helpers and the
+// process-wide diagnostic counters behind prof_counter (engine.hip).
+#pragma once
+#include "engine.h"
+
+#include <atomic>
+#include <cstdlib>
+
+namespace mogp {
+
+#define HIPCK(x) hip_check((x), #x)
+
+inline int roundup(int x, int m) { return (x + m - 1) / m * m; }
+
+// sets a flag for the lifetime of a scope (cleared again when the scope is left through an exception)
+struct FlagGuard {
+  bool& b;
+  explicit FlagGuard(bool& f) : b(f) { b = true; }
+  ~FlagGuard() { b = false; }
+};
+
+// bytes one chunk of a prediction may take (12 GB: one cross-covariance chunk for 64 x n=2000 x m=10^4)
+inline double ks_budget_bytes() {
+  static const double budget = [] { const char* e = getenv("MOGP_KS_BUDGET_GB"); return (e ? atof(e) : 12.0) * 1e9; }();
+  return budget;
+}
+
+inline std::atomic<long long> g_bs_timeouts{0}, g_obj_evals{0}, g_grad_evals{0}, g_mc_aborts{0};
+inline std::atomic<long long> g_lb_iters{0}, g_ls_short{0}, g_ls_long{0}, g_lb_runs{0}, g_pool_rounds{0}, g_pool_slot_rounds{0}, g_rep_build_us{0}, g_rep_pool_us{0}, g_retarget_us{0}, g_retargets{0}, g_rep_reused{0};
+inline std::atomic<long long> g_inputs_restored{0};
+
+}  // namespace mogp

@@ -162,4 +162,106 @@ struct MeanFunc {
   }
 };
 
+// Analytic mean with priors beta ~ N(b, B) (weak: B^-1 = 0, b = 0), from the Gram matrix G = [t,H]^T K^-1 [t,H] (row stride rmax):
+//   A = H^T K^-1 H + B^-1 (calc_Ainv, linalg_utils.py:5-40),  r = H^T K^-1 (t - H b),
+//   beta_hat = A^-1 (r + B^-1 b) (calc_mean_params, :88-121),  quadratic form (t-Hb)^T K^-1 (t-Hb) - r^T A^-1 r
+struct AnalyticMean {
+  bool ok = false;               // A is positive definite; false: only LA (as far as the factorisation got) is written
+  double quad = 0., logdetA = 0.;   // the quadratic form; log|A| (+ log|B| with informative priors)
+  int n_coeff = 0;               // n - q with weak priors, n otherwise (GaussianProcess.py:674-677)
+  std::vector<double> beta, LA;  // beta_hat (q); q x q lower Cholesky factor of A
+  // combination matrix over Z = K^-1 [t, h_1..h_q], (q + 2) rows of rmax:
+  //   row 0 -> K^-1 (t - H beta_hat) (predictions);  row c -> g_c = sum_d (LA^-1)[c][d] K^-1 h_d  (d log|A|);
+  //   row R = q + 1 -> K^-1 (t - H (b + beta')) (gradient of the quadratic form; = row 0 with weak priors)
+  std::vector<double> M;
+};
+// mp_*: the emulator's mean priors (GPState; mp_b empty = weak).  `out` is the caller's so that its vectors keep their storage from one
+// emulator to the next.
+inline void analytic_mean(const double* G, int rmax, int q, int n, const std::vector<double>& mp_b, const std::vector<double>& mp_Binv,
+                          const std::vector<double>& mp_Binvb, double mp_logdetB, AnalyticMean& out) {
+  const int R = 1 + q;
+  const bool weak = mp_b.empty();
+  std::vector<double>& LA = out.LA;
+  out.ok = true;
+  out.quad = G[0];
+  out.logdetA = 0.;
+  out.n_coeff = n;
+  std::vector<double> Am((size_t)q * q), rv(q), bb(q, 0.);
+  if (!weak) bb = mp_b;
+  for (int r = 0; r < q; ++r) {
+    double s = G[(1 + r) * rmax];
+    for (int c = 0; c < q; ++c) {
+      s -= G[(1 + r) * rmax + (1 + c)] * bb[c];
+      Am[r * q + c] = G[(1 + r) * rmax + (1 + c)] + (weak ? 0. : mp_Binv[r * q + c]);
+    }
+    rv[r] = s;
+  }
+  if (!weak) {
+    double bSb = 0., bv = 0.;
+    for (int r = 0; r < q; ++r) {
+      bv += bb[r] * G[(1 + r) * rmax];
+      for (int c = 0; c < q; ++c) bSb += bb[r] * G[(1 + r) * rmax + (1 + c)] * bb[c];
+    }
+    out.quad = G[0] - 2. * bv + bSb;
+  }
+  LA.assign((size_t)q * q, 0.);
+  for (int r = 0; r < q && out.ok; ++r)
+    for (int c = 0; c <= r; ++c) {
+      double s = Am[r * q + c];
+      for (int p = 0; p < c; ++p) s -= LA[r * q + p] * LA[c * q + p];
+      if (r == c) {
+        if (!(s > 0.)) { out.ok = false; break; }
+        LA[r * q + r] = std::sqrt(s);
+      } else {
+        LA[r * q + c] = s / LA[c * q + c];
+      }
+    }
+  if (!out.ok) return;
+  auto solveA = [&](std::vector<double> x) {          // A^-1 x by the two triangular solves with LA
+    for (int r = 0; r < q; ++r) {
+      double s = x[r];
+      for (int p = 0; p < r; ++p) s -= LA[r * q + p] * x[p];
+      x[r] = s / LA[r * q + r];
+    }
+    for (int r = q - 1; r >= 0; --r) {
+      double s = x[r];
+      for (int p = r + 1; p < q; ++p) s -= LA[p * q + r] * x[p];
+      x[r] = s / LA[r * q + r];
+    }
+    return x;
+  };
+  std::vector<double> w(q), Linv((size_t)q * q, 0.);
+  for (int r = 0; r < q; ++r) {               // w = LA^-1 r
+    double s = rv[r];
+    for (int p = 0; p < r; ++p) s -= LA[r * q + p] * w[p];
+    w[r] = s / LA[r * q + r];
+    out.quad -= w[r] * w[r];
+    out.logdetA += 2. * std::log(LA[r * q + r]);
+  }
+  const std::vector<double> bgrad = solveA(rv);           // beta' = A^-1 r: residual of the gradient's quadratic form
+  std::vector<double> rhs(rv);
+  if (!weak)
+    for (int r = 0; r < q; ++r) rhs[r] += mp_Binvb[r];
+  out.beta = solveA(rhs);
+  for (int c = 0; c < q; ++c) {               // LA^-1 (lower), column by column
+    for (int r = c; r < q; ++r) {
+      double s = (r == c) ? 1. : 0.;
+      for (int p = c; p < r; ++p) s -= LA[r * q + p] * Linv[p * q + c];
+      Linv[r * q + c] = s / LA[r * q + r];
+    }
+  }
+  std::vector<double>& M = out.M;
+  M.assign((size_t)(R + 1) * rmax, 0.);
+  M[0] = 1.;
+  M[R * rmax] = 1.;
+  for (int c = 0; c < q; ++c) {
+    M[1 + c] = -out.beta[c];
+    M[R * rmax + 1 + c] = -(bb[c] + bgrad[c]);
+  }
+  for (int c = 0; c < q; ++c)
+    for (int d = 0; d <= c; ++d) M[(1 + c) * rmax + (1 + d)] = Linv[c * q + d];
+  if (weak) out.n_coeff = n - q;
+  else out.logdetA += mp_logdetB;             // + log|B| (priors.mean.logdet_cov)
+}
+
 }  // namespace mogp

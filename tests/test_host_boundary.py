@@ -446,6 +446,147 @@ def test_lean_exp_matches_long_double(tmp_path):
     assert_allclose(vals, 2.0 ** (np.arange(256) / 256.0), rtol=3e-16)
 
 
+def _build_host_check(tmp_path, name):
+    import shutil
+    import subprocess
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    exe = str(tmp_path / name)
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-I", os.path.join(ROOT, "mogp_emulator_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "c", name + ".cpp"), "-o", exe])
+    return exe
+
+
+def test_cholesky_schedule_choice(tmp_path):
+    """choose_cholesky_schedule (csrc/chol_schedule.h), compiled for the host, against the schedule numbers worked out by hand from the
+    rules it replaced in Engine::factorize_blocked: tiles64 = nb (NP / 64), tiles128 = nb (NP / 128); legacy = 1 (right-looking) below
+    256 tiles64, else 0 (two groups) from 1024 tiles128, else 3 (look-ahead); one launch (4) below 16384 tiles128 unless more than 512
+    single-block matrices; precedence hook > MOGP_CHOL > regime; 5 = legacy; one launch -> legacy from 2^32 bytes per matrix or after
+    an abort."""
+    import subprocess
+    exe = _build_host_check(tmp_path, "chol_schedule_check")
+    own = lambda NP: NP * NP * 8
+    # (nb, NP, matrix bytes, hook, forced, force_legacy) -> schedule
+    cases = [
+        ((64, 2048, own(2048), -1, -1, 0), 4),          # tiles128 = 1024 < 16384
+        ((64, 2048, own(2048), -1, 5, 0), 0),           # its legacy: tiles64 = 2048, tiles128 = 1024 >= 1024
+        ((8, 2048, own(2048), -1, -1, 0), 4),
+        ((8, 2048, own(2048), -1, 5, 0), 3),            # tiles64 = 256 is not below 256, tiles128 = 128 < 1024
+        ((1, 16128, own(16128), -1, -1, 0), 4),         # tiles128 = 126
+        ((1, 16128, own(16128), 5, -1, 0), 1),          # tiles64 = 252 < 256
+        ((600, 128, own(128), -1, -1, 0), 3),           # nb > 512 at a single block: not one launch; tiles64 = 1200, tiles128 = 600
+        ((512, 128, own(128), -1, -1, 0), 4),
+        ((512, 128, own(128), -1, 5, 0), 3),            # tiles64 = 1024, tiles128 = 512
+        ((513, 128, own(128), -1, -1, 0), 3),
+        ((513, 256, own(256), -1, -1, 0), 4),           # more than one block column: the 512 limit does not apply
+        ((1, 128, own(128), -1, -1, 0), 4),
+        ((1, 128, own(128), -1, 5, 0), 1),
+        ((5461, 384, own(384), -1, -1, 0), 4),          # tiles128 = 16383
+        ((8192, 256, own(256), -1, -1, 0), 0),          # tiles128 = 16384
+        ((8192, 256, own(256), 4, -1, 0), 4),           # (the hook may still force the one launch there)
+        ((1, 23168, 2 ** 32, -1, -1, 0), 3),            # exactly 2^32 bytes: tiles64 = 362, tiles128 = 181
+        ((1, 23168, 2 ** 32 - 128, -1, -1, 0), 4),
+        ((1, 23168, 2 ** 32, 4, -1, 0), 3),             # ... also when it is forced
+        ((64, 2048, 2 ** 32, -1, 4, 0), 0),
+        ((64, 2048, own(2048), -1, -1, 1), 0),          # force_legacy
+        ((64, 2048, own(2048), 4, -1, 1), 0),
+        ((64, 2048, own(2048), -1, 4, 1), 0),
+        ((8, 2048, own(2048), -1, -1, 1), 3),
+        ((1, 16128, own(16128), -1, -1, 1), 1),
+        ((600, 128, own(128), -1, -1, 1), 3),
+        ((64, 2048, own(2048), -1, 3, 1), 3),           # (a forced multi-launch schedule is not touched)
+        ((64, 2048, own(2048), 1, -1, 1), 1),
+    ]
+    # precedence at 8 x NP 2048 (regime: one launch, legacy: look-ahead): rows = hook, columns = forced, both over -1 0 1 3 4 5
+    values = [-1, 0, 1, 3, 4, 5]
+    table = [[4, 0, 1, 3, 4, 3],
+             [0, 0, 0, 0, 0, 0],
+             [1, 1, 1, 1, 1, 1],
+             [3, 3, 3, 3, 3, 3],
+             [4, 4, 4, 4, 4, 4],
+             [3, 3, 3, 3, 3, 3]]
+    for r, hook in enumerate(values):
+        for c, forced in enumerate(values):
+            cases.append(((8, 2048, own(2048), hook, forced, 0), table[r][c]))
+    text = "".join(" ".join(str(x) for x in case) + "\n" for case, _ in cases)
+    out = subprocess.run([exe], input=text, capture_output=True, text=True, check=True).stdout.split()
+    assert len(out) == len(cases)
+    for (case, want), got in zip(cases, out):
+        assert int(got) == want, (case, want, got)
+
+
+def test_analytic_mean_algebra(tmp_path):
+    """analytic_mean (csrc/hostmath.h: the q x q algebra of Engine::eval for a mean function whose coefficients are integrated out),
+    compiled for the host, on the Gram block of a random SPD K (n = 12) against the general branch of the oracle (GPRefMean.fit:
+    calc_Ainv / calc_mean_params), and the rows of the combination matrix against their definition."""
+    exe = _build_host_check(tmp_path, "analytic_mean_check")
+    for q in (1, 3, 7):
+        for informative in (False, True):
+            _check_analytic_mean(exe, q, informative)
+
+
+def _check_analytic_mean(exe, q, informative):
+    import subprocess
+    from scipy import linalg
+    from oracle import cpu_ref as R
+    RMAX, n = 8, 12
+    rng = np.random.default_rng(100 * q + informative)
+    W = rng.normal(size=(n, n))
+    K = W @ W.T / n + np.eye(n)
+    H = rng.normal(size=(n, q))
+    t = rng.normal(size=n)
+    Y = np.column_stack([t, H])
+    G = np.zeros((RMAX, RMAX))
+    G[:q + 1, :q + 1] = Y.T @ np.linalg.solve(K, Y)
+
+    def run(G, priors):
+        text = "%d %d %d\n" % (q, n, 1 if priors else 0) + " ".join(repr(float(x)) for x in G.ravel()) + "\n"
+        for p in priors:
+            text += " ".join(repr(float(x)) for x in np.ravel(p)) + "\n"
+        return subprocess.run([exe], input=text, capture_output=True, text=True, check=True).stdout.splitlines()
+
+    if informative:
+        b = 0.3 * rng.normal(size=q)
+        V = rng.normal(size=(q, q))
+        Bcov = V @ V.T / q + np.eye(q)
+        Binv = np.linalg.inv(Bcov)
+        Binvb, logdetB = Binv @ b, float(np.linalg.slogdet(Bcov)[1])
+        priors = [b, Binv, Binvb, logdetB]
+    else:
+        b, Binv, Binvb, logdetB, priors = np.zeros(q), 0., 0., 0., []
+    out = run(G, priors)
+    assert int(out[0]) == 1
+    quad, logdetA, n_coeff = float(out[1]), float(out[2]), int(out[3])
+    beta = np.array(out[4].split(), dtype=float)
+    LA = np.array(out[5].split(), dtype=float).reshape(q, q)
+    Mrows = np.array(out[6].split(), dtype=float).reshape(q + 2, RMAX)
+    # GPRefMean.fit, oracle/cpu_ref.py
+    L = linalg.cholesky(K, lower=True)
+    m = H @ b
+    A = H.T @ R.cho_solve_L(L, H) + Binv
+    LA_ref = R.fixed_cholesky(A)
+    Kinv_t = R.cho_solve_L(L, t - m)
+    H_Kinv_t = H.T @ Kinv_t
+    beta_ref = R.cho_solve_L(LA_ref, H_Kinv_t + Binvb)
+    quad_ref = np.dot(t - m, Kinv_t) - np.dot(H_Kinv_t, R.cho_solve_L(LA_ref, H_Kinv_t))
+    assert_allclose(quad, quad_ref, rtol=1e-12)
+    assert_allclose(logdetA, R.logdet_L(LA_ref) + logdetB, rtol=1e-12)
+    assert n_coeff == (n if informative else n - q)
+    assert_allclose(beta, beta_ref, rtol=1e-12)
+    assert_allclose(LA, LA_ref, rtol=1e-12, atol=1e-15)
+    # row 0 = [1, -beta_hat], rows c = LA^-1, row R = [1, -(b + A^-1 r)], zero beyond column q
+    want = np.zeros((q + 2, RMAX))
+    want[0, 0] = want[q + 1, 0] = 1.
+    want[0, 1:q + 1] = -beta_ref
+    want[1:q + 1, 1:q + 1] = linalg.solve_triangular(LA_ref, np.eye(q), lower=True)
+    want[q + 1, 1:q + 1] = -(b + R.cho_solve_L(LA_ref, H_Kinv_t))
+    assert_allclose(Mrows, want, rtol=1e-12, atol=1e-15)
+    # A not positive definite: reported, not computed with
+    Gbad = G.copy()
+    Gbad[q, q] = -Gbad[q, q] - 10.
+    assert int(run(Gbad, priors)[0]) == 0
+
+
 def test_hip_runtime_preload_only_for_matching_soname(tmp_path, monkeypatch):
     """the loader puts a PyTorch wheel's bundled HIP runtime in front of libmogp_hip.so only when that copy's DT_SONAME is
     the libamdhip64.so.N this library was linked against; another ROCm major is left alone."""
