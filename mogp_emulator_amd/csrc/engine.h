@@ -214,10 +214,22 @@ class Engine {
   const std::function<void(const BatchView&)>* prebuilt = nullptr;   // factor_prebuilt: build_cov runs this instead
   std::vector<char> z_armed;     // per emulator: its solution row holds the sentinel pattern of the one-launch back substitution
   void set_theta(int i, const double* theta);
-  // implausibility / implausibility_top: validation, then per chunk of query points the means and variances in dMean / dVar (nb, MC);
-  // tail(dPrm, c0, mc, MC) consumes them (the stream is synchronised after it: the next chunk reuses the buffers)
-  void implausibility_chunks(const std::vector<int>& ids, const double* Xs, int m, const double* obs, const double* obs_var,
-                             const double* discrepancy, bool include_nugget, const std::function<void(const double*, int, int, int)>& tail);
+  void require_factored(const std::vector<int>& ids) const;      // throws unless every emulator of ids holds a factor
+  // the steps of predict (engine_predict.hip).  PredictPlace: where means / variances / derivatives / dot products live on the device
+  struct PredictPlace {
+    double *fm, *fv, *fd, *dots;
+    long ld, dots_ld;
+  };
+  PredictPlace place_predict_outputs(int nb, int m, double* means, double* vars, double* derivs, long out_ld, bool out_on_device);
+  void predict_chunks(const BatchView& v, const double* dXsrc, int m, const PredictPlace& o);
+  void add_mean_terms(const std::vector<int>& ids, const double* dXsrc, int m, const PredictPlace& o);
+  void copy_out_predictions(const PredictPlace& o, int nb, int m, double* means, double* vars, long out_ld, double* derivs);
+  // implausibility / implausibility_top.  implausibility_chunk_points: their shared refusals, then MC, the query points per chunk (0: empty
+  // input).  implausibility_chunks: the remaining validation, then per chunk the means and variances in dMean / dVar (nb, MC);
+  // tail(dPrm, c0, mc) consumes them (the stream is synchronised after it: the next chunk reuses the buffers)
+  int implausibility_chunk_points(const std::vector<int>& ids, int m) const;
+  void implausibility_chunks(const std::vector<int>& ids, const double* Xs, int m, int MC, const double* obs, const double* obs_var,
+                             const double* discrepancy, bool include_nugget, const std::function<void(const double*, int, int)>& tail);
   void ensure_predict_scratch(int nb, int MC);
 
   DevBuf<double> dX, dP, dT, dA, dLinv, dKinv, dAlpha;

@@ -1,7 +1,8 @@
-// What engine.hip, engine_chol.hip and engine_fit.hip share and nobody else sees: the error-check macro, small helpers and the
+// What engine.hip, engine_chol.hip, engine_fit.hip and engine_predict.hip share and nobody else sees: the error-check macro, small helpers and the
 // process-wide diagnostic counters behind prof_counter (engine.hip).
 #pragma once
 #include "engine.h"
+#include "predict_plan.h"
 
 #include <atomic>
 #include <cstdlib>

@@ -264,4 +264,26 @@ inline void analytic_mean(const double* G, int rmax, int q, int n, const std::ve
   else out.logdetA += mp_logdetB;             // + log|B| (priors.mean.logdet_cov)
 }
 
+// The analytic mean's terms of predict(full_cov=True) at m points (GaussianProcess.py:899-911; calc_R, linalg_utils.py:123-168), with
+// R = H*^T - H^T K^-1 k*:  mu += h(x*)^T beta,  rm = LA^-1 R,  C += rm^T rm.  Hs (q x m): basis columns at the test points; dots ((1 + q) x m):
+// row 1 + c = k*^T K^-1 h_c; beta (q), LA (q x q) of the fit.  mu (m) and C (m x m) are updated in place; rm (q x m) is the caller's scratch.
+inline void fullcov_mean_terms(int q, int m, const double* beta, const double* LA, const double* Hs, const double* dots, double* mu,
+                               double* rm, double* C) {
+  for (int j = 0; j < m; ++j) {
+    for (int c = 0; c < q; ++c) {
+      mu[j] += beta[c] * Hs[(size_t)c * m + j];
+      double s = Hs[(size_t)c * m + j] - dots[(size_t)(1 + c) * m + j];
+      for (int p = 0; p < c; ++p) s -= LA[c * q + p] * rm[(size_t)p * m + j];
+      rm[(size_t)c * m + j] = s / LA[c * q + c];
+    }
+  }
+  for (int i = 0; i < m; ++i)
+    for (int c = 0; c < q; ++c) {
+      const double ri = rm[(size_t)c * m + i];
+      const double* rc = rm + (size_t)c * m;
+      double* row = C + (size_t)i * m;
+      for (int j = 0; j < m; ++j) row[j] += ri * rc[j];
+    }
+}
+
 }  // namespace mogp

@@ -1,0 +1,46 @@
+// How the prediction family of Engine (engine_predict.hip) and Engine::hessian cut their work to a byte budget, and where the mean-function
+// terms of a prediction are staged.  Plain host arithmetic with no HIP in it, so that a host compiler takes it and
+// tests/c/predict_plan_check.cpp can check it without a device.  The caps that need the device (MOGP_KS_BUDGET_GB, free memory) are passed in.
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <cstddef>
+
+namespace mogp {
+
+// query points per chunk of a prediction of nb emulators: as many whole 128-point tiles of cross-covariance rows (LD doubles per point and
+// emulator) as cap_bytes holds, at least one tile, at most the m points rounded up to tiles (one chunk)
+inline int predict_chunk_points(double cap_bytes, int nb, int LD, int m) {
+  const long all = ((long)m + 127) / 128 * 128;
+  const long MC = (long)(cap_bytes / ((double)nb * LD * 8.0)) / 128 * 128;
+  return (int)std::max<long>(128, std::min<long>(MC, all));
+}
+
+// the chunk budget of implausibility / implausibility_top
+constexpr double implausibility_cap_bytes = 6.0e9;
+
+// base rows per chunk of pass 2 of Engine::sobol: per row the D inputs of AB_i, its nb means, predict()'s R dot-product rows per emulator
+// (analytic mean only) and the basis columns of the mean function; whole 128-row tiles, at least one, never more than the N rows
+inline long sobol_chunk_rows(double cap_bytes, int D, int nb, int R, int mean_kind, int n_poly_terms, long N) {
+  const double per_row = 8.0 * ((double)D + (double)nb * (1.0 + (R > 1 ? R : 0)) + (mean_kind == 3 ? 2.0 * n_poly_terms + 1.0 : 1.0));
+  const long CH = (long)(cap_bytes / per_row) / 128 * 128;
+  return std::min<long>(std::max<long>(128, CH), N);
+}
+
+// emulators per group of Engine::hessian: as many of the n_good as the budget holds at per_bytes of scratch each, at least one
+inline std::size_t hessian_group_size(double budget, double per_bytes, std::size_t n_good) {
+  return (std::size_t)std::max(1.0, std::min((double)n_good, std::floor(budget / per_bytes)));
+}
+
+// Offsets (in doubles) into the staging block of the mean-function terms of a prediction of nb emulators at m points:
+//   basis (nbasis x m) | dbasis (nterm x m) | coef (nb x nbasis) | LA (nb x qq x qq) | dims, powers (2 nterm ints, in nterm + 1 doubles)
+// nterm = terms of a polynomial mean (0 otherwise), nbasis = 1 + nterm, qq = columns of the analytic mean (0 without).  The first two are
+// filled on the device, the rest is staged from the host in one copy.
+struct MeanStage {
+  std::size_t o_basis, o_dbasis, o_coef, o_la, o_int, total;
+  MeanStage(int nb, int m, int nbasis, int nterm, int qq)
+      : o_basis(0), o_dbasis(o_basis + (std::size_t)nbasis * m), o_coef(o_dbasis + (std::size_t)nterm * m),
+        o_la(o_coef + (std::size_t)nb * nbasis), o_int(o_la + (std::size_t)nb * qq * qq), total(o_int + (std::size_t)nterm + 1) {}
+};
+
+}  // namespace mogp

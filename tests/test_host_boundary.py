@@ -515,6 +515,78 @@ def test_cholesky_schedule_choice(tmp_path):
         assert int(got) == want, (case, want, got)
 
 
+def test_prediction_plan_sizes(tmp_path):
+    """The sizing rules of the prediction family (csrc/predict_plan.h), compiled for the host, against values worked out by hand from the
+    rules as they stood inline in Engine::predict / implausibility* / sobol / hessian:
+      chunk points  MC = max(128, min(floor(cap / (nb LD 8)) rounded down to 128, m rounded up to 128))
+      sobol rows    CH = min(max(128, floor(cap / per_row) rounded down to 128), N), per_row = 8 (D + nb (1 + (R if R > 1)) + (2 terms + 1 if
+                    polynomial else 1))
+      hessian group = max(1, min(n_good, floor(budget / per)))
+      MeanStage     basis (nbasis m) | dbasis (nterm m) | coef (nb nbasis) | LA (nb qq qq) | ints (nterm + 1 doubles)"""
+    import subprocess
+    exe = _build_host_check(tmp_path, "predict_plan_check")
+    # chunk rule: (cap, nb, LD, m) -> (points per chunk, chunks)
+    chunk = [
+        ((12e9, 3, 128, 255), (256, 1)),                # cap / 3072 = 3906250 -> 3906176, far above roundup(m): one chunk; m below a multiple of 128
+        ((12e9, 3, 128, 256), (256, 1)),                # ... at it
+        ((12e9, 3, 128, 257), (384, 1)),                # ... just above it
+        ((1e4, 3, 128, 300), (128, 3)),                 # 10 kB / 3072 = 3 points -> 0 tiles: the floor of one tile, 128 + 128 + 44
+        ((1e4, 3, 128, 100), (128, 1)),
+        ((2e6, 2, 256, 1000), (384, 3)),                # 2e6 / 4096 = 488 -> 384; 384 + 384 + 232
+        ((2e6, 2, 256, 300), (384, 1)),                 # roundup(300) = 384 = the cap's 384
+        ((2e6, 2, 256, 385), (384, 2)),
+        ((1e6, 2, 256, 1000), (128, 8)),                # 244 -> 128
+        ((12e9, 64, 2048, 10000), (10112, 1)),          # the benchmark's shape: 11444 -> 11392 >= roundup(10^4) = 10112
+        ((12e9, 64, 2048, 20000), (11392, 2)),
+        ((6e9, 3, 128, 2000000), (1953024, 2)),         # the implausibility budget: 1953125 -> 15258 tiles = 1953024 < roundup(m) = 2000000
+        ((6e9, 3, 128, 1953024), (1953024, 1)),
+        ((6e9, 3, 128, 1953025), (1953024, 2)),
+    ]
+    # sobol: (cap, D, nb, R, mean kind, polynomial terms, N) -> (rows per chunk, chunks)
+    sobol = [
+        ((1e4, 4, 4, 1, 0, 0, 1000), (128, 8)),         # test_gpu_sobol's small budget: per_row = 8 (4 + 4 + 1) = 72, 138 -> 128; 7 x 128 + 104
+        ((12e9, 4, 4, 1, 0, 0, 100), (100, 1)),         # N < 128
+        ((1e4, 4, 4, 1, 0, 0, 50), (50, 1)),            # ... also where the cap gives the floor of 128
+        ((12e9, 4, 4, 1, 0, 0, 1000), (1000, 1)),
+        ((1e6, 3, 2, 5, 3, 3, 10000), (5632, 2)),       # analytic polynomial: per_row = 8 (3 + 2 (1 + 5) + 7) = 176, 5681 -> 5632
+        ((1e6, 3, 2, 1, 3, 3, 10000), (10000, 1)),      # polynomial in theta: per_row = 8 (3 + 2 + 7) = 96, 10416 -> 10368 >= N
+        ((1e6, 3, 2, 1, 3, 3, 20000), (10368, 2)),
+        ((1e6, 3, 2, 2, 2, 0, 20000), (12416, 2)),      # analytic constant: per_row = 8 (3 + 2 (1 + 2) + 1) = 80, 12500 -> 12416
+    ]
+    # hessian: (budget, bytes per emulator, emulators) -> emulators per group
+    hess = [((1e6, 2e6, 5), 1), ((1e9, 1e6, 5), 5), ((1e7, 3e6, 5), 3), ((6e6, 3e6, 5), 2), ((5.9e6, 3e6, 5), 1), ((1e9, 1e6, 1), 1)]
+    # MeanStage: (nb, m, nbasis, nterm, qq) -> (o_basis, o_dbasis, o_coef, o_la, o_int, total)
+    stage = [
+        ((3, 300, 1, 0, 0), (0, 300, 300, 303, 303, 304)),          # fixed mean / constant in theta: one basis column, no terms
+        ((3, 300, 3, 2, 0), (0, 900, 1500, 1509, 1509, 1512)),      # polynomial in theta, two terms
+        ((2, 9, 3, 2, 3), (0, 27, 45, 51, 69, 72)),                 # analytic polynomial: qq = nbasis = 3, LA 2 x 9
+        ((3, 5, 1, 0, 1), (0, 5, 5, 8, 11, 12)),                    # analytic constant
+        ((1, 1, 7, 6, 7), (0, 7, 13, 20, 69, 76)),                  # the most columns an analytic mean may have (RMAX - 1)
+    ]
+    text = "".join("chunk " + " ".join(repr(x) for x in c) + "\n" for c, _ in chunk)
+    text += "".join("sobol " + " ".join(repr(x) for x in c) + "\n" for c, _ in sobol)
+    text += "".join("hess " + " ".join(repr(x) for x in c) + "\n" for c, _ in hess)
+    text += "".join("stage " + " ".join(repr(x) for x in c) + "\n" for c, _ in stage) + "icap\n"
+    out = subprocess.run([exe], input=text, capture_output=True, text=True, check=True).stdout.splitlines()
+    assert len(out) == len(chunk) + len(sobol) + len(hess) + len(stage) + 1
+    it = iter(out)
+    for case, (want, chunks) in chunk:
+        got = int(next(it))
+        assert got == want and -(-case[3] // got) == chunks, ("chunk", case, want, got)
+    for case, (want, chunks) in sobol:
+        got = int(next(it))
+        assert got == want and -(-case[6] // got) == chunks, ("sobol", case, want, got)
+    for case, want in hess:
+        got = int(next(it))
+        assert got == want, ("hess", case, want, got)
+    for case, want in stage:
+        got = tuple(int(x) for x in next(it).split())
+        assert got == want, ("stage", case, want, got)
+        o_int, total, nterm = got[4], got[5], case[3]
+        assert (total - o_int) * 8 >= 2 * nterm * 4, ("the dims / powers do not fit behind the doubles", case)
+    assert float(next(it)) == 6.0e9
+
+
 def test_analytic_mean_algebra(tmp_path):
     """analytic_mean (csrc/hostmath.h: the q x q algebra of Engine::eval for a mean function whose coefficients are integrated out),
     compiled for the host, on the Gram block of a random SPD K (n = 12) against the general branch of the oracle (GPRefMean.fit:
@@ -585,6 +657,41 @@ def _check_analytic_mean(exe, q, informative):
     Gbad = G.copy()
     Gbad[q, q] = -Gbad[q, q] - 10.
     assert int(run(Gbad, priors)[0]) == 0
+
+
+def test_fullcov_mean_terms(tmp_path):
+    """fullcov_mean_terms (csrc/hostmath.h: what Engine::predict_full_cov adds for a mean function whose coefficients are integrated out),
+    compiled for the host, on random basis columns, dot products and coefficients with LA from the construction of
+    _check_analytic_mean, against the full_cov branch of the oracle (GPRefMean.predict: mu + Hs beta, LA^-1 R by solve_L, + (LA^-1 R)^T
+    (LA^-1 R)) restated on the same numbers."""
+    import subprocess
+    from scipy import linalg
+    from oracle import cpu_ref as R
+    exe = _build_host_check(tmp_path, "fullcov_mean_check")
+    n = 12
+    for q in (1, 3, 7):
+        for m in (1, 9):
+            rng = np.random.default_rng(1000 * q + m)
+            W = rng.normal(size=(n, n))
+            K = W @ W.T / n + np.eye(n)
+            H = rng.normal(size=(n, q))
+            LA = R.fixed_cholesky(H.T @ R.cho_solve_L(linalg.cholesky(K, lower=True), H))
+            beta = rng.normal(size=q)
+            Hs = rng.normal(size=(q, m))                      # basis columns at the test points (Hs.T of the oracle)
+            dots = rng.normal(size=(1 + q, m))                # row 0: k*^T K^-1 (t - H beta), rows 1..: H^T K^-1 k*
+            V = rng.normal(size=(m, m))
+            C = V @ V.T                                       # Kss - (L^-1 k*)^T (L^-1 k*), from the device
+            text = "%d %d\n" % (q, m) + "".join(" ".join(repr(float(x)) for x in np.ravel(a)) + "\n" for a in (beta, LA, Hs, dots, C))
+            out = subprocess.run([exe], input=text, capture_output=True, text=True, check=True).stdout.splitlines()
+            mu = np.array(out[0].split(), dtype=float)
+            rm = np.array(out[1].split(), dtype=float).reshape(q, m)
+            cov = np.array(out[2].split(), dtype=float).reshape(m, m)
+            mu_ref = np.dot(Hs.T, beta) + dots[0]
+            Rm = Hs - dots[1:]
+            LAinv_R = R.solve_L(LA, Rm)
+            cov_ref = C + np.dot(LAinv_R.T, LAinv_R)
+            for got, want in ((mu, mu_ref), (rm, LAinv_R), (cov, cov_ref)):
+                assert_allclose(got, want, rtol=1e-12, atol=1e-15 * np.max(np.abs(want)), err_msg="q = %d, m = %d" % (q, m))
 
 
 def test_hip_runtime_preload_only_for_matching_soname(tmp_path, monkeypatch):
