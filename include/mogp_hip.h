@@ -149,6 +149,24 @@ int mogp_densegp_sobol(mogp_densegp*, const double* A, const double* B, int N, i
  * bits in every call.  Refused: nugget type "pivot", the analytic mean, a mean function with parameters in theta, the ProductMat52
  * kernel, and a theta at which the covariance matrix cannot be factorised. */
 int mogp_densegp_logpost_hessian(mogp_densegp*, const double* theta, int len, double* out /* len*len */);
+/* Prediction averaged over S hyperparameter samples (law of total variance), reduced over the samples on the device.  thetas (S, len): full
+ * vectors [mean | data], len = n_params.  EXACTLY ONE of weights (S, non-negative, any scale) and log_q (S, the log proposal density up to
+ * a constant) is not NULL; with log_q the weights are w_s ~ exp(-(F_s - F_min) - (log_q_s - log_q at the arg-min)), F the negative
+ * log-posterior (self-normalised importance sampling).  Every sample is factored on a replica engine, S at a time or max_slots (0: the
+ * library's choice) -- an adaptive nugget runs its jitter ladder per sample -- and the emulator itself, which must be fit, keeps its
+ * factor, theta and log-posterior.  A sample that cannot be factorised gets ok_out = 0, weight 0 and logpost_out NaN; the others are
+ * normalised to sum 1.  With mu_s, var_s the prediction of sample s, the PIVOT mu_0 = the mean of sample 0 (whatever its weight; the first
+ * sample with ok = 1 where sample 0 failed) and d_s = mu_s - mu_0:
+ *   mean_out = mu_0 + sum w_s d_s,   within_out = sum w_s max(var_s + (include_nugget ? nugget of sample s : 0), 0),
+ *   between_out = max(sum w_s d_s^2 - (sum w_s d_s)^2, 0)                                    (m each; the total variance is their sum)
+ * All samples failing, or weights that sum to 0, give NaN in all three and in weights_out -- status 0, not an error.  The sums are taken in
+ * sample order with one add per sample and no atomics: the same inputs give the same bits in every call, for every max_slots >= 1 and
+ * every max_points >= 1 (query points per chunk; 0: the library's choice).  Refused: nugget type "pivot", the analytic mean, S < 1,
+ * non-finite thetas / weights / log_q / testing, negative weights, D other than the emulator's, an emulator that is not fit. */
+int mogp_densegp_predict_mixture(mogp_densegp*, const double* thetas /* S*len */, int S, int len, const double* weights /* S or NULL */,
+                                 const double* log_q /* S or NULL; exactly one of the two */, const double* testing, int m, int D,
+                                 int include_nugget, int max_slots, int max_points, double* mean_out, double* within_out,
+                                 double* between_out /* m each */, double* weights_out, double* logpost_out, int* ok_out /* S each */);
 int mogp_densegp_get_K(mogp_densegp*, double* out /* n*n */);
 int mogp_densegp_get_invQ(mogp_densegp*, double* out /* n*n */);
 int mogp_densegp_get_invQt(mogp_densegp*, double* out /* n */);
@@ -228,6 +246,15 @@ int mogp_mogp_sobol(mogp_mogp*, const double* A, const double* B, int N, int D, 
  * emulator filled and NaN elsewhere.  ok_out[i] = 0 and a NaN block where the factorisation fails at row i, or where the row starts
  * with NaN (the emulator is then skipped); the other emulators are not affected. */
 int mogp_mogp_hessian(mogp_mogp*, const double* thetas, int n_rows, int n_cols, double* hess_out /* n_rows*n_cols*n_cols */, int* ok_out);
+/* mogp_densegp_predict_mixture for every emulator, all (emulator, sample) pairs of a part in one batched pass: thetas (n_out, S, n_cols),
+ * n_cols = the largest n_params of the model, every row read up to its emulator's own n_params; weights / log_q (n_out, S);
+ * mean_out / within_out / between_out (n_out, m); weights_out / logpost_out / ok_out (n_out, S); ok_all_out (n_out, may be NULL) = 0
+ * where the emulator's rows are NaN.  Row e is bit for bit what the single-emulator call gives for emulator e.  Emulators that are not
+ * fit give NaN rows, ok_out = 0 and ok_all_out = 0 (their thetas, weights and log_q are not read). */
+int mogp_mogp_predict_mixture(mogp_mogp*, const double* thetas, int S, int n_cols, const double* weights, const double* log_q,
+                              const double* testing, int m, int D, int include_nugget, int max_slots, int max_points, double* mean_out,
+                              double* within_out, double* between_out, double* weights_out, double* logpost_out, int* ok_out,
+                              int* ok_all_out);
 /* predict_variance_batch (multioutputgp_gpu.hpp:182-192) with DEVICE pointers: inputs already resident in HBM, results stay in HBM
  * (every mean function; rows of emulators that are not fit are filled with NaN, MultiOutputGP_GPU.py:288-296) */
 int mogp_mogp_predict_variance_batch_dev(mogp_mogp*, const double* d_testing, int m, int D, double* d_means, double* d_vars);

@@ -91,6 +91,7 @@ class LaplaceResult(object):
         self.covariance = np.full((P, P), np.nan)
         self.stderr = np.full(P, np.nan)
         self._chol_cov = None
+        self._chol_hess = None
         self.is_minimum = False
         if not np.all(np.isfinite(self.hessian)):
             return
@@ -107,6 +108,7 @@ class LaplaceResult(object):
         self.covariance = Linv.T @ Linv
         self.stderr = np.sqrt(np.diag(self.covariance))
         self._chol_cov = Linv.T                 # covariance = Linv^T Linv
+        self._chol_hess = L
 
     def sample(self, n, rng=None):
         """``n`` draws theta ~ N(theta_hat, H^-1), shape (n, P); ``rng``: a ``numpy.random.Generator``, a seed or None"""
@@ -115,6 +117,18 @@ class LaplaceResult(object):
         rng = rng if isinstance(rng, np.random.Generator) else np.random.default_rng(rng)
         z = rng.standard_normal((int(n), self.theta.size))
         return self.theta + z @ self._chol_cov.T
+
+    def logpdf(self, thetas):
+        """log N(theta; theta_hat, H^-1) of every row of ``thetas`` (S, P) -- or of one theta (P,) -- with its constant:
+        -P/2 log 2 pi + 1/2 log|H| - 1/2 (theta - theta_hat)^T H (theta - theta_hat), through the Cholesky factor of H"""
+        if not self.is_minimum:
+            raise ValueError("the Hessian is not positive definite: there is no Gaussian density")
+        th = np.asarray(thetas, dtype=np.float64)
+        P = self.theta.size
+        if th.shape[-1:] != (P,) or th.ndim > 2:
+            raise ValueError("thetas must have shape (S, %d) or (%d,)" % (P, P))
+        y = (th - self.theta) @ self._chol_hess                           # rows (theta - theta_hat)^T L,  H = L L^T
+        return -0.5 * P * np.log(2. * np.pi) + np.sum(np.log(np.diag(self._chol_hess))) - 0.5 * np.sum(y * y, axis=-1)
 
     def __repr__(self):
         return "LaplaceResult(is_minimum=%s, theta=%s, stderr=%s)" % (self.is_minimum, self.theta, self.stderr)

@@ -357,6 +357,20 @@ int mogp_densegp_logpost_hessian(mogp_densegp* h, const double* theta, int len, 
     if (!ok) throw std::runtime_error("logpost_hessian: the covariance matrix could not be factorised at theta");
   });
 }
+int mogp_densegp_predict_mixture(mogp_densegp* h, const double* thetas, int S, int len, const double* weights, const double* log_q,
+                                 const double* testing, int m, int D, int include_nugget, int max_slots, int max_points, double* mean_out,
+                                 double* within_out, double* between_out, double* weights_out, double* logpost_out, int* ok_out) {
+  DGUARD(h, {
+    Engine* e = h->eng;
+    if (D != e->D) throw std::runtime_error("testing points must have D columns");
+    if (S >= 1 && len != e->n_theta(h->idx)) throw std::runtime_error("Shape of new GPParams object does not match existing one");
+    const GPState& g = e->gp[h->idx];
+    if (!(g.has_data && g.factored)) throw std::runtime_error("Hyperparameters have not been fit for this Gaussian Process");
+    std::vector<int> ids{h->idx};
+    e->predict_mixture(ids, thetas, S, len, weights, log_q, testing, m, include_nugget != 0, max_slots, max_points, mean_out, within_out,
+                       between_out, weights_out, logpost_out, ok_out, nullptr);
+  });
+}
 int mogp_densegp_loo_variance(mogp_densegp* h, double* out) { DGUARD(h, h->eng->loo_variance(h->idx, out)); }
 int mogp_densegp_get_K(mogp_densegp* h, double* out) { DGUARD(h, h->eng->get_K(h->idx, out)); }
 int mogp_densegp_get_invQ(mogp_densegp* h, double* out) { DGUARD(h, h->eng->get_invQ(h->idx, out)); }
@@ -775,6 +789,69 @@ int mogp_mogp_sobol(mogp_mogp* h, const double* A, const double* B, int N, int D
       const size_t lo = p.lo;
       engine_sobol(p.eng.get(), A, B, N, unc != 0, include_nugget != 0, S + lo * D, ST + lo * D, mean_out + lo, variance_out + lo,
                    ev ? ev + lo : nullptr);
+    });
+  });
+}
+// every part: its fitted emulators in one Engine::predict_mixture, the rows of the others NaN
+int mogp_mogp_predict_mixture(mogp_mogp* h, const double* thetas, int S, int n_cols, const double* weights, const double* log_q,
+                              const double* testing, int m, int D, int include_nugget, int max_slots, int max_points, double* mean_out,
+                              double* within_out, double* between_out, double* weights_out, double* logpost_out, int* ok_out,
+                              int* ok_all_out) {
+  GUARD({
+    if (D != h->eng->D) throw std::runtime_error("testing points must have D columns");
+    if (S < 1) throw std::runtime_error("predict_mixture: at least one sample per emulator is needed (S = " + std::to_string(S) + ")");
+    if (!thetas || !mean_out || !within_out || !between_out || !weights_out || !logpost_out || !ok_out)
+      throw std::runtime_error("predict_mixture: null buffer");
+    if ((weights != nullptr) == (log_q != nullptr)) throw std::runtime_error("predict_mixture: exactly one of weights and log_q must be given");
+    int widest = 0;
+    for (const auto& v : h->views) widest = std::max(widest, v.eng->n_theta(v.idx));
+    if (n_cols != widest) throw std::runtime_error("Shape of new GPParams object does not match existing one");
+    const size_t mm = (size_t)std::max(m, 0);
+    const size_t SS = (size_t)S;
+    for_parts(h, [&](mogp_part& p, int) {
+      Engine* e = p.eng.get();
+      const std::vector<int> ids = fitted_ids(e);
+      const size_t nf = ids.size(), lo = (size_t)p.lo;
+      const double nan = std::numeric_limits<double>::quiet_NaN();
+      if ((int)nf == e->B) {
+        e->predict_mixture(ids, thetas + lo * SS * n_cols, S, n_cols, weights ? weights + lo * SS : nullptr, log_q ? log_q + lo * SS : nullptr,
+                           testing, m, include_nugget != 0, max_slots, max_points, mean_out + lo * mm, within_out + lo * mm,
+                           between_out + lo * mm, weights_out + lo * SS, logpost_out + lo * SS, ok_out + lo * SS,
+                           ok_all_out ? ok_all_out + lo : nullptr);
+        return;
+      }
+      for (int i = 0; i < e->B; ++i) {
+        const size_t r = lo + i;
+        std::fill(mean_out + r * mm, mean_out + (r + 1) * mm, nan);
+        std::fill(within_out + r * mm, within_out + (r + 1) * mm, nan);
+        std::fill(between_out + r * mm, between_out + (r + 1) * mm, nan);
+        std::fill(weights_out + r * SS, weights_out + (r + 1) * SS, nan);
+        std::fill(logpost_out + r * SS, logpost_out + (r + 1) * SS, nan);
+        std::fill(ok_out + r * SS, ok_out + (r + 1) * SS, 0);
+        if (ok_all_out) ok_all_out[r] = 0;
+      }
+      if (nf == 0) return;
+      // the fitted emulators, compact
+      std::vector<double> th(nf * SS * n_cols), wq(nf * SS), mu(nf * mm), wi(nf * mm), be(nf * mm), wo(nf * SS), lp(nf * SS);
+      std::vector<int> ok(nf * SS), oka(nf);
+      const double* src = weights ? weights : log_q;
+      for (size_t k = 0; k < nf; ++k) {
+        const size_t r = lo + ids[k];
+        std::memcpy(th.data() + k * SS * n_cols, thetas + r * SS * n_cols, SS * n_cols * sizeof(double));
+        std::memcpy(wq.data() + k * SS, src + r * SS, SS * sizeof(double));
+      }
+      e->predict_mixture(ids, th.data(), S, n_cols, weights ? wq.data() : nullptr, log_q ? wq.data() : nullptr, testing, m, include_nugget != 0,
+                         max_slots, max_points, mu.data(), wi.data(), be.data(), wo.data(), lp.data(), ok.data(), oka.data());
+      for (size_t k = 0; k < nf; ++k) {
+        const size_t r = lo + ids[k];
+        std::memcpy(mean_out + r * mm, mu.data() + k * mm, mm * sizeof(double));
+        std::memcpy(within_out + r * mm, wi.data() + k * mm, mm * sizeof(double));
+        std::memcpy(between_out + r * mm, be.data() + k * mm, mm * sizeof(double));
+        std::memcpy(weights_out + r * SS, wo.data() + k * SS, SS * sizeof(double));
+        std::memcpy(logpost_out + r * SS, lp.data() + k * SS, SS * sizeof(double));
+        std::memcpy(ok_out + r * SS, ok.data() + k * SS, SS * sizeof(int));
+        if (ok_all_out) ok_all_out[r] = oka[k];
+      }
     });
   });
 }

@@ -127,6 +127,21 @@ class Engine {
   // entry, the leading n_theta x n_theta block filled; ok[k] = 0 and NaN where the factorisation fails.  Throws for what it does not
   // cover (nugget="pivot", analytic mean, mean parameters in theta, ProductMat52).  The cached state of a fitted emulator is kept.
   void hessian(const std::vector<int>& ids, const std::vector<const double*>& thetas, double* H, int ld, int* ok);
+  // Prediction averaged over S hyperparameter samples per emulator (kernels_mixture.hip).  thetas (E, S, ld): full vectors [mean | data]
+  // of emulator ids[e], the first n_theta of each row used; EXACTLY ONE of weights (E, S, non-negative) and log_q (E, S, the log proposal
+  // density up to a constant: self-normalised importance weights exp(-(F - F_min) - (log_q - log_q at the arg-min)), predict_plan.h
+  // mixture_weights); Xs host (m, D).  The (emulator, sample) pairs are factored on a replica engine (as fit_map's starts are), emulator-major
+  // and sample-ascending, `slots` at a time; THIS engine's emulators are not refitted -- factor, L^-1, K^-1, theta and logpost stay.
+  // Per emulator and point, with the PIVOT mu_0 = the mean of sample 0 -- whatever its weight -- or, where sample 0 failed to factorise,
+  // of the first sample that did, d_s = mu_s - mu_0 and v_s = max(variance + (include_nugget ? sample s's own nugget : 0), 0) as predict()
+  // reports it:   mean = mu_0 + sum w_s d_s,  within = sum w_s v_s,  between = max(sum w_s d_s^2 - (sum w_s d_s)^2, 0)     -- (E, m) each.
+  // Per sample (E, S): the normalised weights, F (the value eval returns, NaN where it failed) and ok.  A sample that fails gets weight 0;
+  // an emulator whose samples all fail or whose weights sum to 0 gets NaN rows and ok_all[e] = 0 (ok_all may be null) -- not an error.
+  // The sums are updated in sample order with one add per sample and no atomics: the same bits for every max_slots >= 1 (slots per pass)
+  // and max_points >= 1 (query points per chunk); 0 = the library's choice.  Throws for nugget="pivot" and the analytic mean.
+  void predict_mixture(const std::vector<int>& ids, const double* thetas, int S, int ld, const double* weights, const double* log_q,
+                       const double* Xs, int m, bool include_nugget, int max_slots, int max_points, double* mean_out, double* within_out,
+                       double* between_out, double* weights_out, double* logpost_out, int* ok_out, int* ok_all);
   // leave-one-out predictive variance of emulator i at its own training inputs (MICEFastGP.fast_predict for every index)
   void loo_variance(int i, double* out);
   // predict(full_cov=True), GaussianProcess.py:899-911: means (nb, m), covs (nb, m, m) host buffers, nugget NOT included

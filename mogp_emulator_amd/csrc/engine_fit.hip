@@ -324,6 +324,44 @@ void Engine::reset_inputs(const std::vector<double>& X) {
   }
 }
 
+// The replica engine of the LAST multi-start fit (or mixture prediction) of the process is kept (one engine per device) and taken again
+// when the next caller has the same shape (n, D, slots, kernel, mean function, device): its 3 x slots matrices are tens of GB, and on SOME
+// boxes fresh allocations of that size cost 0.9 - 1.5 s per fit (bench.py run behind the GPU test suite on the same box: fit_GP_MAP 3.1
+// instead of 2.15 s, every call with 256 slots; on a fresh box 2.13 s from the first call; writing 200 GB from another process beforehand
+// did not reproduce it -- profiles/r06_fitmap_context_and_grad_chain.txt).  A caller of another shape frees it.  MOGP_REPLICA_CACHE=0:
+// every caller builds and frees its own.
+ReplicaLease::ReplicaLease(const Engine& src, long slots, const std::vector<double>& targets, int nug_type, double nug_size) {
+  static const bool on = [] { const char* e = getenv("MOGP_REPLICA_CACHE"); return !e || atoi(e) != 0; }();
+  cache_on = on;
+  {
+    std::lock_guard<std::mutex> lk(replica_cache_mutex());
+    int dev = -1;
+    (void)hipGetDevice(&dev);
+    std::unique_ptr<Engine>& slot = replica_cache(dev);
+    if (slot && cache_on && slot->n == src.n && slot->D == src.D && slot->B == (int)slots && slot->kernel_type == src.kernel_type &&
+        slot->analytic == src.analytic && slot->testing_size == src.testing_size && slot->device_id() == dev &&
+        slot->mean.kind == src.mean.kind && slot->mean.value == src.mean.value && slot->mean.dims == src.mean.dims &&
+        slot->mean.powers == src.mean.powers) {
+      rep = std::move(slot);
+      rep->reset_inputs(src.hX);
+      g_rep_reused += 1;
+    } else {
+      slot.reset();                                   // (frees the old one BEFORE the new one is allocated)
+    }
+  }
+  if (!rep)
+    rep.reset(new Engine(src.hX.data(), src.n, src.D, targets.data(), (int)slots, src.testing_size, src.mean, src.kernel_type, nug_type, nug_size,
+                         src.analytic));
+}
+
+// hand the engine back to the cache when the scope is left normally (an exception destroys it)
+ReplicaLease::~ReplicaLease() {
+  if (!cache_on || !rep || std::uncaught_exceptions() > 0) return;
+  const int dev = rep->device_id();
+  std::lock_guard<std::mutex> lk(replica_cache_mutex());
+  replica_cache(dev) = std::move(rep);
+}
+
 // Multi-start MAP fit (fitting.hpp:61-128, fitting.py:219-266): n_tries L-BFGS runs per emulator, the best end point wins.
 // All (emulator, start) runs go through ONE slot pool (run_pool).  The runs are independent, so as many of them as pay run
 // CONCURRENTLY on a replica engine whose slots take the targets and priors of whatever run they are handed (retarget): small
@@ -414,42 +452,8 @@ void Engine::fit_map_from(const std::vector<int>& ids, const Starts& x0) {
       std::copy(hT.begin() + (size_t)ids[e] * n, hT.begin() + (size_t)(ids[e] + 1) * n, targets.begin() + (size_t)k * n);
     }
     const auto tc0 = std::chrono::steady_clock::now();
-    // The replica engine of the LAST multi-start fit of the process is kept (one engine, process-wide) and taken again when the next fit
-    // has the same shape (n, D, slots, kernel, mean function, device): its 3 x slots matrices are tens of GB, and on SOME boxes fresh
-    // allocations of that size cost 0.9 - 1.5 s per fit (bench.py run behind the GPU test suite on the same box: fit_GP_MAP 3.1 instead of
-    // 2.15 s, every call with 256 slots; on a fresh box 2.13 s from the first call; writing 200 GB from another process beforehand did not
-    // reproduce it -- profiles/r06_fitmap_context_and_grad_chain.txt).  A fit of another shape frees it.  MOGP_REPLICA_CACHE=0: every fit
-    // builds and frees its own.
-    static const bool cache_on = [] { const char* e = getenv("MOGP_REPLICA_CACHE"); return !e || atoi(e) != 0; }();
-    std::unique_ptr<Engine> rep;
-    {
-      std::lock_guard<std::mutex> lk(replica_cache_mutex());
-      int dev = -1;
-      (void)hipGetDevice(&dev);
-      std::unique_ptr<Engine>& slot = replica_cache(dev);
-      if (slot && cache_on && slot->n == n && slot->D == D && slot->B == (int)slots_n && slot->kernel_type == kernel_type && slot->analytic == analytic &&
-          slot->testing_size == testing_size && slot->device == dev && slot->mean.kind == mean.kind && slot->mean.value == mean.value &&
-          slot->mean.dims == mean.dims && slot->mean.powers == mean.powers) {
-        rep = std::move(slot);
-        rep->reset_inputs(hX);
-        g_rep_reused += 1;
-      } else {
-        slot.reset();                                   // (frees the old one BEFORE the new one is allocated)
-      }
-    }
-    if (!rep)
-      rep.reset(new Engine(hX.data(), n, D, targets.data(), (int)slots_n, testing_size, mean, kernel_type, gp[ids[0]].nug_type, gp[ids[0]].nug_size, analytic));
-    // hand the engine back to the cache when this block is left normally (an exception destroys it)
-    struct Keep {
-      std::unique_ptr<Engine>& rep;
-      bool on;
-      ~Keep() {
-        if (!on || !rep || std::uncaught_exceptions() > 0) return;
-        const int dev = rep->device;
-        std::lock_guard<std::mutex> lk(replica_cache_mutex());
-        replica_cache(dev) = std::move(rep);
-      }
-    } keep{rep, cache_on};
+    // (the cached replica engine of the device where its shape matches, else a new one: ReplicaLease, above)
+    ReplicaLease rep(*this, slots_n, targets, gp[ids[0]].nug_type, gp[ids[0]].nug_size);
     g_rep_build_us += std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - tc0).count();
     std::vector<int> holds(slots_n, -1);          // which emulator (index into ids) a slot's targets and priors belong to
     std::vector<int> rslots(slots_n);

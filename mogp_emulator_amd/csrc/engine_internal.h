@@ -6,6 +6,7 @@
 
 #include <atomic>
 #include <cstdlib>
+#include <memory>
 
 namespace mogp {
 
@@ -25,6 +26,25 @@ inline double ks_budget_bytes() {
   static const double budget = [] { const char* e = getenv("MOGP_KS_BUDGET_GB"); return (e ? atof(e) : 12.0) * 1e9; }();
   return budget;
 }
+
+// A replica engine of `slots` slots with the inputs, kernel and mean function of `src`, for the lifetime of a scope (engine_fit.hip): the
+// cached one of the device when its shape matches (taken out of the cache, its inputs reset), else a new one -- whatever the cache held
+// is freed first.  When the scope is left normally the engine goes back into the cache (MOGP_REPLICA_CACHE=0: never); an exception
+// destroys it.  `targets` (slots, n), nug_type and nug_size only initialise a NEW engine: every slot is given its emulator by
+// Engine::retarget before it is used.  Shared by fit_map_from and predict_mixture.
+class ReplicaLease {
+ public:
+  ReplicaLease(const Engine& src, long slots, const std::vector<double>& targets, int nug_type, double nug_size);
+  ~ReplicaLease();
+  ReplicaLease(const ReplicaLease&) = delete;
+  ReplicaLease& operator=(const ReplicaLease&) = delete;
+  Engine* operator->() const { return rep.get(); }
+  Engine& operator*() const { return *rep; }
+
+ private:
+  std::unique_ptr<Engine> rep;
+  bool cache_on;
+};
 
 inline std::atomic<long long> g_bs_timeouts{0}, g_obj_evals{0}, g_grad_evals{0}, g_mc_aborts{0};
 inline std::atomic<long long> g_lb_iters{0}, g_ls_short{0}, g_ls_long{0}, g_lb_runs{0}, g_pool_rounds{0}, g_pool_slot_rounds{0}, g_rep_build_us{0}, g_rep_pool_us{0}, g_retarget_us{0}, g_retargets{0}, g_rep_reused{0};

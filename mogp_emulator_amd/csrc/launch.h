@@ -221,6 +221,20 @@ void launch_hess_pair(const BatchView& v, const double* Xs, double* partial, dou
 // V, U (nb, D, NPh): v_p = M_p^T t, u_p = M_p alpha;  Zv (nb, NPh) = Q^-1 alpha
 void launch_hess_vectors(const BatchView& v, const double* M, double* V, double* U, double* Zv, hipStream_t s);
 
+// --- mixture prediction over hyperparameter samples (kernels_mixture.hip) -------------------------
+// One pass of Engine::predict_mixture: mu / var (rows, ld) are the means and raw variances of the pass's slots that factorised, at the mc
+// query points [c0, c0 + mc) of m.  The pass's slots are emulator-major, sample-ascending; emulator entry b < nemu of the pass is
+//   etab[4 b ..] = { emulator e, its first slot, its number of slots, the row of its pivot sample or -1 (the pivot is of an earlier pass) }
+// and slot k has rows[k] (its row of mu / var, -1: the sample failed and is skipped) and prm[2 k ..] = { weight, nugget to add }.
+// acc (E, 3, m): the running sums  sum w d,  sum w max(var + nugget, 0),  sum w d^2  with d = mu - pivot mean; pivot (E, m): the pivot
+// mean, written by the pass that holds the pivot sample.  One thread per (emulator, point), one add per sample and sum in slot order,
+// plain multiplies and adds (contraction off), no atomics: the sums do not depend on how samples fall into passes or points into chunks.
+void launch_mixture_accumulate(const double* mu, const double* var, long ld, int mc, int nemu, const int* etab, const int* rows,
+                               const double* prm, double* acc, double* pivot, long m, long c0, hipStream_t s);
+// in place, per emulator e < E and point: acc[e][0] <- pivot + sum w d (mean), acc[e][1] stays (within), acc[e][2] <- max(sum w d^2 -
+// (sum w d)^2, 0) (between); all three NaN where alive[e] == 0
+void launch_mixture_finalise(int E, long m, const int* alive, const double* pivot, double* acc, hipStream_t s);
+
 // --- utilities -------------------------------------------------------------------------------
 // out (n,n) <- tile of src (NP,NP): mode 0 copy, mode 1 transpose, mode 2 symmetrise from lower
 void launch_extract(const double* src, int NP, int n, double* out, int mode, hipStream_t s);

@@ -32,6 +32,60 @@ inline std::size_t hessian_group_size(double budget, double per_bytes, std::size
   return (std::size_t)std::max(1.0, std::min((double)n_good, std::floor(budget / per_bytes)));
 }
 
+// Engine::predict_mixture: how many replica slots one pass takes and how many query points one chunk.  The E * S (emulator, sample) pairs
+// are laid out emulator-major, sample-ascending, and pass g takes the pairs [g * slots, (g + 1) * slots): a slot always holds one whole
+// sample, and a contiguous cut of that order never puts a later sample of an emulator in front of an earlier one.  slots: at least one,
+// never more than the E * S pairs, the `device_slots` the device holds beside the source engine, or max_slots (0: the library's choice);
+// above 8 the library's own choice is a multiple of 8, as fit_map's is.  points: max_points where given (at least one, at most m), else the
+// chunk rule of predict() for `slots` emulators (predict_chunk_points).
+struct MixturePlan {
+  long slots;
+  int points;
+};
+inline MixturePlan mixture_plan(long E, long S, int LD, long device_slots, int m, int max_slots, int max_points, double cap_bytes) {
+  const long pairs = std::max<long>(1, E * S);
+  long slots = std::min(pairs, std::max<long>(1, device_slots));
+  if (max_slots > 0) slots = std::min<long>(slots, max_slots);
+  else if (slots > 8 && slots < pairs) slots -= slots % 8;
+  slots = std::max<long>(1, slots);
+  int points;
+  if (max_points > 0) points = std::max(1, std::min(max_points, std::max(1, m)));
+  else points = predict_chunk_points(cap_bytes, (int)std::min<long>(slots, 1L << 30), LD, m);
+  return {slots, points};
+}
+
+// Stage 2 of Engine::predict_mixture: the normalised weights of the S samples of one emulator, from their negative log-posteriors F and
+// ok flags and EITHER explicit weights w_in OR the log proposal density log_q (up to a constant).  With log_q:
+//   l_s = -(F_s - F_min) - (log_q_s - log_q_a),  a = the first ok sample with F_a = F_min over the ok samples,  w_s = exp(l_s - max l)
+// (the shift by max l changes nothing but the range of exp).  Samples that are not ok get weight 0; the rest is divided by its sum.
+// Returns false -- and fills w_out with NaN -- when no sample is ok or the sum is not a positive finite number.
+// mogp_emulator_amd/Marginal.py mixture_weights is the same formula in NumPy.
+inline bool mixture_weights(int S, const double* F, const int* ok, const double* w_in, const double* log_q, double* w_out) {
+  int a = -1;
+  for (int s = 0; s < S; ++s)
+    if (ok[s] && (a < 0 || F[s] < F[a])) a = s;
+  double sum = 0.;
+  if (a >= 0) {
+    if (log_q) {
+      double lmax = -INFINITY;
+      for (int s = 0; s < S; ++s) {
+        w_out[s] = ok[s] ? -(F[s] - F[a]) - (log_q[s] - log_q[a]) : -INFINITY;
+        if (ok[s] && w_out[s] > lmax) lmax = w_out[s];
+      }
+      for (int s = 0; s < S; ++s) w_out[s] = ok[s] ? std::exp(w_out[s] - lmax) : 0.;
+    } else {
+      for (int s = 0; s < S; ++s) w_out[s] = ok[s] ? w_in[s] : 0.;
+    }
+    for (int s = 0; s < S; ++s) sum += w_out[s];
+  }
+  if (!(sum > 0.) || !std::isfinite(sum)) {
+    for (int s = 0; s < S; ++s) w_out[s] = std::nan("");
+    return false;
+  }
+  for (int s = 0; s < S; ++s) w_out[s] /= sum;
+  return true;
+}
+
 // Offsets (in doubles) into the staging block of the mean-function terms of a prediction of nb emulators at m points:
 //   basis (nbasis x m) | dbasis (nterm x m) | coef (nb x nbasis) | LA (nb x qq x qq) | dims, powers (2 nterm ints, in nterm + 1 doubles)
 // nterm = terms of a polynomial mean (0 otherwise), nbasis = 1 + nterm, qq = columns of the analytic mean (0 without).  The first two are

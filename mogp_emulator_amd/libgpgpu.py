@@ -109,6 +109,20 @@ def _outbuf(a, name):
     return a
 
 
+def _mixture_weight_args(weights, log_q, shape):
+    """(weights, log_q) of predict_mixture as contiguous float64 arrays of `shape` or None: exactly one of the two is given"""
+    if (weights is None) == (log_q is None):
+        raise RuntimeError("predict_mixture: exactly one of weights and log_q must be given")
+    out = []
+    for a, name in ((weights, "weights"), (log_q, "log_q")):
+        if a is not None:
+            a = _f64(a, len(shape), name)
+            if a.shape != tuple(shape):
+                raise RuntimeError("predict_mixture: %s must have shape %s" % (name, tuple(shape)))
+        out.append(a)
+    return out
+
+
 def _sobol_call(fn, handle, D, n_out, A, B, unc, include_nugget):
     """shared by DenseGP_GPU.sobol and MultiOutputGP_GPU.sobol: (S, ST, mean, variance, emulator_variance or None), one row per output"""
     a, b = _f64(A, 2, "A"), _f64(B, 2, "B")
@@ -742,6 +756,21 @@ class DenseGP_GPU(object):
         check(_lib.mogp_densegp_logpost_hessian(self._h, dptr(th), int(th.size), dptr(out)))
         return out
 
+    def predict_mixture(self, thetas, testing, weights=None, log_q=None, include_nugget=True, max_slots=0, max_points=0):
+        """Prediction averaged over the S hyperparameter samples thetas (S, n_params), reduced over the samples on the device:
+        (mean, within, between (m,), weights, logpost (S,), ok (S,) bool).  Exactly one of weights (S,) and log_q (S,); the fitted
+        state of the emulator is not touched.  See mogp_densegp_predict_mixture (include/mogp_hip.h)."""
+        th = _f64(thetas, 2, "thetas")
+        x = self._testing(testing)
+        S, m = th.shape[0], x.shape[0]
+        w, q = _mixture_weight_args(weights, log_q, (S,))
+        mean, within, between = np.zeros(m), np.zeros(m), np.zeros(m)
+        wout, lp, ok = np.zeros(S), np.zeros(S), np.zeros(S, dtype=np.int32)
+        check(_lib.mogp_densegp_predict_mixture(self._h, dptr(th), S, th.shape[1], dptr(w), dptr(q), dptr(x), m, x.shape[1],
+                                                int(bool(include_nugget)), int(max_slots), int(max_points), dptr(mean), dptr(within),
+                                                dptr(between), dptr(wout), dptr(lp), iptr(ok)))
+        return mean, within, between, wout, lp, ok.astype(bool)
+
     # -- predict ------------------------------------------------------------------------------
     def _testing(self, testing):
         x = _f64(testing)
@@ -1045,6 +1074,25 @@ class MultiOutputGP_GPU(object):
         """Sobol indices of every emulator in one batched pass per part: (S, ST (n_emulators, D), mean, variance, emulator_variance
         or None (n_emulators,)); rows of emulators that are not fit are NaN"""
         return _sobol_call(_lib.mogp_mogp_sobol, self._h, self.D(), self.n_emulators(), A, B, unc, include_nugget)
+
+    def predict_mixture(self, thetas, testing, weights=None, log_q=None, include_nugget=True, max_slots=0, max_points=0):
+        """DenseGP_GPU.predict_mixture for every emulator, all (emulator, sample) pairs of a part in one batched pass: thetas
+        (n_emulators, S, widest n_params), weights or log_q (n_emulators, S) -> (mean, within, between (n_emulators, m), weights,
+        logpost (n_emulators, S), ok (n_emulators, S) bool, ok_all (n_emulators,) bool).  Rows of emulators that are not fit are NaN."""
+        th = _f64(thetas, 3, "thetas")
+        x = self._testing(testing)
+        ne = self.n_emulators()
+        if th.shape[0] != ne:
+            raise RuntimeError("thetas must have one block of samples per emulator")
+        S, m = th.shape[1], x.shape[0]
+        w, q = _mixture_weight_args(weights, log_q, (ne, S))
+        mean, within, between = np.zeros((ne, m)), np.zeros((ne, m)), np.zeros((ne, m))
+        wout, lp, ok = np.zeros((ne, S)), np.zeros((ne, S)), np.zeros((ne, S), dtype=np.int32)
+        ok_all = np.zeros(ne, dtype=np.int32)
+        check(_lib.mogp_mogp_predict_mixture(self._h, dptr(th), S, th.shape[2], dptr(w), dptr(q), dptr(x), m, x.shape[1],
+                                             int(bool(include_nugget)), int(max_slots), int(max_points), dptr(mean), dptr(within),
+                                             dptr(between), dptr(wout), dptr(lp), iptr(ok), iptr(ok_all)))
+        return mean, within, between, wout, lp, ok.astype(bool), ok_all.astype(bool)
 
     def predict_variance_batch_dev(self, d_testing, m, d_means, d_vars):
         """Device-pointer variant: inputs already resident in HBM, results stay in HBM."""
