@@ -121,7 +121,7 @@ class ShardedMultiOutputGP(object):
                     torch.cuda.set_device(int(device_index))
             except ImportError:
                 pass
-            # the default per-rank model predicts into device buffers whatever its mean function is (capi.hip mogp_mogp_predict_dev)
+            # the default per-rank model predicts into device buffers whatever its mean function is (capi_mogp_predict.hip mogp_mogp_predict_dev)
             self._dev_predict = True
         else:
             self._dev_predict = False

@@ -1,0 +1,23 @@
+"""The rule for a partly fitted model (csrc/fitted_rows.h: compact rows for the emulators that run, scatter, fill the others) through a
+sanitised host program."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_with_rows_properties(tmp_path):
+    """tests/c/fitted_rows_check.cpp sweeps (B, every subset as ids, row lengths) itself and exits non-zero at the first property that
+    fails; built with the address and undefined-behaviour sanitisers"""
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    exe = str(tmp_path / "fitted_rows_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall",
+                           "-I", os.path.join(ROOT, "mogp_emulator_amd", "csrc"), os.path.join(ROOT, "tests", "c", "fitted_rows_check.cpp"),
+                           "-o", exe])
+    out = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "cases ok" in out.stdout
