@@ -167,6 +167,19 @@ int mogp_densegp_predict_mixture(mogp_densegp*, const double* thetas /* S*len */
                                  const double* log_q /* S or NULL; exactly one of the two */, const double* testing, int m, int D,
                                  int include_nugget, int max_slots, int max_points, double* mean_out, double* within_out,
                                  double* between_out /* m each */, double* weights_out, double* logpost_out, int* ok_out /* S each */);
+/* Leave-one-out / k-fold cross-validation of a fitted emulator at its fitted hyperparameters, on the device and without refitting.
+ * labels (n_labels = n): the fold of every training point, values 0 .. k-1, every fold non-empty, 2 <= k <= n; k = n with one point per
+ * fold is leave-one-out (one pass over L^-1).  With Q the factored matrix (nugget included), alpha = Q^-1 (t - m(X)) and
+ * S = (Q^-1)_FF of a fold F, the held-out error is e_F = S^-1 alpha_F and the held-out covariance of the observations S^-1:
+ *   mean_out[i] = t_i - e_i,   var_out[i] = (S^-1)_ii  (include_nugget = 0: max(that - the nugget used, 0))              (n each)
+ *   maha_out[f] = e_F^T S e_F,   log_score_out[f] = log density of t_F given the other folds,   ok_out[f] = 1           (k each)
+ * A fold whose S cannot be factorised gets NaN for its points and scalars and ok_out = 0 (no jitter, status 0).  The folds go through a
+ * scratch engine max_slots at a time (0: the library's choice); the emulator keeps its factor, theta and log-posterior.  No atomics: the
+ * same call returns the same bits.  Refused: nugget type "pivot", the analytic mean, an emulator that is not fit, k < 2 or k > n, a label
+ * outside [0, k), an empty fold, n_labels != n. */
+int mogp_densegp_cross_validate(mogp_densegp*, const int* labels, int n_labels, int k, int include_nugget, int max_slots,
+                                double* mean_out, double* var_out /* n each */, double* maha_out, double* log_score_out,
+                                int* ok_out /* k each */);
 int mogp_densegp_get_K(mogp_densegp*, double* out /* n*n */);
 int mogp_densegp_get_invQ(mogp_densegp*, double* out /* n*n */);
 int mogp_densegp_get_invQt(mogp_densegp*, double* out /* n */);
@@ -255,6 +268,10 @@ int mogp_mogp_predict_mixture(mogp_mogp*, const double* thetas, int S, int n_col
                               const double* testing, int m, int D, int include_nugget, int max_slots, int max_points, double* mean_out,
                               double* within_out, double* between_out, double* weights_out, double* logpost_out, int* ok_out,
                               int* ok_all_out);
+/* mogp_densegp_cross_validate for every emulator with the same folds, all (emulator, fold) pairs of a part in batched passes: mean_out /
+ * var_out (n_out, n), maha_out / log_score_out / ok_out (n_out, k).  Emulators that are not fit give NaN rows and ok_out = 0. */
+int mogp_mogp_cross_validate(mogp_mogp*, const int* labels, int n_labels, int k, int include_nugget, int max_slots, double* mean_out,
+                             double* var_out, double* maha_out, double* log_score_out, int* ok_out);
 /* predict_variance_batch (multioutputgp_gpu.hpp:182-192) with DEVICE pointers: inputs already resident in HBM, results stay in HBM
  * (every mean function; rows of emulators that are not fit are filled with NaN, MultiOutputGP_GPU.py:288-296) */
 int mogp_mogp_predict_variance_batch_dev(mogp_mogp*, const double* d_testing, int m, int D, double* d_means, double* d_vars);

@@ -8,6 +8,7 @@ mogp_emulator_amd -- MI355X (gfx950) native fit + predict backend for mogp_emula
                    host-side mirrors of the reference's GPU-facing Python interface
   HistoryMatching.py, SequentialDesign.py, validation.py
                    consumers of the batched prediction (implausibility, MICE scoring and the sequential-design drivers, validation errors)
+                   and leave-one-out / k-fold cross-validation at the fitted hyperparameters on the device (validation.cross_validate)
   SensitivityAnalysis.py
                    first-order and total-effect Sobol indices of the predictive mean, fused behind the batched prediction
   ExperimentalDesign.py
@@ -34,5 +35,6 @@ if HAVE_LIBGPGPU:
     from .SequentialDesign import MICEFastGP, mice_criterion, SequentialDesign, MICEDesign   # noqa: F401
     from .SensitivityAnalysis import sobol_indices, SobolResult          # noqa: F401
     from . import validation                                                # noqa: F401
+    from .validation import cross_validate, CrossValidationResult, kfold_labels   # noqa: F401
 
 __version__ = "0.1.0"

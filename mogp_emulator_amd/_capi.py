@@ -89,6 +89,8 @@ SIGNATURES = {
     "mogp_densegp_logpost_hessian": (c_int, [c_void_p, c_double_p, c_int, c_double_p]),
     "mogp_densegp_predict_mixture": (c_int, [c_void_p, c_double_p, c_int, c_int, c_double_p, c_double_p, c_double_p, c_int, c_int, c_int, c_int,
                                              c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int_p]),
+    "mogp_densegp_cross_validate": (c_int, [c_void_p, c_int_p, c_int, c_int, c_int, c_int, c_double_p, c_double_p, c_double_p, c_double_p,
+                                            c_int_p]),
     "mogp_densegp_loo_variance": (c_int, [c_void_p, c_double_p]),
     "mogp_densegp_get_K": (c_int, [c_void_p, c_double_p]),
     "mogp_densegp_get_invQ": (c_int, [c_void_p, c_double_p]),
@@ -132,6 +134,8 @@ SIGNATURES = {
     "mogp_mogp_hessian": (c_int, [c_void_p, c_double_p, c_int, c_int, c_double_p, c_int_p]),
     "mogp_mogp_predict_mixture": (c_int, [c_void_p, c_double_p, c_int, c_int, c_double_p, c_double_p, c_double_p, c_int, c_int, c_int, c_int,
                                           c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int_p, c_int_p]),
+    "mogp_mogp_cross_validate": (c_int, [c_void_p, c_int_p, c_int, c_int, c_int, c_int, c_double_p, c_double_p, c_double_p, c_double_p,
+                                         c_int_p]),
     "mogp_mogp_implausibility": (c_int, [c_void_p, c_double_p, c_int, c_int, c_double_p, c_double_p, c_double_p, c_int, c_int, c_double_p]),
     "mogp_mogp_predict_full_cov": (c_int, [c_void_p, c_double_p, c_int, c_int, c_double_p, c_double_p]),
     "mogp_mogp_predict_variance_batch_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),

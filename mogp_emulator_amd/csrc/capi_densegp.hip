@@ -230,6 +230,16 @@ int mogp_densegp_predict_mixture(mogp_densegp* h, const double* thetas, int S, i
                        between_out, weights_out, logpost_out, ok_out, nullptr);
   });
 }
+int mogp_densegp_cross_validate(mogp_densegp* h, const int* labels, int n_labels, int k, int include_nugget, int max_slots, double* mean_out,
+                                double* var_out, double* maha_out, double* log_score_out, int* ok_out) {
+  return on_engine_device(h, [&] {
+    Engine* e = h->eng;
+    const GPState& g = e->gp[h->idx];
+    if (!(g.has_data && g.factored)) throw std::runtime_error("Hyperparameters have not been fit for this Gaussian Process");
+    if (n_labels != e->n) throw std::runtime_error("cross_validate: one fold label per training point is needed");
+    e->cross_validate({h->idx}, labels, k, include_nugget != 0, max_slots, mean_out, var_out, maha_out, log_score_out, ok_out);
+  });
+}
 int mogp_densegp_loo_variance(mogp_densegp* h, double* out) { return on_engine_device(h, [&] { h->eng->loo_variance(h->idx, out); }); }
 int mogp_densegp_get_K(mogp_densegp* h, double* out) { return on_engine_device(h, [&] { h->eng->get_K(h->idx, out); }); }
 int mogp_densegp_get_invQ(mogp_densegp* h, double* out) { return on_engine_device(h, [&] { h->eng->get_invQ(h->idx, out); }); }

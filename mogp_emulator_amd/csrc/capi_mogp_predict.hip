@@ -242,6 +242,26 @@ int mogp_mogp_predict_mixture(mogp_mogp* h, const double* thetas, int S, int n_c
     });
   });
 }
+// every part: its fitted emulators in one Engine::cross_validate, the rows of the others NaN and ok = 0
+int mogp_mogp_cross_validate(mogp_mogp* h, const int* labels, int n_labels, int k, int include_nugget, int max_slots, double* mean_out,
+                             double* var_out, double* maha_out, double* log_score_out, int* ok_out) {
+  return guarded([&] {
+    if (!labels || !mean_out || !var_out || !maha_out || !log_score_out || !ok_out) throw std::runtime_error("cross_validate: null buffer");
+    if (n_labels != h->eng->n) throw std::runtime_error("cross_validate: one fold label per training point is needed");
+    if (k < 2 || k > n_labels) throw std::runtime_error("cross_validate: the number of folds must be between 2 and the number of training points");
+    const size_t nn = (size_t)n_labels, kk = (size_t)k;
+    for_parts(h, [&](mogp_part& p, int) {
+      Engine* e = p.eng.get();
+      const size_t lo = (size_t)p.lo;
+      with_fitted_rows(e,
+                       {Rows::out(mean_out + lo * nn, nn, true), Rows::out(var_out + lo * nn, nn, true), Rows::out(maha_out + lo * kk, kk, true),
+                        Rows::out(log_score_out + lo * kk, kk, true), Rows::out(ok_out + lo * kk, kk, true)},
+                       [&](const std::vector<int>& ids, const std::vector<Rows>& a) {
+                         e->cross_validate(ids, labels, k, include_nugget != 0, max_slots, a[0].d(), a[1].d(), a[2].d(), a[3].d(), a[4].i());
+                       });
+    });
+  });
+}
 int mogp_mogp_predict_variance_batch_dev(mogp_mogp* h, const double* d_testing, int m, int D, double* d_means, double* d_vars) {
   return guarded([&] { mogp_predict_dev_common(h, d_testing, m, D, d_means, d_vars, nullptr); });
 }

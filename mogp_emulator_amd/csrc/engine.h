@@ -142,6 +142,18 @@ class Engine {
   void predict_mixture(const std::vector<int>& ids, const double* thetas, int S, int ld, const double* weights, const double* log_q,
                        const double* Xs, int m, bool include_nugget, int max_slots, int max_points, double* mean_out, double* within_out,
                        double* between_out, double* weights_out, double* logpost_out, int* ok_out, int* ok_all);
+  // Leave-one-out / k-fold predictive errors of emulators `ids` at their fitted hyperparameters, without refitting (kernels_cv.hip).
+  // labels (n): the fold of every training point, values 0 .. k-1, every fold non-empty, 2 <= k <= n.  With Q the factored matrix,
+  // alpha = Q^-1 r and S = (Q^-1)_FF of a fold F: the held-out error is e_F = S^-1 alpha_F and the held-out covariance of the
+  // observations S^-1.  mean / var (ids, n): mean_i = t_i - e_i and var_i = (S^-1)_ii -- with include_nugget false max(var_i - nugget
+  // used, 0) --, in training order.  maha / log_score / ok (ids, k): e_F^T S e_F, the log predictive density of the fold given the
+  // rest, and whether S factorised (0: NaN for the fold's points and scalars; no jitter, no exception).  Every fold a single point:
+  // one pass over L^-1.  Otherwise K^-1 is formed and the (emulator, fold) pairs go, emulator-major and fold-ascending, `slots` per
+  // pass (cv_plan of predict_plan.h; max_slots = 0: the library's choice) through a sub-engine of the call.  THIS engine is only
+  // read, apart from gaining L^-1 / K^-1: theta, factor, alpha and logpost stay.  No atomics: the same call returns the same bits.
+  // Throws for nugget="pivot", the analytic mean, an emulator that is not fit, bad k, a label outside [0, k) and an empty fold.
+  void cross_validate(const std::vector<int>& ids, const int* labels, int k, bool include_nugget, int max_slots, double* mean, double* var,
+                      double* maha, double* log_score, int* ok);
   // leave-one-out predictive variance of emulator i at its own training inputs (MICEFastGP.fast_predict for every index)
   void loo_variance(int i, double* out);
   // predict(full_cov=True), GaussianProcess.py:899-911: means (nb, m), covs (nb, m, m) host buffers, nugget NOT included

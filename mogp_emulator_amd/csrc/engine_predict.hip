@@ -1,5 +1,5 @@
 // The prediction family of Engine: predict and what is fused behind it (full covariance, implausibility, Sobol indices, the mixture over
-// hyperparameter samples, leave-one-out variance).  How each cuts its query points to a byte budget is plain arithmetic in predict_plan.h.
+// hyperparameter samples, cross-validation, leave-one-out variance).  How each cuts its query points to a byte budget is plain arithmetic in predict_plan.h.
 #include "engine_internal.h"
 
 #include <cmath>
@@ -498,6 +498,132 @@ void Engine::predict_mixture(const std::vector<int>& ids, const double* thetas, 
     std::copy(r + mm, r + 2 * mm, within_out + (size_t)e * mm);
     std::copy(r + 2 * mm, r + 3 * mm, between_out + (size_t)e * mm);
   }
+}
+
+// Cross-validation at the fitted hyperparameters (engine.h has the contract, kernels_cv.hip the formulas and the kernels).
+//   every fold a single point: L^-1 and ONE launch of cv_loo_kernel;
+//   otherwise K^-1, then the (emulator, fold) pairs in passes of `slots` (cv_plan) through a sub-engine of nsub = the largest fold size
+//   rows, built as gkdr_R builds its own: per pass factor_prebuilt with cv_gather_kernel as the fill, the log-determinant and L^-T y
+//   launchers on the slots that factorised, cv_finish_kernel; ONE download at the end.
+// The sub-engine and every buffer here are scratch of the call.
+void Engine::cross_validate(const std::vector<int>& ids, const int* labels, int k, bool include_nugget, int max_slots, double* mean_out,
+                            double* var_out, double* maha_out, double* log_score_out, int* ok_out) {
+  const long E = (long)ids.size();
+  if (E == 0) return;
+  require_factored(ids);
+  if (analytic) throw std::runtime_error("cross_validate: not available with analytic_mean=True (a held-out fold changes the mean coefficients)");
+  for (int i : ids)
+    if (gp[i].nug_type == NUG_PIVOT || gp[i].permuted)
+      throw std::runtime_error("cross_validate: not available with nugget=\"pivot\" (a pivoted, possibly rank-deficient factor)");
+  if (!labels || !mean_out || !var_out || !maha_out || !log_score_out || !ok_out) throw std::runtime_error("cross_validate: null buffer");
+  if (k < 2 || k > n) throw std::runtime_error("cross_validate: the number of folds must be between 2 and the number of training points (k = " + std::to_string(k) + ", n = " + std::to_string(n) + ")");
+  if (max_slots < 0) throw std::runtime_error("cross_validate: max_slots must not be negative");
+  if (E * (long)k > (1L << 30)) throw std::runtime_error("cross_validate: too many (emulator, fold) pairs");
+  std::vector<int> size(k, 0);
+  for (int i = 0; i < n; ++i) {
+    if (labels[i] < 0 || labels[i] >= k) throw std::runtime_error("cross_validate: fold label " + std::to_string(labels[i]) + " of point " + std::to_string(i) + " is outside [0, " + std::to_string(k) + ")");
+    size[labels[i]] += 1;
+  }
+  int nsub = 0;
+  for (int f = 0; f < k; ++f) {
+    if (size[f] == 0) throw std::runtime_error("cross_validate: fold " + std::to_string(f) + " is empty");
+    nsub = std::max(nsub, size[f]);
+  }
+
+  // what both paths share: the observations and nuggets of the rows, the result buffers
+  const size_t nn = (size_t)n, kk = (size_t)k;
+  std::vector<double> traw((size_t)E * nn), eta(E);
+  for (long e = 0; e < E; ++e) {
+    std::copy(hT.begin() + (size_t)ids[e] * nn, hT.begin() + (size_t)(ids[e] + 1) * nn, traw.begin() + (size_t)e * nn);
+    eta[e] = gp[ids[e]].nugget_used;
+  }
+  DevBuf<double> dTraw(traw.size()), dEta(eta.size()), dMeanO((size_t)E * nn), dVarO((size_t)E * nn), dMaha((size_t)E * kk), dLs((size_t)E * kk);
+  DevBuf<int> dOk((size_t)E * kk);
+  auto stage = [&](hipStream_t st) {
+    HIPCK(hipMemcpyAsync(dTraw, traw.data(), traw.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCK(hipMemcpyAsync(dEta, eta.data(), eta.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCK(hipMemsetAsync(dMeanO, 0xFF, (size_t)E * nn * sizeof(double), st));
+    HIPCK(hipMemsetAsync(dVarO, 0xFF, (size_t)E * nn * sizeof(double), st));
+    HIPCK(hipMemsetAsync(dMaha, 0xFF, (size_t)E * kk * sizeof(double), st));
+    HIPCK(hipMemsetAsync(dLs, 0xFF, (size_t)E * kk * sizeof(double), st));
+    HIPCK(hipMemsetAsync(dOk, 0, (size_t)E * kk * sizeof(int), st));
+  };
+  auto download = [&](hipStream_t st) {
+    HIPCK(hipMemcpyAsync(mean_out, dMeanO, (size_t)E * nn * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCK(hipMemcpyAsync(var_out, dVarO, (size_t)E * nn * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCK(hipMemcpyAsync(maha_out, dMaha, (size_t)E * kk * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCK(hipMemcpyAsync(log_score_out, dLs, (size_t)E * kk * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCK(hipMemcpyAsync(ok_out, dOk, (size_t)E * kk * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCK(hipStreamSynchronize(st));
+    HIPCK(hipGetLastError());
+  };
+
+  if (nsub == 1) {
+    // leave-one-out: L^-1 only
+    DevBuf<int> dLab(nn);
+    SyncOnUnwind drained{stream};
+    ensure_linv(ids);
+    upload_idx(ids);
+    stage(stream);
+    HIPCK(hipMemcpyAsync(dLab, labels, nn * sizeof(int), hipMemcpyHostToDevice, stream));
+    launch_cv_loo(view((int)E), dLab, dTraw, dEta, include_nugget, dMeanO, dVarO, dMaha, dLs, dOk, stream);
+    download(stream);
+    return;
+  }
+
+  // fold index lists (k, nsub), -1 behind the end of a short fold; the points of a fold in ascending order
+  std::vector<int> folds((size_t)k * nsub, -1), fillp(k, 0);
+  for (int i = 0; i < n; ++i) folds[(size_t)labels[i] * nsub + fillp[labels[i]]++] = i;
+  const int NPsub = roundup(nsub + 1, TILE);
+  const long pairs = E * k;
+  long device_slots = pairs;
+  {
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
+      device_slots = (long)std::max(1.0, std::floor(0.5 * (double)free_b / cv_slot_bytes(NPsub)));
+  }
+  const long slots = cv_plan(E, k, NPsub, device_slots, max_slots);
+
+  ensure_kinv(ids, false);
+  HIPCK(hipStreamSynchronize(stream));        // the sub-engine reads K^-1 and alpha on its own stream
+  const BatchView src = view(0);
+  const std::vector<double> zeros((size_t)slots * nsub, 0.0);
+  Engine sub(zeros.data(), nsub, 1, zeros.data(), (int)slots, 0, MeanFunc(), 0, NUG_FIXED, 0.0);
+  if (sub.NP != NPsub) throw std::runtime_error("cross_validate: unexpected layout of the sub-engine");
+  hipStream_t st = sub.stream;
+  DevBuf<int> dFolds(folds.size()), dTab(4 * (size_t)slots);
+  SyncOnUnwind drained{st};
+  stage(st);
+  HIPCK(hipMemcpyAsync(dFolds, folds.data(), folds.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  std::vector<int> tab(4 * (size_t)slots), info, okslots;
+  const std::function<void(const BatchView&)> fill = [&](const BatchView& sv) {
+    if (sv.nb != (int)slots) throw std::runtime_error("cross_validate: the factorisation must cover every slot");
+    launch_cv_gather(src, dFolds, dTab, (int)slots, sv.A, nsub, NPsub, st);
+  };
+  for (long p0 = 0; p0 < pairs; p0 += slots) {
+    const long cnt = std::min(slots, pairs - p0);
+    for (long s = 0; s < slots; ++s) {
+      const long e = (p0 + s) / k, f = (p0 + s) % k;
+      int* t = tab.data() + 4 * s;
+      if (s < cnt) { t[0] = ids[(size_t)e]; t[1] = (int)e; t[2] = (int)f; t[3] = size[f]; }
+      else { t[0] = -1; t[1] = t[2] = t[3] = 0; }     // not used: an identity, so that the batch factorises
+    }
+    HIPCK(hipMemcpyAsync(dTab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    sub.factor_prebuilt(fill, info);
+    okslots.clear();
+    for (long s = 0; s < cnt; ++s)
+      if (info[s] == 0) okslots.push_back((int)s);
+    if (!okslots.empty()) {
+      sub.upload_idx(okslots);
+      const BatchView sv = sub.view((int)okslots.size());
+      launch_logdet(sv, sub.dInfo, sub.dRes, st);
+      launch_alpha_from_linv(sv, st);
+    }
+    launch_cv_finish(dFolds, dTab, (int)cnt, sub.dLinv, sub.dAlpha, sub.dRes, sub.dInfo, nsub, NPsub, dTraw, dEta, include_nugget, n, k, dMeanO,
+                     dVarO, dMaha, dLs, dOk, st);
+    HIPCK(hipStreamSynchronize(st));          // `tab` is rewritten by the next pass
+  }
+  download(st);
 }
 
 void Engine::loo_variance(int i, double* out) {

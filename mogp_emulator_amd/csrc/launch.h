@@ -235,6 +235,22 @@ void launch_mixture_accumulate(const double* mu, const double* var, long ld, int
 // (sum w d)^2, 0) (between); all three NaN where alive[e] == 0
 void launch_mixture_finalise(int E, long m, const int* alive, const double* pivot, double* acc, hipStream_t s);
 
+// --- cross-validation at the fitted hyperparameters (kernels_cv.hip) -------------------------------
+// Result rows are in the order of the launch's slots (caller rows): mean / var (rows, n), maha / log_score / ok (rows, k); targets (rows, n)
+// are the observations t themselves (mean = t - e), eta (rows) the nugget taken off var again without include_nugget.
+// Leave-one-out from L^-1 and alpha of the slots of v: labels (n) = the fold of every point, a permutation of 0 .. n-1 (k = n).
+void launch_cv_loo(const BatchView& v, const int* labels, const double* targets, const double* eta, bool include_nugget, double* mean,
+                   double* var, double* maha, double* log_score, int* ok, hipStream_t s);
+// One pass of the k-fold path over `nslots` slots of a sub-engine of nsub rows (NPsub = roundup(nsub + 1, 128)).  tab: four ints per slot,
+// { source emulator (index into v's buffers; -1: slot not used), caller row, fold, fold size }; folds (k, nsub): the training indices of
+// every fold, -1 where it is shorter than nsub.  gather: subA[slot] <- the factor-matrix layout above with S = Kinv[F, F] (lower tiles of
+// Kinv mirrored on load), alpha[F] in row nsub, a unit diagonal and a zero target for the missing points of a short fold (and for a
+// slot that is not used).  finish: Linv / sol / res / info are the sub-engine's L^-1, solution rows, launch_logdet words and status words.
+void launch_cv_gather(const BatchView& v, const int* folds, const int* tab, int nslots, double* subA, int nsub, int NPsub, hipStream_t s);
+void launch_cv_finish(const int* folds, const int* tab, int nslots, const double* Linv, const double* sol, const double* res, const int* info,
+                      int nsub, int NPsub, const double* targets, const double* eta, bool include_nugget, int n, int k, double* mean,
+                      double* var, double* maha, double* log_score, int* ok, hipStream_t s);
+
 // --- utilities -------------------------------------------------------------------------------
 // out (n,n) <- tile of src (NP,NP): mode 0 copy, mode 1 transpose, mode 2 symmetrise from lower
 void launch_extract(const double* src, int NP, int n, double* out, int mode, hipStream_t s);

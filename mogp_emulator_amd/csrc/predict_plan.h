@@ -54,6 +54,21 @@ inline MixturePlan mixture_plan(long E, long S, int LD, long device_slots, int m
   return {slots, points};
 }
 
+// Engine::cross_validate: how many (emulator, fold) pairs one pass of the sub-engine takes.  The E * k pairs are laid out emulator-major,
+// fold-ascending, and pass g takes the pairs [g * slots, (g + 1) * slots).  slots: at least one, never more than the E * k pairs, the
+// `device_slots` that half of the free memory holds at 3 NPsub^2 doubles per slot (factor, L^-1 and its scratch; cv_slot_bytes), the batch
+// bound predict_mixture's replica engine observes (cv_slot_bound: the batched kernels of a factorisation stay in the range of tiles per
+// launch they run at there, and a slot is one grid row), or max_slots (0: the library's choice).
+inline double cv_slot_bytes(int NPsub) { return 3.0 * (double)NPsub * (double)NPsub * 8.0; }
+inline long cv_slot_bound(int NPsub) { return std::min<long>(65535, 4095 / std::max(1, NPsub / 128) + 1); }
+inline long cv_plan(long E, long k, int NPsub, long device_slots, int max_slots) {
+  const long pairs = std::max<long>(1, E * k);
+  long slots = std::min(pairs, std::max<long>(1, device_slots));
+  slots = std::min(slots, cv_slot_bound(NPsub));
+  if (max_slots > 0) slots = std::min<long>(slots, max_slots);
+  return std::max<long>(1, slots);
+}
+
 // Stage 2 of Engine::predict_mixture: the normalised weights of the S samples of one emulator, from their negative log-posteriors F and
 // ok flags and EITHER explicit weights w_in OR the log proposal density log_q (up to a constant).  With log_q:
 //   l_s = -(F_s - F_min) - (log_q_s - log_q_a),  a = the first ok sample with F_a = F_min over the ok samples,  w_s = exp(l_s - max l)

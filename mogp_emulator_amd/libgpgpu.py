@@ -109,6 +109,16 @@ def _outbuf(a, name):
     return a
 
 
+def _cv_labels(labels, n):
+    """fold labels of cross_validate as a contiguous int32 vector with one entry per training point"""
+    lab = np.asarray(labels)
+    if lab.ndim != 1 or lab.shape[0] != n:
+        raise RuntimeError("cross_validate: one fold label per training point is needed")
+    if not np.issubdtype(lab.dtype, np.integer):
+        raise RuntimeError("cross_validate: the fold labels must be integers")
+    return np.ascontiguousarray(lab, dtype=np.int32)
+
+
 def _mixture_weight_args(weights, log_q, shape):
     """(weights, log_q) of predict_mixture as contiguous float64 arrays of `shape` or None: exactly one of the two is given"""
     if (weights is None) == (log_q is None):
@@ -771,6 +781,19 @@ class DenseGP_GPU(object):
                                                 dptr(between), dptr(wout), dptr(lp), iptr(ok)))
         return mean, within, between, wout, lp, ok.astype(bool)
 
+    def cross_validate(self, labels, k, include_nugget=True, max_slots=0):
+        """Leave-one-out / k-fold predictive errors at the fitted hyperparameters, on the device and without refitting: labels (n,)
+        ints in [0, k) -> (mean, var (n,), mahalanobis, log_score (k,), ok (k,) bool).  The fitted state of the emulator is not
+        touched.  See mogp_densegp_cross_validate (include/mogp_hip.h)."""
+        n = self.n()
+        lab = _cv_labels(labels, n)
+        k = int(k)
+        mean, var = np.zeros(n), np.zeros(n)
+        maha, ls, ok = np.zeros(max(k, 0)), np.zeros(max(k, 0)), np.zeros(max(k, 0), dtype=np.int32)
+        check(_lib.mogp_densegp_cross_validate(self._h, iptr(lab), n, k, int(bool(include_nugget)), int(max_slots), dptr(mean), dptr(var),
+                                               dptr(maha), dptr(ls), iptr(ok)))
+        return mean, var, maha, ls, ok.astype(bool)
+
     # -- predict ------------------------------------------------------------------------------
     def _testing(self, testing):
         x = _f64(testing)
@@ -1093,6 +1116,20 @@ class MultiOutputGP_GPU(object):
                                              int(bool(include_nugget)), int(max_slots), int(max_points), dptr(mean), dptr(within),
                                              dptr(between), dptr(wout), dptr(lp), iptr(ok), iptr(ok_all)))
         return mean, within, between, wout, lp, ok.astype(bool), ok_all.astype(bool)
+
+    def cross_validate(self, labels, k, include_nugget=True, max_slots=0):
+        """DenseGP_GPU.cross_validate for every emulator with the same folds, all (emulator, fold) pairs of a part in batched
+        passes: (mean, var (n_emulators, n), mahalanobis, log_score (n_emulators, k), ok (n_emulators, k) bool).  Rows of emulators
+        that are not fit are NaN with ok False."""
+        n, ne = self.n(), self.n_emulators()
+        lab = _cv_labels(labels, n)
+        k = int(k)
+        kk = max(k, 0)
+        mean, var = np.zeros((ne, n)), np.zeros((ne, n))
+        maha, ls, ok = np.zeros((ne, kk)), np.zeros((ne, kk)), np.zeros((ne, kk), dtype=np.int32)
+        check(_lib.mogp_mogp_cross_validate(self._h, iptr(lab), n, k, int(bool(include_nugget)), int(max_slots), dptr(mean), dptr(var),
+                                            dptr(maha), dptr(ls), iptr(ok)))
+        return mean, var, maha, ls, ok.astype(bool)
 
     def predict_variance_batch_dev(self, d_testing, m, d_means, d_vars):
         """Device-pointer variant: inputs already resident in HBM, results stay in HBM."""
