@@ -35,6 +35,9 @@ struct DeviceGuard {
   DeviceGuard& operator=(const DeviceGuard&) = delete;
 };
 
+struct CvBuffers;      // engine_analysis.hip
+struct CvFolds;        // predict_plan.h
+
 struct GPState {
   std::vector<double> data;      // n_data: corr_raw (NC), log sigma^2, [log nugget]
   std::vector<double> meanp;     // n_mean
@@ -258,6 +261,22 @@ class Engine {
   void implausibility_chunks(const std::vector<int>& ids, const double* Xs, int m, int MC, const double* obs, const double* obs_var,
                              const double* discrepancy, bool include_nugget, const std::function<void(const double*, int, int)>& tail);
   void ensure_predict_scratch(int nb, int MC);
+  // free device memory in bytes; false: the runtime could not tell (the callers then keep their own fallback)
+  bool free_device_bytes(double& free_bytes) const;
+  // the steps of hessian (engine_analysis.hip).  hessian_move_to: the emulators to their thetas -- fine[k] = 1 where ids[k] holds a factor
+  // there, before[k] = the theta it has to be put back at (hessian_put_back).  hessian_group_sums: the device sums of one group of emulators
+  // into their host copies (six launches behind the gradient's, six downloads, one synchronisation)
+  struct HessianScratch;
+  struct HessianSums;
+  void hessian_move_to(const std::vector<int>& ids, const std::vector<const double*>& thetas, double* H, int ld, std::vector<int>& fine,
+                       std::vector<std::vector<double>>& before);
+  void hessian_group_sums(const std::vector<int>& grp, HessianScratch& d, HessianSums& h);
+  void hessian_put_back(const std::vector<int>& ids, const std::vector<std::vector<double>>& before);
+  // the two paths of cross_validate (engine_analysis.hip): every fold a single point / the folds of cf through a sub-engine
+  void cv_leave_one_out(const std::vector<int>& ids, const int* labels, bool include_nugget, CvBuffers& b, double* mean_out, double* var_out,
+                        double* maha_out, double* log_score_out, int* ok_out);
+  void cv_kfold(const std::vector<int>& ids, const CvFolds& cf, int k, bool include_nugget, int max_slots, CvBuffers& b, double* mean_out,
+                double* var_out, double* maha_out, double* log_score_out, int* ok_out);
 
   DevBuf<double> dX, dP, dT, dA, dLinv, dKinv, dAlpha;
   // signal word of the stream memory operations of the look-ahead schedule.  The one raw pointer of the engine: signal memory comes from

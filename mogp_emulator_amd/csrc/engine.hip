@@ -208,6 +208,13 @@ double Engine::nugget_size(int i) const {
   return g.nug_size;
 }
 
+bool Engine::free_device_bytes(double& free_bytes) const {
+  size_t free_b = 0, total_b = 0;
+  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return false;
+  free_bytes = (double)free_b;
+  return true;
+}
+
 // K build of the slots in dIdx.  With one right-hand side it also presets the solution rows to the all-ones pattern the one-launch
 // back substitution polls for (backsolve_chain_kernel<SENT>); `z_armed` records that, so that a chain launched on a row that has
 // not been preset since its last solve arms it itself instead of reading stale values as "already there".
@@ -633,164 +640,6 @@ void Engine::grad_current(const std::vector<int>& ids, double* grad, int grad_ld
       }
     }
   }
-}
-
-// Hessian of the negative log-posterior at per-emulator thetas (kernels_hess.hip, DESIGN.md section 3 "Hessian"): H holds one ld x ld
-// row-major block per entry of ids, its leading n_theta x n_theta block filled (both triangles, exactly symmetric) and the rest of it
-// NaN (an emulator narrower than ld), all of it NaN where the factorisation fails (ok = 0).  An emulator already fit at exactly theta is not evaluated again; one that was fit elsewhere is put back
-// at its own theta afterwards, so its cached state is what it was.  The planes M_p are scratch of this call, taken per group of
-// emulators within the prediction's chunk budget and freed before it returns.
-void Engine::hessian(const std::vector<int>& ids, const std::vector<const double*>& thetas, double* H, int ld, int* ok) {
-  const int nb = (int)ids.size();
-  if (nb == 0) return;
-  if (analytic) throw std::runtime_error("logpost_hessian: not available with analytic_mean=True (the mean coefficients are integrated out of theta)");
-  if (n_mean() > 0) throw std::runtime_error("logpost_hessian: not available for a mean function with parameters in theta");
-  if (kernel_type == 2) throw std::runtime_error("logpost_hessian: not available for the ProductMat52 kernel");
-  for (int i : ids)
-    if (gp[i].nug_type == NUG_PIVOT)
-      throw std::runtime_error("logpost_hessian: not available with nugget=\"pivot\" (a pivoted, possibly rank-deficient factor)");
-  const double nan = std::numeric_limits<double>::quiet_NaN();
-  std::vector<std::vector<double>> before(nb);      // theta of the emulators that have to be put back
-  std::vector<int> ev_ids, ev_pos;
-  std::vector<const double*> ev_th;
-  std::vector<int> fine(nb, 0);
-  for (int k = 0; k < nb; ++k) {
-    const int i = ids[k];
-    const GPState& g = gp[i];
-    const int P = n_theta(i);
-    if (P > ld) throw std::runtime_error("logpost_hessian: the result buffer passed was too small");
-    std::fill(H + (size_t)k * ld * ld, H + (size_t)(k + 1) * ld * ld, nan);
-    const bool fit = g.has_data && g.factored;
-    if (fit && !g.logpost_stale && std::equal(g.data.begin(), g.data.end(), thetas[k])) {
-      fine[k] = 1;
-      continue;
-    }
-    if (fit) before[k] = g.data;
-    ev_ids.push_back(i);
-    ev_pos.push_back(k);
-    ev_th.push_back(thetas[k]);
-  }
-  if (!ev_ids.empty()) {
-    std::vector<double> f(ev_ids.size());
-    std::vector<int> okv(ev_ids.size());
-    eval(ev_ids, ev_th, false, f.data(), nullptr, 0, okv.data());
-    for (size_t e = 0; e < ev_ids.size(); ++e) fine[ev_pos[e]] = okv[e];
-  }
-  std::vector<int> good, gpos;
-  for (int k = 0; k < nb; ++k)
-    if (fine[k]) {
-      good.push_back(ids[k]);
-      gpos.push_back(k);
-    }
-  if (!good.empty()) {
-    ensure_kinv(good, true);
-    const int NPh = hess_np(n), NQ = D + 3, TQ = D + 2, TS = (D + 1) * TQ, TG = hess_trace_groups(n), PGR = hess_pair_groups(n);
-    const size_t plane = (size_t)NPh * NPh;
-    const double per = 8.0 * ((double)D * plane + (double)NPh * (3.0 * D + 1.0) + (double)TS * (TG + 1.0) + (double)D * D * (PGR + 1.0));
-    const size_t gsz = hessian_group_size(ks_budget_bytes(), per, good.size());
-    std::vector<double> go((size_t)B * NQ), To, Po, V, U, Zv, al(n), tt(n), dpr(NC + 2), Fd((size_t)TQ * TQ);
-    for (size_t g0 = 0; g0 < good.size(); g0 += gsz) {
-      const std::vector<int> grp(good.begin() + g0, good.begin() + std::min(good.size(), g0 + gsz));
-      const size_t m = grp.size();
-      DevBuf<double> dXs(m * NPh * D), dMp(m * D * plane), dTp(m * TG * TS), dTo(m * TS), dPp(m * PGR * D * D), dPo(m * D * D), dV(m * D * NPh),
-          dU(m * D * NPh), dZv(m * NPh);
-      SyncOnUnwind drained{stream};
-      upload_idx(grp);
-      BatchView v = view((int)m);
-      launch_grad(v, dGradPartial, dGradOut, stream);
-      launch_hess_scale(v, dXs, stream);
-      launch_hess_planes(v, dXs, dMp, stream);
-      launch_hess_trace(v, dMp, dTp, dTo, stream);
-      launch_hess_pair(v, dXs, dPp, dPo, stream);
-      launch_hess_vectors(v, dMp, dV, dU, dZv, stream);
-      To.resize(m * TS); Po.resize(m * D * D); V.resize(m * D * NPh); U.resize(m * D * NPh); Zv.resize(m * NPh);
-      HIPCK(hipMemcpyAsync(go.data(), dGradOut, go.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-      HIPCK(hipMemcpyAsync(To.data(), dTo, To.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-      HIPCK(hipMemcpyAsync(Po.data(), dPo, Po.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-      HIPCK(hipMemcpyAsync(V.data(), dV, V.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-      HIPCK(hipMemcpyAsync(U.data(), dU, U.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-      HIPCK(hipMemcpyAsync(Zv.data(), dZv, Zv.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-      HIPCK(hipStreamSynchronize(stream));
-      HIPCK(hipGetLastError());
-      for (size_t s = 0; s < m; ++s) {
-        const int i = grp[s], k = gpos[g0 + s];
-        const GPState& g = gp[i];
-        HIPCK(hipMemcpy(al.data(), dAlpha + (size_t)i * RA * LD, n * sizeof(double), hipMemcpyDeviceToHost));
-        HIPCK(hipMemcpy(tt.data(), dT + (size_t)i * n, n * sizeof(double), hipMemcpyDeviceToHost));
-        const double eta = g.nugget_used, eta2 = eta * eta;
-        const double* o = go.data() + (size_t)i * NQ;
-        const double* T = To.data() + s * TS;
-        const double* A = Po.data() + s * D * D;
-        const double* z = Zv.data() + s * NPh;
-        auto dot = [&](const double* a, const double* b) {
-          double acc = 0.;
-          for (int e = 0; e < n; ++e) acc += a[e] * b[e];
-          return acc;
-        };
-        const double ta = dot(tt.data(), al.data()), aa = dot(al.data(), al.data()), az = dot(al.data(), z);
-        const double trK = o[D + 1], trK2 = T[D * TQ + D];
-        // per-dimension matrix over [corr_0 .. corr_{D-1} | cov | nugget], upper triangle
-        std::fill(Fd.begin(), Fd.end(), 0.);
-        for (int p = 0; p < D; ++p) {
-          const double* vp = V.data() + (s * D + p) * NPh;
-          for (int q = p; q < D; ++q)
-            Fd[p * TQ + q] = dot(vp, U.data() + (s * D + q) * NPh) - 0.5 * T[p * TQ + q] + 0.5 * A[p * D + q] + (p == q ? o[p] : 0.);
-          const double va = dot(vp, al.data()), vz = dot(vp, z);
-          Fd[p * TQ + D] = (va - eta * vz) - 0.5 * (T[p * TQ + D + 1] - eta * T[p * TQ + D]) + o[p];
-          Fd[p * TQ + D + 1] = eta * vz - 0.5 * eta * T[p * TQ + D];
-        }
-        Fd[D * TQ + D] = (ta - 2. * eta * aa + eta2 * az) - 0.5 * ((double)n - 2. * eta * trK + eta2 * trK2) + o[D];
-        Fd[D * TQ + D + 1] = (eta * aa - eta2 * az) - 0.5 * (eta * trK - eta2 * trK2);
-        Fd[(D + 1) * TQ + D + 1] = eta2 * az - 0.5 * eta2 * trK2 + 0.5 * eta * (trK - o[D + 2]);
-        // theta order [corr (NC) | cov | nugget (fit only)]; one shared length scale: the sums of the per-dimension block and rows
-        const int P = n_theta(i);
-        std::vector<double> Hm((size_t)P * P, 0.);
-        auto fd = [&](int p, int q) { return p <= q ? Fd[p * TQ + q] : Fd[q * TQ + p]; };
-        auto src = [&](int r) { return r < NC ? r : D + (r - NC); };      // per-dimension index of a non-correlation parameter
-        for (int r = 0; r < P; ++r)
-          for (int c = r; c < P; ++c) {
-            double val;
-            if (!uniform() || r >= NC) val = fd(src(r), src(c));
-            else if (c >= NC) {
-              val = 0.;
-              for (int p = 0; p < D; ++p) val += fd(p, src(c));
-            } else {
-              val = 0.;
-              for (int p = 0; p < D; ++p)
-                for (int q = 0; q < D; ++q) val += fd(p, q);
-            }
-            Hm[(size_t)r * P + c] = val;
-          }
-        g.pri.d2logpdtheta2(g.data, NC, g.nug_type, dpr.data());
-        bool finite = true;
-        for (int r = 0; r < P; ++r) {
-          Hm[(size_t)r * P + r] -= dpr[r];
-          for (int c = r; c < P; ++c) finite = finite && std::isfinite(Hm[(size_t)r * P + c]);
-        }
-        if (!finite) {
-          fine[k] = 0;
-          continue;
-        }
-        for (int r = 0; r < P; ++r)
-          for (int c = r; c < P; ++c) H[((size_t)k * ld + r) * ld + c] = H[((size_t)k * ld + c) * ld + r] = Hm[(size_t)r * P + c];
-      }
-    }
-  }
-  // back to where the emulators were
-  std::vector<int> rb_ids;
-  std::vector<const double*> rb_th;
-  for (int k = 0; k < nb; ++k)
-    if (!before[k].empty()) {
-      rb_ids.push_back(ids[k]);
-      rb_th.push_back(before[k].data());
-    }
-  if (!rb_ids.empty()) {
-    std::vector<double> f(rb_ids.size());
-    std::vector<int> okv(rb_ids.size());
-    eval(rb_ids, rb_th, false, f.data(), nullptr, 0, okv.data());
-  }
-  if (ok)
-    for (int k = 0; k < nb; ++k) ok[k] = fine[k];
 }
 
 void Engine::unpermute(int i, double* vec) const {

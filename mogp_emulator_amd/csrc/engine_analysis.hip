@@ -1,0 +1,446 @@
+// The analysis family of Engine: what is computed AROUND a fit rather than by it -- the Hessian of the log-posterior, the prediction
+// averaged over hyperparameter samples and cross-validation.  Each reads as its steps; the host algebra of the Hessian is
+// hessian_assemble (hostmath.h), the sizing rules and the index tables of the passes are plain arithmetic in predict_plan.h.
+#include "engine_internal.h"
+
+#include <cmath>
+#include <limits>
+
+namespace mogp {
+
+// ---------------------------------------------------------------------------------------------
+// Hessian of the negative log-posterior at per-emulator thetas (kernels_hess.hip, DESIGN.md section 3 "Hessian"): H holds one ld x ld
+// row-major block per entry of ids, its leading n_theta x n_theta block filled (both triangles, exactly symmetric) and the rest of it
+// NaN (an emulator narrower than ld), all of it NaN where the factorisation fails (ok = 0).  An emulator already fit at exactly theta is not evaluated again; one that was fit elsewhere is put back
+// at its own theta afterwards, so its cached state is what it was.  The planes M_p are scratch of this call, taken per group of
+// emulators within the prediction's chunk budget and freed before it returns.
+// ---------------------------------------------------------------------------------------------
+
+// the device scratch of one group of m emulators; `drained` comes last, so that the stream is drained before the buffers go when the
+// group is left through an exception
+struct Engine::HessianScratch {
+  DevBuf<double> dXs, dMp, dTp, dTo, dPp, dPo, dV, dU, dZv;
+  SyncOnUnwind drained;
+  HessianScratch(size_t m, int NPh, int D, int TG, int PGR, hipStream_t st)
+      : dXs(m * NPh * D), dMp(m * D * ((size_t)NPh * NPh)), dTp(m * TG * ((D + 1) * (D + 2))), dTo(m * ((D + 1) * (D + 2))), dPp(m * PGR * D * D),
+        dPo(m * D * D), dV(m * D * NPh), dU(m * D * NPh), dZv(m * NPh), drained{st} {}
+};
+
+// the host copies of a group's sums (kept from one group to the next)
+struct Engine::HessianSums {
+  std::vector<double> go, To, Po, V, U, Zv;
+};
+
+// Brings the emulators of ids to their thetas: fine[k] = 1 where emulator ids[k] holds a factor at thetas[k] afterwards -- it was there
+// already, or it was evaluated there --, before[k] = the theta a fitted emulator was moved away from (empty: nothing to put back).
+// Every block of H is set to NaN on the way.
+void Engine::hessian_move_to(const std::vector<int>& ids, const std::vector<const double*>& thetas, double* H, int ld, std::vector<int>& fine,
+                             std::vector<std::vector<double>>& before) {
+  const int nb = (int)ids.size();
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  std::vector<int> ev_ids, ev_pos;
+  std::vector<const double*> ev_th;
+  for (int k = 0; k < nb; ++k) {
+    const int i = ids[k];
+    const GPState& g = gp[i];
+    const int P = n_theta(i);
+    if (P > ld) throw std::runtime_error("logpost_hessian: the result buffer passed was too small");
+    std::fill(H + (size_t)k * ld * ld, H + (size_t)(k + 1) * ld * ld, nan);
+    const bool fit = g.has_data && g.factored;
+    if (fit && !g.logpost_stale && std::equal(g.data.begin(), g.data.end(), thetas[k])) {
+      fine[k] = 1;
+      continue;
+    }
+    if (fit) before[k] = g.data;
+    ev_ids.push_back(i);
+    ev_pos.push_back(k);
+    ev_th.push_back(thetas[k]);
+  }
+  if (!ev_ids.empty()) {
+    std::vector<double> f(ev_ids.size());
+    std::vector<int> okv(ev_ids.size());
+    eval(ev_ids, ev_th, false, f.data(), nullptr, 0, okv.data());
+    for (size_t e = 0; e < ev_ids.size(); ++e) fine[ev_pos[e]] = okv[e];
+  }
+}
+
+// back to where the emulators were
+void Engine::hessian_put_back(const std::vector<int>& ids, const std::vector<std::vector<double>>& before) {
+  std::vector<int> rb_ids;
+  std::vector<const double*> rb_th;
+  for (size_t k = 0; k < ids.size(); ++k)
+    if (!before[k].empty()) {
+      rb_ids.push_back(ids[k]);
+      rb_th.push_back(before[k].data());
+    }
+  if (!rb_ids.empty()) {
+    std::vector<double> f(rb_ids.size());
+    std::vector<int> okv(rb_ids.size());
+    eval(rb_ids, rb_th, false, f.data(), nullptr, 0, okv.data());
+  }
+}
+
+// the device sums of the emulators of grp (K^-1 is there): the gradient's, then scale, planes, trace, pair and vectors; six downloads,
+// ONE synchronisation
+void Engine::hessian_group_sums(const std::vector<int>& grp, HessianScratch& d, HessianSums& h) {
+  const size_t m = grp.size();
+  const int NPh = hess_np(n), TS = (D + 1) * (D + 2);
+  upload_idx(grp);
+  BatchView v = view((int)m);
+  launch_grad(v, dGradPartial, dGradOut, stream);
+  launch_hess_scale(v, d.dXs, stream);
+  launch_hess_planes(v, d.dXs, d.dMp, stream);
+  launch_hess_trace(v, d.dMp, d.dTp, d.dTo, stream);
+  launch_hess_pair(v, d.dXs, d.dPp, d.dPo, stream);
+  launch_hess_vectors(v, d.dMp, d.dV, d.dU, d.dZv, stream);
+  h.To.resize(m * TS); h.Po.resize(m * D * D); h.V.resize(m * D * NPh); h.U.resize(m * D * NPh); h.Zv.resize(m * NPh);
+  HIPCK(hipMemcpyAsync(h.go.data(), dGradOut, h.go.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+  HIPCK(hipMemcpyAsync(h.To.data(), d.dTo, h.To.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+  HIPCK(hipMemcpyAsync(h.Po.data(), d.dPo, h.Po.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+  HIPCK(hipMemcpyAsync(h.V.data(), d.dV, h.V.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+  HIPCK(hipMemcpyAsync(h.U.data(), d.dU, h.U.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+  HIPCK(hipMemcpyAsync(h.Zv.data(), d.dZv, h.Zv.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+  HIPCK(hipStreamSynchronize(stream));
+  HIPCK(hipGetLastError());
+}
+
+void Engine::hessian(const std::vector<int>& ids, const std::vector<const double*>& thetas, double* H, int ld, int* ok) {
+  const int nb = (int)ids.size();
+  if (nb == 0) return;
+  if (analytic) throw std::runtime_error("logpost_hessian: not available with analytic_mean=True (the mean coefficients are integrated out of theta)");
+  if (n_mean() > 0) throw std::runtime_error("logpost_hessian: not available for a mean function with parameters in theta");
+  if (kernel_type == 2) throw std::runtime_error("logpost_hessian: not available for the ProductMat52 kernel");
+  for (int i : ids)
+    if (gp[i].nug_type == NUG_PIVOT)
+      throw std::runtime_error("logpost_hessian: not available with nugget=\"pivot\" (a pivoted, possibly rank-deficient factor)");
+  std::vector<std::vector<double>> before(nb);      // theta of the emulators that have to be put back
+  std::vector<int> fine(nb, 0);
+  hessian_move_to(ids, thetas, H, ld, fine, before);
+  std::vector<int> good, gpos;
+  for (int k = 0; k < nb; ++k)
+    if (fine[k]) {
+      good.push_back(ids[k]);
+      gpos.push_back(k);
+    }
+  if (!good.empty()) {
+    ensure_kinv(good, true);
+    const int NPh = hess_np(n), NQ = D + 3, TQ = D + 2, TS = (D + 1) * TQ, TG = hess_trace_groups(n), PGR = hess_pair_groups(n);
+    const size_t gsz = hessian_group_size(ks_budget_bytes(), hessian_scratch_bytes(NPh, D, TG, PGR), good.size());
+    HessianSums h;
+    h.go.resize((size_t)B * NQ);
+    std::vector<double> al(n), tt(n), dpr(NC + 2), Fd((size_t)TQ * TQ);
+    for (size_t g0 = 0; g0 < good.size(); g0 += gsz) {
+      const std::vector<int> grp(good.begin() + g0, good.begin() + std::min(good.size(), g0 + gsz));
+      HessianScratch dev(grp.size(), NPh, D, TG, PGR, stream);      // (lives to the end of the iteration, as the planes always did)
+      hessian_group_sums(grp, dev, h);
+      for (size_t s = 0; s < grp.size(); ++s) {
+        const int i = grp[s], k = gpos[g0 + s];
+        const GPState& g = gp[i];
+        HIPCK(hipMemcpy(al.data(), dAlpha + (size_t)i * RA * LD, n * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCK(hipMemcpy(tt.data(), dT + (size_t)i * n, n * sizeof(double), hipMemcpyDeviceToHost));
+        const int P = n_theta(i);
+        std::vector<double> Hm((size_t)P * P, 0.);
+        g.pri.d2logpdtheta2(g.data, NC, g.nug_type, dpr.data());
+        if (!hessian_assemble(n, D, NC, uniform(), g.nug_type == NUG_FIT, g.nugget_used, h.go.data() + (size_t)i * NQ, h.To.data() + s * TS,
+                              h.Po.data() + s * D * D, h.V.data() + s * D * NPh, h.U.data() + s * D * NPh, NPh, h.Zv.data() + s * NPh, al.data(),
+                              tt.data(), dpr.data(), Fd.data(), Hm.data())) {
+          fine[k] = 0;
+          continue;
+        }
+        for (int r = 0; r < P; ++r)
+          for (int c = r; c < P; ++c) H[((size_t)k * ld + r) * ld + c] = H[((size_t)k * ld + c) * ld + r] = Hm[(size_t)r * P + c];
+      }
+    }
+  }
+  hessian_put_back(ids, before);
+  if (ok)
+    for (int k = 0; k < nb; ++k) ok[k] = fine[k];
+}
+
+// ---------------------------------------------------------------------------------------------
+// Prediction averaged over hyperparameter samples (engine.h has the contract, kernels_mixture.hip the reduction).
+//   1. every (emulator, sample) pair is factored on a replica engine, `slots` pairs per pass: F, ok and the nugget used per pair;
+//   2. the weights, on the host (mixture_weights);
+//   3. per pass and chunk of points the batched mean + variance prediction of the pass's slots, then mixture_accumulate into the
+//      (E, 3, m) sums; with more than one pass the slots were overwritten in step 1, so a pass is factored again first (the same bits);
+//   4. mixture_finalise and ONE download.
+// ---------------------------------------------------------------------------------------------
+
+namespace {
+
+// the refusals of predict_mixture
+void check_mixture_args(const Engine& eng, const std::vector<int>& ids, const double* thetas, int S, int ld, const double* weights, const double* log_q,
+                        const double* Xs, int m, int max_slots, int max_points, const double* mean_out, const double* within_out,
+                        const double* between_out, const double* weights_out, const double* logpost_out, const int* ok_out) {
+  const long E = (long)ids.size();
+  if (S < 1) throw std::runtime_error("predict_mixture: at least one sample per emulator is needed (S = " + std::to_string(S) + ")");
+  if (eng.analytic) throw std::runtime_error("predict_mixture: not available with analytic_mean=True (the mean coefficients are integrated out of theta)");
+  for (int i : ids)
+    if (eng.gp[i].nug_type == NUG_PIVOT)
+      throw std::runtime_error("predict_mixture: not available with nugget=\"pivot\" (a pivoted, possibly rank-deficient factor)");
+  if (!thetas || (m > 0 && !Xs)) throw std::runtime_error("predict_mixture: null input buffer");
+  if ((weights != nullptr) == (log_q != nullptr)) throw std::runtime_error("predict_mixture: exactly one of weights and log_q must be given");
+  if (!mean_out || !within_out || !between_out || !weights_out || !logpost_out || !ok_out) throw std::runtime_error("predict_mixture: null result buffer");
+  if (m < 0 || max_slots < 0 || max_points < 0) throw std::runtime_error("predict_mixture: m, max_slots and max_points must not be negative");
+  if (E * (long)S > (1L << 30)) throw std::runtime_error("predict_mixture: too many (emulator, sample) pairs");
+  for (long e = 0; e < E; ++e) {
+    const int P = eng.n_theta(ids[e]);
+    if (P > ld) throw std::runtime_error("Shape of new GPParams object does not match existing one");
+    for (int s = 0; s < S; ++s) {
+      const double* th = thetas + ((size_t)e * S + s) * ld;
+      for (int k = 0; k < P; ++k)
+        if (!std::isfinite(th[k])) throw std::runtime_error("predict_mixture: the hyperparameter samples must be finite");
+      const double x = weights ? weights[e * S + s] : log_q[e * S + s];
+      if (!std::isfinite(x)) throw std::runtime_error(weights ? "predict_mixture: the weights must be finite" : "predict_mixture: log_q must be finite");
+      if (weights && x < 0.) throw std::runtime_error("predict_mixture: the weights must not be negative");
+    }
+  }
+  for (size_t k = 0; k < (size_t)m * eng.D; ++k)
+    if (!std::isfinite(Xs[k])) throw std::runtime_error("predict_mixture: the query points must be finite");
+}
+
+}  // namespace
+
+void Engine::predict_mixture(const std::vector<int>& ids, const double* thetas, int S, int ld, const double* weights, const double* log_q,
+                             const double* Xs, int m, bool include_nugget, int max_slots, int max_points, double* mean_out,
+                             double* within_out, double* between_out, double* weights_out, double* logpost_out, int* ok_out, int* ok_all) {
+  const long E = (long)ids.size();
+  if (E == 0) return;
+  check_mixture_args(*this, ids, thetas, S, ld, weights, log_q, Xs, m, max_slots, max_points, mean_out, within_out, between_out, weights_out,
+                     logpost_out, ok_out);
+
+  // plan.  slots: what fits beside this engine and what pays (fit_map_from's rule); points: predict()'s chunk rule on the smaller budget
+  const long pairs = E * S;
+  long device_slots = pairs;
+  double cap = ks_budget_bytes(), free_b = 0.;
+  if (free_device_bytes(free_b)) {
+    device_slots = slots_in_half_of(free_b, replica_slot_bytes(MS, LD));
+    cap = std::min(cap, 0.25 * free_b);
+  }
+  device_slots = std::min<long>(device_slots, std::max<long>(E, replica_slot_bound(NP, TILE)));
+  const MixturePlan plan = mixture_plan(E, S, LD, device_slots, m, max_slots, max_points, cap);
+  const long slots = plan.slots, ngroups = (pairs + slots - 1) / slots;
+  const int MC = plan.points;
+  if (slots > 65535) throw std::runtime_error("predict_mixture: more than 65535 slots per pass are not supported");
+
+  // lease
+  std::vector<double> targets((size_t)slots * n);
+  for (long k = 0; k < slots; ++k) {
+    const int i = ids[(size_t)(k / S)];
+    std::copy(hT.begin() + (size_t)i * n, hT.begin() + (size_t)(i + 1) * n, targets.begin() + (size_t)k * n);
+  }
+  ReplicaLease rep(*this, slots, targets, gp[ids[0]].nug_type, gp[ids[0]].nug_size);
+  hipStream_t st = rep->stream;
+
+  // 1. F, ok and the nugget of every pair
+  std::vector<double> F(pairs), nug(pairs, 0.), w(pairs);
+  std::vector<int> okv(pairs, 0), holds(slots, -1);
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  auto factor_group = [&](long g) {
+    const long p0 = g * slots, cnt = std::min(slots, pairs - p0);
+    std::vector<int> sl(cnt);
+    std::vector<const double*> th(cnt);
+    for (long k = 0; k < cnt; ++k) {
+      const int e = (int)((p0 + k) / S);
+      if (holds[k] != e) {
+        rep->retarget((int)k, *this, ids[e]);
+        holds[k] = e;
+      }
+      sl[k] = (int)k;
+      th[k] = thetas + (size_t)(p0 + k) * ld;
+    }
+    rep->eval(sl, th, false, F.data() + p0, nullptr, 0, okv.data() + p0);
+    for (long k = 0; k < cnt; ++k) {
+      nug[p0 + k] = okv[p0 + k] ? rep->nugget_size((int)k) : 0.;
+      if (!okv[p0 + k]) F[p0 + k] = nan;
+    }
+  };
+  for (long g = 0; g < ngroups; ++g) factor_group(g);
+
+  // 2. weights; the pivot of an emulator is its first sample that factorised
+  std::vector<int> alive(E, 0), pivot_pair(E, -1);
+  for (long e = 0; e < E; ++e) {
+    alive[e] = mixture_weights(S, F.data() + e * S, okv.data() + e * S, weights ? weights + e * S : nullptr, log_q ? log_q + e * S : nullptr,
+                               w.data() + e * S) ? 1 : 0;
+    for (int s = 0; s < S && pivot_pair[e] < 0; ++s)
+      if (okv[e * S + s]) pivot_pair[e] = (int)(e * S + s);
+    if (ok_all) ok_all[e] = alive[e];
+  }
+  std::copy(w.begin(), w.end(), weights_out);
+  std::copy(F.begin(), F.end(), logpost_out);
+  std::copy(okv.begin(), okv.end(), ok_out);
+  if (m == 0) return;
+
+  // 3. the passes
+  const size_t mm = (size_t)m;
+  DevBuf<double> dXq(mm * D), dAcc((size_t)E * 3 * mm), dPivot((size_t)E * mm), dMu((size_t)slots * MC), dVa((size_t)slots * MC), dPrm(2 * (size_t)slots);
+  DevBuf<int> dTab(4 * (size_t)slots), dRows((size_t)slots), dAlive((size_t)E);
+  SyncOnUnwind drained{st};
+  HIPCK(hipMemcpyAsync(dXq, Xs, mm * D * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCK(hipMemsetAsync(dAcc, 0, (size_t)E * 3 * mm * sizeof(double), st));
+  HIPCK(hipMemsetAsync(dPivot, 0, (size_t)E * mm * sizeof(double), st));
+  HIPCK(hipMemcpyAsync(dAlive, alive.data(), (size_t)E * sizeof(int), hipMemcpyHostToDevice, st));
+  for (long g = 0; g < ngroups; ++g) {
+    const long p0 = g * slots, cnt = std::min(slots, pairs - p0);
+    const MixturePassTables t = mixture_pass_tables(p0, cnt, S, okv.data(), w.data(), nug.data(), include_nugget, alive.data(), pivot_pair.data());
+    if (t.okslots.empty()) continue;
+    if (ngroups > 1) {
+      // the slots hold the last pass of step 1: factor this pass again.  What step 2 was computed from must be what is predicted from.
+      // (Also where the pass is then skipped for an empty etab: the tables depend on step 1 alone.)
+      const std::vector<double> F1(F.begin() + p0, F.begin() + p0 + cnt);
+      const std::vector<int> ok1(okv.begin() + p0, okv.begin() + p0 + cnt);
+      factor_group(g);
+      for (long k = 0; k < cnt; ++k)
+        if (okv[p0 + k] != ok1[k] || (ok1[k] && F[p0 + k] != F1[k]))
+          throw std::runtime_error("predict_mixture: a sample did not factorise to the same bits twice");
+    }
+    if (t.etab.empty()) continue;
+    HIPCK(hipMemcpyAsync(dTab, t.etab.data(), t.etab.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCK(hipMemcpyAsync(dRows, t.rows.data(), t.rows.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCK(hipMemcpyAsync(dPrm, t.prm.data(), t.prm.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    for (int c0 = 0; c0 < m; c0 += MC) {
+      const int mc = std::min(MC, m - c0);
+      rep->predict(t.okslots, dXq + (size_t)c0 * D, mc, true, dMu, dVa, MC, true, nullptr);
+      launch_mixture_accumulate(dMu, dVa, MC, mc, (int)(t.etab.size() / 4), dTab, dRows, dPrm, dAcc, dPivot, m, c0, st);
+    }
+    HIPCK(hipStreamSynchronize(st));        // the tables are temporaries, and the next pass overwrites the slots
+  }
+  // 4. finalise, one download
+  launch_mixture_finalise((int)E, m, dAlive, dPivot, dAcc, st);
+  std::vector<double> res((size_t)E * 3 * mm);
+  HIPCK(hipMemcpyAsync(res.data(), dAcc, res.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCK(hipStreamSynchronize(st));
+  HIPCK(hipGetLastError());
+  for (long e = 0; e < E; ++e) {
+    const double* r = res.data() + (size_t)e * 3 * mm;
+    std::copy(r, r + mm, mean_out + (size_t)e * mm);
+    std::copy(r + mm, r + 2 * mm, within_out + (size_t)e * mm);
+    std::copy(r + 2 * mm, r + 3 * mm, between_out + (size_t)e * mm);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Cross-validation at the fitted hyperparameters (engine.h has the contract, kernels_cv.hip the formulas and the kernels).
+//   every fold a single point: L^-1 and ONE launch of cv_loo_kernel (cv_leave_one_out);
+//   otherwise K^-1, then the (emulator, fold) pairs in passes of `slots` (cv_plan) through a sub-engine of nsub = the largest fold size
+//   rows, built as gkdr_R builds its own: per pass factor_prebuilt with cv_gather_kernel as the fill, the log-determinant and L^-T y
+//   launchers on the slots that factorised, cv_finish_kernel; ONE download at the end (cv_kfold).
+// The sub-engine and every buffer here are scratch of the call.
+// ---------------------------------------------------------------------------------------------
+
+// what both paths share: the observations and nuggets of the rows of E emulators and the result buffers (n points, k folds)
+struct CvBuffers {
+  std::vector<double> traw, eta;
+  size_t En, Ek;
+  DevBuf<double> dTraw, dEta, dMeanO, dVarO, dMaha, dLs;
+  DevBuf<int> dOk;
+  CvBuffers(size_t E, size_t n, size_t k)
+      : traw(E * n), eta(E), En(E * n), Ek(E * k), dTraw(traw.size()), dEta(eta.size()), dMeanO(En), dVarO(En), dMaha(Ek), dLs(Ek), dOk(Ek) {}
+  // inputs up, results preset to NaN / not ok
+  void stage(hipStream_t st) {
+    HIPCK(hipMemcpyAsync(dTraw, traw.data(), traw.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCK(hipMemcpyAsync(dEta, eta.data(), eta.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCK(hipMemsetAsync(dMeanO, 0xFF, En * sizeof(double), st));
+    HIPCK(hipMemsetAsync(dVarO, 0xFF, En * sizeof(double), st));
+    HIPCK(hipMemsetAsync(dMaha, 0xFF, Ek * sizeof(double), st));
+    HIPCK(hipMemsetAsync(dLs, 0xFF, Ek * sizeof(double), st));
+    HIPCK(hipMemsetAsync(dOk, 0, Ek * sizeof(int), st));
+  }
+  void download(hipStream_t st, double* mean_out, double* var_out, double* maha_out, double* log_score_out, int* ok_out) {
+    HIPCK(hipMemcpyAsync(mean_out, dMeanO, En * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCK(hipMemcpyAsync(var_out, dVarO, En * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCK(hipMemcpyAsync(maha_out, dMaha, Ek * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCK(hipMemcpyAsync(log_score_out, dLs, Ek * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCK(hipMemcpyAsync(ok_out, dOk, Ek * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCK(hipStreamSynchronize(st));
+    HIPCK(hipGetLastError());
+  }
+};
+
+// leave-one-out: L^-1 only
+void Engine::cv_leave_one_out(const std::vector<int>& ids, const int* labels, bool include_nugget, CvBuffers& b, double* mean_out, double* var_out,
+                              double* maha_out, double* log_score_out, int* ok_out) {
+  const size_t nn = (size_t)n;
+  DevBuf<int> dLab(nn);
+  SyncOnUnwind drained{stream};
+  ensure_linv(ids);
+  upload_idx(ids);
+  b.stage(stream);
+  HIPCK(hipMemcpyAsync(dLab, labels, nn * sizeof(int), hipMemcpyHostToDevice, stream));
+  launch_cv_loo(view((int)ids.size()), dLab, b.dTraw, b.dEta, include_nugget, b.dMeanO, b.dVarO, b.dMaha, b.dLs, b.dOk, stream);
+  b.download(stream, mean_out, var_out, maha_out, log_score_out, ok_out);
+}
+
+// k folds: K^-1, then the (emulator, fold) pairs in passes through a sub-engine of the call
+void Engine::cv_kfold(const std::vector<int>& ids, const CvFolds& cf, int k, bool include_nugget, int max_slots, CvBuffers& b, double* mean_out,
+                      double* var_out, double* maha_out, double* log_score_out, int* ok_out) {
+  const long E = (long)ids.size();
+  const int nsub = cf.nsub, NPsub = roundup(nsub + 1, TILE);
+  const long pairs = E * k;
+  long device_slots = pairs;
+  double free_b = 0.;
+  if (free_device_bytes(free_b)) device_slots = slots_in_half_of(free_b, cv_slot_bytes(NPsub));
+  const long slots = cv_plan(E, k, NPsub, device_slots, max_slots);
+
+  ensure_kinv(ids, false);
+  HIPCK(hipStreamSynchronize(stream));        // the sub-engine reads K^-1 and alpha on its own stream
+  const BatchView src = view(0);
+  const std::vector<double> zeros((size_t)slots * nsub, 0.0);
+  Engine sub(zeros.data(), nsub, 1, zeros.data(), (int)slots, 0, MeanFunc(), 0, NUG_FIXED, 0.0);
+  if (sub.NP != NPsub) throw std::runtime_error("cross_validate: unexpected layout of the sub-engine");
+  hipStream_t st = sub.stream;
+  DevBuf<int> dFolds(cf.folds.size()), dTab(4 * (size_t)slots);
+  SyncOnUnwind drained{st};
+  b.stage(st);
+  HIPCK(hipMemcpyAsync(dFolds, cf.folds.data(), cf.folds.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  std::vector<int> tab(4 * (size_t)slots), info, okslots;
+  const std::function<void(const BatchView&)> fill = [&](const BatchView& sv) {
+    if (sv.nb != (int)slots) throw std::runtime_error("cross_validate: the factorisation must cover every slot");
+    launch_cv_gather(src, dFolds, dTab, (int)slots, sv.A, nsub, NPsub, st);
+  };
+  for (long p0 = 0; p0 < pairs; p0 += slots) {
+    const long cnt = std::min(slots, pairs - p0);
+    cv_pass_table(p0, cnt, slots, k, ids.data(), cf.size.data(), tab.data());
+    HIPCK(hipMemcpyAsync(dTab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    sub.factor_prebuilt(fill, info);
+    okslots.clear();
+    for (long s = 0; s < cnt; ++s)
+      if (info[s] == 0) okslots.push_back((int)s);
+    if (!okslots.empty()) {
+      sub.upload_idx(okslots);
+      const BatchView sv = sub.view((int)okslots.size());
+      launch_logdet(sv, sub.dInfo, sub.dRes, st);
+      launch_alpha_from_linv(sv, st);
+    }
+    launch_cv_finish(dFolds, dTab, (int)cnt, sub.dLinv, sub.dAlpha, sub.dRes, sub.dInfo, nsub, NPsub, b.dTraw, b.dEta, include_nugget, n, k,
+                     b.dMeanO, b.dVarO, b.dMaha, b.dLs, b.dOk, st);
+    HIPCK(hipStreamSynchronize(st));          // `tab` is rewritten by the next pass
+  }
+  b.download(st, mean_out, var_out, maha_out, log_score_out, ok_out);
+}
+
+void Engine::cross_validate(const std::vector<int>& ids, const int* labels, int k, bool include_nugget, int max_slots, double* mean_out,
+                            double* var_out, double* maha_out, double* log_score_out, int* ok_out) {
+  const long E = (long)ids.size();
+  if (E == 0) return;
+  require_factored(ids);
+  if (analytic) throw std::runtime_error("cross_validate: not available with analytic_mean=True (a held-out fold changes the mean coefficients)");
+  for (int i : ids)
+    if (gp[i].nug_type == NUG_PIVOT || gp[i].permuted)
+      throw std::runtime_error("cross_validate: not available with nugget=\"pivot\" (a pivoted, possibly rank-deficient factor)");
+  if (!labels || !mean_out || !var_out || !maha_out || !log_score_out || !ok_out) throw std::runtime_error("cross_validate: null buffer");
+  if (k < 2 || k > n) throw std::runtime_error("cross_validate: the number of folds must be between 2 and the number of training points (k = " + std::to_string(k) + ", n = " + std::to_string(n) + ")");
+  if (max_slots < 0) throw std::runtime_error("cross_validate: max_slots must not be negative");
+  if (E * (long)k > (1L << 30)) throw std::runtime_error("cross_validate: too many (emulator, fold) pairs");
+  const CvFolds cf = cv_folds(labels, n, k);
+
+  CvBuffers b((size_t)E, (size_t)n, (size_t)k);
+  for (long e = 0; e < E; ++e) {
+    std::copy(hT.begin() + (size_t)ids[e] * n, hT.begin() + (size_t)(ids[e] + 1) * n, b.traw.begin() + (size_t)e * n);
+    b.eta[e] = gp[ids[e]].nugget_used;
+  }
+  if (cf.nsub == 1) cv_leave_one_out(ids, labels, include_nugget, b, mean_out, var_out, maha_out, log_score_out, ok_out);
+  else cv_kfold(ids, cf, k, include_nugget, max_slots, b, mean_out, var_out, maha_out, log_score_out, ok_out);
+}
+
+}  // namespace mogp

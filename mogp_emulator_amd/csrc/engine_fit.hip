@@ -421,14 +421,11 @@ void Engine::fit_map_from(const std::vector<int>& ids, const Starts& x0) {
   const long total = (long)ne * n_tries;
   long slots_n = ne;
   if (parallel_starts && n_tries > 1) {
-    size_t free_b = 0, total_b = 0;
     long fit = total;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-      const double per_emu = 3.0 * (double)MS * sizeof(double) + 16.0 * LD * sizeof(double);
-      fit = (long)std::max(1.0, std::floor(0.5 * (double)free_b / per_emu));
-    }
+    double free_b = 0.;
+    if (free_device_bytes(free_b)) fit = slots_in_half_of(free_b, replica_slot_bytes(MS, LD));
     static const long replica_cap = [] { const char* e = getenv("MOGP_START_REPLICAS"); return e ? atol(e) : 0L; }();
-    const long cap = replica_cap > 0 ? replica_cap : std::max<long>(ne, 4095 / std::max(1, NP / TILE) + 1);
+    const long cap = replica_cap > 0 ? replica_cap : std::max<long>(ne, replica_slot_bound(NP, TILE));
     slots_n = std::min(total, std::min(fit, cap));
     if (slots_n > 8) slots_n -= slots_n % 8;      // (batches that are multiples of 8 give every XCD whole emulators)
   }

@@ -1,5 +1,8 @@
-// What engine.hip, engine_chol.hip, engine_fit.hip and engine_predict.hip share and nobody else sees: the error-check macro, small helpers and the
-// process-wide diagnostic counters behind prof_counter (engine.hip).
+// What engine.hip, engine_chol.hip, engine_fit.hip, engine_predict.hip and engine_analysis.hip share and nobody else sees: the error-check
+// macro, small helpers and the process-wide diagnostic counters behind prof_counter (engine.hip).  What lives where: engine.hip the
+// construction, the cached state, eval's steps, L^-1 / K^-1 and the gradient; engine_chol.hip the factorisation schedules; engine_fit.hip
+// the optimiser, the slot pool and the replica engines; engine_predict.hip predict, full covariance, implausibility, Sobol and loo_variance;
+// engine_analysis.hip the Hessian, the mixture over hyperparameter samples and cross-validation.
 #pragma once
 #include "engine.h"
 #include "predict_plan.h"
@@ -31,7 +34,7 @@ inline double ks_budget_bytes() {
 // cached one of the device when its shape matches (taken out of the cache, its inputs reset), else a new one -- whatever the cache held
 // is freed first.  When the scope is left normally the engine goes back into the cache (MOGP_REPLICA_CACHE=0: never); an exception
 // destroys it.  `targets` (slots, n), nug_type and nug_size only initialise a NEW engine: every slot is given its emulator by
-// Engine::retarget before it is used.  Shared by fit_map_from and predict_mixture.
+// Engine::retarget before it is used.  Shared by fit_map_from and predict_mixture (engine_analysis.hip).
 class ReplicaLease {
  public:
   ReplicaLease(const Engine& src, long slots, const std::vector<double>& targets, int nug_type, double nug_size);

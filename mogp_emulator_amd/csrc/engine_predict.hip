@@ -1,5 +1,5 @@
-// The prediction family of Engine: predict and what is fused behind it (full covariance, implausibility, Sobol indices, the mixture over
-// hyperparameter samples, cross-validation, leave-one-out variance).  How each cuts its query points to a byte budget is plain arithmetic in predict_plan.h.
+// The prediction family of Engine: predict and what is fused behind it (full covariance, implausibility, Sobol indices, leave-one-out
+// variance).  How each cuts its query points to a byte budget is plain arithmetic in predict_plan.h.
 #include "engine_internal.h"
 
 #include <cmath>
@@ -334,296 +334,6 @@ void Engine::sobol(const std::vector<int>& ids, const double* A, const double* B
       ST[(size_t)k * D + d] = V > 0. ? sums[((size_t)k * D + d) * 2 + 1] / (2. * V) : nan;
     }
   }
-}
-
-// Prediction averaged over hyperparameter samples (engine.h has the contract, kernels_mixture.hip the reduction).
-//   1. every (emulator, sample) pair is factored on a replica engine, `slots` pairs per pass: F, ok and the nugget used per pair;
-//   2. the weights, on the host (mixture_weights);
-//   3. per pass and chunk of points the batched mean + variance prediction of the pass's slots, then mixture_accumulate into the
-//      (E, 3, m) sums; with more than one pass the slots were overwritten in step 1, so a pass is factored again first (the same bits);
-//   4. mixture_finalise and ONE download.
-void Engine::predict_mixture(const std::vector<int>& ids, const double* thetas, int S, int ld, const double* weights, const double* log_q,
-                             const double* Xs, int m, bool include_nugget, int max_slots, int max_points, double* mean_out,
-                             double* within_out, double* between_out, double* weights_out, double* logpost_out, int* ok_out, int* ok_all) {
-  const long E = (long)ids.size();
-  if (E == 0) return;
-  if (S < 1) throw std::runtime_error("predict_mixture: at least one sample per emulator is needed (S = " + std::to_string(S) + ")");
-  if (analytic) throw std::runtime_error("predict_mixture: not available with analytic_mean=True (the mean coefficients are integrated out of theta)");
-  for (int i : ids)
-    if (gp[i].nug_type == NUG_PIVOT)
-      throw std::runtime_error("predict_mixture: not available with nugget=\"pivot\" (a pivoted, possibly rank-deficient factor)");
-  if (!thetas || (m > 0 && !Xs)) throw std::runtime_error("predict_mixture: null input buffer");
-  if ((weights != nullptr) == (log_q != nullptr)) throw std::runtime_error("predict_mixture: exactly one of weights and log_q must be given");
-  if (!mean_out || !within_out || !between_out || !weights_out || !logpost_out || !ok_out) throw std::runtime_error("predict_mixture: null result buffer");
-  if (m < 0 || max_slots < 0 || max_points < 0) throw std::runtime_error("predict_mixture: m, max_slots and max_points must not be negative");
-  if (E * (long)S > (1L << 30)) throw std::runtime_error("predict_mixture: too many (emulator, sample) pairs");
-  for (long e = 0; e < E; ++e) {
-    const int P = n_theta(ids[e]);
-    if (P > ld) throw std::runtime_error("Shape of new GPParams object does not match existing one");
-    for (int s = 0; s < S; ++s) {
-      const double* th = thetas + ((size_t)e * S + s) * ld;
-      for (int k = 0; k < P; ++k)
-        if (!std::isfinite(th[k])) throw std::runtime_error("predict_mixture: the hyperparameter samples must be finite");
-      const double x = weights ? weights[e * S + s] : log_q[e * S + s];
-      if (!std::isfinite(x)) throw std::runtime_error(weights ? "predict_mixture: the weights must be finite" : "predict_mixture: log_q must be finite");
-      if (weights && x < 0.) throw std::runtime_error("predict_mixture: the weights must not be negative");
-    }
-  }
-  for (size_t k = 0; k < (size_t)m * D; ++k)
-    if (!std::isfinite(Xs[k])) throw std::runtime_error("predict_mixture: the query points must be finite");
-
-  // slots: what fits beside this engine (fit_map_from's estimate: A, L^-1, K^-1 per slot plus the small per-emulator buffers) and what pays
-  const long pairs = E * S;
-  long device_slots = pairs;
-  double cap = ks_budget_bytes();
-  {
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-      const double per_emu = 3.0 * (double)MS * sizeof(double) + 16.0 * LD * sizeof(double);
-      device_slots = (long)std::max(1.0, std::floor(0.5 * (double)free_b / per_emu));
-      cap = std::min(cap, 0.25 * (double)free_b);
-    }
-    device_slots = std::min<long>(device_slots, std::max<long>(E, 4095 / std::max(1, NP / TILE) + 1));
-  }
-  const MixturePlan plan = mixture_plan(E, S, LD, device_slots, m, max_slots, max_points, cap);
-  const long slots = plan.slots, ngroups = (pairs + slots - 1) / slots;
-  const int MC = plan.points;
-  if (slots > 65535) throw std::runtime_error("predict_mixture: more than 65535 slots per pass are not supported");
-
-  std::vector<double> targets((size_t)slots * n);
-  for (long k = 0; k < slots; ++k) {
-    const int i = ids[(size_t)(k / S)];
-    std::copy(hT.begin() + (size_t)i * n, hT.begin() + (size_t)(i + 1) * n, targets.begin() + (size_t)k * n);
-  }
-  ReplicaLease rep(*this, slots, targets, gp[ids[0]].nug_type, gp[ids[0]].nug_size);
-  hipStream_t st = rep->stream;
-
-  // 1. F, ok and the nugget of every pair
-  std::vector<double> F(pairs), nug(pairs, 0.), w(pairs);
-  std::vector<int> okv(pairs, 0), holds(slots, -1);
-  const double nan = std::numeric_limits<double>::quiet_NaN();
-  auto factor_group = [&](long g) {
-    const long p0 = g * slots, cnt = std::min(slots, pairs - p0);
-    std::vector<int> sl(cnt);
-    std::vector<const double*> th(cnt);
-    for (long k = 0; k < cnt; ++k) {
-      const int e = (int)((p0 + k) / S);
-      if (holds[k] != e) {
-        rep->retarget((int)k, *this, ids[e]);
-        holds[k] = e;
-      }
-      sl[k] = (int)k;
-      th[k] = thetas + (size_t)(p0 + k) * ld;
-    }
-    rep->eval(sl, th, false, F.data() + p0, nullptr, 0, okv.data() + p0);
-    for (long k = 0; k < cnt; ++k) {
-      nug[p0 + k] = okv[p0 + k] ? rep->nugget_size((int)k) : 0.;
-      if (!okv[p0 + k]) F[p0 + k] = nan;
-    }
-  };
-  for (long g = 0; g < ngroups; ++g) factor_group(g);
-
-  // 2. weights; the pivot of an emulator is its first sample that factorised
-  std::vector<int> alive(E, 0), pivot_pair(E, -1);
-  for (long e = 0; e < E; ++e) {
-    alive[e] = mixture_weights(S, F.data() + e * S, okv.data() + e * S, weights ? weights + e * S : nullptr, log_q ? log_q + e * S : nullptr,
-                               w.data() + e * S) ? 1 : 0;
-    for (int s = 0; s < S && pivot_pair[e] < 0; ++s)
-      if (okv[e * S + s]) pivot_pair[e] = (int)(e * S + s);
-    if (ok_all) ok_all[e] = alive[e];
-  }
-  std::copy(w.begin(), w.end(), weights_out);
-  std::copy(F.begin(), F.end(), logpost_out);
-  std::copy(okv.begin(), okv.end(), ok_out);
-  if (m == 0) return;
-
-  // 3. the passes
-  const size_t mm = (size_t)m;
-  DevBuf<double> dXq(mm * D), dAcc((size_t)E * 3 * mm), dPivot((size_t)E * mm), dMu((size_t)slots * MC), dVa((size_t)slots * MC), dPrm(2 * (size_t)slots);
-  DevBuf<int> dTab(4 * (size_t)slots), dRows((size_t)slots), dAlive((size_t)E);
-  SyncOnUnwind drained{st};
-  HIPCK(hipMemcpyAsync(dXq, Xs, mm * D * sizeof(double), hipMemcpyHostToDevice, st));
-  HIPCK(hipMemsetAsync(dAcc, 0, (size_t)E * 3 * mm * sizeof(double), st));
-  HIPCK(hipMemsetAsync(dPivot, 0, (size_t)E * mm * sizeof(double), st));
-  HIPCK(hipMemcpyAsync(dAlive, alive.data(), (size_t)E * sizeof(int), hipMemcpyHostToDevice, st));
-  for (long g = 0; g < ngroups; ++g) {
-    const long p0 = g * slots, cnt = std::min(slots, pairs - p0);
-    std::vector<int> okslots, rows(cnt, -1), etab;
-    std::vector<double> prm(2 * (size_t)cnt, 0.);
-    for (long k = 0; k < cnt; ++k) {
-      if (!okv[p0 + k]) continue;
-      rows[k] = (int)okslots.size();
-      okslots.push_back((int)k);
-      prm[2 * k] = w[p0 + k];
-      prm[2 * k + 1] = include_nugget ? nug[p0 + k] : 0.;
-    }
-    if (okslots.empty()) continue;
-    if (ngroups > 1) {
-      // the slots hold the last pass of step 1: factor this pass again.  What step 2 was computed from must be what is predicted from.
-      const std::vector<double> F1(F.begin() + p0, F.begin() + p0 + cnt);
-      const std::vector<int> ok1(okv.begin() + p0, okv.begin() + p0 + cnt);
-      factor_group(g);
-      for (long k = 0; k < cnt; ++k)
-        if (okv[p0 + k] != ok1[k] || (ok1[k] && F[p0 + k] != F1[k]))
-          throw std::runtime_error("predict_mixture: a sample did not factorise to the same bits twice");
-    }
-    for (long e = p0 / S; e <= (p0 + cnt - 1) / S; ++e) {
-      const long first = std::max(e * S, p0) - p0, last = std::min((e + 1) * S, p0 + cnt) - p0;
-      bool any = false;
-      for (long k = first; k < last; ++k) any = any || rows[k] >= 0;
-      if (!any || !alive[e]) continue;
-      const long pp = pivot_pair[e] - p0;
-      etab.insert(etab.end(), {(int)e, (int)first, (int)(last - first), (pp >= 0 && pp < cnt) ? rows[pp] : -1});
-    }
-    if (etab.empty()) continue;
-    HIPCK(hipMemcpyAsync(dTab, etab.data(), etab.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    HIPCK(hipMemcpyAsync(dRows, rows.data(), rows.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    HIPCK(hipMemcpyAsync(dPrm, prm.data(), prm.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    for (int c0 = 0; c0 < m; c0 += MC) {
-      const int mc = std::min(MC, m - c0);
-      rep->predict(okslots, dXq + (size_t)c0 * D, mc, true, dMu, dVa, MC, true, nullptr);
-      launch_mixture_accumulate(dMu, dVa, MC, mc, (int)(etab.size() / 4), dTab, dRows, dPrm, dAcc, dPivot, m, c0, st);
-    }
-    HIPCK(hipStreamSynchronize(st));        // the tables are temporaries, and the next pass overwrites the slots
-  }
-  // 4. finalise, one download
-  launch_mixture_finalise((int)E, m, dAlive, dPivot, dAcc, st);
-  std::vector<double> res((size_t)E * 3 * mm);
-  HIPCK(hipMemcpyAsync(res.data(), dAcc, res.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPCK(hipStreamSynchronize(st));
-  HIPCK(hipGetLastError());
-  for (long e = 0; e < E; ++e) {
-    const double* r = res.data() + (size_t)e * 3 * mm;
-    std::copy(r, r + mm, mean_out + (size_t)e * mm);
-    std::copy(r + mm, r + 2 * mm, within_out + (size_t)e * mm);
-    std::copy(r + 2 * mm, r + 3 * mm, between_out + (size_t)e * mm);
-  }
-}
-
-// Cross-validation at the fitted hyperparameters (engine.h has the contract, kernels_cv.hip the formulas and the kernels).
-//   every fold a single point: L^-1 and ONE launch of cv_loo_kernel;
-//   otherwise K^-1, then the (emulator, fold) pairs in passes of `slots` (cv_plan) through a sub-engine of nsub = the largest fold size
-//   rows, built as gkdr_R builds its own: per pass factor_prebuilt with cv_gather_kernel as the fill, the log-determinant and L^-T y
-//   launchers on the slots that factorised, cv_finish_kernel; ONE download at the end.
-// The sub-engine and every buffer here are scratch of the call.
-void Engine::cross_validate(const std::vector<int>& ids, const int* labels, int k, bool include_nugget, int max_slots, double* mean_out,
-                            double* var_out, double* maha_out, double* log_score_out, int* ok_out) {
-  const long E = (long)ids.size();
-  if (E == 0) return;
-  require_factored(ids);
-  if (analytic) throw std::runtime_error("cross_validate: not available with analytic_mean=True (a held-out fold changes the mean coefficients)");
-  for (int i : ids)
-    if (gp[i].nug_type == NUG_PIVOT || gp[i].permuted)
-      throw std::runtime_error("cross_validate: not available with nugget=\"pivot\" (a pivoted, possibly rank-deficient factor)");
-  if (!labels || !mean_out || !var_out || !maha_out || !log_score_out || !ok_out) throw std::runtime_error("cross_validate: null buffer");
-  if (k < 2 || k > n) throw std::runtime_error("cross_validate: the number of folds must be between 2 and the number of training points (k = " + std::to_string(k) + ", n = " + std::to_string(n) + ")");
-  if (max_slots < 0) throw std::runtime_error("cross_validate: max_slots must not be negative");
-  if (E * (long)k > (1L << 30)) throw std::runtime_error("cross_validate: too many (emulator, fold) pairs");
-  std::vector<int> size(k, 0);
-  for (int i = 0; i < n; ++i) {
-    if (labels[i] < 0 || labels[i] >= k) throw std::runtime_error("cross_validate: fold label " + std::to_string(labels[i]) + " of point " + std::to_string(i) + " is outside [0, " + std::to_string(k) + ")");
-    size[labels[i]] += 1;
-  }
-  int nsub = 0;
-  for (int f = 0; f < k; ++f) {
-    if (size[f] == 0) throw std::runtime_error("cross_validate: fold " + std::to_string(f) + " is empty");
-    nsub = std::max(nsub, size[f]);
-  }
-
-  // what both paths share: the observations and nuggets of the rows, the result buffers
-  const size_t nn = (size_t)n, kk = (size_t)k;
-  std::vector<double> traw((size_t)E * nn), eta(E);
-  for (long e = 0; e < E; ++e) {
-    std::copy(hT.begin() + (size_t)ids[e] * nn, hT.begin() + (size_t)(ids[e] + 1) * nn, traw.begin() + (size_t)e * nn);
-    eta[e] = gp[ids[e]].nugget_used;
-  }
-  DevBuf<double> dTraw(traw.size()), dEta(eta.size()), dMeanO((size_t)E * nn), dVarO((size_t)E * nn), dMaha((size_t)E * kk), dLs((size_t)E * kk);
-  DevBuf<int> dOk((size_t)E * kk);
-  auto stage = [&](hipStream_t st) {
-    HIPCK(hipMemcpyAsync(dTraw, traw.data(), traw.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCK(hipMemcpyAsync(dEta, eta.data(), eta.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCK(hipMemsetAsync(dMeanO, 0xFF, (size_t)E * nn * sizeof(double), st));
-    HIPCK(hipMemsetAsync(dVarO, 0xFF, (size_t)E * nn * sizeof(double), st));
-    HIPCK(hipMemsetAsync(dMaha, 0xFF, (size_t)E * kk * sizeof(double), st));
-    HIPCK(hipMemsetAsync(dLs, 0xFF, (size_t)E * kk * sizeof(double), st));
-    HIPCK(hipMemsetAsync(dOk, 0, (size_t)E * kk * sizeof(int), st));
-  };
-  auto download = [&](hipStream_t st) {
-    HIPCK(hipMemcpyAsync(mean_out, dMeanO, (size_t)E * nn * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCK(hipMemcpyAsync(var_out, dVarO, (size_t)E * nn * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCK(hipMemcpyAsync(maha_out, dMaha, (size_t)E * kk * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCK(hipMemcpyAsync(log_score_out, dLs, (size_t)E * kk * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCK(hipMemcpyAsync(ok_out, dOk, (size_t)E * kk * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCK(hipStreamSynchronize(st));
-    HIPCK(hipGetLastError());
-  };
-
-  if (nsub == 1) {
-    // leave-one-out: L^-1 only
-    DevBuf<int> dLab(nn);
-    SyncOnUnwind drained{stream};
-    ensure_linv(ids);
-    upload_idx(ids);
-    stage(stream);
-    HIPCK(hipMemcpyAsync(dLab, labels, nn * sizeof(int), hipMemcpyHostToDevice, stream));
-    launch_cv_loo(view((int)E), dLab, dTraw, dEta, include_nugget, dMeanO, dVarO, dMaha, dLs, dOk, stream);
-    download(stream);
-    return;
-  }
-
-  // fold index lists (k, nsub), -1 behind the end of a short fold; the points of a fold in ascending order
-  std::vector<int> folds((size_t)k * nsub, -1), fillp(k, 0);
-  for (int i = 0; i < n; ++i) folds[(size_t)labels[i] * nsub + fillp[labels[i]]++] = i;
-  const int NPsub = roundup(nsub + 1, TILE);
-  const long pairs = E * k;
-  long device_slots = pairs;
-  {
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
-      device_slots = (long)std::max(1.0, std::floor(0.5 * (double)free_b / cv_slot_bytes(NPsub)));
-  }
-  const long slots = cv_plan(E, k, NPsub, device_slots, max_slots);
-
-  ensure_kinv(ids, false);
-  HIPCK(hipStreamSynchronize(stream));        // the sub-engine reads K^-1 and alpha on its own stream
-  const BatchView src = view(0);
-  const std::vector<double> zeros((size_t)slots * nsub, 0.0);
-  Engine sub(zeros.data(), nsub, 1, zeros.data(), (int)slots, 0, MeanFunc(), 0, NUG_FIXED, 0.0);
-  if (sub.NP != NPsub) throw std::runtime_error("cross_validate: unexpected layout of the sub-engine");
-  hipStream_t st = sub.stream;
-  DevBuf<int> dFolds(folds.size()), dTab(4 * (size_t)slots);
-  SyncOnUnwind drained{st};
-  stage(st);
-  HIPCK(hipMemcpyAsync(dFolds, folds.data(), folds.size() * sizeof(int), hipMemcpyHostToDevice, st));
-  std::vector<int> tab(4 * (size_t)slots), info, okslots;
-  const std::function<void(const BatchView&)> fill = [&](const BatchView& sv) {
-    if (sv.nb != (int)slots) throw std::runtime_error("cross_validate: the factorisation must cover every slot");
-    launch_cv_gather(src, dFolds, dTab, (int)slots, sv.A, nsub, NPsub, st);
-  };
-  for (long p0 = 0; p0 < pairs; p0 += slots) {
-    const long cnt = std::min(slots, pairs - p0);
-    for (long s = 0; s < slots; ++s) {
-      const long e = (p0 + s) / k, f = (p0 + s) % k;
-      int* t = tab.data() + 4 * s;
-      if (s < cnt) { t[0] = ids[(size_t)e]; t[1] = (int)e; t[2] = (int)f; t[3] = size[f]; }
-      else { t[0] = -1; t[1] = t[2] = t[3] = 0; }     // not used: an identity, so that the batch factorises
-    }
-    HIPCK(hipMemcpyAsync(dTab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    sub.factor_prebuilt(fill, info);
-    okslots.clear();
-    for (long s = 0; s < cnt; ++s)
-      if (info[s] == 0) okslots.push_back((int)s);
-    if (!okslots.empty()) {
-      sub.upload_idx(okslots);
-      const BatchView sv = sub.view((int)okslots.size());
-      launch_logdet(sv, sub.dInfo, sub.dRes, st);
-      launch_alpha_from_linv(sv, st);
-    }
-    launch_cv_finish(dFolds, dTab, (int)cnt, sub.dLinv, sub.dAlpha, sub.dRes, sub.dInfo, nsub, NPsub, dTraw, dEta, include_nugget, n, k, dMeanO,
-                     dVarO, dMaha, dLs, dOk, st);
-    HIPCK(hipStreamSynchronize(st));          // `tab` is rewritten by the next pass
-  }
-  download(st);
 }
 
 void Engine::loo_variance(int i, double* out) {

@@ -2,6 +2,7 @@
 // Counterparts of mogp_gpu/src/gppriors.hpp, meanfunc.hpp, gpparams.hpp (arithmetic follows the
 // CPU oracle: Priors.py:291-354, 842-1128; GPParams.py:35-147).
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <random>
 #include <stdexcept>
@@ -284,6 +285,68 @@ inline void fullcov_mean_terms(int q, int m, const double* beta, const double* L
       double* row = C + (size_t)i * m;
       for (int j = 0; j < m; ++j) row[j] += ri * rc[j];
     }
+}
+
+// The host algebra of Engine::hessian (engine_analysis.hip) for one emulator: the P x P block of the Hessian of the negative log-posterior,
+// P = NC + 1 (+ 1 with a fitted nugget), theta order [corr (NC) | cov | nugget], from the device sums of kernels_hess.hip:
+//   o (D + 3)              the gradient's sums as launch_grad leaves them: 0.5 sum W o Q_p (p < D), 0.5 sum W o sigma^2 C, tr Q^-1, ., alpha^T alpha
+//   T ((D + 1) x (D + 2))  T[p][q] = sum_ab P_p[a,b] P_q[b,a] over the planes M_0 .. M_{D-1}, Q^-1, I (upper entries; T[D][D] = tr Q^-2)
+//   A (D x D)              sum W o sigma^2 k'' s_p s_q (upper entries)
+//   V, U (D rows of stride NPh)   v_p = M_p^T t = Q_p alpha,  u_p = M_p alpha;     z = Q^-1 alpha,  alpha = Q^-1 t,  t the residual targets (n each)
+//   dpr (P)                the prior's second derivatives (Priors::d2logpdtheta2)
+// First the matrix Fd over the per-dimension parameters [corr_0 .. corr_{D-1} | cov | nugget] (scratch of (D + 2)^2 doubles), then -- one
+// shared length scale (uniform) -- theta_0 moves every length at once: its row is the sum of the D correlation rows, its diagonal entry the
+// sum of the D x D block.  Hm (P x P, row-major) receives the UPPER triangle, the rest of it zeros.  Returns false when an entry is not
+// finite.  Every dot product runs in ascending index with one accumulator: the same inputs give the same bits.
+inline bool hessian_assemble(int n, int D, int NC, bool uniform, bool nug_fit, double eta, const double* o, const double* T, const double* A,
+                             const double* V, const double* U, int NPh, const double* z, const double* alpha, const double* t, const double* dpr,
+                             double* Fd, double* Hm) {
+  const int TQ = D + 2, P = NC + 1 + (nug_fit ? 1 : 0);
+  const double eta2 = eta * eta;
+  auto dot = [&](const double* a, const double* b) {
+    double acc = 0.;
+    for (int e = 0; e < n; ++e) acc += a[e] * b[e];
+    return acc;
+  };
+  const double ta = dot(t, alpha), aa = dot(alpha, alpha), az = dot(alpha, z);
+  const double trK = o[D + 1], trK2 = T[D * TQ + D];
+  // per-dimension matrix over [corr_0 .. corr_{D-1} | cov | nugget], upper triangle
+  std::fill(Fd, Fd + (size_t)TQ * TQ, 0.);
+  for (int p = 0; p < D; ++p) {
+    const double* vp = V + (size_t)p * NPh;
+    for (int q = p; q < D; ++q)
+      Fd[p * TQ + q] = dot(vp, U + (size_t)q * NPh) - 0.5 * T[p * TQ + q] + 0.5 * A[p * D + q] + (p == q ? o[p] : 0.);
+    const double va = dot(vp, alpha), vz = dot(vp, z);
+    Fd[p * TQ + D] = (va - eta * vz) - 0.5 * (T[p * TQ + D + 1] - eta * T[p * TQ + D]) + o[p];
+    Fd[p * TQ + D + 1] = eta * vz - 0.5 * eta * T[p * TQ + D];
+  }
+  Fd[D * TQ + D] = (ta - 2. * eta * aa + eta2 * az) - 0.5 * ((double)n - 2. * eta * trK + eta2 * trK2) + o[D];
+  Fd[D * TQ + D + 1] = (eta * aa - eta2 * az) - 0.5 * (eta * trK - eta2 * trK2);
+  Fd[(D + 1) * TQ + D + 1] = eta2 * az - 0.5 * eta2 * trK2 + 0.5 * eta * (trK - o[D + 2]);
+  // theta order [corr (NC) | cov | nugget (fit only)]; one shared length scale: the sums of the per-dimension block and rows
+  std::fill(Hm, Hm + (size_t)P * P, 0.);
+  auto fd = [&](int p, int q) { return p <= q ? Fd[p * TQ + q] : Fd[q * TQ + p]; };
+  auto src = [&](int r) { return r < NC ? r : D + (r - NC); };      // per-dimension index of a non-correlation parameter
+  for (int r = 0; r < P; ++r)
+    for (int c = r; c < P; ++c) {
+      double val;
+      if (!uniform || r >= NC) val = fd(src(r), src(c));
+      else if (c >= NC) {
+        val = 0.;
+        for (int p = 0; p < D; ++p) val += fd(p, src(c));
+      } else {
+        val = 0.;
+        for (int p = 0; p < D; ++p)
+          for (int q = 0; q < D; ++q) val += fd(p, q);
+      }
+      Hm[(size_t)r * P + c] = val;
+    }
+  bool finite = true;
+  for (int r = 0; r < P; ++r) {
+    Hm[(size_t)r * P + r] -= dpr[r];
+    for (int c = r; c < P; ++c) finite = finite && std::isfinite(Hm[(size_t)r * P + c]);
+  }
+  return finite;
 }
 
 }  // namespace mogp

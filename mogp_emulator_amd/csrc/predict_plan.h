@@ -1,10 +1,14 @@
-// How the prediction family of Engine (engine_predict.hip) and Engine::hessian cut their work to a byte budget, and where the mean-function
-// terms of a prediction are staged.  Plain host arithmetic with no HIP in it, so that a host compiler takes it and
-// tests/c/predict_plan_check.cpp can check it without a device.  The caps that need the device (MOGP_KS_BUDGET_GB, free memory) are passed in.
+// How the prediction family of Engine (engine_predict.hip) and the analysis family (engine_analysis.hip: hessian, predict_mixture,
+// cross_validate) cut their work to a byte budget, the index tables of their passes, and where the mean-function terms of a prediction are
+// staged.  Plain host arithmetic with no HIP in it, so that a host compiler takes it and tests/c/predict_plan_check.cpp, mixture_plan_check.cpp
+// and cv_plan_check.cpp can check it without a device.  The caps that need the device (MOGP_KS_BUDGET_GB, free memory) are passed in.
 #pragma once
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
+#include <stdexcept>
+#include <string>
+#include <vector>
 
 namespace mogp {
 
@@ -31,6 +35,22 @@ inline long sobol_chunk_rows(double cap_bytes, int D, int nb, int R, int mean_ki
 inline std::size_t hessian_group_size(double budget, double per_bytes, std::size_t n_good) {
   return (std::size_t)std::max(1.0, std::min((double)n_good, std::floor(budget / per_bytes)));
 }
+
+// bytes of scratch one emulator of a group of Engine::hessian takes: the D planes M_p (NPh x NPh, NPh = hess_np(n)), Xs, V, U and z, the
+// trace table ((D + 1) x (D + 2)) in TG partial slots and its sum, the pair table (D x D) in PGR slots and its sum (launch.h has TG / PGR)
+inline double hessian_scratch_bytes(int NPh, int D, int TG, int PGR) {
+  const std::size_t plane = (std::size_t)NPh * NPh;
+  const int TS = (D + 1) * (D + 2);
+  return 8.0 * ((double)D * plane + (double)NPh * (3.0 * D + 1.0) + (double)TS * (TG + 1.0) + (double)D * D * (PGR + 1.0));
+}
+
+// The one rule for "slots that fit beside this engine" (fit_map_from, predict_mixture, cross_validate): half of the free device memory
+// at bytes_per_slot each, at least one.
+inline long slots_in_half_of(double free_bytes, double bytes_per_slot) { return (long)std::max(1.0, std::floor(0.5 * free_bytes / bytes_per_slot)); }
+// a slot of a replica engine: A, L^-1 and K^-1 (MS doubles each) plus the small per-emulator buffers
+inline double replica_slot_bytes(std::size_t MS, int LD) { return 3.0 * (double)MS * 8.0 + 16.0 * LD * 8.0; }
+// replicas beyond what fills the device buy nothing: the batched kernels of a factorisation stay below 4096 tile rows per launch
+inline long replica_slot_bound(int NP, int TILE) { return 4095 / std::max(1, NP / TILE) + 1; }
 
 // Engine::predict_mixture: how many replica slots one pass takes and how many query points one chunk.  The E * S (emulator, sample) pairs
 // are laid out emulator-major, sample-ascending, and pass g takes the pairs [g * slots, (g + 1) * slots): a slot always holds one whole
@@ -69,6 +89,42 @@ inline long cv_plan(long E, long k, int NPsub, long device_slots, int max_slots)
   return std::max<long>(1, slots);
 }
 
+// The folds of Engine::cross_validate from the labels (n) of the training points: size (k) = points per fold, nsub = the largest fold,
+// folds (k, nsub) = the points of every fold in ascending order, -1 behind the end of a short one.  Throws for a label outside [0, k)
+// and for an empty fold.
+struct CvFolds {
+  std::vector<int> size;
+  int nsub;
+  std::vector<int> folds;
+};
+inline CvFolds cv_folds(const int* labels, int n, int k) {
+  CvFolds c{std::vector<int>(k, 0), 0, {}};
+  for (int i = 0; i < n; ++i) {
+    if (labels[i] < 0 || labels[i] >= k) throw std::runtime_error("cross_validate: fold label " + std::to_string(labels[i]) + " of point " + std::to_string(i) + " is outside [0, " + std::to_string(k) + ")");
+    c.size[labels[i]] += 1;
+  }
+  for (int f = 0; f < k; ++f) {
+    if (c.size[f] == 0) throw std::runtime_error("cross_validate: fold " + std::to_string(f) + " is empty");
+    c.nsub = std::max(c.nsub, c.size[f]);
+  }
+  c.folds.assign((std::size_t)k * c.nsub, -1);
+  std::vector<int> fillp(k, 0);
+  for (int i = 0; i < n; ++i) c.folds[(std::size_t)labels[i] * c.nsub + fillp[labels[i]]++] = i;
+  return c;
+}
+
+// The slot table (slots, 4) of the pass of Engine::cross_validate that starts at pair p0 and holds cnt pairs: per slot
+// [emulator of the engine, its position in ids, fold, size of the fold]; the slots behind cnt are [-1, 0, 0, 0] -- not used: an identity,
+// so that the batch factorises.
+inline void cv_pass_table(long p0, long cnt, long slots, long k, const int* ids, const int* size, int* tab) {
+  for (long s = 0; s < slots; ++s) {
+    const long e = (p0 + s) / k, f = (p0 + s) % k;
+    int* t = tab + 4 * s;
+    if (s < cnt) { t[0] = ids[e]; t[1] = (int)e; t[2] = (int)f; t[3] = size[f]; }
+    else { t[0] = -1; t[1] = t[2] = t[3] = 0; }
+  }
+}
+
 // Stage 2 of Engine::predict_mixture: the normalised weights of the S samples of one emulator, from their negative log-posteriors F and
 // ok flags and EITHER explicit weights w_in OR the log proposal density log_q (up to a constant).  With log_q:
 //   l_s = -(F_s - F_min) - (log_q_s - log_q_a),  a = the first ok sample with F_a = F_min over the ok samples,  w_s = exp(l_s - max l)
@@ -99,6 +155,42 @@ inline bool mixture_weights(int S, const double* F, const int* ok, const double*
   }
   for (int s = 0; s < S; ++s) w_out[s] /= sum;
   return true;
+}
+
+// The tables of the pass of Engine::predict_mixture that holds the pairs [p0, p0 + cnt) (ok, w, nug: per pair; alive, pivot_pair: per
+// emulator, pivot_pair = the first pair of the emulator that factorised or -1):
+//   okslots  the slots whose sample factorised, ascending -- what is predicted, row r of the prediction = slot okslots[r];
+//   rows     (cnt) the prediction row of a slot, -1 where its sample failed;
+//   prm      (cnt, 2) weight and -- with include_nugget -- nugget of the slot's sample (0, 0 where it failed);
+//   etab     (., 4) per alive emulator with a row in the pass [emulator, first slot, slots, row of its pivot or -1 where the pivot pair lies
+//            in another pass].
+// An empty okslots or etab: nothing to accumulate, the pass is skipped.
+struct MixturePassTables {
+  std::vector<int> okslots, rows, etab;
+  std::vector<double> prm;
+};
+inline MixturePassTables mixture_pass_tables(long p0, long cnt, long S, const int* ok, const double* w, const double* nug, bool include_nugget,
+                                             const int* alive, const int* pivot_pair) {
+  MixturePassTables t;
+  t.rows.assign(cnt, -1);
+  t.prm.assign(2 * (std::size_t)cnt, 0.);
+  for (long k = 0; k < cnt; ++k) {
+    if (!ok[p0 + k]) continue;
+    t.rows[k] = (int)t.okslots.size();
+    t.okslots.push_back((int)k);
+    t.prm[2 * k] = w[p0 + k];
+    t.prm[2 * k + 1] = include_nugget ? nug[p0 + k] : 0.;
+  }
+  if (t.okslots.empty()) return t;
+  for (long e = p0 / S; e <= (p0 + cnt - 1) / S; ++e) {
+    const long first = std::max(e * S, p0) - p0, last = std::min((e + 1) * S, p0 + cnt) - p0;
+    bool any = false;
+    for (long k = first; k < last; ++k) any = any || t.rows[k] >= 0;
+    if (!any || !alive[e]) continue;
+    const long pp = pivot_pair[e] - p0;
+    t.etab.insert(t.etab.end(), {(int)e, (int)first, (int)(last - first), (pp >= 0 && pp < cnt) ? t.rows[pp] : -1});
+  }
+  return t;
 }
 
 // Offsets (in doubles) into the staging block of the mean-function terms of a prediction of nb emulators at m points:

@@ -4,8 +4,11 @@
 //   * with no cap in the way everything goes in one pass;
 //   * walking the passes [g * slots, (g + 1) * slots) over the emulator-major, fold-ascending pairs visits every (emulator, fold) exactly
 //     once, in order.
+// Then cv_folds (n = 7, k = 3, unequal folds, and its three refusals) and cv_pass_table (a padded last pass) on tables worked out by hand.
 // tests/test_cv_host.py builds it with -fsanitize=address,undefined.
 #include <cstdio>
+#include <stdexcept>
+#include <string>
 #include <vector>
 
 #include "predict_plan.h"
@@ -13,6 +16,16 @@
 static int fail(const char* what, long E, long k, int NP, long dev, int ms) {
   std::printf("FAILED %s: E=%ld k=%ld NPsub=%d device_slots=%ld max_slots=%d\n", what, E, k, NP, dev, ms);
   return 1;
+}
+
+// the message cv_folds refuses the labels with ("" when it does not)
+static std::string refusal(const std::vector<int>& labels, int k) {
+  try {
+    mogp::cv_folds(labels.data(), (int)labels.size(), k);
+  } catch (const std::runtime_error& e) {
+    return e.what();
+  }
+  return "";
 }
 
 int main() {
@@ -49,6 +62,25 @@ int main() {
             ++cases;
           }
   if (mogp::cv_slot_bytes(256) != 3.0 * 256 * 256 * 8) return fail("bytes per slot", 0, 0, 256, 0, 0);
+  {
+    const std::vector<int> labels = {2, 0, 2, 1, 2, 0, 2};
+    const mogp::CvFolds c = mogp::cv_folds(labels.data(), 7, 3);
+    if (c.size != std::vector<int>{2, 1, 4} || c.nsub != 4 || c.folds != std::vector<int>{1, 5, -1, -1, 3, -1, -1, -1, 0, 2, 4, 6})
+      return fail("cv_folds: n = 7, k = 3", 1, 3, 0, 0, 0);
+    const mogp::CvFolds one = mogp::cv_folds(std::vector<int>{1, 0, 2}.data(), 3, 3);      // every fold a single point
+    if (one.nsub != 1 || one.folds != std::vector<int>{1, 0, 2}) return fail("cv_folds: leave-one-out", 1, 3, 0, 0, 0);
+    if (refusal({2, 0, -1, 1}, 3) != "cross_validate: fold label -1 of point 2 is outside [0, 3)") return fail("cv_folds: negative label", 1, 3, 0, 0, 0);
+    if (refusal({2, 0, 1, 3}, 3) != "cross_validate: fold label 3 of point 3 is outside [0, 3)") return fail("cv_folds: label = k", 1, 3, 0, 0, 0);
+    if (refusal({2, 0, 2, 0}, 3) != "cross_validate: fold 1 is empty") return fail("cv_folds: empty fold", 1, 3, 0, 0, 0);
+    if (refusal({3, 0, 2, 0}, 3) != "cross_validate: fold label 3 of point 0 is outside [0, 3)") return fail("cv_folds: the label comes first", 1, 3, 0, 0, 0);
+    // two emulators (5 and 9 of the engine), these folds, four slots: six pairs, the second pass padded with identities
+    const int ids[2] = {5, 9};
+    std::vector<int> tab(16, 77);
+    mogp::cv_pass_table(0, 4, 4, 3, ids, c.size.data(), tab.data());
+    if (tab != std::vector<int>{5, 0, 0, 2, 5, 0, 1, 1, 5, 0, 2, 4, 9, 1, 0, 2}) return fail("cv_pass_table: pass 0", 2, 3, 0, 0, 4);
+    mogp::cv_pass_table(4, 2, 4, 3, ids, c.size.data(), tab.data());
+    if (tab != std::vector<int>{9, 1, 1, 1, 9, 1, 2, 4, -1, 0, 0, 0, -1, 0, 0, 0}) return fail("cv_pass_table: padded pass", 2, 3, 0, 0, 4);
+  }
   std::printf("%ld cases ok\n", cases);
   return 0;
 }

@@ -522,7 +522,11 @@ def test_prediction_plan_sizes(tmp_path):
       sobol rows    CH = min(max(128, floor(cap / per_row) rounded down to 128), N), per_row = 8 (D + nb (1 + (R if R > 1)) + (2 terms + 1 if
                     polynomial else 1))
       hessian group = max(1, min(n_good, floor(budget / per)))
-      MeanStage     basis (nbasis m) | dbasis (nterm m) | coef (nb nbasis) | LA (nb qq qq) | ints (nterm + 1 doubles)"""
+      MeanStage     basis (nbasis m) | dbasis (nterm m) | coef (nb nbasis) | LA (nb qq qq) | ints (nterm + 1 doubles)
+    and from the rules as they stood inline in Engine::hessian / fit_map_from / predict_mixture / cross_validate:
+      hessian scratch  8 (D NPh^2 + NPh (3 D + 1) + (D + 1)(D + 2)(TG + 1) + D^2 (PGR + 1)) bytes per emulator
+      slots in half    max(1, floor(0.5 free / per))
+      replica slot     3 MS 8 + 16 LD 8 bytes;  bound 4095 // max(1, NP // TILE) + 1"""
     import subprocess
     exe = _build_host_check(tmp_path, "predict_plan_check")
     # chunk rule: (cap, nb, LD, m) -> (points per chunk, chunks)
@@ -563,12 +567,28 @@ def test_prediction_plan_sizes(tmp_path):
         ((3, 5, 1, 0, 1), (0, 5, 5, 8, 11, 12)),                    # analytic constant
         ((1, 1, 7, 6, 7), (0, 7, 13, 20, 69, 76)),                  # the most columns an analytic mean may have (RMAX - 1)
     ]
+    # hessian scratch: (NPh, D, TG, PGR) -> bytes
+    hscr = [((64, 3, 1, 1), 103888.0),                  # 8 (3 x 4096 + 64 x 10 + 20 x 2 + 9 x 2) = 8 x 12986
+            ((2048, 10, 256, 256), 336529216.0)]        # 8 (41943040 + 63488 + 132 x 257 + 100 x 257) = 8 x 42066152
+    # replica slots at NP = LD = 128, 2048, 16000 (MS = NP^2, TILE = 128): (MS, LD, NP, TILE) -> (bytes per slot, batch bound)
+    rslot = [((128 * 128, 128, 128, 128), (409600.0, 4096)),              # 393216 + 16384; one tile row: 4095 + 1
+             ((2048 * 2048, 2048, 2048, 128), (100925440.0, 256)),       # 100663296 + 262144; 16 tile rows: 255 + 1
+             ((16000 * 16000, 16000, 16000, 128), (6146048000.0, 33))]   # 6144000000 + 2048000; 125 tile rows: 32 + 1
+    # slots in half of the free memory: (free bytes, bytes per slot) -> slots
+    half = [((200e9, 409600.0), 244140),                # 1e11 / 409600 = 244140.6
+            ((200e9, 100925440.0), 990),                # 990 slots = 99 916 185 600 <= 1e11 < 991 slots = 100 017 111 040
+            ((200e9, 6146048000.0), 16),                # 16.27
+            ((1e5, 409600.0), 1),                       # 0.12: the floor of one
+            ((2457600.0, 409600.0), 3)]                 # exactly three
     text = "".join("chunk " + " ".join(repr(x) for x in c) + "\n" for c, _ in chunk)
     text += "".join("sobol " + " ".join(repr(x) for x in c) + "\n" for c, _ in sobol)
     text += "".join("hess " + " ".join(repr(x) for x in c) + "\n" for c, _ in hess)
     text += "".join("stage " + " ".join(repr(x) for x in c) + "\n" for c, _ in stage) + "icap\n"
+    text += "".join("hscr " + " ".join(repr(x) for x in c) + "\n" for c, _ in hscr)
+    text += "".join("rslot " + " ".join(repr(x) for x in c) + "\n" for c, _ in rslot)
+    text += "".join("half " + " ".join(repr(x) for x in c) + "\n" for c, _ in half)
     out = subprocess.run([exe], input=text, capture_output=True, text=True, check=True).stdout.splitlines()
-    assert len(out) == len(chunk) + len(sobol) + len(hess) + len(stage) + 1
+    assert len(out) == len(chunk) + len(sobol) + len(hess) + len(stage) + 1 + len(hscr) + len(rslot) + len(half)
     it = iter(out)
     for case, (want, chunks) in chunk:
         got = int(next(it))
@@ -585,6 +605,15 @@ def test_prediction_plan_sizes(tmp_path):
         o_int, total, nterm = got[4], got[5], case[3]
         assert (total - o_int) * 8 >= 2 * nterm * 4, ("the dims / powers do not fit behind the doubles", case)
     assert float(next(it)) == 6.0e9
+    for case, want in hscr:
+        got = float(next(it))
+        assert got == want, ("hscr", case, want, got)
+    for case, want in rslot:
+        got = next(it).split()
+        assert (float(got[0]), int(got[1])) == want, ("rslot", case, want, got)
+    for case, want in half:
+        got = int(next(it))
+        assert got == want, ("half", case, want, got)
 
 
 def test_analytic_mean_algebra(tmp_path):
