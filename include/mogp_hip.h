@@ -180,6 +180,28 @@ int mogp_densegp_predict_mixture(mogp_densegp*, const double* thetas /* S*len */
 int mogp_densegp_cross_validate(mogp_densegp*, const int* labels, int n_labels, int k, int include_nugget, int max_slots,
                                 double* mean_out, double* var_out /* n each */, double* maha_out, double* log_score_out,
                                 int* ok_out /* k each */);
+/* S joint draws f(X*) ~ N(mu*, Sigma~) of a fitted emulator at the m points testing (m, D), on the device.  With mu* and Sigma* what
+ * mogp_densegp_predict_full_cov returns (the same launches, the same bits; nugget not included):
+ *   Sigma~ = Sigma* + ((include_nugget ? nugget used by the fit : 0) + jitter + delta) I = L L^T,   samples_out[s][:] = mu* + L z[s][:]
+ * Jitter ladder: delta = 0 on the first try; where Sigma~ does not factorise it is tried again with delta = mean(diag Sigma*) 1e-6 10^t,
+ * t = 0 .. 4 (the adaptive-nugget rule of the fit); jitter_used_out = jitter + delta.  After the fifth failure ok_out = 0 and samples_out
+ * is NaN -- status 0, not an error.
+ * Normals: z_in (S, m), the caller's (z_in_per_emulator is ignored for a single emulator), or NULL: generated on the device by a
+ * counter-based generator, so that a value depends on (seed, stream, draw s, point j) alone and never on how the work was cut:
+ * Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85), key = (seed & 0xffffffff, seed >> 32),
+ * counter = (p, s, stream0, 0) with p = j >> 1; from the output words x0 .. x3
+ *   u1 = ((x0 >> 5) 2^26 + (x1 >> 6) + 1) 2^-53 in (0, 1],   u2 = ((x2 >> 5) 2^26 + (x3 >> 6)) 2^-53 in [0, 1),
+ *   r = sqrt(-2 ln u1),   z[2p] = r cos(2 pi u2),   z[2p + 1] = r sin(2 pi u2)          (an odd m drops the last sine).
+ * z_out (S, m) or NULL: the normals used.  mean_out (m) = mu*.  The draws go max_draws per chunk (0: the library's choice) through a
+ * scratch engine of m rows; everything is scratch of the call, the emulator keeps its factor, theta and log-posterior.  One writer per
+ * output, a fixed summation order, no atomics: the same call returns the same bits, and max_draws changes none.  Refused: nugget type
+ * "pivot", the analytic mean, an emulator that is not fit, D other than the emulator's, non-finite testing or z_in, S < 1, jitter < 0,
+ * negative max_slots / max_draws, scratch of more than half of the free device memory for one emulator and one tile of 64 draws, and
+ * what predict_full_cov's 64 GB rule refuses. */
+int mogp_densegp_sample_posterior(mogp_densegp*, const double* testing, int m, int D, int S, unsigned long long seed, unsigned int stream0,
+                                  const double* z_in /* S*m or NULL */, int z_in_per_emulator, int include_nugget, double jitter,
+                                  int max_slots, int max_draws, double* samples_out /* S*m */, double* mean_out /* m */,
+                                  double* z_out /* S*m or NULL */, double* jitter_used_out /* 1 */, int* ok_out /* 1 */);
 int mogp_densegp_get_K(mogp_densegp*, double* out /* n*n */);
 int mogp_densegp_get_invQ(mogp_densegp*, double* out /* n*n */);
 int mogp_densegp_get_invQt(mogp_densegp*, double* out /* n */);
@@ -272,6 +294,14 @@ int mogp_mogp_predict_mixture(mogp_mogp*, const double* thetas, int S, int n_col
  * var_out (n_out, n), maha_out / log_score_out / ok_out (n_out, k).  Emulators that are not fit give NaN rows and ok_out = 0. */
 int mogp_mogp_cross_validate(mogp_mogp*, const int* labels, int n_labels, int k, int include_nugget, int max_slots, double* mean_out,
                              double* var_out, double* maha_out, double* log_score_out, int* ok_out);
+/* mogp_densegp_sample_posterior for every emulator, max_slots emulators per pass (0: the library's choice): samples_out (n_out, S, m),
+ * mean_out (n_out, m), z_out (n_out, S, m) or NULL, jitter_used_out / ok_out (n_out).  z_in: (S, m) shared by all emulators, with
+ * z_in_per_emulator (n_out, S, m), or NULL.  Emulator e draws from stream stream0 + e, e its index in the model whatever part it lies in:
+ * its normals are those of the single-emulator call with that stream.  Only the emulators whose Sigma~ fails are tried again on the
+ * jitter ladder.  Emulators that are not fit give NaN rows, jitter_used_out NaN and ok_out = 0. */
+int mogp_mogp_sample_posterior(mogp_mogp*, const double* testing, int m, int D, int S, unsigned long long seed, unsigned int stream0,
+                               const double* z_in, int z_in_per_emulator, int include_nugget, double jitter, int max_slots, int max_draws,
+                               double* samples_out, double* mean_out, double* z_out, double* jitter_used_out, int* ok_out);
 /* predict_variance_batch (multioutputgp_gpu.hpp:182-192) with DEVICE pointers: inputs already resident in HBM, results stay in HBM
  * (every mean function; rows of emulators that are not fit are filled with NaN, MultiOutputGP_GPU.py:288-296) */
 int mogp_mogp_predict_variance_batch_dev(mogp_mogp*, const double* d_testing, int m, int D, double* d_means, double* d_vars);

@@ -17,6 +17,7 @@ mogp_emulator_amd -- MI355X (gfx950) native fit + predict backend for mogp_emula
                    gKDR dimension reduction; R of a whole (X_scale, Y_scale) grid in one device call
   Laplace.py       Hessian of the log-posterior on the device and the Laplace approximation N(theta_hat, H^-1) around a MAP fit
   Marginal.py      predictions averaged over hyperparameter samples (Laplace draws, importance weighted, or the caller's own), reduced on the device
+  Sampling.py      joint posterior sample paths f(X*) ~ N(mu*, Sigma*): covariance, Cholesky factor, normals and mu + L z on the device
   dist.py          one-process-per-GPU sharding of emulators + single gather (torch.distributed/RCCL)
 """
 from .LibGPGPU import HAVE_LIBGPGPU, gpu_usable            # noqa: F401
@@ -24,6 +25,7 @@ from .DimensionReduction import gKDR                        # noqa: F401
 from .ExperimentalDesign import ExperimentalDesign, MonteCarloDesign, LatinHypercubeDesign, MaxiMinLHC   # noqa: F401
 from .Laplace import LaplaceResult, logpost_hessian, laplace_approximation   # noqa: F401
 from .Marginal import predict_marginal, MarginalPredictResult, mixture_weights   # noqa: F401
+from .Sampling import sample_posterior, PosteriorSamples, philox_normals   # noqa: F401
 
 if HAVE_LIBGPGPU:
     from .GaussianProcessGPU import GaussianProcessGPU, PredictResult   # noqa: F401

@@ -240,6 +240,19 @@ int mogp_densegp_cross_validate(mogp_densegp* h, const int* labels, int n_labels
     e->cross_validate({h->idx}, labels, k, include_nugget != 0, max_slots, mean_out, var_out, maha_out, log_score_out, ok_out);
   });
 }
+int mogp_densegp_sample_posterior(mogp_densegp* h, const double* testing, int m, int D, int S, unsigned long long seed, unsigned int stream0,
+                                  const double* z_in, int z_in_per_emulator, int include_nugget, double jitter, int max_slots, int max_draws,
+                                  double* samples_out, double* mean_out, double* z_out, double* jitter_used_out, int* ok_out) {
+  return on_engine_device(h, [&] {
+    Engine* e = h->eng;
+    check_D(D, e);
+    const GPState& g = e->gp[h->idx];
+    if (!(g.has_data && g.factored)) throw std::runtime_error("Hyperparameters have not been fit for this Gaussian Process");
+    (void)z_in_per_emulator;      // one emulator: (S, m) either way
+    e->sample_posterior({h->idx}, &stream0, testing, m, S, seed, z_in, false, include_nugget != 0, jitter, max_slots, max_draws, samples_out,
+                        mean_out, z_out, jitter_used_out, ok_out);
+  });
+}
 int mogp_densegp_loo_variance(mogp_densegp* h, double* out) { return on_engine_device(h, [&] { h->eng->loo_variance(h->idx, out); }); }
 int mogp_densegp_get_K(mogp_densegp* h, double* out) { return on_engine_device(h, [&] { h->eng->get_K(h->idx, out); }); }
 int mogp_densegp_get_invQ(mogp_densegp* h, double* out) { return on_engine_device(h, [&] { h->eng->get_invQ(h->idx, out); }); }

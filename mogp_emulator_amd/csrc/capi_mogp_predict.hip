@@ -262,6 +262,35 @@ int mogp_mogp_cross_validate(mogp_mogp* h, const int* labels, int n_labels, int 
     });
   });
 }
+// every part: its fitted emulators in one Engine::sample_posterior, each on stream stream0 + its index in the model; the rows of the
+// others NaN and ok = 0
+int mogp_mogp_sample_posterior(mogp_mogp* h, const double* testing, int m, int D, int S, unsigned long long seed, unsigned int stream0,
+                               const double* z_in, int z_in_per_emulator, int include_nugget, double jitter, int max_slots, int max_draws,
+                               double* samples_out, double* mean_out, double* z_out, double* jitter_used_out, int* ok_out) {
+  return guarded([&] {
+    check_D(D, h->eng);
+    if (!testing || !samples_out || !mean_out || !jitter_used_out || !ok_out) throw std::runtime_error("sample_posterior: null buffer");
+    if (m < 1) throw std::runtime_error("sample_posterior: at least one query point is needed");
+    if (S < 1) throw std::runtime_error("sample_posterior: at least one draw is needed (n_draws = " + std::to_string(S) + ")");
+    if (h->eng->analytic) throw std::runtime_error("sample_posterior: not available with analytic_mean=True (its covariance term is finished on the host)");
+    if (h->nug_type0 == NUG_PIVOT) throw std::runtime_error("sample_posterior: not available with nugget=\"pivot\" (a pivoted, possibly rank-deficient factor)");
+    const size_t mm = (size_t)m, sm = (size_t)S * mm;
+    const bool per = z_in && z_in_per_emulator != 0;
+    for_parts(h, [&](mogp_part& p, int) {
+      Engine* e = p.eng.get();
+      const size_t lo = (size_t)p.lo;
+      with_fitted_rows(e,
+                       {Rows::in(per ? z_in + lo * sm : nullptr, sm), Rows::out(samples_out + lo * sm, sm, true), Rows::out(mean_out + lo * mm, mm, true),
+                        Rows::out(z_out ? z_out + lo * sm : nullptr, sm, true), Rows::out(jitter_used_out + lo, 1, true), Rows::out(ok_out + lo, 1, true)},
+                       [&](const std::vector<int>& ids, const std::vector<Rows>& a) {
+                         std::vector<unsigned> streams(ids.size());
+                         for (size_t k = 0; k < ids.size(); ++k) streams[k] = stream0 + (unsigned)(p.lo + ids[k]);
+                         e->sample_posterior(ids, streams.data(), testing, m, S, seed, per ? a[0].d() : z_in, per, include_nugget != 0, jitter,
+                                             max_slots, max_draws, a[1].d(), a[2].d(), a[3].d(), a[4].d(), a[5].i());
+                       });
+    });
+  });
+}
 int mogp_mogp_predict_variance_batch_dev(mogp_mogp* h, const double* d_testing, int m, int D, double* d_means, double* d_vars) {
   return guarded([&] { mogp_predict_dev_common(h, d_testing, m, D, d_means, d_vars, nullptr); });
 }

@@ -161,6 +161,21 @@ class Engine {
   void loo_variance(int i, double* out);
   // predict(full_cov=True), GaussianProcess.py:899-911: means (nb, m), covs (nb, m, m) host buffers, nugget NOT included
   void predict_full_cov(const std::vector<int>& ids, const double* Xs, int m, double* means, double* covs);
+  // Joint posterior draws of emulators `ids` at the m query points Xs (host, (m, D)) -- kernels_sample.hip, DESIGN.md section 3 "Sampling".
+  // With Sigma*_e, mu*_e what predict_full_cov returns (the same launches, the same bits; nugget not included):
+  //   Sigma~_e = Sigma*_e + ((include_nugget ? nugget used by the fit : 0) + jitter + delta_e) I = L_e L_e^T,
+  //   samples[e][s][:] = mu*_e + L_e z[e][s][:]                                              samples (ids, S, m), mean (ids, m).
+  // delta_e = 0 on the first try; an emulator whose Sigma~ does not factorise is tried again -- it alone -- with delta_e =
+  // sample_ladder_delta(t, mean diag Sigma*_e), t = 0 .. 4 (predict_plan.h); jitter_used[e] = jitter + delta_e; after the fifth failure
+  // ok[e] = 0 and its samples are NaN (no exception).  The factor's diagonal is finished from its rows with the correctly rounded square root.  z: z_in (S, m) shared by all emulators or, with z_per_emulator, (ids, S, m); null:
+  // generated on the device, value (e, s, j) from (seed, streams[e], s, j) alone (philox_dev.h).  z_out (ids, S, m) or null: the normals used.
+  // The emulators go `slots` per pass and the draws `draws` per chunk (sample_plan; max_slots / max_draws = 0: the library's choice)
+  // through a scratch engine of m rows; every buffer is scratch of the call.  THIS engine is only read, apart from gaining L^-1.  One writer
+  // per output, no atomics: the same call returns the same bits, and max_draws changes none.  Throws for nugget="pivot", the analytic mean,
+  // an emulator that is not fit, S < 1, jitter < 0, negative max_*, non-finite Xs / z_in and scratch beyond sample_plan's limits.
+  void sample_posterior(const std::vector<int>& ids, const unsigned* streams, const double* Xs, int m, int S, unsigned long long seed,
+                        const double* z_in, bool z_per_emulator, bool include_nugget, double jitter, int max_slots, int max_draws,
+                        double* samples, double* mean, double* z_out, double* jitter_used, int* ok);
   void get_invQ(int i, double* out);
   void get_invQt(int i, double* out);
   void get_chol(int i, double* out);
@@ -192,8 +207,12 @@ class Engine {
   // gKDR (kernels_gkdr.hip): every slot's matrix is written into the factor buffer by `fill` -- the launch of the covariance build,
   // with the same layout (launch.h) -- and factored with the schedule of the regime; info (indexed by slot) as factorize.  The
   // slots that factor form L^-1 (linv_buffer(), lower triangle).  Needs nugget type "fixed" on every slot.
-  void factor_prebuilt(const std::function<void(const BatchView&)>& fill, std::vector<int>& info);
+  // only (sample_posterior): the slots to factor instead of all -- the others keep their factor and state, info is meaningful for the listed
+  // slots alone; want_linv = false: L^-1 is not formed.
+  void factor_prebuilt(const std::function<void(const BatchView&)>& fill, std::vector<int>& info, const std::vector<int>* only = nullptr,
+                       bool want_linv = true);
   const double* linv_buffer() const { return dLinv; }
+  double* factor_buffer() const { return dA; }
 
   // (streams and events are declared in front of every buffer: members go in reverse order, so the streams are destroyed last)
   Stream stream;                     // main stream: covariance build, trailing updates, everything else
@@ -277,6 +296,18 @@ class Engine {
                         double* maha_out, double* log_score_out, int* ok_out);
   void cv_kfold(const std::vector<int>& ids, const CvFolds& cf, int k, bool include_nugget, int max_slots, CvBuffers& b, double* mean_out,
                 double* var_out, double* maha_out, double* log_score_out, int* ok_out);
+  // the two halves of predict_full_cov (engine_predict.hip), shared with sample_posterior.  fullcov_launches: the device part on `stream`
+  // for the emulators in dIdx -- dC (nb, m, m) = Sigma*, dDots (nb, R, m) the dot products; dKf (nb, MP, LD) and dV (nb, NP, MP) are scratch.
+  // fullcov_host_means: the means (nb, m) from the downloaded dot products, mean-function terms added; with the analytic mean its
+  // covariance term goes into covs (host, may be null without it).
+  void fullcov_launches(int nb, const double* dXf, int m, int MP, double* dKf, double* dV, double* dC, double* dDots);
+  void fullcov_host_means(const std::vector<int>& ids, const double* Xs, int m, const double* dots, double* means, double* covs);
+  // the steps of sample_posterior (engine_analysis.hip)
+  struct SamplePass;
+  void sample_build(const std::vector<int>& grp, const double* Xs, const double* dXq, int m, SamplePass& p, double* mean_out);
+  void sample_factor(Engine& sub, const std::vector<int>& grp, bool include_nugget, double jitter, SamplePass& p, double* jitter_used, int* ok);
+  void sample_draws(Engine& sub, long e0, long cnt, int m, int S, int Sc, unsigned long long seed, const double* z_in, bool z_per_emulator,
+                    SamplePass& p, double* samples, double* z_out);
 
   DevBuf<double> dX, dP, dT, dA, dLinv, dKinv, dAlpha;
   // signal word of the stream memory operations of the look-ahead schedule.  The one raw pointer of the engine: signal memory comes from

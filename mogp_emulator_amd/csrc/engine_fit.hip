@@ -281,11 +281,19 @@ void Engine::retarget(int slot, const Engine& src, int i) {
   gp[slot] = std::move(d);
 }
 
-void Engine::factor_prebuilt(const std::function<void(const BatchView&)>& fill, std::vector<int>& info) {
-  std::vector<int> ids(B);
-  for (int i = 0; i < B; ++i) {
+void Engine::factor_prebuilt(const std::function<void(const BatchView&)>& fill, std::vector<int>& info, const std::vector<int>* only,
+                             bool want_linv) {
+  std::vector<int> ids;
+  if (only) {
+    ids = *only;
+  } else {
+    ids.resize(B);
+    for (int i = 0; i < B; ++i) ids[i] = i;
+  }
+  if (ids.empty()) return;
+  for (int i : ids) {
+    if (i < 0 || i >= B) throw std::runtime_error("factor_prebuilt: slot out of range");
     if (gp[i].nug_type != NUG_FIXED || gp[i].permuted) throw std::runtime_error("factor_prebuilt: every slot needs nugget type fixed");
-    ids[i] = i;
     gp[i].nugget_used = gp[i].nug_size;
   }
   struct Reset {      // build_cov is the covariance build again when this returns or throws
@@ -301,7 +309,7 @@ void Engine::factor_prebuilt(const std::function<void(const BatchView&)>& fill, 
     g.factored = info[i] == 0;
     if (g.factored) ok.push_back(i);
   }
-  if (!ok.empty()) ensure_linv(ok);
+  if (want_linv && !ok.empty()) ensure_linv(ok);
 }
 
 // The inputs of a cached replica engine taken by a fit with other inputs of the same shape: everything the engine derived from X

@@ -153,22 +153,33 @@ void Engine::predict_full_cov(const std::vector<int>& ids, const double* Xs, int
                              " test points need more than 64 GB of device scratch; use fewer points per call");
   ensure_linv(ids);
   upload_idx(ids);
-  BatchView v = view(nb);
   DevBuf<double> dXf((size_t)m * D), dKf((size_t)nb * MP * LD), dV((size_t)nb * NP * MP), dC((size_t)nb * m * m), dDots((size_t)nb * R * m);
   HIPCK(hipMemcpyAsync(dXf, Xs, (size_t)m * D * sizeof(double), hipMemcpyHostToDevice, stream));
-  launch_cross_cov_mean(v, dXf, m, MP, dKf, dDots, m, stream);
-  launch_cov_self_batch(v, dXf, m, dC, stream);
-  launch_predict_fullcov(v, dKf, m, MP, dV, dC, stream);
+  fullcov_launches(nb, dXf, m, MP, dKf, dV, dC, dDots);
   std::vector<double> dots((size_t)nb * R * m);
   HIPCK(hipMemcpyAsync(dots.data(), dDots, dots.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
   HIPCK(hipMemcpyAsync(covs, dC, (size_t)nb * m * m * sizeof(double), hipMemcpyDeviceToHost, stream));
   HIPCK(hipStreamSynchronize(stream));
   HIPCK(hipGetLastError());
+  fullcov_host_means(ids, Xs, m, dots.data(), means, covs);
+}
+
+// the device part of predict_full_cov for the emulators in dIdx: cross covariance and dot products, K**, Sigma* = K** - V^T V
+void Engine::fullcov_launches(int nb, const double* dXf, int m, int MP, double* dKf, double* dV, double* dC, double* dDots) {
+  const BatchView v = view(nb);
+  launch_cross_cov_mean(v, dXf, m, MP, dKf, dDots, m, stream);
+  launch_cov_self_batch(v, dXf, m, dC, stream);
+  launch_predict_fullcov(v, dKf, m, MP, dV, dC, stream);
+}
+
+// the host part: the means from the dot products, the mean-function terms added (and, with the analytic mean, its covariance term)
+void Engine::fullcov_host_means(const std::vector<int>& ids, const double* Xs, int m, const double* dots, double* means, double* covs) {
+  const int nb = (int)ids.size();
   std::vector<double> mv(m), Hs((size_t)q * m), rm((size_t)q * m), dummy(std::max(q, 1), 0.);
   if (R > 1) mean.mean_deriv(Xs, m, D, dummy.data(), q, Hs.data());
   for (int k = 0; k < nb; ++k) {
     const GPState& g = gp[ids[k]];
-    const double* dk = dots.data() + (size_t)k * R * m;
+    const double* dk = dots + (size_t)k * R * m;
     double* mu = means + (size_t)k * m;
     for (int j = 0; j < m; ++j) mu[j] = dk[j];
     if (R > 1) {

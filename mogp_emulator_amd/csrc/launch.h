@@ -251,6 +251,28 @@ void launch_cv_finish(const int* folds, const int* tab, int nslots, const double
                       int nsub, int NPsub, const double* targets, const double* eta, bool include_nugget, int n, int k, double* mean,
                       double* var, double* maha, double* log_score, int* ok, hipStream_t s);
 
+// --- joint posterior draws (kernels_sample.hip) -----------------------------------------------------
+// The scratch engine of Engine::sample_posterior has n' = m rows (NPs = roundup(m + 1, 128)); `sv` is ITS view, batch entry z of the launch
+// = its slot sv.idx[z].  gather: A[slot] <- the factor-matrix layout above with Sigma* = cov[src[slot]] (m x m dense, row stride m) plus
+// shift[slot] on its diagonal; the target row m is neutral (zeros, PAD_BIG on the diagonal), rows > m identity, src[slot] < 0 an identity
+// matrix.  Only the 64 x 64 tiles on and below the diagonal carry the matrix: the tiles above it are written as exact zeros (the
+// factorisation reads the lower triangle only, and sample_apply reads whole 128 x 128 diagonal blocks of the factor).
+void launch_sample_gather(const BatchView& sv, const double* cov, const int* src, const double* shift, int m, hipStream_t s);
+// Behind the factorisation, for the slots 0 .. nslots - 1 of the scratch engine with src[slot] >= 0: the diagonal of the factor recomputed from
+// its finished row, L[j][j] = sqrt(Sigma~[j][j] - sum_{k<j} L[j][k]^2) with the correctly rounded square root (the factorisation's own diagonal
+// comes from a reciprocal square root and may be one unit in the last place off; with a single point the draw is then mu + sqrt(Sigma~) z to
+// the bit).  One wave per row, lane-strided partial sums added in a fixed order; a value that is not a positive finite number is not stored.
+void launch_sample_polish(double* A, int NPs, int nslots, const double* cov, const int* src, const double* shift, int m, hipStream_t s);
+// Z (nslots, zrows, MP) row-major, MP = roundup(m, 128): rows r < sc of every slot <- the standard normals of draws s0 + r at the points
+// 0 .. m-1 of stream streams[slot] (philox_dev.h: a value depends on (seed, stream, draw, point) alone).  Columns >= m are not written.
+void launch_sample_normals(double* Z, int nslots, long zrows, int MP, int m, int sc, long s0, unsigned long long seed, const unsigned* streams,
+                           hipStream_t s);
+// Y (nslots, yrows, m): Y[slot][r][j] = mu[slot][j] + sum_k L[slot][j][k] Z[slot][r][k] for r < sc, j < m; L = the lower triangle of
+// A[slot] (nslots matrices NPs x NPs), its 128 x 128 diagonal blocks read whole (their strict upper triangle must hold zeros), Z as above
+// with zrows a multiple of 64 and columns >= m zero.  fp64 MFMA, one writer per output, a fixed k order, no atomics.
+void launch_sample_apply(const double* A, int NPs, const double* Z, long zrows, int MP, const double* mu, int m, int sc, int nslots,
+                         double* Y, long yrows, hipStream_t s);
+
 // --- utilities -------------------------------------------------------------------------------
 // out (n,n) <- tile of src (NP,NP): mode 0 copy, mode 1 transpose, mode 2 symmetrise from lower
 void launch_extract(const double* src, int NP, int n, double* out, int mode, hipStream_t s);

@@ -1,7 +1,7 @@
 // How the prediction family of Engine (engine_predict.hip) and the analysis family (engine_analysis.hip: hessian, predict_mixture,
-// cross_validate) cut their work to a byte budget, the index tables of their passes, and where the mean-function terms of a prediction are
-// staged.  Plain host arithmetic with no HIP in it, so that a host compiler takes it and tests/c/predict_plan_check.cpp, mixture_plan_check.cpp
-// and cv_plan_check.cpp can check it without a device.  The caps that need the device (MOGP_KS_BUDGET_GB, free memory) are passed in.
+// cross_validate, sample_posterior) cut their work to a byte budget, the index tables of their passes, and where the mean-function terms of a prediction are
+// staged.  Plain host arithmetic with no HIP in it, so that a host compiler takes it and tests/c/predict_plan_check.cpp, mixture_plan_check.cpp,
+// cv_plan_check.cpp and sample_plan_check.cpp can check it without a device.  The caps that need the device (MOGP_KS_BUDGET_GB, free memory) are passed in.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -123,6 +123,62 @@ inline void cv_pass_table(long p0, long cnt, long slots, long k, const int* ids,
     if (s < cnt) { t[0] = ids[e]; t[1] = (int)e; t[2] = (int)f; t[3] = size[f]; }
     else { t[0] = -1; t[1] = t[2] = t[3] = 0; }
   }
+}
+
+// Engine::sample_posterior: how many emulators one pass takes and how many draws one chunk.  The emulators go in passes [p0, p0 + slots)
+// in caller order and, inside a pass, the S draws in chunks [s0, s0 + draws): every (emulator, draw) pair is computed exactly once.
+// Bytes of one slot (sample_slot_bytes):
+//   Sigma* and what predict_full_cov builds it from: K* (MP x LD), V (NP x MP), Sigma* (m x m), the R dot-product rows   (MP = roundup(m, 128))
+//   the scratch engine's factor matrix NPs x NPs (NPs = roundup(m + 1, 128)) and its small per-slot rows, mu* (m)
+//   Z and Y of one chunk: 2 x roundup(draws, 64) x MP doubles (sample_apply_kernel reads whole tiles of 64 draws)
+// and a pass never takes more than HALF of the free device memory.  draws: max_draws where given, else SAMPLE_DEFAULT_DRAWS, at most S and
+// SAMPLE_MAX_DRAWS (a chunk's draws are one grid dimension of the generator), cut to whole tiles of 64 where one slot would not fit
+// otherwise.  slots: what the budget holds at that chunk, at most E, max_slots where given, the batch bound of cv_plan and what
+// predict_full_cov's own 64 GB rule allows.  Throws when one slot with a single tile of draws does not fit, when one emulator trips the
+// 64 GB rule, and for negative max_slots / max_draws.
+constexpr long SAMPLE_DRAW_TILE = 64, SAMPLE_DEFAULT_DRAWS = 1024, SAMPLE_MAX_DRAWS = 32768;
+struct SamplePlan {
+  long slots, draws;
+};
+inline long sample_mp(int m) { return ((long)m + 127) / 128 * 128; }
+inline long sample_nps(int m) { return ((long)m + 128) / 128 * 128; }
+inline long sample_draw_rows(long draws) { return (draws + SAMPLE_DRAW_TILE - 1) / SAMPLE_DRAW_TILE * SAMPLE_DRAW_TILE; }
+inline double sample_fixed_bytes(int m, int LD, int NP, int R) {
+  const double MP = (double)sample_mp(m), NPs = (double)sample_nps(m);
+  return 8.0 * (MP * LD + (double)NP * MP + (double)m * m + (double)R * m + NPs * NPs + 16.0 * NPs + (double)m);
+}
+inline double sample_draw_bytes(int m, long draws) { return 2.0 * 8.0 * (double)sample_draw_rows(draws) * (double)sample_mp(m); }
+inline double sample_slot_bytes(int m, int LD, int NP, int R, long draws) { return sample_fixed_bytes(m, LD, NP, R) + sample_draw_bytes(m, draws); }
+inline double fullcov_rule_bytes(int m, int LD) { return 8.0 * ((double)LD * (double)sample_mp(m) * 2.0 + (double)m * m); }
+inline SamplePlan sample_plan(long E, int m, long S, int LD, int NP, int R, double free_bytes, int max_slots, int max_draws) {
+  if (max_slots < 0 || max_draws < 0) throw std::runtime_error("sample_posterior: max_slots and max_draws must not be negative");
+  if (fullcov_rule_bytes(m, LD) > 64.0e9)
+    throw std::runtime_error("sample_posterior: " + std::to_string(m) + " test points need more than 64 GB of device scratch; use fewer points per call");
+  const double budget = 0.5 * free_bytes, fixed = sample_fixed_bytes(m, LD, NP, R);
+  if (fixed + sample_draw_bytes(m, 1) > budget)
+    throw std::runtime_error("sample_posterior: one emulator at " + std::to_string(m) + " test points needs " +
+                             std::to_string((long long)(fixed + sample_draw_bytes(m, 1))) +
+                             " bytes of device scratch, more than half of the free device memory; use fewer points per call");
+  long draws = std::max<long>(1, std::min<long>(std::max<long>(1, S), max_draws > 0 ? max_draws : SAMPLE_DEFAULT_DRAWS));
+  draws = std::min(draws, SAMPLE_MAX_DRAWS);
+  if (fixed + sample_draw_bytes(m, draws) > budget) {
+    const long tiles = (long)std::floor((budget - fixed) / sample_draw_bytes(m, 1));
+    draws = std::min(draws, std::max<long>(1, tiles) * SAMPLE_DRAW_TILE);
+  }
+  long slots = (long)std::max(1.0, std::floor(budget / (fixed + sample_draw_bytes(m, draws))));
+  slots = std::min(slots, std::max<long>(1, E));
+  slots = std::min(slots, (long)std::max(1.0, std::floor(64.0e9 / fullcov_rule_bytes(m, LD))));
+  slots = std::min(slots, cv_slot_bound((int)sample_nps(m)));
+  if (max_slots > 0) slots = std::min<long>(slots, max_slots);
+  return {std::max<long>(1, slots), draws};
+}
+// The jitter ladder of sample_posterior: rung t = 0 .. SAMPLE_LADDER_RUNGS - 1 adds 10^-6 * 10^t * (mean diagonal of Sigma*) -- the adaptive
+// rule of the fit applied to the predictive covariance, the factor ten applied t times as there.
+constexpr int SAMPLE_LADDER_RUNGS = 5;
+inline double sample_ladder_delta(int t, double mean_diag) {
+  double d = mean_diag * 1e-6;
+  for (int i = 0; i < t; ++i) d *= 10.0;
+  return d;
 }
 
 // Stage 2 of Engine::predict_mixture: the normalised weights of the S samples of one emulator, from their negative log-posteriors F and

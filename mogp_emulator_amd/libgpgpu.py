@@ -133,6 +133,31 @@ def _mixture_weight_args(weights, log_q, shape):
     return out
 
 
+def _sample_call(fn, handle, lead, x, n_draws, seed, stream, z, include_nugget, jitter, max_slots, max_draws, return_z):
+    """shared by DenseGP_GPU.sample_posterior and MultiOutputGP_GPU.sample_posterior: `lead` = () or (n_emulators,); z None, (S, m) or
+    lead + (S, m) -> (samples lead + (S, m), mean lead + (m,), z or None, jitter_used lead, ok lead bool)"""
+    m = x.shape[0]
+    per = 0
+    if z is not None:
+        z = _f64(z, name="z")
+        if not ((z.ndim == 2 and z.shape[1] == m) or (bool(lead) and z.ndim == 3 and z.shape[0] == lead[0] and z.shape[2] == m)):
+            raise ValueError("sample_posterior: z must have shape (n_draws, m)%s" % (" or (n_emulators, n_draws, m)" if lead else ""))
+        per = int(z.ndim == 3)
+        n_draws = z.shape[-2]
+    S = int(n_draws)
+    if S < 1:
+        raise ValueError("sample_posterior: n_draws must be at least 1")
+    samples, mean = np.zeros(lead + (S, m)), np.zeros(lead + (m,))
+    zout = np.zeros(lead + (S, m)) if return_z else None
+    ju, ok = np.zeros(lead or (1,)), np.zeros(lead or (1,), dtype=np.int32)
+    check(fn(handle, dptr(x), m, x.shape[1], S, int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream) & 0xFFFFFFFF, dptr(z), per,
+             int(bool(include_nugget)), float(jitter), int(max_slots), int(max_draws), dptr(samples), dptr(mean), dptr(zout), dptr(ju),
+             iptr(ok)))
+    if not lead:
+        return samples, mean, zout, float(ju[0]), bool(ok[0])
+    return samples, mean, zout, ju, ok.astype(bool)
+
+
 def _sobol_call(fn, handle, D, n_out, A, B, unc, include_nugget):
     """shared by DenseGP_GPU.sobol and MultiOutputGP_GPU.sobol: (S, ST, mean, variance, emulator_variance or None), one row per output"""
     a, b = _f64(A, 2, "A"), _f64(B, 2, "B")
@@ -794,6 +819,14 @@ class DenseGP_GPU(object):
                                                dptr(maha), dptr(ls), iptr(ok)))
         return mean, var, maha, ls, ok.astype(bool)
 
+    def sample_posterior(self, testing, n_draws=1, seed=0, stream=0, z=None, include_nugget=True, jitter=0., max_slots=0, max_draws=0,
+                         return_z=False):
+        """n_draws joint draws of the emulated function at testing (m, D), factored and multiplied on the device:
+        (samples (S, m), mean (m,), z (S, m) or None, jitter_used, ok).  z (S, m): the caller's normals, else generated on the device from
+        (seed, stream).  The fitted state of the emulator is not touched.  See mogp_densegp_sample_posterior (include/mogp_hip.h)."""
+        return _sample_call(_lib.mogp_densegp_sample_posterior, self._h, (), self._testing(testing), n_draws, seed, stream, z,
+                            include_nugget, jitter, max_slots, max_draws, return_z)
+
     # -- predict ------------------------------------------------------------------------------
     def _testing(self, testing):
         x = _f64(testing)
@@ -1130,6 +1163,14 @@ class MultiOutputGP_GPU(object):
         check(_lib.mogp_mogp_cross_validate(self._h, iptr(lab), n, k, int(bool(include_nugget)), int(max_slots), dptr(mean), dptr(var),
                                             dptr(maha), dptr(ls), iptr(ok)))
         return mean, var, maha, ls, ok.astype(bool)
+
+    def sample_posterior(self, testing, n_draws=1, seed=0, stream=0, z=None, include_nugget=True, jitter=0., max_slots=0, max_draws=0,
+                         return_z=False):
+        """DenseGP_GPU.sample_posterior for every emulator, max_slots emulators per pass: (samples (n_emulators, S, m), mean
+        (n_emulators, m), z or None, jitter_used (n_emulators,), ok (n_emulators,) bool); emulator e draws from stream + e.  z: (S, m)
+        shared or (n_emulators, S, m).  Rows of emulators that are not fit are NaN with ok False."""
+        return _sample_call(_lib.mogp_mogp_sample_posterior, self._h, (self.n_emulators(),), self._testing(testing), n_draws, seed, stream,
+                            z, include_nugget, jitter, max_slots, max_draws, return_z)
 
     def predict_variance_batch_dev(self, d_testing, m, d_means, d_vars):
         """Device-pointer variant: inputs already resident in HBM, results stay in HBM."""
