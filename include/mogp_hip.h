@@ -348,6 +348,8 @@ int mogp_mchol_task_table_ahead(int n_plus_rhs, int* out, int capacity);
    path because a wait of the one-launch chain timed out (0 in normal operation); "mchol_aborts" = factorisations the
    one-launch Cholesky gave up on and a multi-launch schedule repeated (0 in normal operation); "objective_evals" / "gradient_evals" =
    emulator objective evaluations so far (all / with gradient), e.g. to turn a fit_GP_MAP wall time into evaluations/s;
+   "alpha_solves" = emulators whose K^-1 t was solved -- with the evaluation (gradient, analytic mean, pivot) or by the first call that
+   read it after an objective-only evaluation, which leaves it out;
    "lbfgs_runs" / "lbfgs_iterations" / "linesearch_shortened" / "linesearch_lengthened" = optimiser runs started by fit_GP_MAP,
    their accepted steps, and the line-search trial points that failed the sufficient-decrease / the curvature test;
    round 6, the slot pool of fit_GP_MAP: "pool_rounds" = batched optimiser rounds, "pool_slot_rounds" = sum over them of the runs that took

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "devmem.h"
+#include "gp_state.h"
 #include "hostmath.h"
 #include "launch.h"
 
@@ -37,35 +38,6 @@ struct DeviceGuard {
 
 struct CvBuffers;      // engine_analysis.hip
 struct CvFolds;        // predict_plan.h
-
-struct GPState {
-  std::vector<double> data;      // n_data: corr_raw (NC), log sigma^2, [log nugget]
-  std::vector<double> meanp;     // n_mean
-  bool has_data = false;
-  int nug_type = NUG_ADAPTIVE;
-  double nug_size = 0.;          // adaptive: jitter found by the last fit; fixed: the constant
-  Priors pri;
-  double logpost = 0.;
-  bool logpost_stale = false;    // the priors changed since `logpost` was computed (the factorisation itself is still valid)
-  bool factored = false;         // A holds L (and y) for `data`
-  bool linv = false, kinv = false;
-  double nugget_used = 0.;       // value actually added to the diagonal in the last factorisation
-  // nugget="pivot": the factor in A, alpha, L^-1, K^-1 and this emulator's copy of the inputs are in pivoted order
-  bool permuted = false;
-  bool kinv_split = false;       // rank < n: Kinv was formed without the rows of L^-1 of the skipped pivots (kept in w2)
-  int rank = 0;                  // pivots accepted by the last pivoted factorisation (n = full rank)
-  std::vector<double> beta;      // analytic mean coefficients (q), GaussianProcess.py:669-670
-  std::vector<double> LA;        // q x q lower Cholesky factor of A = H^T K^-1 H + B^-1
-  // informative mean priors beta ~ N(b, B) of the analytic mean (Priors.py:423-581); empty = weak
-  std::vector<double> mp_b, mp_Binv, mp_Binvb;
-  double mp_logdetB = 0.;
-
-  // The transitions of the cached state.  L^-1 and K^-1 belong to the factor: they are only read where `factored` holds.
-  void drop_factor() { factored = linv = kinv = false; }   // A no longer holds a usable factor (nor the buffers its inverses)
-  void unfit() { has_data = false; drop_factor(); }        // hyper-parameters, nugget or mean priors changed: fit again
-  void set_fit(bool ok) { has_data = factored = ok; }      // outcome of a fit (what was built from the factor since stays as it is)
-  void priors_changed() { logpost_stale = true; }          // `logpost` was computed with the old priors; the factor is still valid
-};
 
 class Engine {
  public:
@@ -100,9 +72,13 @@ class Engine {
 
   // Batched objective (+ gradient) at per-emulator thetas (full vectors [mean | data]).
   // ok[k] = 1 when the factorisation succeeded.  Never throws for numerical failure.
+  // The objective needs log det K and |L^-1 t|^2 only, and the factorisation leaves both behind: without want_grad alpha = K^-1 t is NOT
+  // solved (GPState::alpha stays false) -- whoever reads it asks ensure_alpha first.  With the analytic mean or nugget="pivot" it is solved
+  // at once, as it is with want_grad (under the triangular inversion).
   void eval(const std::vector<int>& ids, const std::vector<const double*>& thetas, bool want_grad, double* f, double* grad,
             int grad_ld, int* ok);
-  // fit(theta) for one emulator: throws std::runtime_error on failure (densegp_gpu.hpp:556-570)
+  // fit(theta) for one emulator: throws std::runtime_error on failure (densegp_gpu.hpp:556-570).  An objective-only eval: the factor,
+  // y = L^-1 t and the log-posterior are there afterwards, alpha when it is first asked for.
   void fit_one(int i, const double* theta, int len);
   void grad_current(const std::vector<int>& ids, double* grad, int grad_ld);
 
@@ -134,7 +110,7 @@ class Engine {
   // of emulator ids[e], the first n_theta of each row used; EXACTLY ONE of weights (E, S, non-negative) and log_q (E, S, the log proposal
   // density up to a constant: self-normalised importance weights exp(-(F - F_min) - (log_q - log_q at the arg-min)), predict_plan.h
   // mixture_weights); Xs host (m, D).  The (emulator, sample) pairs are factored on a replica engine (as fit_map's starts are), emulator-major
-  // and sample-ascending, `slots` at a time; THIS engine's emulators are not refitted -- factor, L^-1, K^-1, theta and logpost stay.
+  // and sample-ascending, `slots` at a time; THIS engine's emulators are not refitted -- factor, alpha, L^-1, K^-1, theta and logpost stay.
   // Per emulator and point, with the PIVOT mu_0 = the mean of sample 0 -- whatever its weight -- or, where sample 0 failed to factorise,
   // of the first sample that did, d_s = mu_s - mu_0 and v_s = max(variance + (include_nugget ? sample s's own nugget : 0), 0) as predict()
   // reports it:   mean = mu_0 + sum w_s d_s,  within = sum w_s v_s,  between = max(sum w_s d_s^2 - (sum w_s d_s)^2, 0)     -- (E, m) each.
@@ -153,7 +129,7 @@ class Engine {
   // rest, and whether S factorised (0: NaN for the fold's points and scalars; no jitter, no exception).  Every fold a single point:
   // one pass over L^-1.  Otherwise K^-1 is formed and the (emulator, fold) pairs go, emulator-major and fold-ascending, `slots` per
   // pass (cv_plan of predict_plan.h; max_slots = 0: the library's choice) through a sub-engine of the call.  THIS engine is only
-  // read, apart from gaining L^-1 / K^-1: theta, factor, alpha and logpost stay.  No atomics: the same call returns the same bits.
+  // read, apart from gaining alpha / L^-1 / K^-1: theta, factor and logpost stay.  No atomics: the same call returns the same bits.
   // Throws for nugget="pivot", the analytic mean, an emulator that is not fit, bad k, a label outside [0, k) and an empty fold.
   void cross_validate(const std::vector<int>& ids, const int* labels, int k, bool include_nugget, int max_slots, double* mean, double* var,
                       double* maha, double* log_score, int* ok);
@@ -170,7 +146,7 @@ class Engine {
   // ok[e] = 0 and its samples are NaN (no exception).  The factor's diagonal is finished from its rows with the correctly rounded square root.  z: z_in (S, m) shared by all emulators or, with z_per_emulator, (ids, S, m); null:
   // generated on the device, value (e, s, j) from (seed, streams[e], s, j) alone (philox_dev.h).  z_out (ids, S, m) or null: the normals used.
   // The emulators go `slots` per pass and the draws `draws` per chunk (sample_plan; max_slots / max_draws = 0: the library's choice)
-  // through a scratch engine of m rows; every buffer is scratch of the call.  THIS engine is only read, apart from gaining L^-1.  One writer
+  // through a scratch engine of m rows; every buffer is scratch of the call.  THIS engine is only read, apart from gaining alpha / L^-1.  One writer
   // per output, no atomics: the same call returns the same bits, and max_draws changes none.  Throws for nugget="pivot", the analytic mean,
   // an emulator that is not fit, S < 1, jitter < 0, negative max_*, non-finite Xs / z_in and scratch beyond sample_plan's limits.
   void sample_posterior(const std::vector<int>& ids, const unsigned* streams, const double* Xs, int m, int S, unsigned long long seed,
@@ -239,12 +215,18 @@ class Engine {
   // the one-launch kernel aborted: count it and factorise again with the multi-launch schedule of the regime
   void refactor_after_abort(const std::vector<int>& ids, std::vector<int>& info, bool defer_info);
   void read_info(std::vector<int>& info, bool defer_info);
-  // the steps of eval.  solve_and_collect: behind a factorisation of `list`, alpha (and L^-1 with want_grad), log-determinants and Gram
-  // matrices in ONE read-back; info_out (may be null) receives the status words the factorisation left on the device
+  // the steps of eval.  solve_and_collect: behind a factorisation of `list`, log-determinants and Gram matrices -- with want_grad, the
+  // analytic mean or a pivoted emulator in the list also alpha (and L^-1 with want_grad) -- in ONE read-back; info_out (may be null)
+  // receives the status words the factorisation left on the device
   void solve_and_collect(const std::vector<int>& list, std::vector<int>* info_out, bool want_grad, std::vector<double>& logdet,
                          std::vector<double>& gram);
-  // the one-launch back substitution of `todo` on stream `st`; true: it also left log-det / status / Gram in dRes
-  bool launch_backsolve_chain_on(hipStream_t st, const BatchView& v, const std::vector<int>& todo);
+  // the one-launch back substitution of `todo` on stream `st`; true: it also left log-det / status / Gram in dRes (never without
+  // with_res: a deferred solve, whose words in dRes were final when the evaluation returned)
+  bool launch_backsolve_chain_on(hipStream_t st, const BatchView& v, const std::vector<int>& todo, bool with_res = true);
+  // whether solve_and_collect leaves alpha of `list` to ensure_alpha
+  bool alpha_is_deferred(const std::vector<int>& list, bool want_grad) const;
+  // the emulators of `timed_out` (their chain gave up on a wait) again with the multi-launch back substitution, on `stream`
+  void resolve_alpha_after_timeout(const std::vector<int>& timed_out);
   // adaptive nugget: the emulators of `failed` with that nugget type are factored again with growing jitter; good[i] = 1 where it worked
   void jitter_ladder(const std::vector<int>& failed, std::vector<int>& info, std::vector<char>& good, bool want_grad,
                      std::vector<double>& logdet, std::vector<double>& gram);
@@ -256,6 +238,9 @@ class Engine {
   void unpermute(int i, double* vec) const;          // vec (n) from pivoted to training order, in place
   void restore_order(int i);                         // emulator i's inputs back to training order (after a pivoted fit)
   void panel(const BatchView& v, int o, int w, hipStream_t st);
+  // alpha of the emulators of ids that hold a factor but not yet alpha: the one-launch chain on `stream`, its time-out words read back
+  // (one small copy and synchronisation of its own), the repeat with the multi-launch path where a wait gave up
+  void ensure_alpha(const std::vector<int>& ids);
   void ensure_linv(const std::vector<int>& ids);
   void ensure_kinv(const std::vector<int>& ids, bool for_gradient = false);
   BatchView view(int nb) const;
@@ -381,7 +366,8 @@ void prof_enable(bool on);
 void prof_reset();
 bool prof_get(const char* tag, double* ms, long long* launches, double* flops, double* bytes);
 // process-wide diagnostic counters (mogp_profile_counter): "backsolve_timeouts" = back substitutions repeated with the
-// multi-launch path after a wait of the one-launch chain timed out
+// multi-launch path after a wait of the one-launch chain timed out; "alpha_solves" = emulators whose alpha was solved, at once
+// (eval with gradient, analytic mean, pivot) or when a reader first asked (ensure_alpha)
 long long prof_counter(const char* name);
 
 }  // namespace mogp

@@ -65,6 +65,7 @@ void prof_enable(bool on) { g_prof_on = on; }
 long long prof_counter(const char* name) {
   const std::string s(name ? name : "");
   if (s == "backsolve_timeouts") return g_bs_timeouts.load();
+  if (s == "alpha_solves") return g_alpha_solves.load();      // emulators whose alpha was solved (with the evaluation or when first read)
   if (s == "mchol_aborts") return g_mc_aborts.load();          // one-launch factorisations repeated with a multi-launch schedule
   if (s == "objective_evals") return g_obj_evals.load();      // emulator objective evaluations (with or without gradient)
   if (s == "gradient_evals") return g_grad_evals.load();      // of which with gradient
@@ -218,6 +219,8 @@ bool Engine::free_device_bytes(double& free_bytes) const {
 // K build of the slots in dIdx.  With one right-hand side it also presets the solution rows to the all-ones pattern the one-launch
 // back substitution polls for (backsolve_chain_kernel<SENT>); `z_armed` records that, so that a chain launched on a row that has
 // not been preset since its last solve arms it itself instead of reading stale values as "already there".
+// A row stays armed for as long as its solve is deferred (ensure_alpha), over any number of calls: nothing but a back substitution of
+// that emulator writes the row, and a reader that forgot to ask finds the pattern -- NaN -- and not the alpha of an older factor.
 void Engine::build_cov(const BatchView& v, const ZeroRanges& zero) {
   if (prebuilt) {
     for (int r = 0; r < 2; ++r)
@@ -291,7 +294,7 @@ void Engine::upload_params(const std::vector<int>& ids) {
 }
 
 // the one-launch back substitution on stream `st` (status words and sentinel rows prepared on the same stream, in front of it)
-bool Engine::launch_backsolve_chain_on(hipStream_t st, const BatchView& v, const std::vector<int>& todo) {
+bool Engine::launch_backsolve_chain_on(hipStream_t st, const BatchView& v, const std::vector<int>& todo, bool with_res) {
   if (!dBsStatus) {
     dBsStatus.reserve(B);
     HIPCK(hipMemsetAsync(dBsStatus, 0, B * sizeof(int), st));
@@ -305,26 +308,73 @@ bool Engine::launch_backsolve_chain_on(hipStream_t st, const BatchView& v, const
     if (!z_armed[i]) HIPCK(hipMemsetAsync(dAlpha + (size_t)i * RA * LD, 0xFF, (size_t)LD * sizeof(double), st));
     z_armed[i] = 0;                                  // consumed by this solve
   }
+  if (!with_res) return launch_backsolve_chain(v, ++bs_epoch, dBsStatus, n_cu, st);
   return launch_backsolve_chain(v, ++bs_epoch, dBsStatus, n_cu, st, dInfo, dRes, mc_used ? dMcCtrl : nullptr);
 }
 
-// One synchronisation per evaluation: the factorisation leaves its status words on the device, log-det / Gram / alpha
-// (and L^-1 on the gradient path) are launched right behind it, and everything is read back together.  An emulator
-// whose factorisation failed has produced garbage there -- it is either retried (adaptive jitter) or reported.
+// Objective-only evaluations with one right-hand side leave alpha to whoever reads it first.  The analytic mean combines the solution
+// rows right behind the solve (launch_combine_rows, with a matrix only eval has), and the pivoted path keeps its order of work.
+bool Engine::alpha_is_deferred(const std::vector<int>& list, bool want_grad) const {
+  if (want_grad || R > 1) return false;
+  for (int i : list)
+    if (gp[i].nug_type == NUG_PIVOT || gp[i].permuted) return false;
+  return true;
+}
+
+void Engine::resolve_alpha_after_timeout(const std::vector<int>& timed_out) {
+  if (timed_out.empty()) return;
+  g_bs_timeouts += (long long)timed_out.size();
+  upload_idx(timed_out);
+  launch_backsolve(view((int)timed_out.size()), stream);
+}
+
+void Engine::ensure_alpha(const std::vector<int>& ids) {
+  std::vector<int> need;
+  for (int i : ids) {
+    if (!gp[i].factored) throw std::runtime_error("emulator has not been fit");
+    if (!gp[i].alpha) need.push_back(i);
+  }
+  if (need.empty()) return;
+  if (R > 1) throw std::logic_error("ensure_alpha: with the analytic mean alpha is solved by the evaluation itself");
+  upload_idx(need);
+  launch_backsolve_chain_on(stream, view((int)need.size()), need, false);
+  // (off the hot path: the evaluations of a fit with gradients solve alpha themselves, grad_current reads these words with its own results)
+  std::vector<int> status(B, 0);
+  HIPCK(hipMemcpyAsync(status.data(), dBsStatus, B * sizeof(int), hipMemcpyDeviceToHost, stream));
+  HIPCK(hipStreamSynchronize(stream));
+  HIPCK(hipGetLastError());
+  std::vector<int> again;
+  for (int i : need)
+    if (status[i] == bs_epoch) again.push_back(i);
+  resolve_alpha_after_timeout(again);
+  for (int i : need) gp[i].have_alpha();
+  g_alpha_solves += (long long)need.size();
+}
+
+// One synchronisation per evaluation: the factorisation leaves its status words on the device, log-det / Gram (and, unless
+// alpha_is_deferred, alpha -- with L^-1 on the gradient path) are launched right behind it, and everything is read back together.
+// An emulator whose factorisation failed has produced garbage there -- it is either retried (adaptive jitter) or reported.
+// Deferred alpha: the factorisation carried the targets along as row n of the factor, so y = L^-1 t is there and launch_logdet forms
+// log det K and |y|^2 with the device function the chain's leftmost chunk runs -- the same bits; the back substitution
+// alpha = L^-T y (213 us per launch of a 3.95 ms fit at 64 x n=2000, profiles/lazy_alpha_ab.txt) is work the objective does not need.
 void Engine::solve_and_collect(const std::vector<int>& list, std::vector<int>* info_out, bool want_grad, std::vector<double>& logdet,
                                std::vector<double>& gram) {
   for (int i : list) gp[i].factored = true;                // provisional (ensure_linv checks it)
   if (info_out) info_out->assign(B, 0);
   // second pass (rare): emulators whose one-launch back substitution gave up waiting are solved again with the
   // multi-launch path, which has no inter-workgroup waits
+  const bool deferred = alpha_is_deferred(list, want_grad);
+  long long solved = 0;                                    // emulators with a good factor whose alpha this call solved (alpha_solves)
   std::vector<int> todo(list);
   for (int pass = 0; pass < 2 && !todo.empty(); ++pass) {
     upload_idx(todo);
     BatchView v = view((int)todo.size());
     bool res_done = false;
     // single right-hand side: the one-launch chain; the per-block launches (launch_backsolve) serve R > 1 and the repeat of a timed-out chain
-    const bool use_chain = R == 1 && pass == 0;
-    if (want_grad) {
+    const bool use_chain = R == 1 && pass == 0 && !deferred;
+    if (deferred) {
+      // (nothing to solve: the sentinel rows the K build laid stay armed for ensure_alpha)
+    } else if (want_grad) {
       if (use_chain) {
         // Round 6: alpha by the SAME one-launch back substitution as a plain fit -- on the panel stream, UNDER the triangular inversion
         // (both only read the factor): the gemv with L^-1 that used to follow the inversion (0.25 ms for 64 x n=2000, HBM-bound) and the
@@ -362,11 +412,16 @@ void Engine::solve_and_collect(const std::vector<int>& list, std::vector<int>* i
         continue;
       }
       logdet[i] = r[0];
+      if (!deferred && (int)r[1] == 0) solved += 1;        // (a failed factorisation has no alpha: what was "solved" from it is garbage)
       if (info_out) (*info_out)[i] = (int)r[1];
       std::memcpy(gram.data() + (size_t)i * RMAX * RMAX, r + 2, sizeof(double) * RMAX * RMAX);
     }
     g_bs_timeouts += (long long)again.size();
     todo.swap(again);
+  }
+  if (!deferred) {
+    for (int i : list) gp[i].have_alpha();                 // (eval drops the factor, and this with it, where the factorisation failed)
+    g_alpha_solves += solved;
   }
 }
 
@@ -546,8 +601,7 @@ void Engine::ensure_linv(const std::vector<int>& ids) {
   BatchView v = view((int)need.size());
   launch_trtri(v, stream);
   for (int i : need) {
-    gp[i].linv = true;
-    gp[i].kinv = false;   // trtri used Kinv as scratch
+    gp[i].have_linv();    // (trtri used Kinv as scratch: K^-1 is gone)
   }
 }
 
@@ -582,15 +636,36 @@ void Engine::ensure_kinv(const std::vector<int>& ids, bool for_gradient) {
     double* rows = dLinv + (size_t)i * MS + (size_t)gp[i].rank * LD;
     HIPCK(hipMemcpy2DAsync(rows, rowb, w2[i], rowb, wb, n - gp[i].rank, hipMemcpyDeviceToDevice, stream));
   }
-  for (int i : need) {
-    gp[i].kinv = true;
-    gp[i].kinv_split = false;
-  }
-  for (int i : split) gp[i].kinv_split = true;
+  for (int i : need) gp[i].have_kinv(false);
+  for (int i : split) gp[i].have_kinv(true);
 }
 
 void Engine::grad_current(const std::vector<int>& ids, double* grad, int grad_ld) {
   if (ids.empty()) return;
+  // alpha that an objective-only evaluation left out (the lazy-gradient line search: run_pool).  Where the same emulators also lack
+  // L^-1 -- fresh factors, the usual case -- the chain runs on the panel stream UNDER the triangular inversion, as in
+  // solve_and_collect, and its time-out words come back with the gradient; otherwise in front, on the main stream.
+  std::vector<int> lazy, no_linv;
+  for (int i : ids) {
+    if (!gp[i].factored) throw std::runtime_error("emulator has not been fit");
+    if (!gp[i].alpha) lazy.push_back(i);
+    if (!gp[i].linv) no_linv.push_back(i);
+  }
+  const bool under = R == 1 && !lazy.empty() && lazy == no_linv;
+  if (under) {
+    upload_idx(lazy);
+    HIPCK(hipEventRecord(evReady, stream));                // the index list is in place (the factor has been since the evaluation)
+    HIPCK(hipStreamWaitEvent(pstream, evReady, 0));
+    launch_backsolve_chain_on(pstream, view((int)lazy.size()), lazy, false);
+    HIPCK(hipEventRecord(evGroup[14], pstream));
+    ensure_linv(lazy);                                     // (the same list: the index list on the device stays as it is)
+    HIPCK(hipStreamWaitEvent(stream, evGroup[14], 0));
+    for (int i : lazy) gp[i].have_alpha();
+    g_alpha_solves += (long long)lazy.size();
+  } else {
+    ensure_alpha(ids);
+  }
+  const int chain_epoch = bs_epoch;
   ensure_kinv(ids, true);
   upload_idx(ids);
   BatchView v = view((int)ids.size());
@@ -606,8 +681,26 @@ void Engine::grad_current(const std::vector<int>& ids, double* grad, int grad_ld
   const int NQ = D + 3;
   std::vector<double> out((size_t)B * NQ);
   HIPCK(hipMemcpyAsync(out.data(), dGradOut, out.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+  std::vector<int> status;
+  if (under) {
+    status.assign(B, 0);
+    HIPCK(hipMemcpyAsync(status.data(), dBsStatus, B * sizeof(int), hipMemcpyDeviceToHost, stream));
+  }
   HIPCK(hipStreamSynchronize(stream));
   HIPCK(hipGetLastError());
+  if (under) {
+    // a chain that gave up on a wait (rare) left an unusable alpha under this gradient: solve it again, then the gradient again
+    std::vector<int> again;
+    for (int i : lazy)
+      if (status[i] == chain_epoch) again.push_back(i);
+    if (!again.empty()) {
+      // One level deep, never more: every emulator of ids holds alpha and L^-1 by its flags now, so the call below finds `lazy` empty,
+      // takes neither the chain nor this branch, and only launches the gradient again behind the repeat on `stream`.
+      resolve_alpha_after_timeout(again);
+      grad_current(ids, grad, grad_ld);
+      return;
+    }
+  }
   const int nm = n_mean();
   std::vector<double> dpr(D + 2);
   for (size_t q = 0; q < ids.size(); ++q) {
@@ -684,7 +777,8 @@ void Engine::get_invQ(int i, double* out) {
 }
 
 void Engine::get_invQt(int i, double* out) {
-  if (!gp[i].factored) throw std::runtime_error("emulator has not been fit");
+  ensure_alpha({i});
+  HIPCK(hipStreamSynchronize(stream));      // (a repeat after a time-out is still in flight)
   HIPCK(hipMemcpy(out, dAlpha + (size_t)i * RA * LD, n * sizeof(double), hipMemcpyDeviceToHost));
   unpermute(i, out);
 }

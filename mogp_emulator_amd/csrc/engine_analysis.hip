@@ -123,6 +123,7 @@ void Engine::hessian(const std::vector<int>& ids, const std::vector<const double
       gpos.push_back(k);
     }
   if (!good.empty()) {
+    ensure_alpha(good);
     ensure_kinv(good, true);
     const int NPh = hess_np(n), NQ = D + 3, TQ = D + 2, TS = (D + 1) * TQ, TG = hess_trace_groups(n), PGR = hess_pair_groups(n);
     const size_t gsz = hessian_group_size(ks_budget_bytes(), hessian_scratch_bytes(NPh, D, TG, PGR), good.size());
@@ -363,6 +364,7 @@ void Engine::cv_leave_one_out(const std::vector<int>& ids, const int* labels, bo
   const size_t nn = (size_t)n;
   DevBuf<int> dLab(nn);
   SyncOnUnwind drained{stream};
+  ensure_alpha(ids);
   ensure_linv(ids);
   upload_idx(ids);
   b.stage(stream);
@@ -382,6 +384,7 @@ void Engine::cv_kfold(const std::vector<int>& ids, const CvFolds& cf, int k, boo
   if (free_device_bytes(free_b)) device_slots = slots_in_half_of(free_b, cv_slot_bytes(NPsub));
   const long slots = cv_plan(E, k, NPsub, device_slots, max_slots);
 
+  ensure_alpha(ids);
   ensure_kinv(ids, false);
   HIPCK(hipStreamSynchronize(stream));        // the sub-engine reads K^-1 and alpha on its own stream
   const BatchView src = view(0);
@@ -474,6 +477,7 @@ struct Engine::SamplePass {
 // 1. Sigma* (p.dC) and mu* (mean_out, p.dMu) of the emulators of grp
 void Engine::sample_build(const std::vector<int>& grp, const double* Xs, const double* dXq, int m, SamplePass& p, double* mean_out) {
   const int nb = (int)grp.size();
+  ensure_alpha(grp);
   ensure_linv(grp);
   upload_idx(grp);
   std::vector<double> dots((size_t)nb * R * m);

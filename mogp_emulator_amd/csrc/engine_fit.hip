@@ -147,6 +147,8 @@ void Engine::run_pool(const std::vector<int>& slots, const std::function<bool(in
       // 8 - 14 % of the trial points of the benchmark fits fail it: 64 emulators x 15 starts of n = 2000, 10 / 100
       // iterations: 2.58 -> 2.34 s / 8.11 -> 7.42 s, same optima.  The second synchronisation per round costs small
       // problems more than it saves (n = 200, 15 starts: 0.045 -> 0.051 s), so it is used from n = 512 (MOGP_LAZY_GRAD=0 / 1).
+      // The objective-only evaluation does not solve alpha either: grad_current does, under the triangular inversion, for the points
+      // that passed -- the others never needed it.
       eval(actid, th, false, fv.data(), nullptr, 0, okv.data());
       std::vector<int> gids, gpos;
       for (size_t q = 0; q < act.size(); ++q) {

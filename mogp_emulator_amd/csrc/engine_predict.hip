@@ -124,6 +124,7 @@ void Engine::predict(const std::vector<int>& ids, const double* Xs, int m, bool 
   const int nb = (int)ids.size();
   if (nb == 0 || m == 0) return;
   require_factored(ids);
+  ensure_alpha(ids);
   if (vars) ensure_linv(ids);
   upload_idx(ids);
   const BatchView v = view(nb);
@@ -151,6 +152,7 @@ void Engine::predict_full_cov(const std::vector<int>& ids, const double* Xs, int
   if (need > 64.0e9)
     throw std::runtime_error("full_cov: " + std::to_string(nb) + " x " + std::to_string(m) +
                              " test points need more than 64 GB of device scratch; use fewer points per call");
+  ensure_alpha(ids);
   ensure_linv(ids);
   upload_idx(ids);
   DevBuf<double> dXf((size_t)m * D), dKf((size_t)nb * MP * LD), dV((size_t)nb * NP * MP), dC((size_t)nb * m * m), dDots((size_t)nb * R * m);
@@ -212,6 +214,7 @@ void Engine::implausibility_chunks(const std::vector<int>& ids, const double* Xs
     prm[3 * k + 1] = obs_var[k] + discrepancy[k] + (include_nugget ? nugget_size(ids[k]) : 0.);
     prm[3 * k + 2] = (mean.kind == 1) ? mean.value : 0.;
   }
+  ensure_alpha(ids);
   ensure_linv(ids);
   upload_idx(ids);
   BatchView v = view(nb);
