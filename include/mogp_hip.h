@@ -202,6 +202,33 @@ int mogp_densegp_sample_posterior(mogp_densegp*, const double* testing, int m, i
                                   const double* z_in /* S*m or NULL */, int z_in_per_emulator, int include_nugget, double jitter,
                                   int max_slots, int max_draws, double* samples_out /* S*m */, double* mean_out /* m */,
                                   double* z_out /* S*m or NULL */, double* jitter_used_out /* 1 */, int* ok_out /* 1 */);
+/* Posterior covariance of the latent function between two point sets at the fitted hyperparameters, on the device.  With Q = K + nugget I
+ * = L L^T as the fit left it and v(x) = L^-1 k(x):
+ *   cov_out[i][j] = c(x1_i, x2_j) = sigma^2 k(x1_i, x2_j) - v(x1_i)^T v(x2_j)                         X1 (m1, D), X2 (m2, D), cov_out (m1, m2)
+ * -- the off-diagonal block of mogp_densegp_predict_full_cov on the stacked set, without the two diagonal blocks; nugget not included.
+ * X2 = NULL: X2 = X1 (m2 is ignored).  V = L^-1 K*^T of either set is built with predict_full_cov's launches and the product runs on fp64
+ * MFMA with sigma^2 k formed in its epilogue.  One writer per output, a fixed summation order: the same call returns the same bits.
+ * Refused: nugget type "pivot", the analytic mean, an emulator that is not fit, D other than the emulator's, non-finite points, m < 1,
+ * negative max_slots, and scratch (V of both sets, the output, the cross-covariance scratch) of more than 64 GB or more than half of the
+ * free device memory for one emulator. */
+int mogp_densegp_predict_cov(mogp_densegp*, const double* X1, int m1, const double* X2 /* or NULL */, int m2, int D, int max_slots,
+                             double* cov_out /* m1*m2 */);
+/* The ALC (active learning Cohn) design criterion: how much one more run at a candidate c, with noise variance tau >= 0, reduces the
+ * latent predictive variance summed over reference points r_j with weights w_j >= 0.  With c(.,.) as above and s^2(x) = max(c(x, x), 0):
+ *   reduction_out[i] = sum_j w_j c(r_j, c_i)^2 / (s^2(c_i) + tau)                        candidates (m_c, D), reference (m_r, D), weights (m_r)
+ *   cand_var_out[i] = s^2(c_i),   ref_var_out[j] = s^2(r_j)     -- the predictive-variance launches of mogp_densegp_predict_variance_batch:
+ *                                                                   the same bits as its variances clipped at 0
+ * The integrated variance after the run is sum_j w_j s^2(r_j) - reduction_out[i].  noise (1) or NULL: the nugget of the fit
+ * (mogp_densegp_get_nugget_size).  Floor: a candidate with s^2 + tau <= (n + 2) 2^-52 sigma^2 -- the rounding of sigma^2 minus a sum of n
+ * squares -- gets reduction_out = 0 and degenerate_out = 1 (a candidate on a training point of an emulator without nugget); never NaN.
+ * The m_c x m_r matrix is never formed: one workgroup per 128 x 128 tile squares, weights and sums it along the reference points, one
+ * partial per (128-point tile of the WHOLE reference set, candidate), added in ascending tile order.  The reference points go max_points per
+ * chunk (rounded down to a multiple of 128, at least 128; 0: the library's choice); no atomics: the same call returns the same bits, and
+ * max_points changes none.  Refused: what mogp_densegp_predict_cov refuses (the scratch rule: one emulator with one 128-point chunk must
+ * fit half of the free device memory), negative or non-finite weights or noise, weights that sum to 0, negative max_points. */
+int mogp_densegp_alc(mogp_densegp*, const double* candidates, int m_c, const double* reference, int m_r, int D, const double* weights,
+                     const double* noise /* 1 or NULL */, int max_slots, int max_points, double* reduction_out, double* cand_var_out /* m_c each */,
+                     double* ref_var_out /* m_r */, int* degenerate_out /* m_c */);
 int mogp_densegp_get_K(mogp_densegp*, double* out /* n*n */);
 int mogp_densegp_get_invQ(mogp_densegp*, double* out /* n*n */);
 int mogp_densegp_get_invQt(mogp_densegp*, double* out /* n */);
@@ -302,6 +329,15 @@ int mogp_mogp_cross_validate(mogp_mogp*, const int* labels, int n_labels, int k,
 int mogp_mogp_sample_posterior(mogp_mogp*, const double* testing, int m, int D, int S, unsigned long long seed, unsigned int stream0,
                                const double* z_in, int z_in_per_emulator, int include_nugget, double jitter, int max_slots, int max_draws,
                                double* samples_out, double* mean_out, double* z_out, double* jitter_used_out, int* ok_out);
+/* mogp_densegp_predict_cov for every emulator, max_slots emulators per group (0: the library's choice): cov_out (n_out, m1, m2).  Row e
+ * is bit for bit the single-emulator call.  Emulators that are not fit give NaN rows. */
+int mogp_mogp_predict_cov(mogp_mogp*, const double* X1, int m1, const double* X2 /* or NULL */, int m2, int D, int max_slots, double* cov_out);
+/* mogp_densegp_alc for every emulator with the same candidates, reference points and weights: noise (n_out) or NULL (every emulator's own
+ * nugget); reduction_out / cand_var_out / degenerate_out (n_out, m_c), ref_var_out (n_out, m_r).  Row e is bit for bit the single-emulator
+ * call, whatever max_slots and max_points.  Emulators that are not fit give NaN rows and degenerate_out = 0 (their noise is not read). */
+int mogp_mogp_alc(mogp_mogp*, const double* candidates, int m_c, const double* reference, int m_r, int D, const double* weights,
+                  const double* noise /* n_out or NULL */, int max_slots, int max_points, double* reduction_out, double* cand_var_out,
+                  double* ref_var_out, int* degenerate_out);
 /* predict_variance_batch (multioutputgp_gpu.hpp:182-192) with DEVICE pointers: inputs already resident in HBM, results stay in HBM
  * (every mean function; rows of emulators that are not fit are filled with NaN, MultiOutputGP_GPU.py:288-296) */
 int mogp_mogp_predict_variance_batch_dev(mogp_mogp*, const double* d_testing, int m, int D, double* d_means, double* d_vars);

@@ -1,7 +1,7 @@
 """
 Sequential designs -- counterpart of mogp_emulator/SequentialDesign.py: the driver classes ``SequentialDesign`` (bookkeeping of inputs,
-targets and candidates, simulator binding, save / load) and ``MICEDesign`` (Mutual Information for Computer Experiments), and the MICE
-candidate scoring they rest on.
+targets and candidates, simulator binding, save / load), ``MICEDesign`` (Mutual Information for Computer Experiments) with the MICE
+candidate scoring it rests on, and ``ALCDesign`` (the integrated-variance criterion of ActiveLearning.py).
 
 ``MICEDesign._eval_metric`` (mogp_emulator/SequentialDesign.py:884-964) scores every candidate point c by
 
@@ -350,3 +350,88 @@ class MICEDesign(SequentialDesign):
                     raise
                 if attempt == self.N_FIT_ATTEMPTS - 1:
                     raise RuntimeError("Unable to find parameters suitable for both GPs") from exc
+
+
+class ALCDesign(SequentialDesign):
+    """ALC sequential design (active learning Cohn; Cohn 1996, Seo et al. 2000, Gramacy & Lee 2009): the next point is the candidate whose
+    run reduces the emulator's predictive variance, averaged over ``n_ref`` fresh reference points drawn from the base design, the most
+    (``ActiveLearning.alc_criterion``) -- equivalently the candidate that leaves the smallest integrated mean squared error.  Where
+    ``MICEDesign`` scores a candidate by the variance at the candidate itself, this asks what the run does for the whole region.
+    ``nugget``: the emulator's nugget as for ``MICEDesign``; ``noise``: the noise variance assumed for the new run (``None``: the
+    emulator's nugget as its fit used it)."""
+
+    N_FIT_ATTEMPTS = MICEDesign.N_FIT_ATTEMPTS
+    _RETRY_ON = MICEDesign._RETRY_ON
+
+    def __init__(self, base_design, f=None, n_samples=None, n_init=10, n_cand=50, n_ref=200, nugget="adaptive", noise=None):
+        if not isinstance(nugget, str):
+            try:
+                float(nugget)
+            except TypeError:
+                raise TypeError("nugget must be a string or convertible to a float")
+            if nugget < 0.:
+                raise ValueError("nugget parameter cannot be negative")
+        if int(n_ref) <= 0:
+            raise ValueError("number of reference points must be positive")
+        if noise is not None and not (float(noise) >= 0. and np.isfinite(float(noise))):
+            raise ValueError("noise variance cannot be negative")
+        self.nugget = nugget if isinstance(nugget, str) else float(nugget)
+        self.n_ref = int(n_ref)
+        self.noise = None if noise is None else float(noise)
+        self.gp = None
+        self.reference = None
+        self._scores = None
+        super().__init__(base_design, f, n_samples, n_init, n_cand)
+
+    def get_nugget(self):
+        return self.nugget
+
+    def get_n_ref(self):
+        return self.n_ref
+
+    def get_noise(self):
+        return self.noise
+
+    def save_design(self, filename):
+        """inputs, targets and candidates as the base class stores them, with n_ref and noise."""
+        np.savez(filename, inputs=self.inputs, targets=self.targets, candidates=self.candidates, n_ref=self.n_ref, noise=self.noise)
+
+    def load_design(self, filename):
+        super().load_design(filename)
+        with np.load(filename, allow_pickle=True) as archive:
+            if "n_ref" in archive.files:
+                self.n_ref = int(archive["n_ref"])
+                noise = _none_or_array(archive["noise"])
+                self.noise = None if noise is None else float(noise)
+
+    def _generate_candidates(self):
+        super()._generate_candidates()
+        self._scores = None                     # scores belong to one candidate set
+
+    def _estimate_next_target(self, next_point):
+        next_point = np.array(next_point)
+        assert next_point.shape == (self.get_n_parameters(),), "bad shape for next_point"
+        return self.gp.predict(next_point, unc=False, deriv=False)[0]
+
+    def _score_candidates(self):
+        """ALC of every current candidate under the fitted ``self.gp`` over fresh reference points: one device call."""
+        from .ActiveLearning import alc_criterion
+        self.reference = self.base_design.sample(self.n_ref)
+        res = alc_criterion(self.gp, self.candidates, self.reference, noise=self.noise)
+        self._scores = res.reduction[0]
+        return int(res.best[0])
+
+    def _eval_metric(self):
+        """Fit the emulator to the current design (up to N_FIT_ATTEMPTS tries, as ``MICEDesign._eval_metric``), score all candidates,
+        return the index of the best."""
+        if not LibGPGPU.gpu_usable():
+            raise RuntimeError("Cannot run an ALCDesign step: the GPU library or a compatible GPU is unavailable")
+        for attempt in range(self.N_FIT_ATTEMPTS):
+            try:
+                self.gp = fit_GP_MAP(GaussianProcessGPU(self.inputs, self.targets, nugget=self.nugget))
+                return int(self._score_candidates())
+            except RuntimeError as exc:
+                if not any(key in str(exc) for key in self._RETRY_ON):
+                    raise
+                if attempt == self.N_FIT_ATTEMPTS - 1:
+                    raise RuntimeError("Unable to find parameters suitable for the emulator") from exc

@@ -7,7 +7,7 @@ mogp_emulator_amd -- MI355X (gfx950) native fit + predict backend for mogp_emula
   LibGPGPU.py, GaussianProcessGPU.py, MultiOutputGP_GPU.py, fitting.py, Priors.py, Kernel.py
                    host-side mirrors of the reference's GPU-facing Python interface
   HistoryMatching.py, SequentialDesign.py, validation.py
-                   consumers of the batched prediction (implausibility, MICE scoring and the sequential-design drivers, validation errors)
+                   consumers of the batched prediction (implausibility, MICE / ALC scoring and the sequential-design drivers, validation errors)
                    and leave-one-out / k-fold cross-validation at the fitted hyperparameters on the device (validation.cross_validate)
   SensitivityAnalysis.py
                    first-order and total-effect Sobol indices of the predictive mean, fused behind the batched prediction
@@ -18,6 +18,8 @@ mogp_emulator_amd -- MI355X (gfx950) native fit + predict backend for mogp_emula
   Laplace.py       Hessian of the log-posterior on the device and the Laplace approximation N(theta_hat, H^-1) around a MAP fit
   Marginal.py      predictions averaged over hyperparameter samples (Laplace draws, importance weighted, or the caller's own), reduced on the device
   Sampling.py      joint posterior sample paths f(X*) ~ N(mu*, Sigma*): covariance, Cholesky factor, normals and mu + L z on the device
+  ActiveLearning.py
+                   posterior covariance between two point sets and the ALC (integrated-variance) design criterion, reduced on the device
   dist.py          one-process-per-GPU sharding of emulators + single gather (torch.distributed/RCCL)
 """
 from .LibGPGPU import HAVE_LIBGPGPU, gpu_usable            # noqa: F401
@@ -26,6 +28,7 @@ from .ExperimentalDesign import ExperimentalDesign, MonteCarloDesign, LatinHyper
 from .Laplace import LaplaceResult, logpost_hessian, laplace_approximation   # noqa: F401
 from .Marginal import predict_marginal, MarginalPredictResult, mixture_weights   # noqa: F401
 from .Sampling import sample_posterior, PosteriorSamples, philox_normals   # noqa: F401
+from .ActiveLearning import predict_cov, alc_criterion, ALCResult   # noqa: F401
 
 if HAVE_LIBGPGPU:
     from .GaussianProcessGPU import GaussianProcessGPU, PredictResult   # noqa: F401
@@ -34,7 +37,7 @@ if HAVE_LIBGPGPU:
     from .Kernel import SquaredExponential, Matern52, ProductMat52, UniformSqExp, UniformMat52   # noqa: F401
     from .Priors import GPPriors, MeanPriors, InvGammaPrior, GammaPrior, LogNormalPrior, WeakPrior   # noqa: F401
     from .HistoryMatching import HistoryMatching                           # noqa: F401
-    from .SequentialDesign import MICEFastGP, mice_criterion, SequentialDesign, MICEDesign   # noqa: F401
+    from .SequentialDesign import MICEFastGP, mice_criterion, SequentialDesign, MICEDesign, ALCDesign   # noqa: F401
     from .SensitivityAnalysis import sobol_indices, SobolResult          # noqa: F401
     from . import validation                                                # noqa: F401
     from .validation import cross_validate, CrossValidationResult, kfold_labels   # noqa: F401

@@ -93,6 +93,9 @@ SIGNATURES = {
                                             c_int_p]),
     "mogp_densegp_sample_posterior": (c_int, [c_void_p, c_double_p, c_int, c_int, c_int, c_ulonglong, c_uint, c_double_p, c_int, c_int, c_double, c_int, c_int,
                                                c_double_p, c_double_p, c_double_p, c_double_p, c_int_p]),
+    "mogp_densegp_predict_cov": (c_int, [c_void_p, c_double_p, c_int, c_double_p, c_int, c_int, c_int, c_double_p]),
+    "mogp_densegp_alc": (c_int, [c_void_p, c_double_p, c_int, c_double_p, c_int, c_int, c_double_p, c_double_p, c_int, c_int, c_double_p, c_double_p,
+                                 c_double_p, c_int_p]),
     "mogp_densegp_loo_variance": (c_int, [c_void_p, c_double_p]),
     "mogp_densegp_get_K": (c_int, [c_void_p, c_double_p]),
     "mogp_densegp_get_invQ": (c_int, [c_void_p, c_double_p]),
@@ -140,6 +143,9 @@ SIGNATURES = {
                                          c_int_p]),
     "mogp_mogp_sample_posterior": (c_int, [c_void_p, c_double_p, c_int, c_int, c_int, c_ulonglong, c_uint, c_double_p, c_int, c_int, c_double, c_int, c_int,
                                             c_double_p, c_double_p, c_double_p, c_double_p, c_int_p]),
+    "mogp_mogp_predict_cov": (c_int, [c_void_p, c_double_p, c_int, c_double_p, c_int, c_int, c_int, c_double_p]),
+    "mogp_mogp_alc": (c_int, [c_void_p, c_double_p, c_int, c_double_p, c_int, c_int, c_double_p, c_double_p, c_int, c_int, c_double_p, c_double_p,
+                              c_double_p, c_int_p]),
     "mogp_mogp_implausibility": (c_int, [c_void_p, c_double_p, c_int, c_int, c_double_p, c_double_p, c_double_p, c_int, c_int, c_double_p]),
     "mogp_mogp_predict_full_cov": (c_int, [c_void_p, c_double_p, c_int, c_int, c_double_p, c_double_p]),
     "mogp_mogp_predict_variance_batch_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),

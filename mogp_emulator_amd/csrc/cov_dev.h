@@ -42,6 +42,20 @@ __device__ __forceinline__ void stage_rows(const double* __restrict__ Xg, int nr
   }
 }
 
+// the same for the dimensions [d0, d0 + ds) alone: sx[(d - d0) * 64 + r] (alc_cross_kernel stages a wide input in slices of dimensions;
+// with d0 = 0 and ds = D it is stage_rows)
+template <bool SC = false>
+__device__ __forceinline__ void stage_rows_slice(const double* __restrict__ Xg, int nrows, int D, int r0, int d0, int ds, double* sx,
+                                                 const double* __restrict__ P = nullptr) {
+  const int cnt = 64 * ds;
+  for (int e = threadIdx.x; e < cnt; e += 256) {
+    const int r = e / ds, d = d0 + (e - r * ds);
+    double x = (r0 + r < nrows) ? Xg[(size_t)(r0 + r) * D + d] : 0.0;
+    if (SC) x *= sqrt(P[d]);
+    sx[(d - d0) * 64 + r] = x;
+  }
+}
+
 // Entry (i, j) of the augmented matrix A: K + nugget I for i, j < n; rows n .. n+R-1 carry the right-hand sides (row n =
 // targets, rows n+1.. = design-matrix columns of the analytic mean) with PAD_BIG on their diagonal; identity beyond.
 //   sk = sigma^2 k(x_i, x_j) (only used for i, j < n)

@@ -152,6 +152,24 @@ class Engine {
   void sample_posterior(const std::vector<int>& ids, const unsigned* streams, const double* Xs, int m, int S, unsigned long long seed,
                         const double* z_in, bool z_per_emulator, bool include_nugget, double jitter, int max_slots, int max_draws,
                         double* samples, double* mean, double* z_out, double* jitter_used, int* ok);
+  // Posterior covariance of the latent function between two point sets, per emulator of `ids` (kernels_alc.hip, DESIGN.md section 3 "Active
+  // learning"): out (ids, m1, m2) = sigma^2 k(X1, X2) - V_1^T V_2 with V = L^-1 K*^T as predict_full_cov stores it; nugget not included.
+  // X2 == null: X2 = X1.  The emulators go in groups sized by the 64 GB rule of predict_full_cov (V_1, V_2, the output and the K* scratch
+  // counted) and half of the free device memory; every buffer is scratch of the call.  THIS engine is only read, apart from gaining L^-1.
+  // Throws for nugget="pivot", the analytic mean, an emulator that is not fit, m < 1, non-finite points, negative max_slots and one emulator
+  // beyond either memory rule.
+  void predict_cov(const std::vector<int>& ids, const double* X1, int m1, const double* X2, int m2, int max_slots, double* out);
+  // The ALC design criterion of emulators `ids` at fixed hyperparameters: with c the covariance above, s^2(x) = max(c(x, x), 0) as predict()
+  // reports it (the engine's own predictive-variance launches: the same bits) and tau[e] >= 0 the noise variance of one more run,
+  //   reduction[e][i] = sum_j w_j c_e(r_j, c_i)^2 / (s_e^2(c_i) + tau[e])           candidates Xc (mc, D), reference Xr (mr, D), weights w (mr) >= 0
+  // reduction / cand_var / degenerate (ids, mc), ref_var (ids, mr).  noise == null: tau[e] = nugget_size(ids[e]).  A candidate with
+  // s^2 + tau <= (n + 2) 2^-52 sigma^2 -- the rounding of sigma^2 minus a sum of n squares -- gets reduction 0 and degenerate 1; no NaN.
+  // The emulators go `slots` per group and the reference points `points` per chunk (alc_plan; max_slots / max_points = 0: the library's
+  // choice); the partial sums are kept per 128-point tile of the WHOLE reference set and added in ascending tile order, so the same call
+  // returns the same bits and neither number changes any.  Throws as predict_cov does, and for negative or non-finite weights or noise and
+  // weights that sum to 0.
+  void alc(const std::vector<int>& ids, const double* Xc, int mc, const double* Xr, int mr, const double* w, const double* noise, int max_slots,
+           int max_points, double* reduction, double* cand_var, double* ref_var, int* degenerate);
   void get_invQ(int i, double* out);
   void get_invQt(int i, double* out);
   void get_chol(int i, double* out);
@@ -293,6 +311,11 @@ class Engine {
   void sample_factor(Engine& sub, const std::vector<int>& grp, bool include_nugget, double jitter, SamplePass& p, double* jitter_used, int* ok);
   void sample_draws(Engine& sub, long e0, long cnt, int m, int S, int Sc, unsigned long long seed, const double* z_in, bool z_per_emulator,
                     SamplePass& p, double* samples, double* z_out);
+
+  // what alc and predict_cov share (engine_analysis.hip): the refusals; and, for the nb emulators in dIdx and the m points at dXq, K*
+  // (scratch), the predictive variance (dVar, rows var_ld apart; null: not wanted) and V = L^-1 K*^T, with predict()'s own launches
+  void check_cov_args(const char* who, const std::vector<int>& ids, const double* X1, int m1, const double* X2, int m2, int max_a, int max_b) const;
+  void points_v(int nb, const double* dXq, int m, int MP, double* dK, double* dDots, double* dPartial, double* dVar, int var_ld, double* dV);
 
   DevBuf<double> dX, dP, dT, dA, dLinv, dKinv, dAlpha;
   // signal word of the stream memory operations of the look-ahead schedule.  The one raw pointer of the engine: signal memory comes from

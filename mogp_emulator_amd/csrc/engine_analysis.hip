@@ -1,5 +1,5 @@
 // The analysis family of Engine: what is computed AROUND a fit rather than by it -- the Hessian of the log-posterior, the prediction
-// averaged over hyperparameter samples, cross-validation and joint posterior draws.  Each reads as its steps; the host algebra of the Hessian is
+// averaged over hyperparameter samples, cross-validation, joint posterior draws and the active-learning criterion.  Each reads as its steps; the host algebra of the Hessian is
 // hessian_assemble (hostmath.h), the sizing rules and the index tables of the passes are plain arithmetic in predict_plan.h.
 #include "engine_internal.h"
 
@@ -616,6 +616,148 @@ void Engine::sample_posterior(const std::vector<int>& ids, const unsigned* strea
     HIPCK(hipMemcpyAsync(p.dStreams, streams + e0, (size_t)cnt * sizeof(unsigned), hipMemcpyHostToDevice, sub.stream));
     sample_factor(sub, grp, include_nugget, jitter, p, jitter_used + e0, ok + e0);
     sample_draws(sub, e0, cnt, m, S, Sc, seed, z_in, z_per_emulator, p, samples, z_out);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Active learning (engine.h has the contracts, kernels_alc.hip the kernels, alc_plan of predict_plan.h the sizing).
+//   alc:  1. refusals   2. the factor and L^-1   3. alc_plan   4. per group of emulators: the candidates once -- K*, s^2 and V_c with
+//         predict()'s own launches --, then per chunk of reference points K*, s^2, V_r and alc_cross into the per-tile partials, then
+//         alc_finish   5. one download per group.
+//   predict_cov: the same with the store epilogue and no reduction.
+// Every device allocation is a DevBuf local of the call.
+// ---------------------------------------------------------------------------------------------
+
+void Engine::check_cov_args(const char* who, const std::vector<int>& ids, const double* X1, int m1, const double* X2, int m2, int max_a,
+                            int max_b) const {
+  const std::string p = std::string(who) + ": ";
+  require_factored(ids);
+  if (analytic) throw std::runtime_error(p + "not available with analytic_mean=True (the covariance gains a term of the mean coefficients)");
+  for (int i : ids)
+    if (gp[i].nug_type == NUG_PIVOT || gp[i].permuted)
+      throw std::runtime_error(p + "not available with nugget=\"pivot\" (a pivoted, possibly rank-deficient factor)");
+  if (!X1 || !X2) throw std::runtime_error(p + "null buffer");
+  if (m1 < 1 || m2 < 1) throw std::runtime_error(p + "at least one point is needed in each set");
+  if (max_a < 0 || max_b < 0) throw std::runtime_error(p + "max_slots and max_points must not be negative");
+  for (size_t k = 0; k < (size_t)m1 * D; ++k)
+    if (!std::isfinite(X1[k])) throw std::runtime_error(p + "the points must be finite");
+  if (X2 != X1)
+    for (size_t k = 0; k < (size_t)m2 * D; ++k)
+      if (!std::isfinite(X2[k])) throw std::runtime_error(p + "the points must be finite");
+}
+
+void Engine::points_v(int nb, const double* dXq, int m, int MP, double* dK, double* dDots, double* dPartial, double* dVar, int var_ld, double* dV) {
+  const BatchView v = view(nb);
+  // (the dot products of the fused mean are not used: alpha need not be there)
+  launch_cross_cov_mean(v, dXq, m, MP, dK, dDots, MP, stream);
+  if (dVar) launch_predict_var(v, dK, m, MP, dPartial, dVar, var_ld, n_cu, stream);
+  launch_predict_v_store(v, dK, m, MP, dV, stream);
+}
+
+void Engine::predict_cov(const std::vector<int>& ids, const double* X1, int m1, const double* X2, int m2, int max_slots, double* out) {
+  const long E = (long)ids.size();
+  if (E == 0) return;
+  const bool same = X2 == nullptr;
+  if (same) { X2 = X1; m2 = m1; }
+  check_cov_args("predict_cov", ids, X1, m1, X2, m2, max_slots, 0);
+  if (!out) throw std::runtime_error("predict_cov: null buffer");
+  ensure_linv(ids);
+  const double per = predict_cov_rule_bytes(m1, m2, LD, NP);
+  if (per > 64.0e9)
+    throw std::runtime_error("predict_cov: " + std::to_string(m1) + " x " + std::to_string(m2) +
+                             " points need more than 64 GB of device scratch; use fewer points per call");
+  double free_b = 0.;
+  if (!free_device_bytes(free_b)) free_b = 2.0 * ks_budget_bytes();
+  if (per > 0.5 * free_b)
+    throw std::runtime_error("predict_cov: one emulator at " + std::to_string(m1) + " x " + std::to_string(m2) +
+                             " points needs more than half of the free device memory; use fewer points per call");
+  long slots = std::min<long>(E, std::min<long>(slots_in_half_of(free_b, per), (long)std::floor(64.0e9 / per)));
+  slots = std::min<long>(slots, 65535);
+  if (max_slots > 0) slots = std::min<long>(slots, max_slots);
+  slots = std::max<long>(1, slots);
+
+  const int MP1 = (int)alc_mp(m1), MP2 = (int)alc_mp(m2), MPmax = std::max(MP1, MP2);
+  const size_t sl = (size_t)slots, mm = (size_t)m1 * m2;
+  DevBuf<double> dX1((size_t)m1 * D), dX2, dK(sl * MPmax * LD), dDots(sl * MPmax), dV1(sl * NP * MP1), dV2, dC(sl * mm);
+  if (!same) {
+    dX2.reserve((size_t)m2 * D);
+    dV2.reserve(sl * NP * MP2);
+  }
+  SyncOnUnwind drained{stream};
+  HIPCK(hipMemcpyAsync(dX1, X1, (size_t)m1 * D * sizeof(double), hipMemcpyHostToDevice, stream));
+  if (!same) HIPCK(hipMemcpyAsync(dX2, X2, (size_t)m2 * D * sizeof(double), hipMemcpyHostToDevice, stream));
+  for (long e0 = 0; e0 < E; e0 += slots) {
+    const int cnt = (int)std::min(slots, E - e0);
+    const std::vector<int> grp(ids.begin() + e0, ids.begin() + e0 + cnt);
+    upload_idx(grp);
+    points_v(cnt, dX1, m1, MP1, dK, dDots, nullptr, nullptr, 0, dV1);
+    if (!same) points_v(cnt, dX2, m2, MP2, dK, dDots, nullptr, nullptr, 0, dV2);
+    launch_alc_store(view(cnt), dV1, MP1, m1, dX1, same ? dV1.get() : dV2.get(), MP2, m2, same ? dX1.get() : dX2.get(), dC, stream);
+    HIPCK(hipMemcpyAsync(out + (size_t)e0 * mm, dC, (size_t)cnt * mm * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIPCK(hipStreamSynchronize(stream));        // the next group overwrites the buffers
+    HIPCK(hipGetLastError());
+  }
+}
+
+void Engine::alc(const std::vector<int>& ids, const double* Xc, int mc, const double* Xr, int mr, const double* w, const double* noise,
+                 int max_slots, int max_points, double* reduction, double* cand_var, double* ref_var, int* degenerate) {
+  const long E = (long)ids.size();
+  if (E == 0) return;
+  // 1. refusals
+  check_cov_args("alc_criterion", ids, Xc, mc, Xr, mr, max_slots, max_points);
+  if (!w || !reduction || !cand_var || !ref_var || !degenerate) throw std::runtime_error("alc_criterion: null buffer");
+  double wsum = 0.;
+  for (int j = 0; j < mr; ++j) {
+    if (!std::isfinite(w[j])) throw std::runtime_error("alc_criterion: the weights must be finite");
+    if (w[j] < 0.) throw std::runtime_error("alc_criterion: the weights must not be negative");
+    wsum += w[j];
+  }
+  if (!(wsum > 0.)) throw std::runtime_error("alc_criterion: the weights must not sum to 0");
+  std::vector<double> tau((size_t)E);
+  for (long e = 0; e < E; ++e) {
+    tau[e] = noise ? noise[e] : nugget_size(ids[e]);
+    if (!(tau[e] >= 0.) || !std::isfinite(tau[e])) throw std::runtime_error("alc_criterion: noise must be a finite number that is not negative");
+  }
+  // 2. the factor is there (check_cov_args); L^-1
+  ensure_linv(ids);
+  // 3. plan
+  double free_b = 0.;
+  if (!free_device_bytes(free_b)) free_b = 2.0 * ks_budget_bytes();
+  const AlcPlan plan = alc_plan(E, mc, mr, LD, NP, free_b, max_slots, max_points);
+  const long slots = plan.slots;
+  const int CH = (int)plan.points, MPc = (int)alc_mp(mc), tiles_r = (int)(alc_mp(mr) / 128), MPmax = std::max(MPc, CH);
+  const size_t sl = (size_t)slots, nti = (size_t)(n + 127) / 128;
+  // 4. the groups
+  DevBuf<double> dXc((size_t)mc * D), dXr((size_t)mr * D), dW((size_t)mr), dTau(sl), dK(sl * MPmax * LD), dDots(sl * MPmax),
+      dPartial(sl * nti * MPmax), dVc(sl * NP * MPc), dVr(sl * NP * CH), dPart(sl * tiles_r * MPc), dVarC(sl * mc), dVarR(sl * mr), dRed(sl * mc);
+  DevBuf<int> dDeg(sl * mc);
+  SyncOnUnwind drained{stream};
+  HIPCK(hipMemcpyAsync(dXc, Xc, (size_t)mc * D * sizeof(double), hipMemcpyHostToDevice, stream));
+  HIPCK(hipMemcpyAsync(dXr, Xr, (size_t)mr * D * sizeof(double), hipMemcpyHostToDevice, stream));
+  HIPCK(hipMemcpyAsync(dW, w, (size_t)mr * sizeof(double), hipMemcpyHostToDevice, stream));
+  for (long e0 = 0; e0 < E; e0 += slots) {
+    const int cnt = (int)std::min(slots, E - e0);
+    const std::vector<int> grp(ids.begin() + e0, ids.begin() + e0 + cnt);
+    upload_idx(grp);
+    const BatchView v = view(cnt);
+    HIPCK(hipMemcpyAsync(dTau, tau.data() + e0, (size_t)cnt * sizeof(double), hipMemcpyHostToDevice, stream));
+    points_v(cnt, dXc, mc, MPc, dK, dDots, dPartial, dVarC, mc, dVc);
+    for (int c0 = 0; c0 < mr; c0 += CH) {
+      const int mrc = std::min(CH, mr - c0), MPr = (int)alc_mp(mrc);
+      points_v(cnt, dXr + (size_t)c0 * D, mrc, MPr, dK, dDots, dPartial, dVarR + c0, mr, dVr);
+      launch_alc_cross(v, dVc, MPc, mc, dXc, dVr, MPr, mrc, dXr + (size_t)c0 * D, dW + c0, c0 / 128, tiles_r, dPart, stream);
+    }
+    launch_alc_finish(v, mc, MPc, tiles_r, dPart, dVarC, mc, dTau, dRed, dDeg, stream);
+    // 5. one download
+    const size_t oc = (size_t)e0 * mc, orr = (size_t)e0 * mr;
+    HIPCK(hipMemcpyAsync(reduction + oc, dRed, (size_t)cnt * mc * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIPCK(hipMemcpyAsync(cand_var + oc, dVarC, (size_t)cnt * mc * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIPCK(hipMemcpyAsync(degenerate + oc, dDeg, (size_t)cnt * mc * sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIPCK(hipMemcpyAsync(ref_var + orr, dVarR, (size_t)cnt * mr * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIPCK(hipStreamSynchronize(stream));        // the next group overwrites the buffers
+    HIPCK(hipGetLastError());
+    for (size_t k = 0; k < (size_t)cnt * mr; ++k)      // s^2 of the reference points as predict() reports it
+      if (ref_var[orr + k] < 0.) ref_var[orr + k] = 0.;
   }
 }
 

@@ -2,7 +2,8 @@
 // macro, small helpers and the process-wide diagnostic counters behind prof_counter (engine.hip).  What lives where: engine.hip the
 // construction, the cached state, eval's steps, L^-1 / K^-1 and the gradient; engine_chol.hip the factorisation schedules; engine_fit.hip
 // the optimiser, the slot pool and the replica engines; engine_predict.hip predict, full covariance, implausibility, Sobol and loo_variance;
-// engine_analysis.hip the Hessian, the mixture over hyperparameter samples, cross-validation and joint posterior draws.
+// engine_analysis.hip the Hessian, the mixture over hyperparameter samples, cross-validation, joint posterior draws and
+// active learning (alc, predict_cov).
 #pragma once
 #include "engine.h"
 #include "predict_plan.h"

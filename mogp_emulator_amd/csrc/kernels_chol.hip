@@ -719,7 +719,7 @@ __global__ void extract_kernel(const double* __restrict__ src, int NP, int n, do
   if (j >= n) return;
   double x;
   if (mode == 0) x = src[(size_t)i * NP + j];
-  else if (mode == 1) x = src[(size_t)j * NP + i];
+  else if (mode == 1) x = (i <= j) ? src[(size_t)j * NP + i] : 0.0;      // (the tiles of a factor above its diagonal are never written)
   else x = (j <= i) ? src[(size_t)i * NP + j] : src[(size_t)j * NP + i];
   out[(size_t)i * n + j] = x;
 }

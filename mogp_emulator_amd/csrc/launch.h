@@ -91,6 +91,8 @@ void launch_implausibility_merge(int nparts, const double* lists, long ld, int m
 void launch_cov_self_batch(const BatchView& v, const double* Xs, int m, double* out, hipStream_t s);
 // full predictive covariance: cov (nb, m, m) holds K** on entry, K** - Ks K^-1 Ks^T on return; V: nb*NP*MP scratch
 void launch_predict_fullcov(const BatchView& v, const double* Ks, int m, int MP, double* V, double* cov, hipStream_t s);
+// its first half alone: V (nb, NP, MP) = L^-1 Ks^T (rows < roundup(n, 128) written; columns >= m are zero as those rows of Ks are)
+void launch_predict_v_store(const BatchView& v, const double* Ks, int m, int MP, double* V, hipStream_t s);
 
 // --- blocked Cholesky ---------------------------------------------------------------------
 size_t lpack128_doubles_per_emulator();   // scratch written by the diagonal-block kernel, read by the panel solve
@@ -273,8 +275,24 @@ void launch_sample_normals(double* Z, int nslots, long zrows, int MP, int m, int
 void launch_sample_apply(const double* A, int NPs, const double* Z, long zrows, int MP, const double* mu, int m, int sc, int nslots,
                          double* Y, long yrows, hipStream_t s);
 
+// --- active learning (kernels_alc.hip) ------------------------------------------------------------------
+// Posterior cross covariance c(x, x') = sigma^2 k(x, x') - v(x)^T v(x') of two point sets from their stored V = L^-1 K*^T (launch_predict_v_store):
+// V1 (nb, NP, MP1) / X1 (m1, D) the rows, V2 (nb, NP, MP2) / X2 (m2, D) the columns, one 128 x 128 tile per workgroup on fp64 MFMA, the prior
+// term formed in the accumulator's layout.  store: out (nb, m1, m2) = c.
+void launch_alc_store(const BatchView& v, const double* V1, int MP1, int m1, const double* X1, const double* V2, int MP2, int m2, const double* X2,
+                      double* out, hipStream_t s);
+// reduce: the columns are one chunk of the reference points, its first 128-point tile number tile0 of tiles_r in the whole set, w its
+// weights (m2); part[(slot * tiles_r + tile0 + tj) * MP1 + i] = sum over the tile's columns j of w_j c(x_i, r_j)^2: ONE writer per entry, a
+// fixed order inside the tile (the lane's four column blocks ascending, a 16-lane butterfly, the two wave columns), no atomics.
+void launch_alc_cross(const BatchView& v, const double* V1, int MP1, int m1, const double* X1, const double* V2, int MP2, int m2, const double* X2,
+                      const double* w, int tile0, int tiles_r, double* part, hipStream_t s);
+// per (slot, candidate i < m1): var[slot * var_ld + i] <- max(var, 0) = s^2; d = s^2 + tau[slot]; with the floor (n + 2) 2^-52 sigma^2:
+// d <= floor (or not a number): red = 0, deg = 1; else red = (sum of the tiles_r partials, ascending) / d, deg = 0
+void launch_alc_finish(const BatchView& v, int m1, int MP1, int tiles_r, const double* part, double* var, int var_ld, const double* tau,
+                       double* red, int* deg, hipStream_t s);
+
 // --- utilities -------------------------------------------------------------------------------
-// out (n,n) <- tile of src (NP,NP): mode 0 copy, mode 1 transpose, mode 2 symmetrise from lower
+// out (n,n) <- tile of src (NP,NP): mode 0 copy, mode 1 transpose of the lower triangle (zeros below the diagonal of out), mode 2 symmetrise from lower
 void launch_extract(const double* src, int NP, int n, double* out, int mode, hipStream_t s);
 
 // --- profiling hooks (bench only) -------------------------------------------------------------

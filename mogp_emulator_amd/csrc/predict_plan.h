@@ -1,7 +1,7 @@
 // How the prediction family of Engine (engine_predict.hip) and the analysis family (engine_analysis.hip: hessian, predict_mixture,
-// cross_validate, sample_posterior) cut their work to a byte budget, the index tables of their passes, and where the mean-function terms of a prediction are
+// cross_validate, sample_posterior, alc, predict_cov) cut their work to a byte budget, the index tables of their passes, and where the mean-function terms of a prediction are
 // staged.  Plain host arithmetic with no HIP in it, so that a host compiler takes it and tests/c/predict_plan_check.cpp, mixture_plan_check.cpp,
-// cv_plan_check.cpp and sample_plan_check.cpp can check it without a device.  The caps that need the device (MOGP_KS_BUDGET_GB, free memory) are passed in.
+// cv_plan_check.cpp, sample_plan_check.cpp and alc_plan_check.cpp can check it without a device.  The caps that need the device (MOGP_KS_BUDGET_GB, free memory) are passed in.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -179,6 +179,51 @@ inline double sample_ladder_delta(int t, double mean_diag) {
   double d = mean_diag * 1e-6;
   for (int i = 0; i < t; ++i) d *= 10.0;
   return d;
+}
+
+// Engine::alc: how many emulators one group takes and how many reference points one chunk.  The emulators go in groups [e0, e0 + slots) in
+// caller order and, inside a group, the m_r reference points in chunks [c0, c0 + points), points a multiple of 128: a chunk is a run of whole
+// 128-point tiles of the reference set, and the partial sums of the criterion are kept per GLOBAL tile, so neither number changes a bit of
+// the result.  Bytes of one slot (alc_slot_bytes), MP_c = roundup(m_c, 128), tiles_r = ceil(m_r / 128):
+//   V_c (NP x MP_c), V_r of one chunk (NP x points), the K* scratch both are built from (LD x max(MP_c, points)), the partials (tiles_r x MP_c)
+// and a group never takes more than HALF of the free device memory (slots_in_half_of).  points: max_points rounded down to a multiple of
+// 128 where given (at least 128), else the whole reference set; cut to what one slot holds where that does not fit.  slots: what the budget
+// holds at that chunk, at most E, 65535 (a slot is one grid row of the variance launches) and max_slots where given.  Throws when one
+// emulator with one 128-point chunk does not fit, and for negative max_slots / max_points.
+struct AlcPlan {
+  long slots, points;
+};
+inline long alc_mp(long m) { return (m + 127) / 128 * 128; }
+inline double alc_slot_bytes(int NP, int LD, long MPc, long points, long tiles_r) {
+  return 8.0 * ((double)NP * MPc + (double)NP * points + (double)LD * std::max(MPc, points) + (double)tiles_r * MPc);
+}
+inline AlcPlan alc_plan(long E, long m_c, long m_r, int LD, int NP, double free_bytes, int max_slots, int max_points) {
+  if (max_slots < 0 || max_points < 0) throw std::runtime_error("alc_criterion: max_slots and max_points must not be negative");
+  const long MPc = alc_mp(std::max<long>(1, m_c)), all = alc_mp(std::max<long>(1, m_r)), tiles_r = all / 128;
+  const double budget = 0.5 * free_bytes;
+  if (alc_slot_bytes(NP, LD, MPc, 128, tiles_r) > budget)
+    throw std::runtime_error("alc_criterion: one emulator at " + std::to_string(m_c) + " candidates and " + std::to_string(m_r) +
+                             " reference points needs " + std::to_string((long long)alc_slot_bytes(NP, LD, MPc, 128, tiles_r)) +
+                             " bytes of device scratch, more than half of the free device memory; use fewer points per call");
+  long points = max_points > 0 ? std::max<long>(128, (long)max_points / 128 * 128) : all;
+  points = std::min(points, all);
+  if (alc_slot_bytes(NP, LD, MPc, points, tiles_r) > budget) {
+    // the largest multiple of 128 one slot holds: first with the K* scratch sized by the chunk, then -- below MP_c -- by the candidates
+    const double fixed = (double)NP * MPc + (double)tiles_r * MPc, doubles = budget / 8.0;
+    long fit = (long)std::floor((doubles - fixed) / ((double)NP + LD));
+    if (fit < MPc) fit = (long)std::floor((doubles - fixed - (double)LD * MPc) / (double)NP);
+    points = std::max<long>(128, std::min(points, fit / 128 * 128));
+  }
+  long slots = slots_in_half_of(free_bytes, alc_slot_bytes(NP, LD, MPc, points, tiles_r));
+  slots = std::min(slots, std::max<long>(1, E));
+  slots = std::min<long>(slots, 65535);
+  if (max_slots > 0) slots = std::min<long>(slots, max_slots);
+  return {std::max<long>(1, slots), points};
+}
+// Engine::predict_cov: V_1, V_2, the output and the K* scratch of one emulator against the 64 GB rule of predict_full_cov
+inline double predict_cov_rule_bytes(long m1, long m2, int LD, int NP) {
+  const double MP1 = (double)alc_mp(m1), MP2 = (double)alc_mp(m2);
+  return 8.0 * ((double)NP * (MP1 + MP2) + (double)m1 * (double)m2 + (double)LD * std::max(MP1, MP2));
 }
 
 // Stage 2 of Engine::predict_mixture: the normalised weights of the S samples of one emulator, from their negative log-posteriors F and

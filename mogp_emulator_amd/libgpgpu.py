@@ -158,6 +158,32 @@ def _sample_call(fn, handle, lead, x, n_draws, seed, stream, z, include_nugget, 
     return samples, mean, zout, ju, ok.astype(bool)
 
 
+def _cov_call(fn, handle, lead, x1, x2, max_slots):
+    """shared by DenseGP_GPU.predict_cov and MultiOutputGP_GPU.predict_cov: `lead` = () or (n_emulators,) -> cov lead + (m1, m2)"""
+    m1, m2 = x1.shape[0], (x1.shape[0] if x2 is None else x2.shape[0])
+    cov = np.zeros(lead + (m1, m2))
+    check(fn(handle, dptr(x1), m1, dptr(x2), m2, x1.shape[1], int(max_slots), dptr(cov)))
+    return cov
+
+
+def _alc_call(fn, handle, lead, xc, xr, weights, noise, max_slots, max_points):
+    """shared by DenseGP_GPU.alc and MultiOutputGP_GPU.alc: weights (m_r), noise None or lead-or-(1,) -> (reduction lead + (m_c,), cand_var
+    lead + (m_c,), ref_var lead + (m_r,), degenerate lead + (m_c,) bool)"""
+    mc, mr = xc.shape[0], xr.shape[0]
+    w = _f64(weights, 1, "weights")
+    if w.shape[0] != mr:
+        raise ValueError("alc_criterion: weights must have one entry per reference point")
+    if noise is not None:
+        noise = _f64(noise, 1, "noise")
+        if noise.shape != (lead or (1,)):
+            raise ValueError("alc_criterion: noise must have one entry per emulator")
+    red, cv, rv = np.zeros(lead + (mc,)), np.zeros(lead + (mc,)), np.zeros(lead + (mr,))
+    deg = np.zeros(lead + (mc,), dtype=np.int32)
+    check(fn(handle, dptr(xc), mc, dptr(xr), mr, xc.shape[1], dptr(w), dptr(noise), int(max_slots), int(max_points), dptr(red), dptr(cv),
+             dptr(rv), iptr(deg)))
+    return red, cv, rv, deg.astype(bool)
+
+
 def _sobol_call(fn, handle, D, n_out, A, B, unc, include_nugget):
     """shared by DenseGP_GPU.sobol and MultiOutputGP_GPU.sobol: (S, ST, mean, variance, emulator_variance or None), one row per output"""
     a, b = _f64(A, 2, "A"), _f64(B, 2, "B")
@@ -827,6 +853,17 @@ class DenseGP_GPU(object):
         return _sample_call(_lib.mogp_densegp_sample_posterior, self._h, (), self._testing(testing), n_draws, seed, stream, z,
                             include_nugget, jitter, max_slots, max_draws, return_z)
 
+    def predict_cov(self, x1, x2=None, max_slots=0):
+        """Posterior covariance (m1, m2) of the latent function between the points x1 (m1, D) and x2 (m2, D; None: x1), nugget not
+        included.  See mogp_densegp_predict_cov (include/mogp_hip.h)."""
+        return _cov_call(_lib.mogp_densegp_predict_cov, self._h, (), self._testing(x1), None if x2 is None else self._testing(x2), max_slots)
+
+    def alc(self, candidates, reference, weights, noise=None, max_slots=0, max_points=0):
+        """The ALC criterion of the candidates (m_c, D) over the reference points (m_r, D) with weights (m_r): (reduction (m_c,), cand_var
+        (m_c,), ref_var (m_r,), degenerate (m_c,) bool); noise: a float or None (the nugget of the fit).  See mogp_densegp_alc."""
+        return _alc_call(_lib.mogp_densegp_alc, self._h, (), self._testing(candidates), self._testing(reference), weights,
+                         None if noise is None else np.array([float(noise)]), max_slots, max_points)
+
     # -- predict ------------------------------------------------------------------------------
     def _testing(self, testing):
         x = _f64(testing)
@@ -1171,6 +1208,18 @@ class MultiOutputGP_GPU(object):
         shared or (n_emulators, S, m).  Rows of emulators that are not fit are NaN with ok False."""
         return _sample_call(_lib.mogp_mogp_sample_posterior, self._h, (self.n_emulators(),), self._testing(testing), n_draws, seed, stream,
                             z, include_nugget, jitter, max_slots, max_draws, return_z)
+
+    def predict_cov(self, x1, x2=None, max_slots=0):
+        """DenseGP_GPU.predict_cov for every emulator: (n_emulators, m1, m2); rows of emulators that are not fit are NaN."""
+        return _cov_call(_lib.mogp_mogp_predict_cov, self._h, (self.n_emulators(),), self._testing(x1),
+                         None if x2 is None else self._testing(x2), max_slots)
+
+    def alc(self, candidates, reference, weights, noise=None, max_slots=0, max_points=0):
+        """DenseGP_GPU.alc for every emulator, max_slots emulators per group and max_points reference points per chunk: (reduction, cand_var
+        (n_emulators, m_c), ref_var (n_emulators, m_r), degenerate (n_emulators, m_c) bool); noise (n_emulators,) or None.  Rows of
+        emulators that are not fit are NaN."""
+        return _alc_call(_lib.mogp_mogp_alc, self._h, (self.n_emulators(),), self._testing(candidates), self._testing(reference), weights,
+                         noise, max_slots, max_points)
 
     def predict_variance_batch_dev(self, d_testing, m, d_means, d_vars):
         """Device-pointer variant: inputs already resident in HBM, results stay in HBM."""
