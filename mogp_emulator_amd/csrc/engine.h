@@ -38,6 +38,10 @@ struct DeviceGuard {
 
 struct CvBuffers;      // engine_analysis.hip
 struct CvFolds;        // predict_plan.h
+class ScratchFactor;   // engine_internal.h
+// what build_cov runs instead of the covariance build when a factorisation is given one (ScratchFactor::factor): it writes every slot's
+// matrix into the factor buffer, with the layout of the covariance build (launch.h)
+using CovFill = std::function<void(const BatchView&)>;
 
 class Engine {
  public:
@@ -128,7 +132,7 @@ class Engine {
   // used, 0) --, in training order.  maha / log_score / ok (ids, k): e_F^T S e_F, the log predictive density of the fold given the
   // rest, and whether S factorised (0: NaN for the fold's points and scalars; no jitter, no exception).  Every fold a single point:
   // one pass over L^-1.  Otherwise K^-1 is formed and the (emulator, fold) pairs go, emulator-major and fold-ascending, `slots` per
-  // pass (cv_plan of predict_plan.h; max_slots = 0: the library's choice) through a sub-engine of the call.  THIS engine is only
+  // pass (cv_plan of predict_plan.h; max_slots = 0: the library's choice) through a ScratchFactor of the call.  THIS engine is only
   // read, apart from gaining alpha / L^-1 / K^-1: theta, factor and logpost stay.  No atomics: the same call returns the same bits.
   // Throws for nugget="pivot", the analytic mean, an emulator that is not fit, bad k, a label outside [0, k) and an empty fold.
   void cross_validate(const std::vector<int>& ids, const int* labels, int k, bool include_nugget, int max_slots, double* mean, double* var,
@@ -146,7 +150,7 @@ class Engine {
   // ok[e] = 0 and its samples are NaN (no exception).  The factor's diagonal is finished from its rows with the correctly rounded square root.  z: z_in (S, m) shared by all emulators or, with z_per_emulator, (ids, S, m); null:
   // generated on the device, value (e, s, j) from (seed, streams[e], s, j) alone (philox_dev.h).  z_out (ids, S, m) or null: the normals used.
   // The emulators go `slots` per pass and the draws `draws` per chunk (sample_plan; max_slots / max_draws = 0: the library's choice)
-  // through a scratch engine of m rows; every buffer is scratch of the call.  THIS engine is only read, apart from gaining alpha / L^-1.  One writer
+  // through a ScratchFactor of m rows; every buffer is scratch of the call.  THIS engine is only read, apart from gaining alpha / L^-1.  One writer
   // per output, no atomics: the same call returns the same bits, and max_draws changes none.  Throws for nugget="pivot", the analytic mean,
   // an emulator that is not fit, S < 1, jitter < 0, negative max_*, non-finite Xs / z_in and scratch beyond sample_plan's limits.
   void sample_posterior(const std::vector<int>& ids, const unsigned* streams, const double* Xs, int m, int S, unsigned long long seed,
@@ -198,15 +202,6 @@ class Engine {
   // new training inputs of the same shape (a cached replica engine taken by another fit): X, the analytic mean's design
   // matrix and every slot's pivot-ordered copy of the inputs
   void reset_inputs(const std::vector<double>& X);
-  // gKDR (kernels_gkdr.hip): every slot's matrix is written into the factor buffer by `fill` -- the launch of the covariance build,
-  // with the same layout (launch.h) -- and factored with the schedule of the regime; info (indexed by slot) as factorize.  The
-  // slots that factor form L^-1 (linv_buffer(), lower triangle).  Needs nugget type "fixed" on every slot.
-  // only (sample_posterior): the slots to factor instead of all -- the others keep their factor and state, info is meaningful for the listed
-  // slots alone; want_linv = false: L^-1 is not formed.
-  void factor_prebuilt(const std::function<void(const BatchView&)>& fill, std::vector<int>& info, const std::vector<int>* only = nullptr,
-                       bool want_linv = true);
-  const double* linv_buffer() const { return dLinv; }
-  double* factor_buffer() const { return dA; }
 
   // (streams and events are declared in front of every buffer: members go in reverse order, so the streams are destroyed last)
   Stream stream;                     // main stream: covariance build, trailing updates, everything else
@@ -217,21 +212,24 @@ class Engine {
   Event evGroup[15];
 
  private:
+  friend class ScratchFactor;      // factors matrices of its caller's with an engine of its own (engine_internal.h)
   void upload_params(const std::vector<int>& ids);
   void upload_idx(const std::vector<int>& ids);
   // defer_info: leave the status words on the device (the caller reads them together with its own results: one
   // synchronisation per evaluation instead of two)
   void factorize(const std::vector<int>& ids, std::vector<int>& info, bool defer_info = false);
-  void factorize_blocked(const std::vector<int>& ids, std::vector<int>& info, bool defer_info);
+  // fill (everywhere below): what fills the factor buffer instead of the covariance build (build_cov); null: the covariance build
+  void factorize_blocked(const std::vector<int>& ids, std::vector<int>& info, bool defer_info, const CovFill* fill = nullptr);
   // the schedules factorize_blocked chooses from (chol_schedule.h); every one leaves the status words in dInfo
-  void chol_one_launch(const std::vector<int>& ids, const BatchView& v, std::vector<int>& info, bool defer_info);
-  void chol_lookahead(const BatchView& v);
-  void chol_two_groups(const BatchView& v);
-  void chol_right_looking(const BatchView& v);
-  void begin_multi_launch(const BatchView& v);       // what the three multi-launch schedules start with: status words cleared, K built
+  void chol_one_launch(const std::vector<int>& ids, const BatchView& v, std::vector<int>& info, bool defer_info, const CovFill* fill = nullptr);
+  void chol_lookahead(const BatchView& v, const CovFill* fill = nullptr);
+  void chol_two_groups(const BatchView& v, const CovFill* fill = nullptr);
+  void chol_right_looking(const BatchView& v, const CovFill* fill = nullptr);
+  // what the three multi-launch schedules start with: status words cleared, K built
+  void begin_multi_launch(const BatchView& v, const CovFill* fill = nullptr);
   void grow_step_events(int K);                      // evPanel / evUpd hold at least K + 1 events each
   // the one-launch kernel aborted: count it and factorise again with the multi-launch schedule of the regime
-  void refactor_after_abort(const std::vector<int>& ids, std::vector<int>& info, bool defer_info);
+  void refactor_after_abort(const std::vector<int>& ids, std::vector<int>& info, bool defer_info, const CovFill* fill = nullptr);
   void read_info(std::vector<int>& info, bool defer_info);
   // the steps of eval.  solve_and_collect: behind a factorisation of `list`, log-determinants and Gram matrices -- with want_grad, the
   // analytic mean or a pivoted emulator in the list also alpha (and L^-1 with want_grad) -- in ONE read-back; info_out (may be null)
@@ -262,11 +260,13 @@ class Engine {
   void ensure_linv(const std::vector<int>& ids);
   void ensure_kinv(const std::vector<int>& ids, bool for_gradient = false);
   BatchView view(int nb) const;
-  void build_cov(const BatchView& v, const ZeroRanges& zero = ZeroRanges());
-  const std::function<void(const BatchView&)>* prebuilt = nullptr;   // factor_prebuilt: build_cov runs this instead
+  void build_cov(const BatchView& v, const ZeroRanges& zero = ZeroRanges(), const CovFill* fill = nullptr);
   std::vector<char> z_armed;     // per emulator: its solution row holds the sentinel pattern of the one-launch back substitution
   void set_theta(int i, const double* theta);
   void require_factored(const std::vector<int>& ids) const;      // throws unless every emulator of ids holds a factor
+  // what cross_validate, sample_posterior, predict_cov and alc refuse alike, as `who`: an emulator without a factor, the analytic mean
+  // (`analytic_reason`: why the caller cannot cover it) and nugget="pivot"
+  void require_plain_fit(const char* who, const std::vector<int>& ids, const char* analytic_reason) const;
   // the steps of predict (engine_predict.hip).  PredictPlace: where means / variances / derivatives / dot products live on the device
   struct PredictPlace {
     double *fm, *fv, *fd, *dots;
@@ -285,6 +285,8 @@ class Engine {
   void ensure_predict_scratch(int nb, int MC);
   // free device memory in bytes; false: the runtime could not tell (the callers then keep their own fallback)
   bool free_device_bytes(double& free_bytes) const;
+  // the same with the fallback of sample_posterior, predict_cov and alc: twice the prediction budget when the runtime cannot tell
+  double free_bytes_or_twice_budget() const;
   // the steps of hessian (engine_analysis.hip).  hessian_move_to: the emulators to their thetas -- fine[k] = 1 where ids[k] holds a factor
   // there, before[k] = the theta it has to be put back at (hessian_put_back).  hessian_group_sums: the device sums of one group of emulators
   // into their host copies (six launches behind the gradient's, six downloads, one synchronisation)
@@ -294,7 +296,7 @@ class Engine {
                        std::vector<std::vector<double>>& before);
   void hessian_group_sums(const std::vector<int>& grp, HessianScratch& d, HessianSums& h);
   void hessian_put_back(const std::vector<int>& ids, const std::vector<std::vector<double>>& before);
-  // the two paths of cross_validate (engine_analysis.hip): every fold a single point / the folds of cf through a sub-engine
+  // the two paths of cross_validate (engine_analysis.hip): every fold a single point / the folds of cf through a ScratchFactor
   void cv_leave_one_out(const std::vector<int>& ids, const int* labels, bool include_nugget, CvBuffers& b, double* mean_out, double* var_out,
                         double* maha_out, double* log_score_out, int* ok_out);
   void cv_kfold(const std::vector<int>& ids, const CvFolds& cf, int k, bool include_nugget, int max_slots, CvBuffers& b, double* mean_out,
@@ -308,8 +310,8 @@ class Engine {
   // the steps of sample_posterior (engine_analysis.hip)
   struct SamplePass;
   void sample_build(const std::vector<int>& grp, const double* Xs, const double* dXq, int m, SamplePass& p, double* mean_out);
-  void sample_factor(Engine& sub, const std::vector<int>& grp, bool include_nugget, double jitter, SamplePass& p, double* jitter_used, int* ok);
-  void sample_draws(Engine& sub, long e0, long cnt, int m, int S, int Sc, unsigned long long seed, const double* z_in, bool z_per_emulator,
+  void sample_factor(ScratchFactor& sub, const std::vector<int>& grp, bool include_nugget, double jitter, SamplePass& p, double* jitter_used, int* ok);
+  void sample_draws(ScratchFactor& sub, long e0, long cnt, int m, int S, int Sc, unsigned long long seed, const double* z_in, bool z_per_emulator,
                     SamplePass& p, double* samples, double* z_out);
 
   // what alc and predict_cov share (engine_analysis.hip): the refusals; and, for the nb emulators in dIdx and the m points at dXq, K*

@@ -216,16 +216,21 @@ bool Engine::free_device_bytes(double& free_bytes) const {
   return true;
 }
 
+double Engine::free_bytes_or_twice_budget() const {
+  double free_b = 0.;
+  return free_device_bytes(free_b) ? free_b : 2.0 * ks_budget_bytes();
+}
+
 // K build of the slots in dIdx.  With one right-hand side it also presets the solution rows to the all-ones pattern the one-launch
 // back substitution polls for (backsolve_chain_kernel<SENT>); `z_armed` records that, so that a chain launched on a row that has
 // not been preset since its last solve arms it itself instead of reading stale values as "already there".
 // A row stays armed for as long as its solve is deferred (ensure_alpha), over any number of calls: nothing but a back substitution of
 // that emulator writes the row, and a reader that forgot to ask finds the pattern -- NaN -- and not the alpha of an older factor.
-void Engine::build_cov(const BatchView& v, const ZeroRanges& zero) {
-  if (prebuilt) {
+void Engine::build_cov(const BatchView& v, const ZeroRanges& zero, const CovFill* fill) {
+  if (fill) {
     for (int r = 0; r < 2; ++r)
       if (zero.p[r] && zero.n[r]) HIPCK(hipMemsetAsync(zero.p[r], 0, zero.n[r] * sizeof(unsigned), stream));
-    (*prebuilt)(v);
+    (*fill)(v);
     if (z_armed.size() != (size_t)B) z_armed.assign(B, 0);
     for (int i : idx_on_device) z_armed[i] = 0;
     return;

@@ -189,15 +189,13 @@ void check_mixture_args(const Engine& eng, const std::vector<int>& ids, const do
     if (P > ld) throw std::runtime_error("Shape of new GPParams object does not match existing one");
     for (int s = 0; s < S; ++s) {
       const double* th = thetas + ((size_t)e * S + s) * ld;
-      for (int k = 0; k < P; ++k)
-        if (!std::isfinite(th[k])) throw std::runtime_error("predict_mixture: the hyperparameter samples must be finite");
+      require_finite(th, (size_t)P, "predict_mixture: the hyperparameter samples must be finite");
       const double x = weights ? weights[e * S + s] : log_q[e * S + s];
       if (!std::isfinite(x)) throw std::runtime_error(weights ? "predict_mixture: the weights must be finite" : "predict_mixture: log_q must be finite");
       if (weights && x < 0.) throw std::runtime_error("predict_mixture: the weights must not be negative");
     }
   }
-  for (size_t k = 0; k < (size_t)m * eng.D; ++k)
-    if (!std::isfinite(Xs[k])) throw std::runtime_error("predict_mixture: the query points must be finite");
+  require_finite(Xs, (size_t)m * eng.D, "predict_mixture: the query points must be finite");
 }
 
 }  // namespace
@@ -320,13 +318,21 @@ void Engine::predict_mixture(const std::vector<int>& ids, const double* thetas, 
   }
 }
 
+void Engine::require_plain_fit(const char* who, const std::vector<int>& ids, const char* analytic_reason) const {
+  const std::string p = std::string(who) + ": not available with ";
+  require_factored(ids);
+  if (analytic) throw std::runtime_error(p + "analytic_mean=True (" + analytic_reason + ")");
+  for (int i : ids)
+    if (gp[i].nug_type == NUG_PIVOT || gp[i].permuted) throw std::runtime_error(p + "nugget=\"pivot\" (a pivoted, possibly rank-deficient factor)");
+}
+
 // ---------------------------------------------------------------------------------------------
 // Cross-validation at the fitted hyperparameters (engine.h has the contract, kernels_cv.hip the formulas and the kernels).
 //   every fold a single point: L^-1 and ONE launch of cv_loo_kernel (cv_leave_one_out);
-//   otherwise K^-1, then the (emulator, fold) pairs in passes of `slots` (cv_plan) through a sub-engine of nsub = the largest fold size
-//   rows, built as gkdr_R builds its own: per pass factor_prebuilt with cv_gather_kernel as the fill, the log-determinant and L^-T y
-//   launchers on the slots that factorised, cv_finish_kernel; ONE download at the end (cv_kfold).
-// The sub-engine and every buffer here are scratch of the call.
+//   otherwise K^-1, then the (emulator, fold) pairs in passes of `slots` (cv_plan) through a ScratchFactor of nsub = the largest fold size
+//   rows: per pass its factor with cv_gather_kernel as the fill, the log-determinant and L^-T y launchers on the slots that factorised
+//   (logdet_and_solve), cv_finish_kernel; ONE download at the end (cv_kfold).
+// The ScratchFactor and every buffer here are scratch of the call.
 // ---------------------------------------------------------------------------------------------
 
 // what both paths share: the observations and nuggets of the rows of E emulators and the result buffers (n points, k folds)
@@ -373,11 +379,11 @@ void Engine::cv_leave_one_out(const std::vector<int>& ids, const int* labels, bo
   b.download(stream, mean_out, var_out, maha_out, log_score_out, ok_out);
 }
 
-// k folds: K^-1, then the (emulator, fold) pairs in passes through a sub-engine of the call
+// k folds: K^-1, then the (emulator, fold) pairs in passes through a ScratchFactor of the call
 void Engine::cv_kfold(const std::vector<int>& ids, const CvFolds& cf, int k, bool include_nugget, int max_slots, CvBuffers& b, double* mean_out,
                       double* var_out, double* maha_out, double* log_score_out, int* ok_out) {
   const long E = (long)ids.size();
-  const int nsub = cf.nsub, NPsub = roundup(nsub + 1, TILE);
+  const int nsub = cf.nsub, NPsub = (int)scratch_np(nsub);
   const long pairs = E * k;
   long device_slots = pairs;
   double free_b = 0.;
@@ -386,18 +392,16 @@ void Engine::cv_kfold(const std::vector<int>& ids, const CvFolds& cf, int k, boo
 
   ensure_alpha(ids);
   ensure_kinv(ids, false);
-  HIPCK(hipStreamSynchronize(stream));        // the sub-engine reads K^-1 and alpha on its own stream
+  HIPCK(hipStreamSynchronize(stream));        // the ScratchFactor reads K^-1 and alpha on its own stream
   const BatchView src = view(0);
-  const std::vector<double> zeros((size_t)slots * nsub, 0.0);
-  Engine sub(zeros.data(), nsub, 1, zeros.data(), (int)slots, 0, MeanFunc(), 0, NUG_FIXED, 0.0);
-  if (sub.NP != NPsub) throw std::runtime_error("cross_validate: unexpected layout of the sub-engine");
-  hipStream_t st = sub.stream;
+  ScratchFactor sub(nsub, slots);
+  hipStream_t st = sub.stream();
   DevBuf<int> dFolds(cf.folds.size()), dTab(4 * (size_t)slots);
   SyncOnUnwind drained{st};
   b.stage(st);
   HIPCK(hipMemcpyAsync(dFolds, cf.folds.data(), cf.folds.size() * sizeof(int), hipMemcpyHostToDevice, st));
   std::vector<int> tab(4 * (size_t)slots), info, okslots;
-  const std::function<void(const BatchView&)> fill = [&](const BatchView& sv) {
+  const CovFill fill = [&](const BatchView& sv) {
     if (sv.nb != (int)slots) throw std::runtime_error("cross_validate: the factorisation must cover every slot");
     launch_cv_gather(src, dFolds, dTab, (int)slots, sv.A, nsub, NPsub, st);
   };
@@ -405,18 +409,13 @@ void Engine::cv_kfold(const std::vector<int>& ids, const CvFolds& cf, int k, boo
     const long cnt = std::min(slots, pairs - p0);
     cv_pass_table(p0, cnt, slots, k, ids.data(), cf.size.data(), tab.data());
     HIPCK(hipMemcpyAsync(dTab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    sub.factor_prebuilt(fill, info);
+    sub.factor(fill, info);
     okslots.clear();
     for (long s = 0; s < cnt; ++s)
       if (info[s] == 0) okslots.push_back((int)s);
-    if (!okslots.empty()) {
-      sub.upload_idx(okslots);
-      const BatchView sv = sub.view((int)okslots.size());
-      launch_logdet(sv, sub.dInfo, sub.dRes, st);
-      launch_alpha_from_linv(sv, st);
-    }
-    launch_cv_finish(dFolds, dTab, (int)cnt, sub.dLinv, sub.dAlpha, sub.dRes, sub.dInfo, nsub, NPsub, b.dTraw, b.dEta, include_nugget, n, k,
-                     b.dMeanO, b.dVarO, b.dMaha, b.dLs, b.dOk, st);
+    sub.logdet_and_solve(okslots);
+    launch_cv_finish(dFolds, dTab, (int)cnt, sub.linv(), sub.solution(), sub.logdet_words(), sub.status(), nsub, NPsub, b.dTraw, b.dEta,
+                     include_nugget, n, k, b.dMeanO, b.dVarO, b.dMaha, b.dLs, b.dOk, st);
     HIPCK(hipStreamSynchronize(st));          // `tab` is rewritten by the next pass
   }
   b.download(st, mean_out, var_out, maha_out, log_score_out, ok_out);
@@ -426,11 +425,7 @@ void Engine::cross_validate(const std::vector<int>& ids, const int* labels, int 
                             double* var_out, double* maha_out, double* log_score_out, int* ok_out) {
   const long E = (long)ids.size();
   if (E == 0) return;
-  require_factored(ids);
-  if (analytic) throw std::runtime_error("cross_validate: not available with analytic_mean=True (a held-out fold changes the mean coefficients)");
-  for (int i : ids)
-    if (gp[i].nug_type == NUG_PIVOT || gp[i].permuted)
-      throw std::runtime_error("cross_validate: not available with nugget=\"pivot\" (a pivoted, possibly rank-deficient factor)");
+  require_plain_fit("cross_validate", ids, "a held-out fold changes the mean coefficients");
   if (!labels || !mean_out || !var_out || !maha_out || !log_score_out || !ok_out) throw std::runtime_error("cross_validate: null buffer");
   if (k < 2 || k > n) throw std::runtime_error("cross_validate: the number of folds must be between 2 and the number of training points (k = " + std::to_string(k) + ", n = " + std::to_string(n) + ")");
   if (max_slots < 0) throw std::runtime_error("cross_validate: max_slots must not be negative");
@@ -451,11 +446,11 @@ void Engine::cross_validate(const std::vector<int>& ids, const int* labels, int 
 // `slots` emulators:
 //   1. sample_build: Sigma* and mu* with predict_full_cov's own launches; Sigma* stays on the device, mu* gets its mean-function terms on
 //      the host and goes up again;
-//   2. sample_factor: Sigma~ gathered into the scratch engine (sample_gather_kernel as the fill of factor_prebuilt, L^-1 not formed), then
+//   2. sample_factor: Sigma~ gathered into the ScratchFactor (sample_gather_kernel as the fill of its factor, L^-1 not formed), then
 //      the jitter ladder on the host over the slots that failed -- they alone are gathered again, from the resident Sigma* --, then
 //      sample_polish_kernel: the factor's diagonal from its finished rows with the correctly rounded square root;
 //   3. sample_draws: per chunk of draws z uploaded or generated, z_out and Y = mu + L z downloaded; NaN rows where Sigma~ never factorised.
-// The scratch engine and every buffer are scratch of the call.
+// The ScratchFactor and every buffer are scratch of the call.
 // ---------------------------------------------------------------------------------------------
 
 // the buffers of a pass, sized for `slots` emulators and `draws` draws per chunk; the guards come last, so that both streams are drained
@@ -491,15 +486,15 @@ void Engine::sample_build(const std::vector<int>& grp, const double* Xs, const d
   }
   fullcov_host_means(grp, Xs, m, dots.data(), mean_out, nullptr);
   HIPCK(hipMemcpyAsync(p.dMu, mean_out, (size_t)nb * m * sizeof(double), hipMemcpyHostToDevice, stream));
-  HIPCK(hipStreamSynchronize(stream));        // the scratch engine reads Sigma* and mu* on its own stream
+  HIPCK(hipStreamSynchronize(stream));        // the ScratchFactor reads Sigma* and mu* on its own stream
 }
 
-// 2. Sigma~ = L L^T in the slots 0 .. grp.size() - 1 of the scratch engine, the ladder over those that fail
-void Engine::sample_factor(Engine& sub, const std::vector<int>& grp, bool include_nugget, double jitter, SamplePass& p, double* jitter_used,
+// 2. Sigma~ = L L^T in the slots 0 .. grp.size() - 1 of the ScratchFactor, the ladder over those that fail
+void Engine::sample_factor(ScratchFactor& sub, const std::vector<int>& grp, bool include_nugget, double jitter, SamplePass& p, double* jitter_used,
                            int* ok) {
   const long cnt = (long)grp.size();
   const int m = p.m;
-  hipStream_t st = sub.stream;
+  hipStream_t st = sub.stream();
   std::vector<int> src((size_t)p.slots, -1), list((size_t)cnt), info;
   std::vector<double> shift((size_t)p.slots, 0.), nug((size_t)cnt), diag((size_t)m);
   for (long k = 0; k < cnt; ++k) {
@@ -509,7 +504,7 @@ void Engine::sample_factor(Engine& sub, const std::vector<int>& grp, bool includ
     jitter_used[k] = jitter;
   }
   HIPCK(hipMemcpyAsync(p.dSrc, src.data(), src.size() * sizeof(int), hipMemcpyHostToDevice, st));
-  const std::function<void(const BatchView&)> fill = [&](const BatchView& sv) {
+  const CovFill fill = [&](const BatchView& sv) {
     HIPCK(hipMemcpyAsync(p.dShift, shift.data(), shift.size() * sizeof(double), hipMemcpyHostToDevice, st));
     launch_sample_gather(sv, p.dC, p.dSrc, p.dShift, m, st);
   };
@@ -519,7 +514,7 @@ void Engine::sample_factor(Engine& sub, const std::vector<int>& grp, bool includ
       if (info[k] != 0) f.push_back(k);
     return f;
   };
-  sub.factor_prebuilt(fill, info, &list, false);
+  sub.factor(fill, info, &list, false);
   std::vector<int> failed = failed_of(list);
   std::vector<double> mean_diag((size_t)cnt, 0.);
   for (int t = 0; t < SAMPLE_LADDER_RUNGS && !failed.empty(); ++t) {
@@ -535,7 +530,7 @@ void Engine::sample_factor(Engine& sub, const std::vector<int>& grp, bool includ
       jitter_used[k] = jitter + delta;
       shift[k] = nug[k] + jitter_used[k];
     }
-    sub.factor_prebuilt(fill, info, &failed, false);
+    sub.factor(fill, info, &failed, false);
     failed = failed_of(failed);
   }
   // (src and shift on the device are those of every slot's last gather; a slot that never factorised is left alone by the kernel's test)
@@ -546,9 +541,9 @@ void Engine::sample_factor(Engine& sub, const std::vector<int>& grp, bool includ
 }
 
 // 3. the draws of the emulators [e0, e0 + cnt) of the call (slots 0 .. cnt - 1), chunk by chunk
-void Engine::sample_draws(Engine& sub, long e0, long cnt, int m, int S, int Sc, unsigned long long seed, const double* z_in, bool z_per_emulator,
+void Engine::sample_draws(ScratchFactor& sub, long e0, long cnt, int m, int S, int Sc, unsigned long long seed, const double* z_in, bool z_per_emulator,
                           SamplePass& p, double* samples, double* z_out) {
-  hipStream_t st = sub.stream;
+  hipStream_t st = sub.stream();
   const size_t row = (size_t)m * sizeof(double), zpitch = (size_t)p.MP * sizeof(double), mm = (size_t)m;
   for (int s0 = 0; s0 < S; s0 += Sc) {
     const int sc = std::min(Sc, S - s0);
@@ -579,41 +574,29 @@ void Engine::sample_posterior(const std::vector<int>& ids, const unsigned* strea
                               double* samples, double* mean_out, double* z_out, double* jitter_used, int* ok) {
   const long E = (long)ids.size();
   if (E == 0) return;
-  require_factored(ids);
-  if (analytic) throw std::runtime_error("sample_posterior: not available with analytic_mean=True (its covariance term is finished on the host)");
-  for (int i : ids)
-    if (gp[i].nug_type == NUG_PIVOT || gp[i].permuted)
-      throw std::runtime_error("sample_posterior: not available with nugget=\"pivot\" (a pivoted, possibly rank-deficient factor)");
+  require_plain_fit("sample_posterior", ids, "its covariance term is finished on the host");
   if (!streams || !Xs || !samples || !mean_out || !jitter_used || !ok) throw std::runtime_error("sample_posterior: null buffer");
   if (m < 1) throw std::runtime_error("sample_posterior: at least one query point is needed");
   if (S < 1) throw std::runtime_error("sample_posterior: at least one draw is needed (n_draws = " + std::to_string(S) + ")");
   if (!(jitter >= 0.) || !std::isfinite(jitter)) throw std::runtime_error("sample_posterior: jitter must be a finite number that is not negative");
   if (max_slots < 0 || max_draws < 0) throw std::runtime_error("sample_posterior: max_slots and max_draws must not be negative");
-  for (size_t k = 0; k < (size_t)m * D; ++k)
-    if (!std::isfinite(Xs[k])) throw std::runtime_error("sample_posterior: the query points must be finite");
-  if (z_in)
-    for (size_t k = 0, nz = (size_t)(z_per_emulator ? E : 1) * S * m; k < nz; ++k)
-      if (!std::isfinite(z_in[k])) throw std::runtime_error("sample_posterior: z must be finite");
+  require_finite(Xs, (size_t)m * D, "sample_posterior: the query points must be finite");
+  if (z_in) require_finite(z_in, (size_t)(z_per_emulator ? E : 1) * S * m, "sample_posterior: z must be finite");
 
-  double free_b = 0.;
-  if (!free_device_bytes(free_b)) free_b = 2.0 * ks_budget_bytes();
-  const SamplePlan plan = sample_plan(E, m, S, LD, NP, R, free_b, max_slots, max_draws);
+  const SamplePlan plan = sample_plan(E, m, S, LD, NP, R, free_bytes_or_twice_budget(), max_slots, max_draws);
   const long slots = plan.slots;
   const int Sc = (int)plan.draws;
 
-  // the scratch engine: `slots` slots of m rows, one input column, nothing of it but the batched Cholesky is used
-  const std::vector<double> zeros((size_t)slots * m, 0.0);
-  Engine sub(zeros.data(), m, 1, zeros.data(), (int)slots, 0, MeanFunc(), 0, NUG_FIXED, 0.0);
-  if (sub.NP != (int)sample_nps(m)) throw std::runtime_error("sample_posterior: unexpected layout of the scratch engine");
+  ScratchFactor sub(m, slots);
   DevBuf<double> dXq((size_t)m * D);
-  SamplePass p(m, slots, Sc, R, stream, sub.stream);
+  SamplePass p(m, slots, Sc, R, stream, sub.stream());
   HIPCK(hipMemcpyAsync(dXq, Xs, (size_t)m * D * sizeof(double), hipMemcpyHostToDevice, stream));
-  HIPCK(hipMemsetAsync(p.dZ, 0, (size_t)slots * p.zrows * p.MP * sizeof(double), sub.stream));      // columns >= m and rows >= Sc: exact zeros
+  HIPCK(hipMemsetAsync(p.dZ, 0, (size_t)slots * p.zrows * p.MP * sizeof(double), sub.stream()));      // columns >= m and rows >= Sc: exact zeros
   for (long e0 = 0; e0 < E; e0 += slots) {
     const long cnt = std::min(slots, E - e0);
     const std::vector<int> grp(ids.begin() + e0, ids.begin() + e0 + cnt);
     sample_build(grp, Xs, dXq, m, p, mean_out + (size_t)e0 * m);
-    HIPCK(hipMemcpyAsync(p.dStreams, streams + e0, (size_t)cnt * sizeof(unsigned), hipMemcpyHostToDevice, sub.stream));
+    HIPCK(hipMemcpyAsync(p.dStreams, streams + e0, (size_t)cnt * sizeof(unsigned), hipMemcpyHostToDevice, sub.stream()));
     sample_factor(sub, grp, include_nugget, jitter, p, jitter_used + e0, ok + e0);
     sample_draws(sub, e0, cnt, m, S, Sc, seed, z_in, z_per_emulator, p, samples, z_out);
   }
@@ -631,19 +614,12 @@ void Engine::sample_posterior(const std::vector<int>& ids, const unsigned* strea
 void Engine::check_cov_args(const char* who, const std::vector<int>& ids, const double* X1, int m1, const double* X2, int m2, int max_a,
                             int max_b) const {
   const std::string p = std::string(who) + ": ";
-  require_factored(ids);
-  if (analytic) throw std::runtime_error(p + "not available with analytic_mean=True (the covariance gains a term of the mean coefficients)");
-  for (int i : ids)
-    if (gp[i].nug_type == NUG_PIVOT || gp[i].permuted)
-      throw std::runtime_error(p + "not available with nugget=\"pivot\" (a pivoted, possibly rank-deficient factor)");
+  require_plain_fit(who, ids, "the covariance gains a term of the mean coefficients");
   if (!X1 || !X2) throw std::runtime_error(p + "null buffer");
   if (m1 < 1 || m2 < 1) throw std::runtime_error(p + "at least one point is needed in each set");
   if (max_a < 0 || max_b < 0) throw std::runtime_error(p + "max_slots and max_points must not be negative");
-  for (size_t k = 0; k < (size_t)m1 * D; ++k)
-    if (!std::isfinite(X1[k])) throw std::runtime_error(p + "the points must be finite");
-  if (X2 != X1)
-    for (size_t k = 0; k < (size_t)m2 * D; ++k)
-      if (!std::isfinite(X2[k])) throw std::runtime_error(p + "the points must be finite");
+  require_finite(X1, (size_t)m1 * D, (p + "the points must be finite").c_str());
+  if (X2 != X1) require_finite(X2, (size_t)m2 * D, (p + "the points must be finite").c_str());
 }
 
 void Engine::points_v(int nb, const double* dXq, int m, int MP, double* dK, double* dDots, double* dPartial, double* dVar, int var_ld, double* dV) {
@@ -666,8 +642,7 @@ void Engine::predict_cov(const std::vector<int>& ids, const double* X1, int m1, 
   if (per > 64.0e9)
     throw std::runtime_error("predict_cov: " + std::to_string(m1) + " x " + std::to_string(m2) +
                              " points need more than 64 GB of device scratch; use fewer points per call");
-  double free_b = 0.;
-  if (!free_device_bytes(free_b)) free_b = 2.0 * ks_budget_bytes();
+  const double free_b = free_bytes_or_twice_budget();
   if (per > 0.5 * free_b)
     throw std::runtime_error("predict_cov: one emulator at " + std::to_string(m1) + " x " + std::to_string(m2) +
                              " points needs more than half of the free device memory; use fewer points per call");
@@ -721,9 +696,7 @@ void Engine::alc(const std::vector<int>& ids, const double* Xc, int mc, const do
   // 2. the factor is there (check_cov_args); L^-1
   ensure_linv(ids);
   // 3. plan
-  double free_b = 0.;
-  if (!free_device_bytes(free_b)) free_b = 2.0 * ks_budget_bytes();
-  const AlcPlan plan = alc_plan(E, mc, mr, LD, NP, free_b, max_slots, max_points);
+  const AlcPlan plan = alc_plan(E, mc, mr, LD, NP, free_bytes_or_twice_budget(), max_slots, max_points);
   const long slots = plan.slots;
   const int CH = (int)plan.points, MPc = (int)alc_mp(mc), tiles_r = (int)(alc_mp(mr) / 128), MPmax = std::max(MPc, CH);
   const size_t sl = (size_t)slots, nti = (size_t)(n + 127) / 128;

@@ -145,7 +145,7 @@ void Engine::read_info(std::vector<int>& info, bool defer_info) {
   HIPCK(hipGetLastError());
 }
 
-void Engine::factorize_blocked(const std::vector<int>& ids, std::vector<int>& info, bool defer_info) {
+void Engine::factorize_blocked(const std::vector<int>& ids, std::vector<int>& info, bool defer_info, const CovFill* fill) {
   const int nb = (int)ids.size();
   upload_idx(ids);
   upload_params(ids);
@@ -160,22 +160,22 @@ void Engine::factorize_blocked(const std::vector<int>& ids, std::vector<int>& in
   }();
   const int schedule = choose_cholesky_schedule(nb, NP, MS * sizeof(double), schedule_override().schedule, forced, mc_force_legacy);
   mc_used = schedule == CHOL_ONE_LAUNCH;
-  if (mc_used) return chol_one_launch(ids, v, info, defer_info);
-  if (schedule == CHOL_LOOKAHEAD) chol_lookahead(v);
-  else if (schedule == CHOL_TWO_GROUPS) chol_two_groups(v);
-  else chol_right_looking(v);
+  if (mc_used) return chol_one_launch(ids, v, info, defer_info, fill);
+  if (schedule == CHOL_LOOKAHEAD) chol_lookahead(v, fill);
+  else if (schedule == CHOL_TWO_GROUPS) chol_two_groups(v, fill);
+  else chol_right_looking(v, fill);
   read_info(info, defer_info);
 }
 
-void Engine::refactor_after_abort(const std::vector<int>& ids, std::vector<int>& info, bool defer_info) {
+void Engine::refactor_after_abort(const std::vector<int>& ids, std::vector<int>& info, bool defer_info, const CovFill* fill) {
   g_mc_aborts += 1;
   FlagGuard legacy_only(mc_force_legacy);          // reset also when the repeat throws
-  factorize_blocked(ids, info, defer_info);
+  factorize_blocked(ids, info, defer_info, fill);
 }
 
-void Engine::begin_multi_launch(const BatchView& v) {
+void Engine::begin_multi_launch(const BatchView& v, const CovFill* fill) {
   HIPCK(hipMemsetAsync(dInfo, 0, B * sizeof(int), stream));
-  build_cov(v);
+  build_cov(v, ZeroRanges(), fill);
 }
 
 void Engine::grow_step_events(int K) {
@@ -186,7 +186,7 @@ void Engine::grow_step_events(int K) {
 }
 
 // ONE LAUNCH: persistent workgroups take the tasks of all block columns from a dependency-ordered queue (kernels_mchol.hip)
-void Engine::chol_one_launch(const std::vector<int>& ids, const BatchView& v, std::vector<int>& info, bool defer_info) {
+void Engine::chol_one_launch(const std::vector<int>& ids, const BatchView& v, std::vector<int>& info, bool defer_info, const CovFill* fill) {
   const int nb = v.nb;
   if (!dMcTable) {
     std::vector<int> tb = mchol_task_table(NP);
@@ -212,13 +212,13 @@ void Engine::chol_one_launch(const std::vector<int>& ids, const BatchView& v, st
   ZeroRanges zr;
   zr.p[0] = reinterpret_cast<unsigned*>(dInfo.get()); zr.n[0] = (unsigned)B;
   zr.p[1] = dMcCtrl; zr.n[1] = (unsigned)mchol_ctrl_ints(NP, nb);
-  build_cov(v, zr);
+  build_cov(v, zr, fill);
   launch_mchol(v, dMcCtrl, mchol_ctrl_ints(NP, nb), dMcTable, mc_ntasks, dMcPacks, dInfo, n_cu, stream, true);
   if (defer_info) return;          // (the caller finds the abort word in the status words it reads: eval)
   read_info(info, false);
   unsigned aborted = 0;
   HIPCK(hipMemcpy(&aborted, dMcCtrl, sizeof(unsigned), hipMemcpyDeviceToHost));
-  if (aborted) refactor_after_abort(ids, info, false);
+  if (aborted) refactor_after_abort(ids, info, false, fill);
 }
 
 // LEFT-LOOKING WITH LOOK-AHEAD.  Block column c receives the panels 0 .. c-2 in one long-K MFMA pass U1(c) on the main
@@ -231,7 +231,7 @@ void Engine::chol_one_launch(const std::vector<int>& ids, const BatchView& v, st
 // earlier schedules paid two of them per block column.  The main stream is one block column ahead, so its events
 // have normally fired by the time the panel stream asks.  Replaces the two-emulator-group schedule (5.37 ms at
 // 64 x n=2000), the right-looking schedule of small batches and of a single large matrix.
-void Engine::chol_lookahead(const BatchView& v) {
+void Engine::chol_lookahead(const BatchView& v, const CovFill* fill) {
   const int nb = v.nb;
   const ScheduleOverride& ovr = schedule_override();
   std::vector<int> cols;
@@ -245,7 +245,7 @@ void Engine::chol_lookahead(const BatchView& v) {
     else launch_update_narrow_pair(v, o, 0, k1, st);
   };
   hipStream_t pst = ovr.single_stream ? stream : pstream;
-  begin_multi_launch(v);
+  begin_multi_launch(v, fill);
   HIPCK(hipEventRecord(evReady, stream));
   HIPCK(hipStreamWaitEvent(pst, evReady, 0));
   // "U1(c) done" in front of U2(c) sits in the dependent chain although U1(c) has normally finished a block column earlier, and
@@ -293,14 +293,14 @@ void Engine::chol_lookahead(const BatchView& v) {
 // latency-bound panel kernels (diagonal block / panel solve: few workgroups) the other group's MFMA update fills the
 // machine.  More than two streams collapse (round 1, 64 x n=2000: 1 group 6.58 ms, 2 groups 6.23 ms, 3 groups 8.3 ms,
 // 4 groups 14.2 ms -- the same when replayed from a captured hipGraph, so it is not host launch overhead).
-void Engine::chol_two_groups(const BatchView& v) {
+void Engine::chol_two_groups(const BatchView& v, const CovFill* fill) {
   const int nb = v.nb;
   constexpr long tail_threshold = 1100L;
   const int G = schedule_override().single_stream ? 1 : std::min(2, std::max(1, nb / 8));
   while ((int)gstreams.size() < G - 1) {
     gstreams.push_back(make_stream(hipStreamNonBlocking));
   }
-  begin_multi_launch(v);
+  begin_multi_launch(v, fill);
   HIPCK(hipEventRecord(evReady, stream));
   std::vector<BatchView> gv(G, v);
   std::vector<hipStream_t> gs(G, stream);
@@ -337,8 +337,8 @@ void Engine::chol_two_groups(const BatchView& v) {
 // while the main stream applies panel k to the rest of the trailing matrix (U_b).  The
 // latency-bound panel kernels (potf2 / trsm, few workgroups) thereby run underneath the MFMA
 // trailing update instead of in front of it.
-void Engine::chol_right_looking(const BatchView& v) {
-  begin_multi_launch(v);
+void Engine::chol_right_looking(const BatchView& v, const CovFill* fill) {
+  begin_multi_launch(v, fill);
   std::vector<int> starts;
   // outer block = K depth of the trailing update (256 / 512 / 1024 -> C5 fit 45.7 / 41.7 / 44.3 ms, round 1)
   constexpr int OUTERW = 512;

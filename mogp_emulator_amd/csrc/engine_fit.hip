@@ -1,4 +1,4 @@
-// Engine: the multi-start MAP fit -- the L-BFGS slot pool, the replica engine and its cache
+// Engine: the multi-start MAP fit -- the L-BFGS slot pool, the replica engine and its cache; ScratchFactor
 #include "engine_internal.h"
 
 #include <chrono>
@@ -283,35 +283,46 @@ void Engine::retarget(int slot, const Engine& src, int i) {
   gp[slot] = std::move(d);
 }
 
-void Engine::factor_prebuilt(const std::function<void(const BatchView&)>& fill, std::vector<int>& info, const std::vector<int>* only,
-                             bool want_linv) {
+ScratchFactor::ScratchFactor(int rows_, long slots_) : ScratchFactor(rows_, slots_, std::vector<double>((size_t)slots_ * rows_, 0.0)) {}
+
+// (the engine never reads its inputs: its covariance build is replaced by the caller's fill)
+ScratchFactor::ScratchFactor(int rows_, long slots_, const std::vector<double>& zeros)
+    : rows(rows_), slots((int)slots_), eng(zeros.data(), rows_, 1, zeros.data(), (int)slots_, 0, MeanFunc(), 0, NUG_FIXED, 0.0) {
+  NP = eng.NP;
+  MS = eng.MS;
+  if (NP != scratch_np(rows)) throw std::runtime_error("ScratchFactor: unexpected layout of the engine");
+}
+
+void ScratchFactor::factor(const CovFill& fill, std::vector<int>& info, const std::vector<int>* only, bool want_linv) {
   std::vector<int> ids;
   if (only) {
     ids = *only;
   } else {
-    ids.resize(B);
-    for (int i = 0; i < B; ++i) ids[i] = i;
+    ids.resize(slots);
+    for (int i = 0; i < slots; ++i) ids[i] = i;
   }
   if (ids.empty()) return;
   for (int i : ids) {
-    if (i < 0 || i >= B) throw std::runtime_error("factor_prebuilt: slot out of range");
-    if (gp[i].nug_type != NUG_FIXED || gp[i].permuted) throw std::runtime_error("factor_prebuilt: every slot needs nugget type fixed");
-    gp[i].nugget_used = gp[i].nug_size;
+    if (i < 0 || i >= slots) throw std::runtime_error("ScratchFactor: slot out of range");
+    eng.gp[i].nugget_used = eng.gp[i].nug_size;
   }
-  struct Reset {      // build_cov is the covariance build again when this returns or throws
-    const std::function<void(const BatchView&)>*& p;
-    ~Reset() { p = nullptr; }
-  } reset{prebuilt};
-  prebuilt = &fill;
-  factorize_blocked(ids, info, false);
+  eng.factorize_blocked(ids, info, false, &fill);
   std::vector<int> ok;
   for (int i : ids) {
-    GPState& g = gp[i];
+    GPState& g = eng.gp[i];
     g.unfit();
     g.factored = info[i] == 0;
     if (g.factored) ok.push_back(i);
   }
-  if (want_linv && !ok.empty()) ensure_linv(ok);
+  if (want_linv && !ok.empty()) eng.ensure_linv(ok);
+}
+
+void ScratchFactor::logdet_and_solve(const std::vector<int>& okslots) {
+  if (okslots.empty()) return;
+  eng.upload_idx(okslots);
+  const BatchView sv = eng.view((int)okslots.size());
+  launch_logdet(sv, eng.dInfo, eng.dRes, eng.stream);
+  launch_alpha_from_linv(sv, eng.stream);
 }
 
 // The inputs of a cached replica engine taken by a fit with other inputs of the same shape: everything the engine derived from X

@@ -1,14 +1,16 @@
 // What engine.hip, engine_chol.hip, engine_fit.hip, engine_predict.hip and engine_analysis.hip share and nobody else sees: the error-check
 // macro, small helpers and the process-wide diagnostic counters behind prof_counter (engine.hip).  What lives where: engine.hip the
 // construction, the cached state, eval's steps, L^-1 / K^-1 and the gradient; engine_chol.hip the factorisation schedules; engine_fit.hip
-// the optimiser, the slot pool and the replica engines; engine_predict.hip predict, full covariance, implausibility, Sobol and loo_variance;
+// the optimiser, the slot pool, the replica engines and ScratchFactor; engine_predict.hip predict, full covariance, implausibility, Sobol and loo_variance;
 // engine_analysis.hip the Hessian, the mixture over hyperparameter samples, cross-validation, joint posterior draws and
-// active learning (alc, predict_cov).
+// active learning (alc, predict_cov).  Whoever needs "factor a batch of matrices I wrote myself" and nothing else of an engine (gkdr_R,
+// cross_validate's k-fold path, sample_posterior) takes a ScratchFactor, below.
 #pragma once
 #include "engine.h"
 #include "predict_plan.h"
 
 #include <atomic>
+#include <cmath>
 #include <cstdlib>
 #include <memory>
 
@@ -49,6 +51,42 @@ class ReplicaLease {
   std::unique_ptr<Engine> rep;
   bool cache_on;
 };
+
+// A batch of `slots` caller-filled symmetric matrices of `rows` rows to factor with the engine's batched Cholesky, for the lifetime of a
+// scope (engine_fit.hip).  It owns the engine that does it -- one dummy input column, zero targets, nugget type "fixed" with nugget 0 --
+// and shows nothing else of it.  A slot's matrix has the layout of the covariance build (launch.h) at NP = scratch_np(rows), MS = NP * NP
+// doubles apart; everything runs on stream().
+class ScratchFactor {
+ public:
+  ScratchFactor(int rows, long slots);
+  const int rows, slots;
+  int NP;
+  size_t MS;
+  hipStream_t stream() const { return eng.stream; }
+  // Every slot's matrix is written into the factor buffer by `fill` -- it stands where the covariance build does -- and factored with the
+  // schedule of the regime; info (indexed by slot): 0 where the slot factorised.  The slots that did form L^-1 (linv(), lower triangle).
+  // only: the slots to factor instead of all -- the others keep their factor and state, info is meaningful for the listed slots alone;
+  // want_linv = false: L^-1 is not formed.
+  void factor(const CovFill& fill, std::vector<int>& info, const std::vector<int>* only = nullptr, bool want_linv = true);
+  // behind factor, for the slots that factorised: the log-determinant words (launch_logdet) and the solution rows (launch_alpha_from_linv)
+  void logdet_and_solve(const std::vector<int>& okslots);
+  // the buffers a caller hands to its own kernels
+  double* factor_buffer() const { return eng.dA; }
+  const double* linv() const { return eng.dLinv; }
+  const double* solution() const { return eng.dAlpha; }
+  const double* logdet_words() const { return eng.dRes; }
+  const int* status() const { return eng.dInfo; }
+
+ private:
+  ScratchFactor(int rows, long slots, const std::vector<double>& zeros);
+  Engine eng;
+};
+
+// throws std::runtime_error(message) unless the `count` values at p are all finite
+inline void require_finite(const double* p, size_t count, const char* message) {
+  for (size_t k = 0; k < count; ++k)
+    if (!std::isfinite(p[k])) throw std::runtime_error(message);
+}
 
 inline std::atomic<long long> g_bs_timeouts{0}, g_obj_evals{0}, g_grad_evals{0}, g_mc_aborts{0}, g_alpha_solves{0};
 inline std::atomic<long long> g_lb_iters{0}, g_ls_short{0}, g_ls_long{0}, g_lb_runs{0}, g_pool_rounds{0}, g_pool_slot_rounds{0}, g_rep_build_us{0}, g_rep_pool_us{0}, g_retarget_us{0}, g_retargets{0}, g_rep_reused{0};

@@ -1,6 +1,6 @@
 // gKDR dimension reduction (Fukumizu and Leng; mogp_emulator/DimensionReduction.py:132-236): the M x M matrix R of every
 // (X_scale, Y_scale) pair of a tuning grid in one call.  Per input scale s (SGX^2) the Gram matrix Kx and A = Kx + N EPS I are built on
-// the device, A = L L^T is factored and L^-1 formed by the engine's batched Cholesky and trtri (Engine::factor_prebuilt); per output
+// the device, A = L L^T is factored and L^-1 formed by the engine's batched Cholesky and trtri (a ScratchFactor, engine_internal.h); per output
 // scale Ky is built the same way.  R is formed WITHOUT the N x N x M tensor of the reference, from the identity (Xc = X - mean(X); R does
 // not change when X is shifted)
 //   s^2 R = Xc^T (F o KxKx) Xc - Xc^T T Xc - (Xc^T T Xc)^T + Xc^T diag(c) Xc,   F = A^-1 Ky A^-1, G = F Kx, T = Kx o G, c_j = sum_i T_ij
@@ -18,12 +18,10 @@
 #include <vector>
 
 #include "cov_dev.h"
-#include "engine.h"
+#include "engine_internal.h"
 #include "gemm_dev.h"
 
 namespace mogp {
-
-#define HIPCK(x) hip_check((x), #x)
 
 namespace {
 
@@ -196,13 +194,12 @@ void gkdr_R(const double* X, int n, int m, const double* y, int nx, const double
     if (!(sgx2[i] > 0.0) || !std::isfinite(sgx2[i])) throw std::runtime_error("gkdr: SGX^2 must be positive and finite");
   for (int i = 0; i < ny; ++i)
     if (!(sgy2[i] > 0.0) || !std::isfinite(sgy2[i])) throw std::runtime_error("gkdr: SGY^2 must be positive and finite");
-  // the engine factors and inverts A; it never sees X (its inputs are a dummy column, its covariance build is replaced)
-  const std::vector<double> zeros((size_t)nx * n, 0.0);
-  Engine eng(zeros.data(), n, 1, zeros.data(), nx, 0, MeanFunc(), 0, NUG_FIXED, 0.0);
-  hipStream_t st = eng.stream;
+  // factors and inverts A; it never sees X (the Gram kernel below stands where its covariance build would)
+  ScratchFactor eng(n, nx);
+  hipStream_t st = eng.stream();
   const int NP = eng.NP;
   const int MP = (m + 127) / 128 * 128;
-  const size_t MS = (size_t)NP * NP;
+  const size_t MS = eng.MS;
   DevBuf<double> dX((size_t)n * m);
   DevBuf<double> dY(n);
   DevBuf<double> dXt((size_t)MP * NP);
@@ -227,13 +224,13 @@ void gkdr_R(const double* X, int n, int m, const double* y, int nx, const double
   }
   const double shift = (double)n * eps;   // N * EPS, as the reference adds it
   const int gt = NP / GT;
-  const std::function<void(const BatchView&)> fill = [&](const BatchView& v) {
+  const CovFill fill = [&](const BatchView& v) {
     if (v.nb != nx) throw std::runtime_error("gkdr: the factorisation must cover every input scale");
     hipLaunchKernelGGL(gkdr_gram_kernel, dim3(gt, gt, nx), dim3(256), 0, st, dX.get(), n, m, dSx.get(), nullptr, dKx.get(), NP, shift, v.A, v.MS);
     HIPCK(hipGetLastError());
   };
   std::vector<int> info;
-  eng.factor_prebuilt(fill, info);
+  eng.factor(fill, info);
   std::vector<int> okx;
   for (int i = 0; i < nx; ++i) {
     info_out[i] = info[i] != 0 ? 1 : 0;
@@ -250,7 +247,7 @@ void gkdr_R(const double* X, int n, int m, const double* y, int nx, const double
   DevBuf<double> dKK((size_t)nx * MS);
   DevBuf<int> dOk(nz);
   HIPCK(hipMemcpyAsync(dOk, okx.data(), nz * sizeof(int), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(gkdr_linv_kernel, dim3(elem_blocks(MS), nz), dim3(256), 0, st, eng.linv_buffer(), eng.MS, dOk, n, NP, dLI, dLT);
+  hipLaunchKernelGGL(gkdr_linv_kernel, dim3(elem_blocks(MS), nz), dim3(256), 0, st, eng.linv(), MS, dOk, n, NP, dLI, dLT);
   HIPCK(hipGetLastError());
   {
     GemmArgs g;

@@ -74,11 +74,13 @@ inline MixturePlan mixture_plan(long E, long S, int LD, long device_slots, int m
   return {slots, points};
 }
 
-// Engine::cross_validate: how many (emulator, fold) pairs one pass of the sub-engine takes.  The E * k pairs are laid out emulator-major,
+// Engine::cross_validate: how many (emulator, fold) pairs one pass of the ScratchFactor takes.  The E * k pairs are laid out emulator-major,
 // fold-ascending, and pass g takes the pairs [g * slots, (g + 1) * slots).  slots: at least one, never more than the E * k pairs, the
-// `device_slots` that half of the free memory holds at 3 NPsub^2 doubles per slot (factor, L^-1 and its scratch; cv_slot_bytes), the batch
+// `device_slots` that half of the free memory holds at 3 NPsub^2 doubles per slot, NPsub = scratch_np(largest fold) (factor, L^-1 and its scratch; cv_slot_bytes), the batch
 // bound predict_mixture's replica engine observes (cv_slot_bound: the batched kernels of a factorisation stay in the range of tiles per
 // launch they run at there, and a slot is one grid row), or max_slots (0: the library's choice).
+// the padded size of the matrices of a ScratchFactor of `rows` rows (engine_internal.h): the rows and one right-hand side, in whole tiles
+inline long scratch_np(long rows) { return (rows + 128) / 128 * 128; }
 inline double cv_slot_bytes(int NPsub) { return 3.0 * (double)NPsub * (double)NPsub * 8.0; }
 inline long cv_slot_bound(int NPsub) { return std::min<long>(65535, 4095 / std::max(1, NPsub / 128) + 1); }
 inline long cv_plan(long E, long k, int NPsub, long device_slots, int max_slots) {
@@ -129,7 +131,7 @@ inline void cv_pass_table(long p0, long cnt, long slots, long k, const int* ids,
 // in caller order and, inside a pass, the S draws in chunks [s0, s0 + draws): every (emulator, draw) pair is computed exactly once.
 // Bytes of one slot (sample_slot_bytes):
 //   Sigma* and what predict_full_cov builds it from: K* (MP x LD), V (NP x MP), Sigma* (m x m), the R dot-product rows   (MP = roundup(m, 128))
-//   the scratch engine's factor matrix NPs x NPs (NPs = roundup(m + 1, 128)) and its small per-slot rows, mu* (m)
+//   the ScratchFactor's factor matrix NPs x NPs (NPs = scratch_np(m)) and its small per-slot rows, mu* (m)
 //   Z and Y of one chunk: 2 x roundup(draws, 64) x MP doubles (sample_apply_kernel reads whole tiles of 64 draws)
 // and a pass never takes more than HALF of the free device memory.  draws: max_draws where given, else SAMPLE_DEFAULT_DRAWS, at most S and
 // SAMPLE_MAX_DRAWS (a chunk's draws are one grid dimension of the generator), cut to whole tiles of 64 where one slot would not fit
@@ -141,7 +143,7 @@ struct SamplePlan {
   long slots, draws;
 };
 inline long sample_mp(int m) { return ((long)m + 127) / 128 * 128; }
-inline long sample_nps(int m) { return ((long)m + 128) / 128 * 128; }
+inline long sample_nps(int m) { return scratch_np(m); }
 inline long sample_draw_rows(long draws) { return (draws + SAMPLE_DRAW_TILE - 1) / SAMPLE_DRAW_TILE * SAMPLE_DRAW_TILE; }
 inline double sample_fixed_bytes(int m, int LD, int NP, int R) {
   const double MP = (double)sample_mp(m), NPs = (double)sample_nps(m);

@@ -1,6 +1,6 @@
 // Host check of cv_plan (csrc/predict_plan.h), with its own sweep: exits non-zero at the first property that fails.  Over
 // (E, k, NPsub, device slots, max_slots):
-//   * at least one slot, never more than E * k, the device slots, the batch bound of the sub-engine (cv_slot_bound) or max_slots;
+//   * at least one slot, never more than E * k, the device slots, the batch bound of the scratch factorisation (cv_slot_bound) or max_slots;
 //   * with no cap in the way everything goes in one pass;
 //   * walking the passes [g * slots, (g + 1) * slots) over the emulator-major, fold-ascending pairs visits every (emulator, fold) exactly
 //     once, in order.
@@ -62,6 +62,10 @@ int main() {
             ++cases;
           }
   if (mogp::cv_slot_bytes(256) != 3.0 * 256 * 256 * 8) return fail("bytes per slot", 0, 0, 256, 0, 0);
+  // the padded size of a scratch matrix: the rows and one right-hand side in whole tiles of 128 -- 127 rows fill one tile, 128 need two
+  for (long rows : {1L, 127L, 128L, 255L, 256L})
+    if (mogp::scratch_np(rows) != (rows + 1 + 127) / 128 * 128) return fail("scratch_np = roundup(rows + 1, 128)", rows, 0, 0, 0, 0);
+  if (mogp::scratch_np(127) != 128 || mogp::scratch_np(128) != 256) return fail("scratch_np at the tile edge", 127, 0, 0, 0, 0);
   {
     const std::vector<int> labels = {2, 0, 2, 1, 2, 0, 2};
     const mogp::CvFolds c = mogp::cv_folds(labels.data(), 7, 3);

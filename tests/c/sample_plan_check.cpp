@@ -90,6 +90,10 @@ int main() {
   if (mogp::sample_mp(300) != 384 || mogp::sample_nps(300) != 384 || mogp::sample_nps(128) != 256 || mogp::sample_mp(128) != 128 ||
       mogp::sample_draw_rows(65) != 128 || mogp::sample_draw_bytes(300, 65) != 2.0 * 8.0 * 128 * 384)
     return fail("layout sizes", 0, 300, 65, 256, 0, 0, 0);
+  for (int rows : {1, 127, 128, 255, 256})
+    if (mogp::scratch_np(rows) != (rows + 1 + 127) / 128 * 128 || mogp::sample_nps(rows) != mogp::scratch_np(rows))
+      return fail("sample_nps = scratch_np = roundup(rows + 1, 128)", 0, rows, 0, 0, 0, 0, 0);
+  if (mogp::scratch_np(127) != 128 || mogp::scratch_np(128) != 256) return fail("scratch_np at the tile edge", 0, 127, 0, 0, 0, 0, 0);
   if (mogp::sample_fixed_bytes(300, 256, 256, 1) != 8.0 * (384.0 * 256 + 256.0 * 384 + 300.0 * 300 + 300 + 384.0 * 384 + 16.0 * 384 + 300))
     return fail("bytes per slot", 0, 300, 0, 256, 0, 0, 0);
   // the ladder: 10^-6 * 10^t * mean diagonal, t = 0 .. 4
