@@ -229,6 +229,25 @@ int mogp_densegp_predict_cov(mogp_densegp*, const double* X1, int m1, const doub
 int mogp_densegp_alc(mogp_densegp*, const double* candidates, int m_c, const double* reference, int m_r, int D, const double* weights,
                      const double* noise /* 1 or NULL */, int max_slots, int max_points, double* reduction_out, double* cand_var_out /* m_c each */,
                      double* ref_var_out /* m_r */, int* degenerate_out /* m_c */);
+/* A greedy ALC batch: n_points picks, the posterior conditioned on each pick before the next is scored, all on the device.  At fixed
+ * hyperparameters the predictive variance does not depend on the targets: a run at p with noise tau appends one row to the Cholesky factor,
+ * which gives every stored v(x) = L^-1 k(x) one more entry u(x) = c(x, p) / sqrt(s^2(p) + tau); c_new(x, x') = c(x, x') - u(x) u(x'),
+ * s^2_new(x) = s^2(x) - u(x)^2.  candidates (m, D): the first n_forced of them are points already submitted -- steps 0 .. n_forced - 1
+ * condition on them in order and mask them --, the other n_points steps pick the unmasked candidate with the largest reduction (ties: the
+ * lowest index; a picked candidate is never picked again).  T = n_forced + n_points steps in all; step t scores with the ALC launches
+ * over n + t rows (floor: (n + t + 2) 2^-52 sigma^2).  A step whose best score is not above 0 or whose denominator is at or below that
+ * floor picks -1 and conditions on nothing (a forced step: only the floor is tested); never NaN, nothing raised.
+ *   picks_out (T): candidate index or -1;   pick_red_out (T): its reduction, 0 for -1
+ *   red_out / deg_out (T, m) or NULL: every step's reduction and degenerate flags
+ *   cand_var_out (m), ref_var_out (m_r): s^2 before any step, the bits of mogp_densegp_alc;   ref_var_after_out (m_r): after the last
+ *   iv_out (T + 1): iv[0] = sum_j w_j ref_var[j] in ascending j, iv[t + 1] = iv[t] - pick_red[t]
+ * The picks are enqueued back to back: one download at the end (and each step's rows where red_out / deg_out are given).  No atomics:
+ * the same call returns the same bits.  Refused: what mogp_densegp_alc refuses, n_points < 1, n_points > m - n_forced, and scratch beyond
+ * half of the free device memory (V of both sets with roundup(T, 16) more rows, the whole reference set resident). */
+int mogp_densegp_alc_batch(mogp_densegp*, const double* candidates, int m, int n_forced, const double* reference, int m_r, int D,
+                           const double* weights, const double* noise /* 1 or NULL */, int n_points, int max_slots, int* picks_out,
+                           double* pick_red_out, double* red_out, int* deg_out, double* cand_var_out, double* ref_var_out,
+                           double* ref_var_after_out, double* iv_out);
 int mogp_densegp_get_K(mogp_densegp*, double* out /* n*n */);
 int mogp_densegp_get_invQ(mogp_densegp*, double* out /* n*n */);
 int mogp_densegp_get_invQt(mogp_densegp*, double* out /* n */);
@@ -338,6 +357,18 @@ int mogp_mogp_predict_cov(mogp_mogp*, const double* X1, int m1, const double* X2
 int mogp_mogp_alc(mogp_mogp*, const double* candidates, int m_c, const double* reference, int m_r, int D, const double* weights,
                   const double* noise /* n_out or NULL */, int max_slots, int max_points, double* reduction_out, double* cand_var_out,
                   double* ref_var_out, int* degenerate_out);
+/* mogp_densegp_alc_batch for every emulator; arrays gain a leading n_out.  select_total = 0: every emulator its own batch; row e is bit
+ * for bit the single-emulator call, whatever max_slots and the split over devices.  select_total = 1: ONE batch for the model: in each
+ * free step the candidate with the largest sum over the fitted emulators of red_e / IV_e (IV_e: emulator e's integrated variance before
+ * that step; an emulator whose IV is not above 0 adds nothing), formed on the host in ascending emulator order from the downloaded rows,
+ * ties to the lowest index; total_picks_out (n_forced + n_points) receives it, -1 from the step at which no score is above 0.  An
+ * emulator for which that candidate is at or below its own floor has picks_out = -1 in that step and is not conditioned.  All fitted
+ * emulators of a device must fit one group; refused otherwise, with the bytes named.  Once stopped, the later rows of red_out are 0.
+ * Emulators that are not fit: NaN rows, deg_out = 0, and picks_out left as the caller set them (their noise is not read). */
+int mogp_mogp_alc_batch(mogp_mogp*, const double* candidates, int m, int n_forced, const double* reference, int m_r, int D,
+                        const double* weights, const double* noise /* n_out or NULL */, int n_points, int select_total, int max_slots,
+                        int* picks_out, double* pick_red_out, double* red_out /* or NULL */, int* deg_out /* or NULL */, double* cand_var_out,
+                        double* ref_var_out, double* ref_var_after_out, double* iv_out, int* total_picks_out /* NULL with select_total = 0 */);
 /* predict_variance_batch (multioutputgp_gpu.hpp:182-192) with DEVICE pointers: inputs already resident in HBM, results stay in HBM
  * (every mean function; rows of emulators that are not fit are filled with NaN, MultiOutputGP_GPU.py:288-296) */
 int mogp_mogp_predict_variance_batch_dev(mogp_mogp*, const double* d_testing, int m, int D, double* d_means, double* d_vars);

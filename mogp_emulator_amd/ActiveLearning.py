@@ -22,7 +22,18 @@ meaningful ratio (a candidate on a training point of an emulator with no nugget)
 exception.
 
 Not covered: ``nugget="pivot"`` and ``analytic_mean=True`` (``RuntimeError``; the covariance gains a rank-q term there),
-``dist.ShardedMultiOutputGP``, greedy batches with conditioning between picks, and ALC averaged over hyperparameter samples.
+``dist.ShardedMultiOutputGP``, and ALC averaged over hyperparameter samples.
+
+Batches (``alc_batch``): at fixed hyperparameters the predictive variance does not depend on the targets, so the posterior can be
+conditioned on a pick before its run has come back.  A run at p with noise tau appends one row to the Cholesky factor, which gives every
+stored v(x) one more entry
+
+    u(x) = c(x, p) / sqrt(s^2(p) + tau),     c_new(x, x') = c(x, x') - u(x) u(x'),     s^2_new(x) = s^2(x) - u(x)^2,
+
+and after t picks the ALC of every remaining candidate is the same product over n + t rows.  V of both point sets is built once per call;
+a pick costs no n^3 and no (m_c + m_r) n^2 work, and in ``select="each"`` the picks of a batch are enqueued back to back without the host
+in between.  Points already submitted (``pending``) are conditioned on first.  Not covered for batches: replicate picks (a picked
+candidate is masked) and the O(m_c m_r D)-per-pick downdate of the numerators, which would trade this exact route for cancellation.
 """
 import numpy as np
 
@@ -100,6 +111,31 @@ def _fit_state(who, gp, single):
     return native
 
 
+def _alc_args(who, gp, candidates, reference, weights, noise):
+    """what alc_criterion and alc_batch check alike, before the device: (candidates, reference, weights, noise) as arrays / float"""
+    D = int(gp.D)
+    candidates = _points("candidates", who, candidates, D)
+    reference = _points("reference", who, reference, D)
+    mr = reference.shape[0]
+    if weights is None:
+        weights = np.full(mr, 1. / mr)
+    else:
+        weights = np.ascontiguousarray(weights, dtype=np.float64)
+        if weights.shape != (mr,):
+            raise ValueError("%s: weights must have shape (m_r,) with m_r = %d" % (who, mr))
+        if not np.all(np.isfinite(weights)):
+            raise ValueError("%s: weights must be finite" % who)
+        if np.any(weights < 0.):
+            raise ValueError("%s: weights must not be negative" % who)
+        if not weights.sum() > 0.:
+            raise ValueError("%s: weights must not sum to 0" % who)
+    if noise is not None:
+        noise = float(noise)
+        if not (noise >= 0. and np.isfinite(noise)):
+            raise ValueError("%s: noise must be a finite number that is not negative" % who)
+    return candidates, reference, weights, noise
+
+
 def predict_cov(gp, X1, X2=None, max_slots=0):
     """The posterior covariance c(X1, X2) of the latent function per emulator of a fitted ``GaussianProcessGPU`` (E = 1) or
     ``MultiOutputGP_GPU`` (the multi-device form included), computed on the device: an ``ndarray`` (E, m1, m2), nugget not included.
@@ -131,26 +167,7 @@ def alc_criterion(gp, candidates, reference, weights=None, noise=None, max_slots
     ``GaussianProcessGPU`` that is not fit; emulators of a ``MultiOutputGP_GPU`` that are not fit give NaN rows.  Returns an ``ALCResult``."""
     who = "alc_criterion"
     single = _native(who, gp, max_slots, max_points)
-    D = int(gp.D)
-    candidates = _points("candidates", who, candidates, D)
-    reference = _points("reference", who, reference, D)
-    mr = reference.shape[0]
-    if weights is None:
-        weights = np.full(mr, 1. / mr)
-    else:
-        weights = np.ascontiguousarray(weights, dtype=np.float64)
-        if weights.shape != (mr,):
-            raise ValueError("%s: weights must have shape (m_r,) with m_r = %d" % (who, mr))
-        if not np.all(np.isfinite(weights)):
-            raise ValueError("%s: weights must be finite" % who)
-        if np.any(weights < 0.):
-            raise ValueError("%s: weights must not be negative" % who)
-        if not weights.sum() > 0.:
-            raise ValueError("%s: weights must not sum to 0" % who)
-    if noise is not None:
-        noise = float(noise)
-        if not (noise >= 0. and np.isfinite(noise)):
-            raise ValueError("%s: noise must be a finite number that is not negative" % who)
+    candidates, reference, weights, noise = _alc_args(who, gp, candidates, reference, weights, noise)
     native = _fit_state(who, gp, single)
     if single:
         tau = np.array([float(gp.nugget) if noise is None else noise])
@@ -161,3 +178,98 @@ def alc_criterion(gp, candidates, reference, weights=None, noise=None, max_slots
         red, cv, rv, deg = native.alc(candidates, reference, weights, noise=np.ascontiguousarray(tau), max_slots=int(max_slots),
                                       max_points=int(max_points))
     return ALCResult(reduction=red, cand_variance=cv, ref_variance=rv, degenerate=deg, noise=tau, weights=weights)
+
+
+class ALCBatchResult(object):
+    """What ``alc_batch`` returns (E = 1 for a ``GaussianProcessGPU``; q = ``n_points``):
+
+    * ``picks``                    ``select="each"``: (E, q) candidate indices, every emulator its own batch; ``select="total"``: (q,),
+                                   one batch for the model.  -1 beyond ``n_picked`` (and in rows of emulators that are not fit)
+    * ``n_picked`` (E,)            picks made before the stopping rule ended the batch; with ``select="total"`` the steps in which that
+                                   emulator was conditioned on the model's pick
+    * ``emulator_picks`` (E, q)    what each emulator was conditioned on (``picks`` itself with ``select="each"``)
+    * ``points``                   the picked rows of ``candidates``, shaped like ``picks`` + (D,); NaN where the pick is -1
+    * ``pick_reduction`` (E, q)    the ALC of each emulator's pick at its step (0 where there is none)
+    * ``reduction`` (E, q, m_c)    with ``keep_scores``: the ALC of every candidate at every step, else None
+    * ``degenerate`` (E, q, m_c)   with ``keep_scores``: the floor rule at every step, else None
+    * ``cand_variance`` (E, m_c), ``ref_variance`` (E, m_r)   s^2 before any pick (pending points included): ``predict``'s own bits
+    * ``ref_variance_after`` (E, m_r)    s^2 at the reference points after the last pick
+    * ``integrated_variance`` (E, q + 1) IV_0 after the pending points, IV_t = IV_{t-1} - reduction_t[pick_t]
+    * ``pending_skipped`` (E,)     pending points that failed the floor test and were not conditioned on
+    * ``noise`` (E,), ``weights`` (m_r,)"""
+
+    def __init__(self, picks, emulator_picks, points, pick_reduction, reduction, degenerate, cand_variance, ref_variance, ref_variance_after,
+                 integrated_variance, pending_skipped, noise, weights):
+        self.picks, self.emulator_picks, self.points, self.pick_reduction = picks, emulator_picks, points, pick_reduction
+        self.reduction, self.degenerate, self.cand_variance, self.ref_variance = reduction, degenerate, cand_variance, ref_variance
+        self.ref_variance_after, self.integrated_variance, self.pending_skipped = ref_variance_after, integrated_variance, pending_skipped
+        self.noise, self.weights = noise, weights
+
+    @property
+    def n_picked(self):
+        return np.sum(self.emulator_picks >= 0, axis=1)
+
+    @property
+    def total_reduction(self):
+        """(E,) what the whole batch takes off the integrated variance: IV_0 - IV_q"""
+        return self.integrated_variance[:, 0] - self.integrated_variance[:, -1]
+
+
+def alc_batch(gp, candidates, reference, n_points, weights=None, noise=None, pending=None, select="each", keep_scores=True, max_slots=0):
+    """A greedy batch of ``n_points`` ALC picks from ``candidates`` (m_c, D) over the reference points ``reference`` (m_r, D) for a fitted
+    ``GaussianProcessGPU`` (E = 1) or ``MultiOutputGP_GPU`` (the multi-device form included): after each pick the posterior is conditioned
+    on a run there with noise variance tau -- on the device, at the fitted hyperparameters, without a target -- and the next pick is
+    scored under it.  See the module docstring for the formulas.
+
+    ``weights`` and ``noise`` as in ``alc_criterion``.  ``pending`` (P, D): points already submitted whose results are not back; the
+    posterior is conditioned on them first, in order, with the same tau.  ``select="each"``: every emulator its own batch;
+    ``select="total"``: one batch for the model, each step the candidate with the largest sum over the fitted emulators of
+    ``reduction_e / IV_e`` (IV_e the integrated variance before that step): ``ALCResult.total(scale=True)`` of the conditioned model.
+    Arg-max ties go to the lowest index, a picked candidate is never picked again, and a batch stops -- picks of -1, nothing NaN, nothing
+    raised -- when the best remaining score is 0 or its denominator is at or below the floor (n + t + 2) 2^-52 sigma^2.
+    ``keep_scores=False`` skips the download of every step's scores.  ``max_slots`` caps the emulators per group in ``select="each"``
+    (0: the library's choice) and changes no bit; ``select="total"`` needs all fitted emulators of a device in one group.
+
+    Every argument is checked before the device is touched; refused: what ``alc_criterion`` refuses, ``n_points < 1``,
+    ``n_points > m_c`` and an unknown ``select``.  Emulators of a ``MultiOutputGP_GPU`` that are not fit give NaN rows and picks of -1 and
+    are left out of ``select="total"``.  Returns an ``ALCBatchResult``."""
+    who = "alc_batch"
+    single = _native(who, gp, max_slots, 0)
+    if select not in ("each", "total"):
+        raise ValueError("%s: select must be \"each\" or \"total\"" % who)
+    candidates, reference, weights, noise = _alc_args(who, gp, candidates, reference, weights, noise)
+    q, mc, D = int(n_points), candidates.shape[0], int(gp.D)
+    if q < 1:
+        raise ValueError("%s: n_points must be at least 1" % who)
+    if q > mc:
+        raise ValueError("%s: n_points must not exceed the number of candidates (%d)" % (who, mc))
+    P = 0
+    x = candidates
+    if pending is not None:
+        pending = _points("pending", who, pending, D)
+        P = pending.shape[0]
+        x = np.ascontiguousarray(np.vstack([pending, candidates]))
+    native = _fit_state(who, gp, single)
+    if single:
+        tau = np.array([float(gp.nugget) if noise is None else noise])
+        r = native.alc_batch(x, P, reference, weights, q, noise=tau[0], max_slots=int(max_slots), keep_scores=bool(keep_scores))
+        r = {k: (v if v is None or k == "total_picks" else v[None]) for k, v in r.items()}
+        if select == "total":
+            r["total_picks"] = r["picks"][0]
+    else:
+        tau = np.asarray(gp._nuggets(), dtype=np.float64) if noise is None else np.full(int(gp.n_emulators), noise)
+        r = native.alc_batch(x, P, reference, weights, q, noise=np.ascontiguousarray(tau), total=select == "total", max_slots=int(max_slots),
+                             keep_scores=bool(keep_scores))
+
+    def index(p):                       # candidate numbers without the pending prefix
+        return np.where(p >= 0, p - P, -1).astype(np.int64)
+    own = index(r["picks"][:, P:])
+    picks = own if select == "each" else index(r["total_picks"][P:])
+    points = np.where((picks >= 0)[..., None], candidates[np.maximum(picks, 0)], np.nan)
+    fitted = ~np.isnan(r["iv"][:, 0])
+    return ALCBatchResult(picks=picks, emulator_picks=own, points=points, pick_reduction=r["pick_red"][:, P:],
+                          reduction=None if r["red"] is None else r["red"][:, P:, P:],
+                          degenerate=None if r["deg"] is None else r["deg"][:, P:, P:],
+                          cand_variance=r["cand_var"][:, P:], ref_variance=r["ref_var"], ref_variance_after=r["ref_var_after"],
+                          integrated_variance=r["iv"][:, P:], pending_skipped=np.where(fitted, np.sum(r["picks"][:, :P] < 0, axis=1), 0),
+                          noise=tau, weights=weights)

@@ -435,3 +435,36 @@ class ALCDesign(SequentialDesign):
                     raise
                 if attempt == self.N_FIT_ATTEMPTS - 1:
                     raise RuntimeError("Unable to find parameters suitable for the emulator") from exc
+
+    def _fit_emulator(self):
+        """``self.gp`` fitted to the current design, with the retries of ``_eval_metric``."""
+        if not LibGPGPU.gpu_usable():
+            raise RuntimeError("Cannot run an ALCDesign step: the GPU library or a compatible GPU is unavailable")
+        for attempt in range(self.N_FIT_ATTEMPTS):
+            try:
+                self.gp = fit_GP_MAP(GaussianProcessGPU(self.inputs, self.targets, nugget=self.nugget))
+                return
+            except RuntimeError as exc:
+                if not any(key in str(exc) for key in self._RETRY_ON):
+                    raise
+                if attempt == self.N_FIT_ATTEMPTS - 1:
+                    raise RuntimeError("Unable to find parameters suitable for the emulator") from exc
+
+    def get_conditioned_batch(self, n_points):
+        """n_points next points from ONE fit, one candidate set, one reference set and one ``ActiveLearning.alc_batch`` call: after each
+        pick the emulator's posterior is conditioned on a run there, on the device, at the fitted hyperparameters -- the variance does
+        not depend on the target, so no stand-in target and no refit are needed (``get_batch_points``, the kriging believer, refits
+        n_points times).  The design then holds the batch as inputs without targets, as ``get_batch_points`` leaves it: supply them with
+        ``set_batch_targets``.  Fewer than n_points rows come back where the criterion has nothing left to gain
+        (``ALCBatchResult.n_picked``); the result of the call is kept in ``self.batch_result``."""
+        from .ActiveLearning import alc_batch
+        n_points = int(n_points)
+        assert n_points > 0, "n_points must be positive"
+        self._check_state(0)
+        self._generate_candidates()
+        self._fit_emulator()
+        self.reference = self.base_design.sample(self.n_ref)
+        self.batch_result = alc_batch(self.gp, self.candidates, self.reference, n_points, noise=self.noise, keep_scores=False)
+        batch = np.array(self.batch_result.points[0][:int(self.batch_result.n_picked[0])])
+        self.inputs = np.vstack([self.inputs, batch])
+        return batch

@@ -28,7 +28,7 @@ from .ExperimentalDesign import ExperimentalDesign, MonteCarloDesign, LatinHyper
 from .Laplace import LaplaceResult, logpost_hessian, laplace_approximation   # noqa: F401
 from .Marginal import predict_marginal, MarginalPredictResult, mixture_weights   # noqa: F401
 from .Sampling import sample_posterior, PosteriorSamples, philox_normals   # noqa: F401
-from .ActiveLearning import predict_cov, alc_criterion, ALCResult   # noqa: F401
+from .ActiveLearning import predict_cov, alc_criterion, ALCResult, alc_batch, ALCBatchResult   # noqa: F401
 
 if HAVE_LIBGPGPU:
     from .GaussianProcessGPU import GaussianProcessGPU, PredictResult   # noqa: F401

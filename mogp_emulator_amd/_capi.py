@@ -96,6 +96,8 @@ SIGNATURES = {
     "mogp_densegp_predict_cov": (c_int, [c_void_p, c_double_p, c_int, c_double_p, c_int, c_int, c_int, c_double_p]),
     "mogp_densegp_alc": (c_int, [c_void_p, c_double_p, c_int, c_double_p, c_int, c_int, c_double_p, c_double_p, c_int, c_int, c_double_p, c_double_p,
                                  c_double_p, c_int_p]),
+    "mogp_densegp_alc_batch": (c_int, [c_void_p, c_double_p, c_int, c_int, c_double_p, c_int, c_int, c_double_p, c_double_p, c_int, c_int, c_int_p,
+                                       c_double_p, c_double_p, c_int_p, c_double_p, c_double_p, c_double_p, c_double_p]),
     "mogp_densegp_loo_variance": (c_int, [c_void_p, c_double_p]),
     "mogp_densegp_get_K": (c_int, [c_void_p, c_double_p]),
     "mogp_densegp_get_invQ": (c_int, [c_void_p, c_double_p]),
@@ -146,6 +148,8 @@ SIGNATURES = {
     "mogp_mogp_predict_cov": (c_int, [c_void_p, c_double_p, c_int, c_double_p, c_int, c_int, c_int, c_double_p]),
     "mogp_mogp_alc": (c_int, [c_void_p, c_double_p, c_int, c_double_p, c_int, c_int, c_double_p, c_double_p, c_int, c_int, c_double_p, c_double_p,
                               c_double_p, c_int_p]),
+    "mogp_mogp_alc_batch": (c_int, [c_void_p, c_double_p, c_int, c_int, c_double_p, c_int, c_int, c_double_p, c_double_p, c_int, c_int, c_int, c_int_p,
+                                    c_double_p, c_double_p, c_int_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int_p]),
     "mogp_mogp_implausibility": (c_int, [c_void_p, c_double_p, c_int, c_int, c_double_p, c_double_p, c_double_p, c_int, c_int, c_double_p]),
     "mogp_mogp_predict_full_cov": (c_int, [c_void_p, c_double_p, c_int, c_int, c_double_p, c_double_p]),
     "mogp_mogp_predict_variance_batch_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),

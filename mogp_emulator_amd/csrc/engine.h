@@ -174,6 +174,63 @@ class Engine {
   // weights that sum to 0.
   void alc(const std::vector<int>& ids, const double* Xc, int mc, const double* Xr, int mr, const double* w, const double* noise, int max_slots,
            int max_points, double* reduction, double* cand_var, double* ref_var, int* degenerate);
+  // Greedy ALC batches at fixed hyperparameters (kernels_alc.hip, DESIGN.md section 3 "Active learning: batches").  The predictive variance
+  // does not depend on the targets, so conditioning on a run at p with noise tau appends one row to the Cholesky factor and one entry
+  // u(x) = c(x, p) / sqrt(s^2(p) + tau) to every stored v(x): c_new(x, x') = c(x, x') - u(x) u(x'), s^2_new(x) = s^2(x) - u(x)^2.  V_c and V_r
+  // are built once, with room for the rows of all T = forced + q steps behind their roundup(n, 16) base rows, and step t is alc's product
+  // over n16 + t rows, alc_finish with the floor of n + t, the pick, and two rank-one updates: no n^3 and no (m_c + m_r) n^2 work per pick.
+  // X (M, D): the candidates; the first `forced` of them are taken in order in steps 0 .. forced - 1 (points already submitted), the other
+  // steps take the unmasked candidate with the largest score, ties to the lowest index.  A step whose best score is not above 0 or whose
+  // denominator is at or below (n + t + 2) 2^-52 sigma^2 picks -1 and conditions on nothing; a picked candidate is masked.
+  // AlcBatch is one group of emulators resident on the device for the whole batch; alc_batch runs the groups of alc_batch_plan one after
+  // another, every step enqueued without a host synchronisation (select = "each").  select = "total" drives one AlcBatch per part from the
+  // C ABI layer: scores() -> the host's sum and arg-max -> apply(pick).  THIS engine is only read, apart from gaining L^-1.
+  struct AlcBatchOut {       // host arrays, rows of the group's emulators; T = forced + q.  red / deg may be null (scores not kept)
+    int* picks;              // (E, T)   -1: nothing picked in that step
+    double* pick_red;        // (E, T)   the score of the pick, 0 where there is none
+    double* red;             // (E, T, M)
+    int* deg;                // (E, T, M)
+    double* cand_var;        // (E, M)   before any step: predict()'s own bits
+    double* ref_var;         // (E, mr)  likewise
+    double* ref_var_after;   // (E, mr)  after the last step, clipped at 0
+    double* iv;              // (E, T + 1)  iv[0] = sum_j w_j ref_var[j] in ascending j, iv[t + 1] = iv[t] - pick_red[t]
+    AlcBatchOut rows_from(size_t e0, int T, int M, int mr) const {
+      return {picks + e0 * T, pick_red + e0 * T, red ? red + e0 * T * M : nullptr, deg ? deg + e0 * T * M : nullptr, cand_var + e0 * M,
+              ref_var + e0 * mr, ref_var_after + e0 * mr, iv + e0 * (T + 1)};
+    }
+  };
+  class AlcBatch {
+   public:
+    // builds V_c, V_r and both variances of emulators grp (tau: their noise variances) and starts the downloads of out.cand_var / ref_var;
+    // out must outlive the object.  The caller has checked the arguments (alc_batch_check) and the memory (alc_batch_plan).
+    AlcBatch(Engine& eng, const std::vector<int>& grp, const double* tau, const double* X, int M, int forced, const double* Xr, int mr,
+             const double* w, int q, const AlcBatchOut& out);
+    int steps() const { return T; }
+    // the scores of step t on the device (product, finish); with out.red they are also on their way to the host
+    void scores(int t);
+    // the same, then waits: row_red / row_deg (E, M) of this step on the host
+    void scores_to_host(int t, double* row_red, int* row_deg);
+    // the pick of step t (forced >= 0: that candidate; -1: the arg-max on the device) and the conditioning on it
+    void apply(int t, int forced);
+    // waits for everything, fills the rest of out
+    void finish();
+
+   private:
+    Engine& e;
+    std::vector<int> ids;
+    AlcBatchOut o;
+    int cnt, M, mr, T, MPc, MPr, tiles_r, rows, n16;
+    std::vector<double> hw;
+    DevBuf<double> dXc, dXr, dW, dTau, dVc, dVr, dPart, dVarC, dVarR, dRed, dPickRed, dPickD;
+    DevBuf<int> dDeg, dMask, dPicks;
+  };
+  // the refusals of a batch, as `alc_batch`; tau (ids) receives the noise variances
+  void alc_batch_check(const std::vector<int>& ids, const double* X, int M, int forced, const double* Xr, int mr, const double* w,
+                       const double* noise, int q, int max_slots, std::vector<double>& tau) const;
+  long alc_batch_slots(long E, int M, int mr, int T, int max_slots, bool total) const;
+  // select = "each": out holds the rows of ids
+  void alc_batch(const std::vector<int>& ids, const double* X, int M, int forced, const double* Xr, int mr, const double* w, const double* noise,
+                 int q, int max_slots, const AlcBatchOut& out);
   void get_invQ(int i, double* out);
   void get_invQt(int i, double* out);
   void get_chol(int i, double* out);

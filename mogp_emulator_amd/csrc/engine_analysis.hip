@@ -718,9 +718,9 @@ void Engine::alc(const std::vector<int>& ids, const double* Xc, int mc, const do
     for (int c0 = 0; c0 < mr; c0 += CH) {
       const int mrc = std::min(CH, mr - c0), MPr = (int)alc_mp(mrc);
       points_v(cnt, dXr + (size_t)c0 * D, mrc, MPr, dK, dDots, dPartial, dVarR + c0, mr, dVr);
-      launch_alc_cross(v, dVc, MPc, mc, dXc, dVr, MPr, mrc, dXr + (size_t)c0 * D, dW + c0, c0 / 128, tiles_r, dPart, stream);
+      launch_alc_cross(v, dVc, MPc, mc, dXc, dVr, MPr, mrc, dXr + (size_t)c0 * D, dW + c0, NP, alc_kend(n), c0 / 128, tiles_r, dPart, stream);
     }
-    launch_alc_finish(v, mc, MPc, tiles_r, dPart, dVarC, mc, dTau, dRed, dDeg, stream);
+    launch_alc_finish(v, n, mc, MPc, tiles_r, dPart, dVarC, mc, dTau, dRed, dDeg, stream);
     // 5. one download
     const size_t oc = (size_t)e0 * mc, orr = (size_t)e0 * mr;
     HIPCK(hipMemcpyAsync(reduction + oc, dRed, (size_t)cnt * mc * sizeof(double), hipMemcpyDeviceToHost, stream));
@@ -731,6 +731,153 @@ void Engine::alc(const std::vector<int>& ids, const double* Xc, int mc, const do
     HIPCK(hipGetLastError());
     for (size_t k = 0; k < (size_t)cnt * mr; ++k)      // s^2 of the reference points as predict() reports it
       if (ref_var[orr + k] < 0.) ref_var[orr + k] = 0.;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Greedy ALC batches (engine.h has the contract, alc_batch_plan of predict_plan.h the sizing).
+//   AlcBatch():  V and s^2 of both sets with predict()'s own launches, V copied behind one another into buffers of n16 + ext rows per slot
+//   scores(t):   alc_cross over the K range [0, n16 + roundup(t, 16)) -- rows not yet written are 0 --, alc_finish with the floor of n + t
+//   apply(t, .): the pick on the device, then the row n16 + t of both sets and their s^2
+//   finish():    the one download of a group
+// ---------------------------------------------------------------------------------------------
+
+void Engine::alc_batch_check(const std::vector<int>& ids, const double* X, int M, int forced, const double* Xr, int mr, const double* w,
+                             const double* noise, int q, int max_slots, std::vector<double>& tau) const {
+  check_cov_args("alc_batch", ids, X, M, Xr, mr, max_slots, 0);
+  if (!w) throw std::runtime_error("alc_batch: null buffer");
+  if (forced < 0 || forced > M) throw std::runtime_error("alc_batch: the pending points are a prefix of the candidates");
+  if (q < 1) throw std::runtime_error("alc_batch: n_points must be at least 1");
+  if (q > M - forced) throw std::runtime_error("alc_batch: n_points must not exceed the number of candidates");
+  double wsum = 0.;
+  for (int j = 0; j < mr; ++j) {
+    if (!std::isfinite(w[j])) throw std::runtime_error("alc_batch: the weights must be finite");
+    if (w[j] < 0.) throw std::runtime_error("alc_batch: the weights must not be negative");
+    wsum += w[j];
+  }
+  if (!(wsum > 0.)) throw std::runtime_error("alc_batch: the weights must not sum to 0");
+  tau.resize(ids.size());
+  for (size_t e = 0; e < ids.size(); ++e) {
+    tau[e] = noise ? noise[e] : nugget_size(ids[e]);
+    if (!(tau[e] >= 0.) || !std::isfinite(tau[e])) throw std::runtime_error("alc_batch: noise must be a finite number that is not negative");
+  }
+}
+
+long Engine::alc_batch_slots(long E, int M, int mr, int T, int max_slots, bool total) const {
+  return alc_batch_plan(E, M, mr, T, LD, NP, free_bytes_or_twice_budget(), max_slots, total);
+}
+
+Engine::AlcBatch::AlcBatch(Engine& eng, const std::vector<int>& grp, const double* tau, const double* X, int M_, int forced, const double* Xr,
+                           int mr_, const double* w, int q, const AlcBatchOut& out)
+    : e(eng), ids(grp), o(out), cnt((int)grp.size()), M(M_), mr(mr_), T(forced + q), MPc((int)alc_mp(M_)), MPr((int)alc_mp(mr_)),
+      tiles_r((int)(alc_mp(mr_) / 128)), rows(alc_kend(eng.n) + (int)alc_ext_rows(forced + q)), n16(alc_kend(eng.n)), hw(w, w + mr_) {
+  const int NP = e.NP, LD = e.LD, D = e.D, MPmax = std::max(MPc, MPr);
+  const size_t sl = (size_t)cnt, nti = (size_t)(e.n + 127) / 128;
+  hipStream_t st = e.stream;
+  e.ensure_linv(ids);
+  dXc.reserve((size_t)M * D), dXr.reserve((size_t)mr * D), dW.reserve((size_t)mr), dTau.reserve(sl);
+  dVc.reserve(sl * rows * MPc), dVr.reserve(sl * rows * MPr), dPart.reserve(sl * tiles_r * MPc);
+  dVarC.reserve(sl * M), dVarR.reserve(sl * mr), dRed.reserve(sl * M), dPickRed.reserve(sl * T), dPickD.reserve(sl * T);
+  dDeg.reserve(sl * M), dMask.reserve(sl * M), dPicks.reserve(sl * T);
+  // scratch of the build alone
+  DevBuf<double> dK(sl * MPmax * LD), dDots(sl * MPmax), dPartial(sl * nti * MPmax), dV(sl * NP * MPmax);
+  SyncOnUnwind drained{st};
+  HIPCK(hipMemcpyAsync(dXc, X, (size_t)M * D * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCK(hipMemcpyAsync(dXr, Xr, (size_t)mr * D * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCK(hipMemcpyAsync(dW, w, (size_t)mr * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCK(hipMemcpyAsync(dTau, tau, sl * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCK(hipMemsetAsync(dVc, 0, sl * rows * MPc * sizeof(double), st));
+  HIPCK(hipMemsetAsync(dVr, 0, sl * rows * MPr * sizeof(double), st));
+  HIPCK(hipMemsetAsync(dMask, 0, sl * M * sizeof(int), st));
+  HIPCK(hipMemsetAsync(dPicks, 0xff, sl * T * sizeof(int), st));
+  HIPCK(hipMemsetAsync(dPickRed, 0, sl * T * sizeof(double), st));
+  e.upload_idx(ids);
+  // the n16 base rows of every slot, from slots NP rows apart to slots `rows` rows apart
+  const auto widen = [&](double* dst, int MP) {
+    for (size_t s = 0; s < sl; ++s)
+      HIPCK(hipMemcpyAsync(dst + s * rows * MP, dV.get() + s * NP * MP, (size_t)n16 * MP * sizeof(double), hipMemcpyDeviceToDevice, st));
+  };
+  e.points_v(cnt, dXc, M, MPc, dK, dDots, dPartial, dVarC, M, dV);
+  widen(dVc, MPc);
+  e.points_v(cnt, dXr, mr, MPr, dK, dDots, dPartial, dVarR, mr, dV);
+  widen(dVr, MPr);
+  HIPCK(hipMemcpyAsync(o.cand_var, dVarC, sl * M * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCK(hipMemcpyAsync(o.ref_var, dVarR, sl * mr * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCK(hipStreamSynchronize(st));            // the scratch goes
+  HIPCK(hipGetLastError());
+  for (size_t k = 0; k < sl * M; ++k)         // s^2 as predict() reports it
+    if (o.cand_var[k] < 0.) o.cand_var[k] = 0.;
+  for (size_t k = 0; k < sl * mr; ++k)
+    if (o.ref_var[k] < 0.) o.ref_var[k] = 0.;
+}
+
+void Engine::AlcBatch::scores(int t) {
+  hipStream_t st = e.stream;
+  e.upload_idx(ids);
+  const BatchView v = e.view(cnt);
+  launch_alc_cross(v, dVc, MPc, M, dXc, dVr, MPr, mr, dXr, dW, rows, n16 + (t + 15) / 16 * 16, 0, tiles_r, dPart, st);
+  launch_alc_finish(v, e.n + t, M, MPc, tiles_r, dPart, dVarC, M, dTau, dRed, dDeg, st);
+  for (int s = 0; s < cnt; ++s) {            // this step's rows of every slot, (T, M) apart on the host
+    if (o.red) HIPCK(hipMemcpyAsync(o.red + ((size_t)s * T + t) * M, dRed.get() + (size_t)s * M, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (o.deg) HIPCK(hipMemcpyAsync(o.deg + ((size_t)s * T + t) * M, dDeg.get() + (size_t)s * M, (size_t)M * sizeof(int), hipMemcpyDeviceToHost, st));
+  }
+}
+
+void Engine::AlcBatch::scores_to_host(int t, double* row_red, int* row_deg) {
+  scores(t);
+  HIPCK(hipMemcpyAsync(row_red, dRed, (size_t)cnt * M * sizeof(double), hipMemcpyDeviceToHost, e.stream));
+  HIPCK(hipMemcpyAsync(row_deg, dDeg, (size_t)cnt * M * sizeof(int), hipMemcpyDeviceToHost, e.stream));
+  HIPCK(hipStreamSynchronize(e.stream));
+  HIPCK(hipGetLastError());
+}
+
+void Engine::AlcBatch::apply(int t, int forced) {
+  hipStream_t st = e.stream;
+  e.upload_idx(ids);
+  const BatchView v = e.view(cnt);
+  launch_alc_argmax(v, t, T, forced, M, dRed, dVarC, M, dTau, dMask, dPicks, dPickRed, dPickD, st);
+  launch_alc_condition(v, t, T, rows, dPicks, dPickD, dVc, MPc, dXc, dVc, MPc, M, dXc, dVarC, M, st);
+  launch_alc_condition(v, t, T, rows, dPicks, dPickD, dVc, MPc, dXc, dVr, MPr, mr, dXr, dVarR, mr, st);
+}
+
+void Engine::AlcBatch::finish() {
+  hipStream_t st = e.stream;
+  const size_t sl = (size_t)cnt;
+  HIPCK(hipMemcpyAsync(o.picks, dPicks, sl * T * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCK(hipMemcpyAsync(o.pick_red, dPickRed, sl * T * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCK(hipMemcpyAsync(o.ref_var_after, dVarR, sl * mr * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCK(hipStreamSynchronize(st));
+  HIPCK(hipGetLastError());
+  for (size_t k = 0; k < sl * mr; ++k)
+    if (o.ref_var_after[k] < 0.) o.ref_var_after[k] = 0.;
+  for (size_t s = 0; s < sl; ++s) {
+    double* iv = o.iv + s * (T + 1);
+    double a = 0.;
+    for (int j = 0; j < mr; ++j) a += hw[j] * o.ref_var[s * mr + j];
+    iv[0] = a;
+    for (int t = 0; t < T; ++t) iv[t + 1] = iv[t] - o.pick_red[s * T + t];
+  }
+}
+
+void Engine::alc_batch(const std::vector<int>& ids, const double* X, int M, int forced, const double* Xr, int mr, const double* w,
+                       const double* noise, int q, int max_slots, const AlcBatchOut& out) {
+  const long E = (long)ids.size();
+  if (E == 0) return;
+  std::vector<double> tau;
+  alc_batch_check(ids, X, M, forced, Xr, mr, w, noise, q, max_slots, tau);
+  if (!out.picks || !out.pick_red || !out.cand_var || !out.ref_var || !out.ref_var_after || !out.iv) throw std::runtime_error("alc_batch: null buffer");
+  const int T = forced + q;
+  const long slots = alc_batch_slots(E, M, mr, T, max_slots, false);
+  for (long e0 = 0; e0 < E; e0 += slots) {
+    const long cnt = std::min(slots, E - e0);
+    const std::vector<int> grp(ids.begin() + e0, ids.begin() + e0 + cnt);
+    AlcBatch run(*this, grp, tau.data() + e0, X, M, forced, Xr, mr, w, q, out.rows_from((size_t)e0, T, M, mr));
+    SyncOnUnwind drained{stream};
+    for (int t = 0; t < T; ++t) {
+      run.scores(t);
+      run.apply(t, t < forced ? t : -1);
+    }
+    run.finish();
   }
 }
 

@@ -284,12 +284,28 @@ void launch_alc_store(const BatchView& v, const double* V1, int MP1, int m1, con
 // reduce: the columns are one chunk of the reference points, its first 128-point tile number tile0 of tiles_r in the whole set, w its
 // weights (m2); part[(slot * tiles_r + tile0 + tj) * MP1 + i] = sum over the tile's columns j of w_j c(x_i, r_j)^2: ONE writer per entry, a
 // fixed order inside the tile (the lane's four column blocks ascending, a 16-lane butterfly, the two wave columns), no atomics.
+// rows: the rows of V per slot (v.NP as launch_predict_v_store leaves them; more where conditioning rows follow the base rows, alc_batch);
+// kend: the K range [0, kend) of the product, whole 16-row steps (alc_kend(n) for the stored V alone).
+inline int alc_kend(int n) { return (n + 15) / 16 * 16; }
 void launch_alc_cross(const BatchView& v, const double* V1, int MP1, int m1, const double* X1, const double* V2, int MP2, int m2, const double* X2,
-                      const double* w, int tile0, int tiles_r, double* part, hipStream_t s);
-// per (slot, candidate i < m1): var[slot * var_ld + i] <- max(var, 0) = s^2; d = s^2 + tau[slot]; with the floor (n + 2) 2^-52 sigma^2:
-// d <= floor (or not a number): red = 0, deg = 1; else red = (sum of the tiles_r partials, ascending) / d, deg = 0
-void launch_alc_finish(const BatchView& v, int m1, int MP1, int tiles_r, const double* part, double* var, int var_ld, const double* tau,
+                      const double* w, int rows, int kend, int tile0, int tiles_r, double* part, hipStream_t s);
+// per (slot, candidate i < m1): var[slot * var_ld + i] <- max(var, 0) = s^2; d = s^2 + tau[slot]; with the floor (nrows + 2) 2^-52 sigma^2
+// (nrows = n, plus the picks conditioned on so far in alc_batch): d <= floor (or not a number): red = 0, deg = 1; else
+// red = (sum of the tiles_r partials, ascending) / d, deg = 0
+void launch_alc_finish(const BatchView& v, int nrows, int m1, int MP1, int tiles_r, const double* part, double* var, int var_ld, const double* tau,
                        double* red, int* deg, hipStream_t s);
+// Greedy ALC batches (Engine::AlcBatch; DESIGN.md section 3 "Active learning: batches").  Per slot, step t of T:
+//   argmax   the pick of step t: forced >= 0 that candidate, else the candidate with mask == 0 and the largest red (ties: the lowest index;
+//            NaN never wins).  With d = max(var[pick], 0) + tau and the floor (n + t + 2) 2^-52 sigma^2: no candidate left, a best score
+//            that is not above 0 or d at or below the floor give picks[slot * T + t] = -1, pick_red = 0 (nothing is conditioned on);
+//            else picks = the index, pick_red = its red, pick_d = d.  mask[pick] = 1 either way.  One workgroup per slot.
+//   condition  for the m points X (V (nb, rows, MP), tracked variances var) and the pick p of step t (Vc (nb, rows, MPc), Xc its
+//            points): u(x) = (sigma^2 k(x, x_p) - sum_{k < n16 + t} V[k][x] Vc[k][p]) / sqrt(pick_d);  V[n16 + t][x] = u(x);
+//            var[x] -= u(x)^2.  A slot whose pick is -1 is left alone (its row stays 0).  k in a fixed order, one owner per output.
+void launch_alc_argmax(const BatchView& v, int t, int T, int forced, int m, const double* red, const double* var, int var_ld, const double* tau,
+                       int* mask, int* picks, double* pick_red, double* pick_d, hipStream_t s);
+void launch_alc_condition(const BatchView& v, int t, int T, int rows, const int* picks, const double* pick_d, const double* Vc, int MPc,
+                          const double* Xc, double* V, int MP, int m, const double* X, double* var, int var_ld, hipStream_t s);
 
 // --- utilities -------------------------------------------------------------------------------
 // out (n,n) <- tile of src (NP,NP): mode 0 copy, mode 1 transpose of the lower triangle (zeros below the diagonal of out), mode 2 symmetrise from lower

@@ -1,7 +1,7 @@
 // How the prediction family of Engine (engine_predict.hip) and the analysis family (engine_analysis.hip: hessian, predict_mixture,
-// cross_validate, sample_posterior, alc, predict_cov) cut their work to a byte budget, the index tables of their passes, and where the mean-function terms of a prediction are
+// cross_validate, sample_posterior, alc, alc_batch, predict_cov) cut their work to a byte budget, the index tables of their passes, and where the mean-function terms of a prediction are
 // staged.  Plain host arithmetic with no HIP in it, so that a host compiler takes it and tests/c/predict_plan_check.cpp, mixture_plan_check.cpp,
-// cv_plan_check.cpp, sample_plan_check.cpp and alc_plan_check.cpp can check it without a device.  The caps that need the device (MOGP_KS_BUDGET_GB, free memory) are passed in.
+// cv_plan_check.cpp, sample_plan_check.cpp, alc_plan_check.cpp and alc_batch_plan_check.cpp can check it without a device.  The caps that need the device (MOGP_KS_BUDGET_GB, free memory) are passed in.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -221,6 +221,42 @@ inline AlcPlan alc_plan(long E, long m_c, long m_r, int LD, int NP, double free_
   slots = std::min<long>(slots, 65535);
   if (max_slots > 0) slots = std::min<long>(slots, max_slots);
   return {std::max<long>(1, slots), points};
+}
+// Engine::alc_batch: how many emulators one group takes.  V_r stays resident across the picks, so the reference set is ONE chunk, and both
+// V carry ext = roundup(steps, 16) conditioning rows behind their base rows (steps = pending points + picks).  Bytes of one slot:
+//   alc_slot_bytes with NP + ext rows and points = MP_r = roundup(m_r, 128)
+//   + 8 NP max(MP_c, MP_r)                      the stored V as launch_predict_v_store leaves it, before it is copied into the wider buffer
+//   + 8 (NP / 128 + 2) max(MP_c, MP_r)          the partial sums of the predictive variance and the unused dot products
+//   + 8 (2 MP_c + MP_r + 2 ext)                 tracked variances of both sets, the scores, the score and the denominator of every pick
+//   + 4 (2 MP_c + ext)                          mask, degenerate flags, picks
+// A group takes at most half of the free device memory.  select = "each": groups of `slots` emulators in caller order, at most E, 65535
+// and max_slots where given; one emulator's picks do not depend on its group.  select = "total" (total = true): every emulator of the call
+// must sit in one group, since each step's score sums over them; refused otherwise, with the bytes named.  Throws when one emulator does not fit.
+inline long alc_ext_rows(long steps) { return (std::max<long>(1, steps) + 15) / 16 * 16; }
+inline double alc_batch_slot_bytes(int NP, int LD, long MPc, long MPr, long tiles_r, long ext) {
+  const double mpx = (double)std::max(MPc, MPr);
+  return alc_slot_bytes(NP + (int)ext, LD, MPc, MPr, tiles_r) + 8.0 * (double)NP * mpx + 8.0 * (double)(NP / 128 + 2) * mpx +
+         8.0 * (double)(2 * MPc + MPr + 2 * ext) + 4.0 * (double)(2 * MPc + ext);
+}
+inline long alc_batch_plan(long E, long m_c, long m_r, long steps, int LD, int NP, double free_bytes, int max_slots, bool total) {
+  if (max_slots < 0) throw std::runtime_error("alc_batch: max_slots must not be negative");
+  const long MPc = alc_mp(std::max<long>(1, m_c)), MPr = alc_mp(std::max<long>(1, m_r));
+  const double per = alc_batch_slot_bytes(NP, LD, MPc, MPr, MPr / 128, alc_ext_rows(steps));
+  const std::string shape = std::to_string(m_c) + " candidates, " + std::to_string(m_r) + " reference points and " + std::to_string(steps) + " steps";
+  if (per > 0.5 * free_bytes)
+    throw std::runtime_error("alc_batch: one emulator at " + shape + " needs " + std::to_string((long long)per) +
+                             " bytes of device scratch, more than half of the free device memory; use fewer points per call");
+  long slots = std::min<long>(slots_in_half_of(free_bytes, per), std::max<long>(1, E));
+  slots = std::min<long>(slots, 65535);
+  if (total) {
+    if (slots < E)
+      throw std::runtime_error("alc_batch: select=\"total\" needs all " + std::to_string(E) + " emulators of a device in one group: at " + shape +
+                               " that is " + std::to_string((long long)(per * (double)E)) + " bytes of device scratch, and half of the free memory is " +
+                               std::to_string((long long)(0.5 * free_bytes)) + "; use fewer points per call or select=\"each\"");
+    return slots;       // (max_slots does not apply)
+  }
+  if (max_slots > 0) slots = std::min<long>(slots, max_slots);
+  return std::max<long>(1, slots);
 }
 // Engine::predict_cov: V_1, V_2, the output and the K* scratch of one emulator against the 64 GB rule of predict_full_cov
 inline double predict_cov_rule_bytes(long m1, long m2, int LD, int NP) {

@@ -184,6 +184,35 @@ def _alc_call(fn, handle, lead, xc, xr, weights, noise, max_slots, max_points):
     return red, cv, rv, deg.astype(bool)
 
 
+def _alc_batch_call(fn, handle, lead, x, n_forced, xr, weights, noise, n_points, total, max_slots, keep_scores):
+    """shared by DenseGP_GPU.alc_batch and MultiOutputGP_GPU.alc_batch: x (m, D) = the pending points then the candidates, T = n_forced +
+    n_points steps -> dict of picks lead + (T,) (-1: none), pick_red lead + (T,), red / deg lead + (T, m) or None, cand_var lead + (m,),
+    ref_var / ref_var_after lead + (m_r,), iv lead + (T + 1,), total_picks (T,) or None"""
+    m, mr, T = x.shape[0], xr.shape[0], int(n_forced) + int(n_points)
+    w = _f64(weights, 1, "weights")
+    if w.shape[0] != mr:
+        raise ValueError("alc_batch: weights must have one entry per reference point")
+    if noise is not None:
+        noise = _f64(noise, 1, "noise")
+        if noise.shape != (lead or (1,)):
+            raise ValueError("alc_batch: noise must have one entry per emulator")
+    picks = np.full(lead + (T,), -1, dtype=np.int32)
+    pick_red, iv = np.zeros(lead + (T,)), np.zeros(lead + (T + 1,))
+    red = np.zeros(lead + (T, m)) if keep_scores else None
+    deg = np.zeros(lead + (T, m), dtype=np.int32) if keep_scores else None
+    cv, rv, rva = np.zeros(lead + (m,)), np.zeros(lead + (mr,)), np.zeros(lead + (mr,))
+    head = (handle, dptr(x), m, int(n_forced), dptr(xr), mr, x.shape[1], dptr(w), dptr(noise), int(n_points))
+    tail = (iptr(picks), dptr(pick_red), dptr(red), iptr(deg), dptr(cv), dptr(rv), dptr(rva), dptr(iv))
+    tp = None
+    if lead:
+        tp = np.full(T, -1, dtype=np.int32) if total else None
+        check(fn(*(head + (int(bool(total)), int(max_slots)) + tail + (iptr(tp),))))
+    else:
+        check(fn(*(head + (int(max_slots),) + tail)))
+    return dict(picks=picks, pick_red=pick_red, red=red, deg=None if deg is None else deg.astype(bool), cand_var=cv, ref_var=rv,
+                ref_var_after=rva, iv=iv, total_picks=tp)
+
+
 def _sobol_call(fn, handle, D, n_out, A, B, unc, include_nugget):
     """shared by DenseGP_GPU.sobol and MultiOutputGP_GPU.sobol: (S, ST, mean, variance, emulator_variance or None), one row per output"""
     a, b = _f64(A, 2, "A"), _f64(B, 2, "B")
@@ -864,6 +893,12 @@ class DenseGP_GPU(object):
         return _alc_call(_lib.mogp_densegp_alc, self._h, (), self._testing(candidates), self._testing(reference), weights,
                          None if noise is None else np.array([float(noise)]), max_slots, max_points)
 
+    def alc_batch(self, x, n_forced, reference, weights, n_points, noise=None, max_slots=0, keep_scores=True):
+        """A greedy ALC batch on the device, the posterior conditioned on every pick: x (m, D) = n_forced pending points, then the
+        candidates.  See _alc_batch_call for what comes back and mogp_densegp_alc_batch (include/mogp_hip.h) for the rules."""
+        return _alc_batch_call(_lib.mogp_densegp_alc_batch, self._h, (), self._testing(x), n_forced, self._testing(reference), weights,
+                               None if noise is None else np.array([float(noise)]), n_points, False, max_slots, keep_scores)
+
     # -- predict ------------------------------------------------------------------------------
     def _testing(self, testing):
         x = _f64(testing)
@@ -1220,6 +1255,12 @@ class MultiOutputGP_GPU(object):
         emulators that are not fit are NaN."""
         return _alc_call(_lib.mogp_mogp_alc, self._h, (self.n_emulators(),), self._testing(candidates), self._testing(reference), weights,
                          noise, max_slots, max_points)
+
+    def alc_batch(self, x, n_forced, reference, weights, n_points, noise=None, total=False, max_slots=0, keep_scores=True):
+        """DenseGP_GPU.alc_batch for every emulator (total False) or one batch for the model (total True: total_picks (T,)); noise
+        (n_emulators,) or None.  Rows of emulators that are not fit are NaN with picks of -1.  See mogp_mogp_alc_batch."""
+        return _alc_batch_call(_lib.mogp_mogp_alc_batch, self._h, (self.n_emulators(),), self._testing(x), n_forced,
+                               self._testing(reference), weights, noise, n_points, total, max_slots, keep_scores)
 
     def predict_variance_batch_dev(self, d_testing, m, d_means, d_vars):
         """Device-pointer variant: inputs already resident in HBM, results stay in HBM."""
