@@ -438,6 +438,24 @@ int mogp_gkdr_R(const double* X, int n, int m, const double* y, int nx, const do
    finite and their squared distances must not overflow: a NaN coordinate is NOT reported (the minimum skips it), and out[t] is
    +infinity when every squared distance of design t overflows.  (The Python shim rejects non-finite designs before the call.) */
 int mogp_design_min_pdist(const double* designs, int T, int n, int D, double* out);
+
+/* ---- local approximate GP prediction for large designs (mogp_emulator_amd/LocalGP.py) ---- */
+/* The handle keeps the design `inputs` (N, D) and E rows of residual targets `residuals` (E, N) -- targets minus the mean function -- on
+   device `device` (< 0: the current device); N < 2^31 - 256, 1 <= D <= 80.  NULL on failure. */
+typedef struct mogp_local mogp_local;
+mogp_local* mogp_local_create(const double* inputs, long long N, int D, const double* residuals, int E, int device);
+/* Predict the residual of row `emulator` at `testing` (m, D) from the k nearest design points of every query, 1 <= k <= min(N, 126).
+   kernel_type: 0 squared exponential, 1 Matern 5/2 of the scaled distance; scale (D): s_d = sqrt(exp(theta_d)).  The device forms
+   x~ = x_d * s_d and q~ = q_d * s_d (one rounded multiply each) and r2 = ((0 + t_0 t_0) + t_1 t_1) + ..., t_d = x~_d - q~_d, in the order
+   d = 0 .. D-1, every operation rounded on its own (no fused multiply-add).  The neighbours of a query are the k smallest pairs
+   (r2, index) in lexicographic order, listed ascending: neighbours_out (m, k) or NULL, radius_out (m) = the r2 of the last one.
+   mean_out (m) = y^T Q^-1 k*, var_out (m, or NULL) = max(sigma2 - k*^T Q^-1 k* + (include_nugget ? nugget : 0), 0) with
+   Q = sigma2 k(.,.) + (nugget + jitter) I over the neighbours; ok_out (m) = 0 where Q is not positive definite (mean and variance NaN).
+   max_points: queries per device pass, 0 = sized by the free device memory; no result bit depends on it. */
+int mogp_local_predict(mogp_local* h, int emulator, int kernel_type, const double* scale, double sigma2, double nugget, double jitter,
+                       int include_nugget, const double* testing, int m, int D, int k, int max_points, double* mean_out, double* var_out,
+                       int* ok_out, double* radius_out, int* neighbours_out);
+void mogp_local_destroy(mogp_local* h);
 /* device memory helpers so a host program can hand device-resident buffers to the *_dev calls */
 void* mogp_dev_malloc(unsigned long long bytes);
 int mogp_dev_free(void* d_ptr);

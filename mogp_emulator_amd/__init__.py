@@ -20,6 +20,7 @@ mogp_emulator_amd -- MI355X (gfx950) native fit + predict backend for mogp_emula
   Sampling.py      joint posterior sample paths f(X*) ~ N(mu*, Sigma*): covariance, Cholesky factor, normals and mu + L z on the device
   ActiveLearning.py
                    posterior covariance between two point sets and the ALC (integrated-variance) design criterion, reduced on the device
+  LocalGP.py       local approximate GP prediction for designs beyond the dense path: k nearest neighbours and one small GP per query, on the device
   dist.py          one-process-per-GPU sharding of emulators + single gather (torch.distributed/RCCL)
 """
 from .LibGPGPU import HAVE_LIBGPGPU, gpu_usable            # noqa: F401
@@ -29,6 +30,7 @@ from .Laplace import LaplaceResult, logpost_hessian, laplace_approximation   # n
 from .Marginal import predict_marginal, MarginalPredictResult, mixture_weights   # noqa: F401
 from .Sampling import sample_posterior, PosteriorSamples, philox_normals   # noqa: F401
 from .ActiveLearning import predict_cov, alc_criterion, ALCResult, alc_batch, ALCBatchResult   # noqa: F401
+from .LocalGP import LocalGP, LocalPrediction, predict_local   # noqa: F401
 
 if HAVE_LIBGPGPU:
     from .GaussianProcessGPU import GaussianProcessGPU, PredictResult   # noqa: F401

@@ -1,6 +1,6 @@
 // Shared by the capi*.hip units only: the handle types behind include/mogp_hip.h, the error channel, the guards that turn C++
 // exceptions into (non-zero status, thread-local message), and the driver of a multi-part handle.  Everything but the handle types
-// (which the C header names) sits in mogp::capi, so that the library's C symbols stay the 119 of the header.
+// (which the C header names) sits in mogp::capi, so that the library's C symbols stay the 122 of the header.
 #pragma once
 #include <cstring>
 #include <exception>

@@ -1,0 +1,46 @@
+// The local-approximate-GP entries of the C ABI: a handle that keeps a large design on the device and predicts every query from its nearest
+// design points alone (LocalGP, kernels_local.hip).  No Engine is involved.
+#include "capi_internal.h"
+
+using namespace mogp;
+using namespace mogp::capi;
+
+struct mogp_local { std::unique_ptr<mogp::LocalGP> gp; };
+
+extern "C" {
+
+mogp_local* mogp_local_create(const double* inputs, long long N, int D, const double* residuals, int E, int device) {
+  mogp_local* h = nullptr;
+  const int status = guarded([&] {
+    std::unique_ptr<mogp_local> p(new mogp_local);
+    if (device < 0) hip_check(hipGetDevice(&device), "hipGetDevice");
+    DeviceGuard g(device);
+    p->gp.reset(new LocalGP(inputs, (long)N, D, residuals, E));
+    h = p.release();
+  });
+  return status == 0 ? h : nullptr;
+}
+
+int mogp_local_predict(mogp_local* h, int emulator, int kernel_type, const double* scale, double sigma2, double nugget, double jitter,
+                       int include_nugget, const double* testing, int m, int D, int k, int max_points, double* mean_out, double* var_out,
+                       int* ok_out, double* radius_out, int* neighbours_out) {
+  return guarded([&] {
+    if (!h || !h->gp) throw std::runtime_error("predict_local: null handle");
+    if (D != h->gp->D) throw std::runtime_error("predict_local: testing points must have D columns");
+    h->gp->predict(emulator, kernel_type, scale, sigma2, nugget, jitter, include_nugget != 0, testing, m, k, max_points, mean_out, var_out, ok_out,
+                   radius_out, neighbours_out);
+  });
+}
+
+void mogp_local_destroy(mogp_local* h) {
+  if (!h) return;
+  (void)guarded([&] {
+    if (h->gp) {
+      DeviceGuard g(h->gp->device_id());
+      h->gp.reset();
+    }
+  });
+  delete h;
+}
+
+}  // extern "C"

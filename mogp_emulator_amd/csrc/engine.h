@@ -434,6 +434,25 @@ constexpr int DESIGN_MAX_PASS = 32768;      // designs per pass (the second grid
 constexpr int DESIGN_MAX_N = 370688;        // points per design: 64 x 64 tiles of the lower triangle x 256 threads < 2^32 work-items
 void design_min_pdist(const double* designs, int T, int n, int D, double* out);
 
+// Local approximate GP prediction (kernels_local.hip; DESIGN.md section 3 "Local prediction"): the design (N, D) and E rows of residual
+// targets stay on the device the handle was created on; every predict() finds the k nearest design points of each query in the metric
+// of `scale` and predicts from that k-point GP alone.  No Engine: nothing here factors the whole design.
+class LocalGP {
+ public:
+  LocalGP(const double* inputs, long N, int D, const double* resid, int E);
+  // host pointers; var / nbr may be null.  kt: 0 squared exponential, 1 Matern 5/2.
+  void predict(int e, int kt, const double* scale, double sigma2, double nugget, double jitter, bool include_nugget, const double* testing, long m,
+               int k, int max_points, double* mean, double* var, int* ok, double* radius, int* nbr);
+  int device_id() const { return device; }
+  const long N;
+  const int D, E;
+
+ private:
+  int device = 0, n_cu = 1;
+  DevBuf<double> dX, dY, dXs, dScale;
+  std::vector<double> hScale;        // the scales dXs was formed with (empty: not formed yet)
+};
+
 // measurement hooks (mogp_profile_schedule): force the Cholesky schedule / serialise it onto one stream so that the
 // HIP-event time of a kernel is its time alone on the device; -1 / false = the library's own choice.
 // FOR MEASUREMENT ONLY: process-global, read by every engine at the start of a factorisation and not synchronised --

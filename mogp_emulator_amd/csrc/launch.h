@@ -307,6 +307,27 @@ void launch_alc_argmax(const BatchView& v, int t, int T, int forced, int m, cons
 void launch_alc_condition(const BatchView& v, int t, int T, int rows, const int* picks, const double* pick_d, const double* Vc, int MPc,
                           const double* Xc, double* V, int MP, int m, const double* X, double* var, int var_ld, hipStream_t s);
 
+// --- local approximate GP (kernels_local.hip) -----------------------------------------------------------
+// Prediction from the k nearest design points of every query alone (DESIGN.md section 3 "Local prediction").  Point indices are int (N < 2^31),
+// element offsets size_t.
+constexpr int LOCAL_MAX_K = 126;        // k neighbours + the target row + the query row share ONE 128 x 128 tile
+constexpr int LOCAL_KNN_QW = 4;         // queries per wave of the neighbour search
+constexpr int LOCAL_KNN_QUERIES = 4 * LOCAL_KNN_QW;    // ... per 256-thread workgroup
+constexpr int LOCAL_KNN_ROWS = 128;     // design rows per staged tile
+// per workgroup of local_gp_kernel: the 128 x 128 tile and the pack chol128_dev writes beside it (chol128_dev.h PACK128_STRIDE)
+constexpr size_t LOCAL_WG_DOUBLES = (size_t)128 * 128 + 128 * 128 + 8 * 256;
+// out[i][d] = x[i][d] * s[d]: one rounded multiply per element
+void launch_local_scale(const double* x, long rows, int D, const double* s, double* out, hipStream_t st);
+// Xs (N, D) and Qs (mc, D) scaled as above.  Per query the k smallest pairs (r2, index) in lexicographic order, ascending, r2 =
+// ((0 + t_0 t_0) + t_1 t_1) + ..., t_d = Xs[i][d] - Qs[q][d], every operation rounded on its own (no FMA): nbr (mc, k), radius (mc) = the
+// r2 of the last one.  One wave per LOCAL_KNN_QW queries, no atomics; a query's result does not depend on the others of the launch.
+void launch_local_knn(const double* Xs, long N, int D, const double* Qs, int mc, int k, int* nbr, double* radius, hipStream_t st);
+// Per query the GP on its k neighbours: mean = y^T Q^-1 k*, var = max(sigma2 - |L^-1 k*|^2 + var_add, 0), Q = sigma2 k(.,.) + diag_add I over
+// the neighbours, kt = 0 squared exponential / 1 Matern 5/2 of the scaled distance; Y (N) residual targets.  ok = 0 and NaN where Q is not
+// positive definite.  grid persistent workgroups, scratch: grid * LOCAL_WG_DOUBLES doubles.  No result bit depends on grid.
+void launch_local_gp(const double* Xs, const double* Y, long N, int D, const double* Qs, int mc, int k, const int* nbr, int kt, double sigma2,
+                     double diag_add, double var_add, double* scratch, int grid, double* mean, double* var, int* ok, hipStream_t st);
+
 // --- utilities -------------------------------------------------------------------------------
 // out (n,n) <- tile of src (NP,NP): mode 0 copy, mode 1 transpose of the lower triangle (zeros below the diagonal of out), mode 2 symmetrise from lower
 void launch_extract(const double* src, int NP, int n, double* out, int mode, hipStream_t s);

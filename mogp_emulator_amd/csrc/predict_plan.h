@@ -264,6 +264,40 @@ inline double predict_cov_rule_bytes(long m1, long m2, int LD, int NP) {
   return 8.0 * ((double)NP * (MP1 + MP2) + (double)m1 * (double)m2 + (double)LD * std::max(MP1, MP2));
 }
 
+// LocalGP::predict (kernels_local.hip): how many queries one pass takes and how many persistent workgroups factor their local matrices.
+// Bytes of one query of a pass (local_point_bytes): its raw and its scaled coordinates (2 D doubles), k neighbour indices and the ok flag
+// (ints), radius, mean and variance (doubles).  Every workgroup owns wg_bytes of scratch (launch.h LOCAL_WG_DOUBLES).
+//   grid    LOCAL_GRID_PER_CU workgroups per compute unit, never more than the queries of a pass, at least one
+//   points  max_points where given, else what half of the free device memory holds beside the scratch of a full grid; at most m and
+//           LOCAL_MAX_PASS, at least one
+// Neither changes a bit of a result: a query's neighbours and its factorisation depend on nothing but the query.  Throws for a negative
+// max_points and when one query beside one workgroup's scratch does not fit.
+constexpr long LOCAL_GRID_PER_CU = 4, LOCAL_MAX_PASS = 1L << 20;
+struct LocalPlan {
+  long points;
+  int grid;
+};
+inline double local_point_bytes(int D, int k) { return 8.0 * (2.0 * D + 3.0) + 4.0 * (k + 1.0); }
+inline LocalPlan local_plan(long m, int D, int k, int n_cu, double free_bytes, int max_points, double wg_bytes) {
+  if (max_points < 0) throw std::runtime_error("predict_local: max_points must not be negative");
+  const long full = LOCAL_GRID_PER_CU * std::max(1, n_cu);
+  const double budget = 0.5 * free_bytes, per = local_point_bytes(D, k);
+  const long want = std::max<long>(1, std::min<long>(m, LOCAL_MAX_PASS));
+  long points;
+  if (max_points > 0) {
+    points = std::min<long>(want, max_points);
+    if ((double)points * per + (double)std::min(points, full) * wg_bytes > budget)
+      throw std::runtime_error("predict_local: " + std::to_string(points) + " queries per pass need more than half of the free device memory; use a smaller max_points");
+  } else {
+    const double left = budget - (double)std::min(want, full) * wg_bytes;
+    if (left < per)
+      throw std::runtime_error("predict_local: the scratch of " + std::to_string(std::min(want, full)) +
+                               " workgroups does not fit half of the free device memory");
+    points = std::min<long>(want, (long)std::floor(left / per));
+  }
+  return {points, (int)std::min(points, full)};
+}
+
 // Stage 2 of Engine::predict_mixture: the normalised weights of the S samples of one emulator, from their negative log-posteriors F and
 // ok flags and EITHER explicit weights w_in OR the log proposal density log_q (up to a constant).  With log_q:
 //   l_s = -(F_s - F_min) - (log_q_s - log_q_a),  a = the first ok sample with F_a = F_min over the ok samples,  w_s = exp(l_s - max l)

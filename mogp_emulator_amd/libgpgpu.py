@@ -26,7 +26,7 @@ __all__ = [
     "WeakPrior", "InvGammaPrior", "GammaPrior", "LogNormalPrior",
     "BaseTransform", "CovTransform", "CorrTransform",
     "SquaredExponentialKernel", "Matern52Kernel", "MeanPriors", "set_fit_options", "set_device", "device_count", "pivot_cholesky",
-    "gkdr_R", "design_min_pdist",
+    "gkdr_R", "design_min_pdist", "LocalGP_GPU",
 ]
 
 
@@ -1335,6 +1335,43 @@ def design_min_pdist(designs):
     if T:
         check(_lib.mogp_design_min_pdist(dptr(designs), T, n, D, dptr(out)))
     return out
+
+
+class LocalGP_GPU(object):
+    """Native handle of ``LocalGP`` (csrc/kernels_local.hip): the design ``inputs`` (N, D) and the residual targets ``residuals`` (E, N) stay
+    on ``device`` (None: the current device) until ``close()``.  The arguments are taken as they are: ``LocalGP.py`` has checked them."""
+
+    def __init__(self, inputs, residuals, device=None):
+        self._h = None
+        inputs, residuals = _f64(inputs, 2, "inputs"), _f64(residuals, 2, "residuals")
+        self.N, self.D = inputs.shape
+        self.E = residuals.shape[0]
+        h = _lib.mogp_local_create(dptr(inputs), self.N, self.D, dptr(residuals), self.E, -1 if device is None else int(device))
+        if not h:
+            raise RuntimeError(_capi.last_error())
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.mogp_local_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def predict(self, emulator, kern, scale, sigma2, nugget, jitter, include_nugget, testing, k, max_points=0, unc=True,
+                return_neighbours=False):
+        """(mean (m), unc (m) or None, ok (m) bool, radius (m), neighbours (m, k) int64 or None) of row ``emulator`` of the residuals"""
+        if not self._h:
+            raise RuntimeError("predict_local: the handle has been closed")
+        testing, scale = _f64(testing, 2, "testing"), _f64(scale, 1, "scale")
+        m = testing.shape[0]
+        mean, radius, ok = np.empty(m), np.empty(m), np.empty(m, dtype=np.int32)
+        var = np.empty(m) if unc else None
+        nbr = np.empty((m, int(k)), dtype=np.int32) if return_neighbours else None
+        check(_lib.mogp_local_predict(self._h, int(emulator), int(kern), dptr(scale), float(sigma2), float(nugget), float(jitter),
+                                      int(bool(include_nugget)), dptr(testing), m, testing.shape[1], int(k), int(max_points), dptr(mean),
+                                      dptr(var), iptr(ok), dptr(radius), iptr(nbr)))
+        return mean, var, ok.astype(bool), radius, None if nbr is None else nbr.astype(np.int64)
 
 
 # --------------------------------------------------------------------------------------
