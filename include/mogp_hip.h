@@ -455,6 +455,27 @@ mogp_local* mogp_local_create(const double* inputs, long long N, int D, const do
 int mogp_local_predict(mogp_local* h, int emulator, int kernel_type, const double* scale, double sigma2, double nugget, double jitter,
                        int include_nugget, const double* testing, int m, int D, int k, int max_points, double* mean_out, double* var_out,
                        int* ok_out, double* radius_out, int* neighbours_out);
+/* ---- Vecchia likelihood on the same handle (mogp_emulator_amd/Vecchia.py) ----
+   The design of the handle counts as ORDERED: log p(y) ~ sum_t log p(y_t | y_c(t)), c(t) = the min(t, k) nearest rows among the rows < t.
+   mogp_local_vecchia_neighbours searches c(t) for every row in the metric of scale (D), s_d = sqrt(exp(theta_d)), 1 <= k <= min(N - 1, 126),
+   and keeps the (N, k) lists on the device for every later mogp_local_vecchia_loglik.  The arithmetic is that of mogp_local_predict: x~ = x_d *
+   s_d (one rounded multiply), r2 = ((0 + t_0 t_0) + t_1 t_1) + ... with t_d = x~_id - x~_td in the order d = 0 .. D-1, every operation rounded
+   on its own (no fused multiply-add); the list of row t holds the min(t, k) smallest pairs (r2, i), i < t, in lexicographic order -- nearest
+   first, ties to the lowest row -- and -1 behind them.  neighbours_out (N, k) or NULL.  A later search replaces the lists. */
+int mogp_local_vecchia_neighbours(mogp_local* h, const double* scale, int k, int* neighbours_out);
+/* The Vecchia log-likelihood of residual row `emulator` (zero mean) on the lists of the last search; k must be the k of that search, scale
+   need not be its scale.  kernel_type: 0 squared exponential, 1 Matern 5/2 of the scaled distance.  Per row t with n_t = min(t, k) + 1 and
+   A = sigma2 k(r2) + (nugget + jitter) I over (c(t), t), A = L L^T, e the last row:
+     terms_out[t] = log N(y_t | y_c(t)) = -log L_ee - (L^-1 y)_e^2 / 2 - log(2 pi) / 2
+   value_out (1) = the sum of the terms; with want_grad != 0, grad_out (D + 2) = its derivatives with respect to theta_d = log s_d^2
+   (d < D: r2 = sum_d exp(theta_d) (x_id - x_jd)^2, one entry per dimension whatever the kernel), log sigma2 (entry D) and log nugget
+   (entry D + 1; jitter is a constant), formed analytically from w = A^-1 e and alpha = A^-1 y.  ok_out (N, or NULL) = 0 where A is not
+   positive definite or the term is not finite: that term and that row's derivatives are NaN, and so are value_out and grad_out; no other
+   row is affected.  terms_out (N) or NULL.  No atomics: value and gradient are summed over the rows in blocks of 1024 in a fixed tree, an
+   order that depends on N alone, so they are the same bits for a repeated call, for any max_points (rows per launch, 0 = the library's
+   choice), and with or without terms_out / ok_out; value_out is the same bits with and without want_grad. */
+int mogp_local_vecchia_loglik(mogp_local* h, int emulator, int kernel_type, const double* scale, double sigma2, double nugget, double jitter, int k,
+                              int want_grad, int max_points, double* value_out, double* grad_out, double* terms_out, int* ok_out);
 void mogp_local_destroy(mogp_local* h);
 /* device memory helpers so a host program can hand device-resident buffers to the *_dev calls */
 void* mogp_dev_malloc(unsigned long long bytes);

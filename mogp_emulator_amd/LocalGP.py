@@ -150,6 +150,20 @@ class LocalGP(object):
         resid = np.stack([targets[e] - _mean_at(h[4], h[5], inputs) for e, h in enumerate(self._hyper)])
         self._native = _create_native(inputs, np.ascontiguousarray(resid), None if device is None else int(device))
 
+    @classmethod
+    def _on_handle(cls, native, hyper, D, N, n_neighbours):
+        """Internal: a single-output view on a native handle that somebody else owns (``VecchiaGP.predict``), at the hyperparameters
+        ``hyper`` = [(kernel 0 / 1, s (D,), sigma^2, nugget, mean function or None, its parameters)] in place of a fitted ``gp``.
+        ``close()`` of the view leaves the handle open."""
+        who = "LocalGP"
+        k = int(n_neighbours)
+        if k != n_neighbours or k < 1 or k > min(N, MAX_NEIGHBOURS):
+            raise ValueError("%s: n_neighbours must be between 1 and min(N, %d) = %d" % (who, MAX_NEIGHBOURS, min(N, MAX_NEIGHBOURS)))
+        self = cls.__new__(cls)
+        self._single, self._D, self._N, self._E, self._k = True, int(D), int(N), 1, k
+        self._hyper, self._native, self._borrowed = list(hyper), native, True
+        return self
+
     n_neighbours = property(lambda self: self._k)
     n = property(lambda self: self._N)
     D = property(lambda self: self._D)
@@ -157,7 +171,7 @@ class LocalGP(object):
 
     def close(self):
         native, self._native = getattr(self, "_native", None), None
-        if native is not None:
+        if native is not None and not getattr(self, "_borrowed", False):
             native.close()
 
     def __del__(self):

@@ -163,6 +163,9 @@ SIGNATURES = {
     "mogp_local_create": (c_void_p, [c_double_p, c_longlong, c_int, c_double_p, c_int, c_int]),
     "mogp_local_predict": (c_int, [c_void_p, c_int, c_int, c_double_p, c_double, c_double, c_double, c_int, c_double_p, c_int, c_int, c_int, c_int,
                                    c_double_p, c_double_p, c_int_p, c_double_p, c_int_p]),
+    "mogp_local_vecchia_neighbours": (c_int, [c_void_p, c_double_p, c_int, c_int_p]),
+    "mogp_local_vecchia_loglik": (c_int, [c_void_p, c_int, c_int, c_double_p, c_double, c_double, c_double, c_int, c_int, c_int, c_double_p,
+                                          c_double_p, c_double_p, c_int_p]),
     "mogp_local_destroy": (None, [c_void_p]),
     "mogp_profile_enable": (c_int, [c_int]),
     "mogp_profile_reset": (c_int, []),

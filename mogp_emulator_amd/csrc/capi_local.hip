@@ -32,6 +32,21 @@ int mogp_local_predict(mogp_local* h, int emulator, int kernel_type, const doubl
   });
 }
 
+int mogp_local_vecchia_neighbours(mogp_local* h, const double* scale, int k, int* neighbours_out) {
+  return guarded([&] {
+    if (!h || !h->gp) throw std::runtime_error("vecchia_neighbours: null handle");
+    h->gp->vecchia_neighbours(scale, k, neighbours_out);
+  });
+}
+
+int mogp_local_vecchia_loglik(mogp_local* h, int emulator, int kernel_type, const double* scale, double sigma2, double nugget, double jitter, int k,
+                              int want_grad, int max_points, double* value_out, double* grad_out, double* terms_out, int* ok_out) {
+  return guarded([&] {
+    if (!h || !h->gp) throw std::runtime_error("vecchia_loglik: null handle");
+    h->gp->vecchia_loglik(emulator, kernel_type, scale, sigma2, nugget, jitter, k, want_grad != 0, max_points, value_out, grad_out, terms_out, ok_out);
+  });
+}
+
 void mogp_local_destroy(mogp_local* h) {
   if (!h) return;
   (void)guarded([&] {

@@ -443,14 +443,25 @@ class LocalGP {
   // host pointers; var / nbr may be null.  kt: 0 squared exponential, 1 Matern 5/2.
   void predict(int e, int kt, const double* scale, double sigma2, double nugget, double jitter, bool include_nugget, const double* testing, long m,
                int k, int max_points, double* mean, double* var, int* ok, double* radius, int* nbr);
+  // Vecchia likelihood (DESIGN.md section 3 "Vecchia fit"): the design counts as ORDERED, the neighbours of row t are rows < t.
+  // vecchia_neighbours searches them in the metric of `scale` and keeps the (N, k) lists on the device (nbr_out: host, may be null);
+  // vecchia_loglik evaluates sum_t log p(y_t | y_nbr(t)) of residual row e on those lists (k must be the k of the search): value_out (1),
+  // grad_out (D + 2: d/d log s_d^2, d/d log sigma2, d/d log nugget; written with want_grad), terms_out (N) / ok_out (N) may be null.
+  void vecchia_neighbours(const double* scale, int k, int* nbr_out);
+  void vecchia_loglik(int e, int kt, const double* scale, double sigma2, double nugget, double jitter, int k, bool want_grad, int max_points,
+                      double* value_out, double* grad_out, double* terms_out, int* ok_out);
   int device_id() const { return device; }
   const long N;
   const int D, E;
 
  private:
+  void ensure_scaled(const double* scale, hipStream_t st);      // dXs = dX * scale, formed again only when the scales change
   int device = 0, n_cu = 1;
   DevBuf<double> dX, dY, dXs, dScale;
   std::vector<double> hScale;        // the scales dXs was formed with (empty: not formed yet)
+  int vk = 0;                        // the k of the Vecchia lists in dVnbr (0: none yet)
+  DevBuf<int> dVnbr, dVok;
+  DevBuf<double> dVout, dVred, dVscratch;
 };
 
 // measurement hooks (mogp_profile_schedule): force the Cholesky schedule / serialise it onto one stream so that the

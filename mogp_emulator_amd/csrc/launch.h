@@ -327,6 +327,20 @@ void launch_local_knn(const double* Xs, long N, int D, const double* Qs, int mc,
 // positive definite.  grid persistent workgroups, scratch: grid * LOCAL_WG_DOUBLES doubles.  No result bit depends on grid.
 void launch_local_gp(const double* Xs, const double* Y, long N, int D, const double* Qs, int mc, int k, const int* nbr, int kt, double sigma2,
                      double diag_add, double var_add, double* scratch, int grid, double* mean, double* var, int* ok, hipStream_t st);
+// Vecchia likelihood on the same handle (DESIGN.md section 3 "Vecchia fit").  The design is stored in the Vecchia order: the neighbours of
+// row t are rows < t.
+constexpr size_t VECCHIA_WG_DOUBLES = LOCAL_WG_DOUBLES + (size_t)128 * 128;      // with the gradient: sigma^2 k'(r2) of the pairs beside the tile
+constexpr size_t VECCHIA_REDUCE_BLOCK = 1024;                                      // points per block of the fixed-order sum
+// nbr (N, k): per row t the min(t, k) smallest pairs (r2, index) over the rows < t, the arithmetic and the order of launch_local_knn; -1 behind them
+void launch_vecchia_knn(const double* Xs, long N, int D, int k, int* nbr, hipStream_t st);
+// The points p0 .. p0 + mc - 1: out[t] = log p(y_t | y_nbr(t)) and, with grad, out[(1 + p) * N + t] = its derivative with respect to
+// theta_p = log s_p^2 (p < D), log sigma2 (p = D) and log nugget (p = D + 1); ok[t] = 0 and NaN where the local matrix sigma2 k + diag_add I
+// is not positive definite.  grid persistent workgroups; scratch: grid * (grad ? VECCHIA_WG_DOUBLES : LOCAL_WG_DOUBLES) doubles.
+void launch_vecchia_ll(const double* Xs, const double* Y, long N, int D, long p0, int mc, int k, const int* nbr, int kt, double sigma2,
+                       double diag_add, double nugget, bool grad, double* scratch, int grid, double* out, int* ok, hipStream_t st);
+// the sums of the columns of in (cols, n), in an order that depends on n alone; a, b: cols * ceil(n / VECCHIA_REDUCE_BLOCK) doubles each;
+// returns the one of them whose first cols entries are the sums
+double* launch_vecchia_reduce(const double* in, long n, int cols, double* a, double* b, hipStream_t st);
 
 // --- utilities -------------------------------------------------------------------------------
 // out (n,n) <- tile of src (NP,NP): mode 0 copy, mode 1 transpose of the lower triangle (zeros below the diagonal of out), mode 2 symmetrise from lower

@@ -1,7 +1,7 @@
 // How the prediction family of Engine (engine_predict.hip) and the analysis family (engine_analysis.hip: hessian, predict_mixture,
 // cross_validate, sample_posterior, alc, alc_batch, predict_cov) cut their work to a byte budget, the index tables of their passes, and where the mean-function terms of a prediction are
 // staged.  Plain host arithmetic with no HIP in it, so that a host compiler takes it and tests/c/predict_plan_check.cpp, mixture_plan_check.cpp,
-// cv_plan_check.cpp, sample_plan_check.cpp, alc_plan_check.cpp and alc_batch_plan_check.cpp can check it without a device.  The caps that need the device (MOGP_KS_BUDGET_GB, free memory) are passed in.
+// cv_plan_check.cpp, sample_plan_check.cpp, alc_plan_check.cpp, alc_batch_plan_check.cpp, local_plan_check.cpp and vecchia_plan_check.cpp can check it without a device.  The caps that need the device (MOGP_KS_BUDGET_GB, free memory) are passed in.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -296,6 +296,37 @@ inline LocalPlan local_plan(long m, int D, int k, int n_cu, double free_bytes, i
     points = std::min<long>(want, (long)std::floor(left / per));
   }
   return {points, (int)std::min(points, full)};
+}
+
+// LocalGP::vecchia_loglik (kernels_local.hip): how many points one launch takes and how many persistent workgroups factor their local
+// matrices.  Held for the whole design, whatever the launches (vecchia_fixed_bytes): per point the term and, with the gradient, its D + 2
+// derivatives (doubles) and the ok flag (int); two buffers of ceil(N / 1024) partial sums per column.  Every workgroup owns wg_bytes of
+// scratch (launch.h LOCAL_WG_DOUBLES, VECCHIA_WG_DOUBLES with the gradient).
+//   points  max_points where given, else LOCAL_MAX_PASS; at most N, at least one
+//   grid    LOCAL_GRID_PER_CU workgroups per compute unit, never more than the points of a launch, at least one
+// Neither changes a bit of a result: a point's term depends on nothing but the point, and the sum runs over the whole design in blocks of 1024
+// afterwards.  Throws for a negative max_points and when the whole does not fit half of the free device memory.
+struct VecchiaPlan {
+  long points;
+  int grid;
+  long blocks;      // partial sums per column after the first pass of the sum
+};
+inline long vecchia_blocks(long N) { return (std::max<long>(1, N) + 1023) / 1024; }
+inline double vecchia_fixed_bytes(long N, int D, bool grad) {
+  const double cols = grad ? D + 3.0 : 1.0;
+  return 8.0 * cols * (double)N + 4.0 * (double)N + 2.0 * 8.0 * cols * (double)vecchia_blocks(N);
+}
+inline VecchiaPlan vecchia_plan(long N, int D, bool grad, int n_cu, double free_bytes, int max_points, double wg_bytes) {
+  if (max_points < 0) throw std::runtime_error("vecchia_loglik: max_points must not be negative");
+  const long full = LOCAL_GRID_PER_CU * std::max(1, n_cu);
+  long points = std::max<long>(1, std::min<long>(N, LOCAL_MAX_PASS));
+  if (max_points > 0) points = std::min<long>(points, max_points);
+  const long grid = std::min(points, full);
+  const double need = vecchia_fixed_bytes(N, D, grad) + (double)grid * wg_bytes;
+  if (need > 0.5 * free_bytes)
+    throw std::runtime_error("vecchia_loglik: " + std::to_string((long long)need) + " bytes of device scratch for " + std::to_string(N) +
+                             " points are more than half of the free device memory");
+  return {points, (int)grid, vecchia_blocks(N)};
 }
 
 // Stage 2 of Engine::predict_mixture: the normalised weights of the S samples of one emulator, from their negative log-posteriors F and

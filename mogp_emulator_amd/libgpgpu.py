@@ -1373,6 +1373,28 @@ class LocalGP_GPU(object):
                                       dptr(var), iptr(ok), dptr(radius), iptr(nbr)))
         return mean, var, ok.astype(bool), radius, None if nbr is None else nbr.astype(np.int64)
 
+    def vecchia_neighbours(self, scale, k, return_neighbours=True):
+        """The ordered search (row t sees rows < t) in the metric ``scale``; the lists stay on the device.  (N, k) int64 in the handle's own
+        numbering, -1 behind the min(t, k) neighbours of row t, or None"""
+        if not self._h:
+            raise RuntimeError("vecchia_neighbours: the handle has been closed")
+        scale = _f64(scale, 1, "scale")
+        nbr = np.empty((self.N, int(k)), dtype=np.int32) if return_neighbours else None
+        check(_lib.mogp_local_vecchia_neighbours(self._h, dptr(scale), int(k), iptr(nbr)))
+        return None if nbr is None else nbr.astype(np.int64)
+
+    def vecchia_loglik(self, emulator, kern, scale, sigma2, nugget, jitter, k, grad=False, return_terms=False, max_points=0):
+        """(value, grad (D + 2) or None, terms (N) or None, ok (N) bool) of row ``emulator`` of the residuals on the lists of the last search"""
+        if not self._h:
+            raise RuntimeError("vecchia_loglik: the handle has been closed")
+        scale = _f64(scale, 1, "scale")
+        value, ok = np.empty(1), np.empty(self.N, dtype=np.int32)
+        g = np.empty(self.D + 2) if grad else None
+        terms = np.empty(self.N) if return_terms else None
+        check(_lib.mogp_local_vecchia_loglik(self._h, int(emulator), int(kern), dptr(scale), float(sigma2), float(nugget), float(jitter), int(k),
+                                             int(bool(grad)), int(max_points), dptr(value), dptr(g), dptr(terms), iptr(ok)))
+        return float(value[0]), g, terms, ok.astype(bool)
+
 
 # --------------------------------------------------------------------------------------
 # stand-alone kernel objects (bindings.cu:340-361; flat layouts of kernel.hpp:47-107), evaluated on the
