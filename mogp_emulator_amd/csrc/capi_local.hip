@@ -1,5 +1,5 @@
 // The local-approximate-GP entries of the C ABI: a handle that keeps a large design on the device and predicts every query from its nearest
-// design points alone (LocalGP, kernels_local.hip).  No Engine is involved.
+// design points alone (LocalGP, engine_local.hip).  No Engine is involved.
 #include "capi_internal.h"
 
 using namespace mogp;

@@ -434,7 +434,7 @@ constexpr int DESIGN_MAX_PASS = 32768;      // designs per pass (the second grid
 constexpr int DESIGN_MAX_N = 370688;        // points per design: 64 x 64 tiles of the lower triangle x 256 threads < 2^32 work-items
 void design_min_pdist(const double* designs, int T, int n, int D, double* out);
 
-// Local approximate GP prediction (kernels_local.hip; DESIGN.md section 3 "Local prediction"): the design (N, D) and E rows of residual
+// Local approximate GP prediction (the handle: engine_local.hip, its kernels: kernels_local.hip; DESIGN.md section 3 "Local prediction"): the design (N, D) and E rows of residual
 // targets stay on the device the handle was created on; every predict() finds the k nearest design points of each query in the metric
 // of `scale` and predicts from that k-point GP alone.  No Engine: nothing here factors the whole design.
 class LocalGP {

@@ -1,9 +1,9 @@
-// What engine.hip, engine_chol.hip, engine_fit.hip, engine_predict.hip and engine_analysis.hip share and nobody else sees: the error-check
+// What engine.hip, engine_chol.hip, engine_fit.hip, engine_predict.hip, engine_analysis.hip and engine_local.hip share and nobody else sees: the error-check
 // macro, small helpers and the process-wide diagnostic counters behind prof_counter (engine.hip).  What lives where: engine.hip the
 // construction, the cached state, eval's steps, L^-1 / K^-1 and the gradient; engine_chol.hip the factorisation schedules; engine_fit.hip
 // the optimiser, the slot pool, the replica engines and ScratchFactor; engine_predict.hip predict, full covariance, implausibility, Sobol and loo_variance;
 // engine_analysis.hip the Hessian, the mixture over hyperparameter samples, cross-validation, joint posterior draws and
-// active learning (alc, predict_cov).  Whoever needs "factor a batch of matrices I wrote myself" and nothing else of an engine (gkdr_R,
+// active learning (alc, predict_cov); engine_local.hip the LocalGP handle, which is no Engine.  Whoever needs "factor a batch of matrices I wrote myself" and nothing else of an engine (gkdr_R,
 // cross_validate's k-fold path, sample_posterior) takes a ScratchFactor, below.
 #pragma once
 #include "engine.h"

@@ -1,3 +1,4 @@
+// The kernels of LocalGP (engine.h; the handle itself is engine_local.hip) and their launchers.
 // Local approximate GP prediction (Emery 2009; Gramacy & Apley 2015): every query is predicted from the GP on its k nearest design points
 // alone, at hyperparameters fitted elsewhere.  m independent k x k problems, k <= 126, and no factorisation of the whole design.
 //
@@ -11,29 +12,20 @@
 //                        offered, the pairs are unique by their index, so ties go to the lowest index and nothing depends on the order of
 //                        the sweep or on which queries share a wave.  After the first tiles an insertion is rare (~ k ln(N / k) per query).
 //   local_gp_kernel      a persistent grid of 256-thread workgroups, each with its own 128 x 128 tile (and chol128_dev's pack) in global
-//                        memory.  Per query: the neighbours' scaled rows and the query are gathered into LDS, the lower triangle of the
-//                        augmented matrix is built -- K + (nugget + jitter) I in rows < k, the residual targets in row k, sigma^2 k(x*, .)
-//                        in row k+1, PAD_BIG on the diagonal of those two and 0 between them, identity beyond -- and chol128_dev factors it
-//                        once.  Row k is then (L^-1 y)^T and row k+1 v^T = (L^-1 k*)^T: mean = <row k, row k+1>, variance = sigma^2 -
-//                        <v, v>, both summed by one wave in a fixed order.  This is why k <= 126.
+//                        memory.  Per query: gather the neighbours' scaled rows and the query into LDS, build_tile the augmented matrix,
+//                        factor_tile it once with chol128_dev, read mean and variance off two rows of the factor.  This is why k <= 126.
 // The Vecchia likelihood on the same handle (its own head below): local_knn_kernel<true> -- the ordered search, a query sees earlier rows
-// only --, vecchia_ll_kernel -- the conditional log-density of every point given its neighbours, with the analytic gradient --, and
-// vecchia_reduce_kernel -- their sums in an order that depends on N alone.
+// only --, vecchia_ll_kernel -- the same three steps per point, then the conditional log-density given its neighbours with the analytic
+// gradient --, and vecchia_reduce_kernel -- their sums in an order that depends on N alone.
 // This file is compiled with -mllvm -amdgpu-mfma-vgpr-form=1 like kernels_panel.hip: chol128_dev reads its MFMA results back after every MFMA.
 #include <algorithm>
 #include <climits>
-#include <cmath>
-#include <stdexcept>
-#include <string>
 
 #include "chol128_dev.h"
 #include "cov_dev.h"
-#include "engine.h"
 #include "predict_plan.h"
 
 namespace mogp {
-
-#define HIPCK(x) hip_check((x), #x)
 
 static_assert(LOCAL_WG_DOUBLES == (size_t)128 * 128 + PACK128_STRIDE, "scratch of one workgroup: the tile and chol128_dev's pack");
 static_assert(LOCAL_MAX_K + 2 == 128, "neighbours, target row and query row fill one tile");
@@ -41,7 +33,6 @@ static_assert(LOCAL_MAX_K + 2 == 128, "neighbours, target row and query row fill
 namespace {
 
 constexpr int KNN_LD = LOCAL_KNN_ROWS + 1;      // row stride of a staged dimension (odd: the transposing stores spread over the banks)
-constexpr long LOCAL_MAX_N = 2147483647L - 256; // a tile's row index j0 + 127 stays an int
 
 __global__ __launch_bounds__(256) void local_scale_kernel(const double* __restrict__ x, size_t total, int D, const double* __restrict__ s,
                                                           double* __restrict__ out) {
@@ -151,92 +142,113 @@ __global__ __launch_bounds__(256) void local_knn_kernel(const double* __restrict
   }
 }
 
-// LDS of local_gp_kernel in doubles: chol128_dev's own, the exponential's table, the targets of the neighbours, the gathered points, the status word
-__host__ __device__ constexpr int local_pts_ld(int D) { return D | 1; }        // odd row stride: rows a lane apart fall on different banks
-size_t local_gp_lds_bytes(int D) { return sizeof(double) * ((size_t)C128_LDS_DOUBLES + 256 + 128 + (size_t)128 * local_pts_ld(D) + 2); }
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// What local_gp_kernel and vecchia_ll_kernel share: one problem is one 128 x 128 tile.  sm is the workgroup's dynamic LDS, carved by
+// o = LocalLds(D, grad) (predict_plan.h); A its tile in global memory with chol128_dev's pack behind it.
+// ---------------------------------------------------------------------------------------------------------------------------------------
+static_assert(LOCAL_CHOL_LDS_DOUBLES == C128_LDS_DOUBLES, "LocalLds starts behind chol128_dev's own LDS");
 
+// Rows 0 .. kn-1 of pts are the design rows nq[0 .. kn-1] (an index outside the design reads row 0), row kn is `last`; yv their targets
+// and, with last_y, that of the last row.  Clears chol128_dev's status word and ends with a barrier.
+__device__ __forceinline__ void gather(double* sm, const LocalLds& o, const double* Xs, const double* Y, int N, int D, const int* nq, int kn,
+                                       const double* last, const double* last_y) {
+  const int t = threadIdx.x, DP = o.ld;
+  double *yv = sm + o.yv, *pts = sm + o.pts;
+  for (int e = t; e < (kn + 1) * D; e += 256) {
+    const int r = e / D, d = e - r * D;
+    const double* src = last;
+    if (r < kn) {
+      const int j = nq[r];
+      src = Xs + (size_t)((unsigned)j < (unsigned)N ? j : 0) * D;
+    }
+    pts[r * DP + d] = src[d];
+  }
+  if (t < kn) {
+    const int j = nq[t];
+    yv[t] = Y[(unsigned)j < (unsigned)N ? j : 0];
+  } else if (last_y && t == kn) {
+    yv[t] = *last_y;
+  }
+  if (t == 0) *reinterpret_cast<int*>(sm + o.info) = 0;
+  __syncthreads();                           // (also: the previous problem's factor and its sums in LDS have been read)
+}
+
+// The lower triangle of the tile from the gathered points.  Rows i < nm: the matrix, sigma2 k(r2) of rows i and j of pts off the diagonal and
+// sigma2 + diag_add on it (GRAD: G_ij = sigma2 k'(r2) beside it).  Row nm: the targets yv, PAD_BIG on the diagonal.  CROSS: row nm + 1 =
+// sigma2 k(r2) of row nm of pts against the matrix rows, 0 against the target row, PAD_BIG on the diagonal.  Identity beyond these nr rows.
+template <int KT, bool CROSS, bool GRAD>
+__device__ __forceinline__ void build_tile(const double* sm, const LocalLds& o, int D, int nm, double sigma2, double diag_add, double* A,
+                                           double* G) {
+  const int t = threadIdx.x, DP = o.ld;
+  const double *tab = sm + o.tab, *yv = sm + o.yv, *pts = sm + o.pts;
+  const int nr = nm + (CROSS ? 2 : 1);
+  // rows p and nr-1-p together (nr + 1 entries): every lane has an entry
+  const int L = nr + 1, np = (nr + 1) / 2;
+  for (int e = t; e < np * L; e += 256) {
+    const int p = e / L, c = e - p * L;
+    int i, j;
+    if (c <= p) {
+      i = p;
+      j = c;
+    } else {
+      i = nr - 1 - p;
+      j = c - p - 1;
+      if (i == p) continue;                  // the middle row of an odd count is its own partner
+    }
+    double val;
+    if (j < nm && i != nm) {
+      if (i == j) {
+        val = sigma2 + diag_add;
+      } else {
+        const double* a = pts + (CROSS && i == nm + 1 ? nm : i) * DP;
+        const double* b = pts + j * DP;
+        double r2 = 0.0;
+        for (int d = 0; d < D; ++d) {
+          const double df = a[d] - b[d];
+          r2 = __builtin_fma(df, df, r2);
+        }
+        val = sigma2 * kern_val<KT>(r2, tab);
+        if (GRAD) G[i * 128 + j] = sigma2 * kern_dr2<KT>(r2, tab);      // (the exponential of kern_val: one for both)
+      }
+    } else if (!CROSS || i == nm) {
+      val = (j < nm) ? yv[j] : PAD_BIG;
+    } else {
+      val = (j == nm) ? 0.0 : PAD_BIG;       // 0 between the two right-hand-side rows
+    }
+    A[i * 128 + j] = val;
+  }
+  for (int e = t; e < (128 - nr) * 128; e += 256) {
+    const int i = nr + (e >> 7), j = e & 127;
+    if (j <= i) A[i * 128 + j] = (i == j) ? 1.0 : 0.0;
+  }
+}
+
+__device__ __forceinline__ void factor_tile(double* sm, const LocalLds& o, double* A) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();                           // the tile is complete: chol128_dev's waves read what other waves stored
+  chol128_dev(A, 128, A + 128 * 128, reinterpret_cast<int*>(sm + o.info), 0, sm);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();                           // the factor's rows (and the info word) are visible to every wave
+}
+
+// Prediction: nm = k matrix rows, the query is row k of pts and the CROSS row of the tile.  After the factorisation row k is (L^-1 y)^T and
+// row k+1 v^T = (L^-1 k*)^T: mean = <row k, row k+1>, variance = sigma^2 - <v, v>, both summed by wave 0 in a fixed order.
 template <int KT>
 __global__ __launch_bounds__(256) void local_gp_kernel(const double* __restrict__ Xs, const double* __restrict__ Y, int N, int D,
                                                        const double* __restrict__ Qs, int mc, int k, const int* __restrict__ nbr, double sigma2,
                                                        double diag_add, double var_add, double* __restrict__ scratch, double* __restrict__ mean,
                                                        double* __restrict__ var, int* __restrict__ ok) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
-  double* lds = sm;                          // chol128_dev
-  double* tab = sm + C128_LDS_DOUBLES;       // 2^(j/256)
-  double* yv = tab + 256;                    // residual targets of the neighbours
-  double* pts = yv + 128;                    // rows 0 .. k-1 the neighbours, row k the query, row stride DP
-  const int DP = local_pts_ld(D);
-  int& info = *reinterpret_cast<int*>(pts + 128 * DP);      // chol128_dev's status word (in the dynamic region: a static one would misalign it)
-  const int t = threadIdx.x, lane = t & 63;
-  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+  const LocalLds o(D, false);
+  const int& info = *reinterpret_cast<int*>(sm + o.info);
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
   double* A = scratch + (size_t)blockIdx.x * LOCAL_WG_DOUBLES;
-  double* pk = A + 128 * 128;
-  const int nr = k + 2;                      // rows that carry the problem
-  stage_exp_tab(tab);
+  stage_exp_tab(sm + o.tab);
   for (int q = blockIdx.x; q < mc; q += gridDim.x) {
-    const int* nq = nbr + (size_t)q * k;
-    for (int e = t; e < (k + 1) * D; e += 256) {
-      const int r = e / D, d = e - r * D;
-      const double* src;
-      if (r < k) {
-        const int j = nq[r];
-        src = Xs + (size_t)((unsigned)j < (unsigned)N ? j : 0) * D;
-      } else {
-        src = Qs + (size_t)q * D;
-      }
-      pts[r * DP + d] = src[d];
-    }
-    if (t < k) {
-      const int j = nq[t];
-      yv[t] = Y[(unsigned)j < (unsigned)N ? j : 0];
-    }
-    if (t == 0) info = 0;
-    __syncthreads();                         // (also: wave 0 has read rows k, k+1 of the previous query's factor)
-    // rows i < nr of the lower triangle, rows p and nr-1-p together (nr + 1 entries): every lane has an entry
-    {
-      const int L = nr + 1, np = (nr + 1) / 2;
-      for (int e = t; e < np * L; e += 256) {
-        const int p = e / L, c = e - p * L;
-        int i, j;
-        if (c <= p) {
-          i = p;
-          j = c;
-        } else {
-          i = nr - 1 - p;
-          j = c - p - 1;
-          if (i == p) continue;              // the middle row of an odd count is its own partner
-        }
-        double val;
-        if (j < k && i != k) {
-          if (i == j) {
-            val = sigma2 + diag_add;
-          } else {
-            const double* a = pts + (i == k + 1 ? k : i) * DP;
-            const double* b = pts + j * DP;
-            double r2 = 0.0;
-            for (int d = 0; d < D; ++d) {
-              const double df = a[d] - b[d];
-              r2 = __builtin_fma(df, df, r2);
-            }
-            val = sigma2 * kern_val<KT>(r2, tab);
-          }
-        } else if (i == k) {
-          val = (j < k) ? yv[j] : PAD_BIG;
-        } else {
-          val = (j == k) ? 0.0 : PAD_BIG;    // i == k+1: 0 between the two right-hand-side rows
-        }
-        A[i * 128 + j] = val;
-      }
-      for (int e = t; e < (128 - nr) * 128; e += 256) {
-        const int i = nr + (e >> 7), j = e & 127;
-        if (j <= i) A[i * 128 + j] = (i == j) ? 1.0 : 0.0;
-      }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();                         // the tile is complete: chol128_dev's waves read what other waves stored
-    chol128_dev(A, 128, pk, &info, 0, lds);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();                         // the factor's rows (and the info word) are visible to wave 0
+    gather(sm, o, Xs, Y, N, D, nbr + (size_t)q * k, k, Qs + (size_t)q * D, nullptr);
+    build_tile<KT, true, false>(sm, o, D, k, sigma2, diag_add, A, nullptr);
+    factor_tile(sm, o, A);
     if (w == 0) {
       const double* ry = A + k * 128;
       const double* rv = ry + 128;
@@ -280,115 +292,28 @@ __global__ __launch_bounds__(256) void local_gp_kernel(const double* __restrict_
 // Results go to out (cols, Ntot) column-major: column 0 the term, 1 .. D the dimensions, D + 1 log sigma^2, D + 2 log nugget; NaN and ok = 0
 // where the matrix is not positive definite.  Nothing depends on the grid or on which workgroup takes a point.
 constexpr double HALF_LOG_2PI = 0.91893853320467274178;
-size_t vecchia_lds_bytes(int D, bool grad) {
-  return sizeof(double) * ((size_t)C128_LDS_DOUBLES + 256 + 128 + (grad ? 2 * 128 + 2 * 256 : 0) + (size_t)128 * local_pts_ld(D) + 2);
-}
-
-// (k(r2), dk/dr2) with one exponential
-template <int KT>
-__device__ __forceinline__ void kern_val_dr2(double r2, const double* tab, double& kv, double& dk) {
-  if (KT == 0) {
-    kv = lean_exp_neg<true>(r2, tab);
-    dk = -0.5 * kv;
-  } else {
-    const double s = sqrt(5.0 * r2);
-    const double e = lean_exp_neg<false>(s, tab);
-    kv = (1.0 + s + (5.0 / 3.0) * r2) * e;
-    dk = -(5.0 / 6.0) * (1.0 + s) * e;
-  }
-}
-
 template <int KT, bool GRAD>
 __global__ __launch_bounds__(256) void vecchia_ll_kernel(const double* __restrict__ Xs, const double* __restrict__ Y, int N, int D, int p0, int mc,
                                                          int k, const int* __restrict__ nbr, double sigma2, double diag_add, double nugget,
                                                          double* __restrict__ scratch, double* __restrict__ out, int* __restrict__ ok) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
-  double* lds = sm;                          // chol128_dev
-  double* tab = sm + C128_LDS_DOUBLES;       // 2^(j/256)
-  double* yv = tab + 256;                    // targets of the neighbours and of the point
-  double* wv = yv + 128;                     // GRAD: w, alpha, the partial sums of a_d and b_d
-  double* av = wv + (GRAD ? 128 : 0);
-  double* reda = av + (GRAD ? 128 : 0);
-  double* redb = reda + (GRAD ? 256 : 0);
-  double* pts = redb + (GRAD ? 256 : 0);     // rows 0 .. kt-1 the neighbours, row kt the point, row stride DP
-  const int DP = local_pts_ld(D);
-  int& info = *reinterpret_cast<int*>(pts + 128 * DP);
+  const LocalLds o(D, GRAD);
+  double *wv = sm + o.wv, *av = sm + o.av, *reda = sm + o.reda, *redb = sm + o.redb;      // GRAD: w, alpha, the partial sums of a_d and b_d
+  const double* pts = sm + o.pts;
+  const int DP = o.ld;
+  const int& info = *reinterpret_cast<int*>(sm + o.info);
   const int t = threadIdx.x, lane = t & 63;
   const int w = __builtin_amdgcn_readfirstlane(t >> 6);
   double* A = scratch + (size_t)blockIdx.x * (GRAD ? VECCHIA_WG_DOUBLES : LOCAL_WG_DOUBLES);
-  double* pk = A + 128 * 128;
   double* G = A + LOCAL_WG_DOUBLES;          // GRAD only: sigma^2 k'(r2_ij), j < i < n
   const double nan = __longlong_as_double(0x7FF8000000000000ll);
-  stage_exp_tab(tab);
+  stage_exp_tab(sm + o.tab);
   for (int q = blockIdx.x; q < mc; q += gridDim.x) {
     const int pt = p0 + q;                   // the point; its neighbours are rows < pt
-    const int kt = min(pt, k), n = kt + 1, nr = n + 1;
-    const int* nq = nbr + (size_t)pt * k;
-    for (int e = t; e < n * D; e += 256) {
-      const int r = e / D, d = e - r * D;
-      int j = pt;
-      if (r < kt) {
-        j = nq[r];
-        j = (unsigned)j < (unsigned)N ? j : 0;
-      }
-      pts[r * DP + d] = Xs[(size_t)j * D + d];
-    }
-    if (t < n) {
-      int j = pt;
-      if (t < kt) {
-        j = nq[t];
-        j = (unsigned)j < (unsigned)N ? j : 0;
-      }
-      yv[t] = Y[j];
-    }
-    if (t == 0) info = 0;
-    __syncthreads();
-    // rows i < nr of the lower triangle, rows p and nr-1-p together (as local_gp_kernel)
-    {
-      const int L = nr + 1, np = (nr + 1) / 2;
-      for (int e = t; e < np * L; e += 256) {
-        const int p = e / L, c = e - p * L;
-        int i, j;
-        if (c <= p) {
-          i = p;
-          j = c;
-        } else {
-          i = nr - 1 - p;
-          j = c - p - 1;
-          if (i == p) continue;
-        }
-        double val;
-        if (i < n) {
-          if (i == j) {
-            val = sigma2 + diag_add;
-          } else {
-            const double* a = pts + i * DP;
-            const double* b = pts + j * DP;
-            double r2 = 0.0;
-            for (int d = 0; d < D; ++d) {
-              const double df = a[d] - b[d];
-              r2 = __builtin_fma(df, df, r2);
-            }
-            double kv, dk;
-            kern_val_dr2<KT>(r2, tab, kv, dk);
-            val = sigma2 * kv;
-            if (GRAD) G[i * 128 + j] = sigma2 * dk;
-          }
-        } else {
-          val = (j < n) ? yv[j] : PAD_BIG;   // i == n: the targets ride along
-        }
-        A[i * 128 + j] = val;
-      }
-      for (int e = t; e < (128 - nr) * 128; e += 256) {
-        const int i = nr + (e >> 7), j = e & 127;
-        if (j <= i) A[i * 128 + j] = (i == j) ? 1.0 : 0.0;
-      }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    chol128_dev(A, 128, pk, &info, 0, lds);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();                         // the factor (and the info word) are visible to every wave
+    const int kt = min(pt, k), n = kt + 1;
+    gather(sm, o, Xs, Y, N, D, nbr + (size_t)pt * k, kt, Xs + (size_t)pt * D, Y + pt);
+    build_tile<KT, false, GRAD>(sm, o, D, n, sigma2, diag_add, A, G);
+    factor_tile(sm, o, A);
     double Lee = 1.0, ze = 0.0;              // wave 0 alone needs them (and the info word: thread 0 clears it for the next point)
     if (w == 0) {
       Lee = A[kt * 128 + kt];
@@ -521,33 +446,42 @@ __global__ __launch_bounds__(256) void vecchia_reduce_kernel(const double* __res
 }
 
 }  // namespace
-
+// one body of the two searches; ORD: half of the N x N sweep, workgroup g stops at the largest limit of its own queries
+template <bool ORD>
+static void launch_knn(const double* Xs, long N, int D, const double* Qs, int mc, int k, int* nbr, double* radius, hipStream_t st) {
+  const char* tag = ORD ? "vecchia_knn" : "local_knn";
+  const int groups = (mc + LOCAL_KNN_QUERIES - 1) / LOCAL_KNN_QUERIES;
+  prof_begin(tag, st);
+  hipLaunchKernelGGL(local_knn_kernel<ORD>, dim3(groups), dim3(256), sizeof(double) * (size_t)D * KNN_LD, st, Xs, (int)N, D, Qs, mc, k, nbr, radius);
+  // algorithmic: a subtraction, a product and an addition per (query, design point, dimension); the design is read once per workgroup
+  prof_end(tag, st, (ORD ? 1.5 : 3.0) * (double)mc * (double)N * D, (ORD ? 4.0 : 8.0) * (double)N * D * groups);
+}
+void launch_local_knn(const double* Xs, long N, int D, const double* Qs, int mc, int k, int* nbr, double* radius, hipStream_t st) {
+  launch_knn<false>(Xs, N, D, Qs, mc, k, nbr, radius, st);
+}
 void launch_vecchia_knn(const double* Xs, long N, int D, int k, int* nbr, hipStream_t st) {
-  const size_t lds = sizeof(double) * (size_t)D * KNN_LD;
-  const int mc = (int)N;
-  prof_begin("vecchia_knn", st);
-  hipLaunchKernelGGL(local_knn_kernel<true>, dim3((mc + LOCAL_KNN_QUERIES - 1) / LOCAL_KNN_QUERIES), dim3(256), lds, st, Xs, mc, D, Xs, mc, k, nbr,
-                     (double*)nullptr);
-  // half of the N x N sweep: workgroup g stops at the largest limit of its own queries
-  prof_end("vecchia_knn", st, 1.5 * (double)N * (double)N * D, 4.0 * (double)N * D * ((mc + LOCAL_KNN_QUERIES - 1) / LOCAL_KNN_QUERIES));
+  launch_knn<true>(Xs, N, D, Xs, (int)N, k, nbr, nullptr, st);
+}
+
+// the instantiation is chosen as a pointer; one launch follows
+void launch_local_gp(const double* Xs, const double* Y, long N, int D, const double* Qs, int mc, int k, const int* nbr, int kt, double sigma2,
+                     double diag_add, double var_add, double* scratch, int grid, double* mean, double* var, int* ok, hipStream_t st) {
+  const auto kern = kt == 0 ? local_gp_kernel<0> : local_gp_kernel<1>;
+  prof_begin("local_gp", st);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), local_lds_bytes(D, false), st, Xs, Y, (int)N, D, Qs, mc, k, nbr, sigma2, diag_add, var_add, scratch,
+                     mean, var, ok);
+  // the factorisation of one whole tile per query (what chol128_dev executes whatever k is); the tile and the pack written once per query
+  prof_end("local_gp", st, (double)mc * 128.0 * 128.0 * 128.0 / 3.0, (double)mc * 8.0 * (double)LOCAL_WG_DOUBLES);
 }
 
 void launch_vecchia_ll(const double* Xs, const double* Y, long N, int D, long p0, int mc, int k, const int* nbr, int kt, double sigma2,
                        double diag_add, double nugget, bool grad, double* scratch, int grid, double* out, int* ok, hipStream_t st) {
-  const size_t lds = vecchia_lds_bytes(D, grad);
+  const auto kern = kt == 0 ? (grad ? vecchia_ll_kernel<0, true> : vecchia_ll_kernel<0, false>)
+                            : (grad ? vecchia_ll_kernel<1, true> : vecchia_ll_kernel<1, false>);
   const char* tag = grad ? "vecchia_ll_grad" : "vecchia_ll";
   prof_begin(tag, st);
-#define MOGP_VLL(KT, GR)                                                                                                                      \
-  hipLaunchKernelGGL((vecchia_ll_kernel<KT, GR>), dim3(grid), dim3(256), lds, st, Xs, Y, (int)N, D, (int)p0, mc, k, nbr, sigma2, diag_add, nugget, \
-                     scratch, out, ok)
-  if (kt == 0) {
-    if (grad) MOGP_VLL(0, true);
-    else MOGP_VLL(0, false);
-  } else {
-    if (grad) MOGP_VLL(1, true);
-    else MOGP_VLL(1, false);
-  }
-#undef MOGP_VLL
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), local_lds_bytes(D, grad), st, Xs, Y, (int)N, D, (int)p0, mc, k, nbr, sigma2, diag_add, nugget,
+                     scratch, out, ok);
   prof_end(tag, st, (double)mc * 128.0 * 128.0 * 128.0 / 3.0, (double)mc * 8.0 * (double)(grad ? VECCHIA_WG_DOUBLES : LOCAL_WG_DOUBLES));
 }
 
@@ -574,161 +508,5 @@ void launch_local_scale(const double* x, long rows, int D, const double* s, doub
   hipLaunchKernelGGL(local_scale_kernel, dim3(grid), dim3(256), 0, st, x, total, D, s, out);
 }
 
-void launch_local_knn(const double* Xs, long N, int D, const double* Qs, int mc, int k, int* nbr, double* radius, hipStream_t st) {
-  const size_t lds = sizeof(double) * (size_t)D * KNN_LD;
-  prof_begin("local_knn", st);
-  hipLaunchKernelGGL(local_knn_kernel<false>, dim3((mc + LOCAL_KNN_QUERIES - 1) / LOCAL_KNN_QUERIES), dim3(256), lds, st, Xs, (int)N, D, Qs, mc, k,
-                     nbr, radius);
-  // algorithmic: a subtraction, a product and an addition per (query, design point, dimension); the design is read once per workgroup
-  prof_end("local_knn", st, 3.0 * (double)mc * (double)N * D, 8.0 * (double)N * D * ((mc + LOCAL_KNN_QUERIES - 1) / LOCAL_KNN_QUERIES));
-}
-
-void launch_local_gp(const double* Xs, const double* Y, long N, int D, const double* Qs, int mc, int k, const int* nbr, int kt, double sigma2,
-                     double diag_add, double var_add, double* scratch, int grid, double* mean, double* var, int* ok, hipStream_t st) {
-  const size_t lds = local_gp_lds_bytes(D);
-  prof_begin("local_gp", st);
-  if (kt == 0)
-    hipLaunchKernelGGL((local_gp_kernel<0>), dim3(grid), dim3(256), lds, st, Xs, Y, (int)N, D, Qs, mc, k, nbr, sigma2, diag_add, var_add, scratch,
-                       mean, var, ok);
-  else
-    hipLaunchKernelGGL((local_gp_kernel<1>), dim3(grid), dim3(256), lds, st, Xs, Y, (int)N, D, Qs, mc, k, nbr, sigma2, diag_add, var_add, scratch,
-                       mean, var, ok);
-  // the factorisation of one whole tile per query (what chol128_dev executes whatever k is); the tile and the pack written once per query
-  prof_end("local_gp", st, (double)mc * 128.0 * 128.0 * 128.0 / 3.0, (double)mc * 8.0 * (double)LOCAL_WG_DOUBLES);
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------------------
-// the handle
-// ---------------------------------------------------------------------------------------------------------------------------------------
-LocalGP::LocalGP(const double* inputs, long N_, int D_, const double* resid, int E_) : N(N_), D(D_), E(E_) {
-  if (!inputs || !resid) throw std::runtime_error("predict_local: null pointer");
-  if (D < 1 || D > MAX_D) throw std::runtime_error("predict_local: number of input dimensions must be between 1 and " + std::to_string(MAX_D));
-  if (N < 1 || N > LOCAL_MAX_N) throw std::runtime_error("predict_local: the design must have between 1 and " + std::to_string(LOCAL_MAX_N) + " points");
-  if (E < 1) throw std::runtime_error("predict_local: at least one row of targets is needed");
-  HIPCK(hipGetDevice(&device));
-  int cus = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) n_cu = cus;
-  const size_t nd = (size_t)N * D;
-  dX.reserve(nd);
-  dXs.reserve(nd);
-  dY.reserve((size_t)E * N);
-  dScale.reserve(D);
-  HIPCK(hipMemcpy(dX, inputs, nd * sizeof(double), hipMemcpyHostToDevice));
-  HIPCK(hipMemcpy(dY, resid, (size_t)E * N * sizeof(double), hipMemcpyHostToDevice));
-}
-
-void LocalGP::ensure_scaled(const double* scale, hipStream_t st) {
-  if (hScale.size() == (size_t)D && std::equal(hScale.begin(), hScale.end(), scale)) return;
-  hScale.clear();
-  HIPCK(hipMemcpyAsync(dScale, scale, D * sizeof(double), hipMemcpyHostToDevice, st));
-  launch_local_scale(dX, N, D, dScale, dXs, st);
-  HIPCK(hipGetLastError());
-  HIPCK(hipStreamSynchronize(st));
-  hScale.assign(scale, scale + D);
-}
-
-void LocalGP::vecchia_neighbours(const double* scale, int k, int* nbr_out) {
-  if (!scale) throw std::runtime_error("vecchia_neighbours: null pointer");
-  if (N < 2 || k < 1 || k > LOCAL_MAX_K || k > N - 1)
-    throw std::runtime_error("vecchia_neighbours: n_neighbours must be between 1 and " + std::to_string(std::min<long>(N - 1, LOCAL_MAX_K)));
-  for (int d = 0; d < D; ++d)
-    if (!(scale[d] > 0.) || !std::isfinite(scale[d])) throw std::runtime_error("vecchia_neighbours: the scales must be positive and finite");
-  DeviceGuard guard(device);
-  hipStream_t st = nullptr;
-  SyncOnUnwind sync{st};
-  vk = 0;
-  dVnbr.reserve((size_t)N * k);
-  ensure_scaled(scale, st);
-  launch_vecchia_knn(dXs, N, D, k, dVnbr, st);
-  HIPCK(hipGetLastError());
-  if (nbr_out) HIPCK(hipMemcpyAsync(nbr_out, dVnbr, (size_t)N * k * sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPCK(hipStreamSynchronize(st));
-  vk = k;
-}
-
-void LocalGP::vecchia_loglik(int e, int kt, const double* scale, double sigma2, double nugget, double jitter, int k, bool want_grad, int max_points,
-                             double* value_out, double* grad_out, double* terms_out, int* ok_out) {
-  if (!scale || !value_out || (want_grad && !grad_out)) throw std::runtime_error("vecchia_loglik: null pointer");
-  if (e < 0 || e >= E) throw std::runtime_error("vecchia_loglik: emulator index out of range");
-  if (kt != 0 && kt != 1) throw std::runtime_error("vecchia_loglik: the kernel must be a function of one scaled distance (squared exponential or Matern 5/2)");
-  if (vk == 0) throw std::runtime_error("vecchia_loglik: the neighbour lists have not been built (vecchia_neighbours)");
-  if (k != vk) throw std::runtime_error("vecchia_loglik: the neighbour lists were built for n_neighbours = " + std::to_string(vk));
-  if (!(sigma2 > 0.) || !std::isfinite(sigma2) || !(nugget >= 0.) || !std::isfinite(nugget) || !(jitter >= 0.) || !std::isfinite(jitter))
-    throw std::runtime_error("vecchia_loglik: sigma^2 must be positive and finite, nugget and jitter finite and not negative");
-  for (int d = 0; d < D; ++d)
-    if (!(scale[d] > 0.) || !std::isfinite(scale[d])) throw std::runtime_error("vecchia_loglik: the scales must be positive and finite");
-  DeviceGuard guard(device);
-  hipStream_t st = nullptr;
-  size_t free_b = 0, total_b = 0;
-  HIPCK(hipMemGetInfo(&free_b, &total_b));
-  const size_t wg = want_grad ? VECCHIA_WG_DOUBLES : LOCAL_WG_DOUBLES;
-  const int cols = want_grad ? D + 3 : 1;
-  // what the handle holds from earlier calls is not free any more but is reused
-  const double held = 8.0 * ((double)dVout.size() + (double)dVred.size() + (double)dVscratch.size()) + 4.0 * (double)dVok.size();
-  const VecchiaPlan plan = vecchia_plan(N, D, want_grad, n_cu, (double)free_b + held, max_points, (double)wg * sizeof(double));
-  SyncOnUnwind sync{st};
-  dVout.reserve((size_t)cols * N);
-  dVok.reserve((size_t)N);
-  dVred.reserve((size_t)2 * cols * plan.blocks);
-  dVscratch.reserve((size_t)plan.grid * wg);
-  ensure_scaled(scale, st);
-  const double* dYe = dY.get() + (size_t)e * N;
-  for (long c0 = 0; c0 < N; c0 += plan.points) {
-    const int mc = (int)std::min<long>(plan.points, N - c0);
-    launch_vecchia_ll(dXs, dYe, N, D, c0, mc, k, dVnbr, kt, sigma2, nugget + jitter, nugget, want_grad, dVscratch, std::min(plan.grid, mc), dVout,
-                      dVok, st);
-  }
-  HIPCK(hipGetLastError());
-  double* half = dVred.get() + (size_t)cols * plan.blocks;
-  const double* sums = launch_vecchia_reduce(dVout, N, cols, dVred, half, st);
-  HIPCK(hipGetLastError());
-  std::vector<double> h(cols);
-  HIPCK(hipMemcpyAsync(h.data(), sums, (size_t)cols * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (terms_out) HIPCK(hipMemcpyAsync(terms_out, dVout, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (ok_out) HIPCK(hipMemcpyAsync(ok_out, dVok, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPCK(hipStreamSynchronize(st));
-  *value_out = h[0];
-  if (want_grad) std::copy(h.begin() + 1, h.end(), grad_out);
-}
-
-void LocalGP::predict(int e, int kt, const double* scale, double sigma2, double nugget, double jitter, bool include_nugget, const double* testing,
-                      long m, int k, int max_points, double* mean, double* var, int* ok, double* radius, int* nbr) {
-  if (!scale || !testing || !mean || !ok || !radius) throw std::runtime_error("predict_local: null pointer");
-  if (e < 0 || e >= E) throw std::runtime_error("predict_local: emulator index out of range");
-  if (kt != 0 && kt != 1) throw std::runtime_error("predict_local: the kernel must be a function of one scaled distance (squared exponential or Matern 5/2)");
-  if (k < 1 || k > LOCAL_MAX_K || k > N)
-    throw std::runtime_error("predict_local: n_neighbours must be between 1 and " + std::to_string(std::min<long>(N, LOCAL_MAX_K)));
-  if (m < 1 || m > INT_MAX) throw std::runtime_error("predict_local: at least one testing point is needed");
-  if (!(sigma2 > 0.) || !std::isfinite(sigma2) || !(nugget >= 0.) || !std::isfinite(nugget) || !(jitter >= 0.) || !std::isfinite(jitter))
-    throw std::runtime_error("predict_local: sigma^2 must be positive and finite, nugget and jitter finite and not negative");
-  for (int d = 0; d < D; ++d)
-    if (!(scale[d] > 0.) || !std::isfinite(scale[d])) throw std::runtime_error("predict_local: the scales must be positive and finite");
-  DeviceGuard guard(device);
-  hipStream_t st = nullptr;
-  size_t free_b = 0, total_b = 0;
-  HIPCK(hipMemGetInfo(&free_b, &total_b));
-  const LocalPlan plan = local_plan(m, D, k, n_cu, (double)free_b, max_points, (double)LOCAL_WG_DOUBLES * sizeof(double));
-  const size_t P = (size_t)plan.points;
-  DevBuf<double> dQ(P * D), dQs(P * D), dRad(P), dMean(P), dVar(P), dScratch((size_t)plan.grid * LOCAL_WG_DOUBLES);
-  DevBuf<int> dNbr(P * k), dOk(P);
-  SyncOnUnwind sync{st};
-  ensure_scaled(scale, st);
-  const double* dYe = dY.get() + (size_t)e * N;
-  for (long c0 = 0; c0 < m; c0 += plan.points) {
-    const int mc = (int)std::min<long>(plan.points, m - c0);
-    const int grid = std::min(plan.grid, mc);
-    HIPCK(hipMemcpyAsync(dQ, testing + (size_t)c0 * D, (size_t)mc * D * sizeof(double), hipMemcpyHostToDevice, st));
-    launch_local_scale(dQ, mc, D, dScale, dQs, st);
-    launch_local_knn(dXs, N, D, dQs, mc, k, dNbr, dRad, st);
-    launch_local_gp(dXs, dYe, N, D, dQs, mc, k, dNbr, kt, sigma2, nugget + jitter, include_nugget ? nugget : 0., dScratch, grid, dMean, dVar, dOk, st);
-    HIPCK(hipGetLastError());
-    HIPCK(hipMemcpyAsync(mean + c0, dMean, (size_t)mc * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (var) HIPCK(hipMemcpyAsync(var + c0, dVar, (size_t)mc * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCK(hipMemcpyAsync(ok + c0, dOk, (size_t)mc * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCK(hipMemcpyAsync(radius + c0, dRad, (size_t)mc * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (nbr) HIPCK(hipMemcpyAsync(nbr + (size_t)c0 * k, dNbr, (size_t)mc * k * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCK(hipStreamSynchronize(st));
-  }
-}
 
 }  // namespace mogp

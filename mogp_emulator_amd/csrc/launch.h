@@ -311,6 +311,7 @@ void launch_alc_condition(const BatchView& v, int t, int T, int rows, const int*
 // Prediction from the k nearest design points of every query alone (DESIGN.md section 3 "Local prediction").  Point indices are int (N < 2^31),
 // element offsets size_t.
 constexpr int LOCAL_MAX_K = 126;        // k neighbours + the target row + the query row share ONE 128 x 128 tile
+constexpr long LOCAL_MAX_N = 2147483647L - 256;        // a tile's row index j0 + 127 of the neighbour search stays an int
 constexpr int LOCAL_KNN_QW = 4;         // queries per wave of the neighbour search
 constexpr int LOCAL_KNN_QUERIES = 4 * LOCAL_KNN_QW;    // ... per 256-thread workgroup
 constexpr int LOCAL_KNN_ROWS = 128;     // design rows per staged tile

@@ -1,7 +1,8 @@
 // How the prediction family of Engine (engine_predict.hip) and the analysis family (engine_analysis.hip: hessian, predict_mixture,
 // cross_validate, sample_posterior, alc, alc_batch, predict_cov) cut their work to a byte budget, the index tables of their passes, and where the mean-function terms of a prediction are
 // staged.  Plain host arithmetic with no HIP in it, so that a host compiler takes it and tests/c/predict_plan_check.cpp, mixture_plan_check.cpp,
-// cv_plan_check.cpp, sample_plan_check.cpp, alc_plan_check.cpp, alc_batch_plan_check.cpp, local_plan_check.cpp and vecchia_plan_check.cpp can check it without a device.  The caps that need the device (MOGP_KS_BUDGET_GB, free memory) are passed in.
+// cv_plan_check.cpp, sample_plan_check.cpp, alc_plan_check.cpp, alc_batch_plan_check.cpp, local_plan_check.cpp, vecchia_plan_check.cpp and local_args_check.cpp (the refusals
+// and the LDS layout of the LocalGP handle, engine_local.hip) can check it without a device.  The caps that need the device (MOGP_KS_BUDGET_GB, free memory) are passed in.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -264,7 +265,44 @@ inline double predict_cov_rule_bytes(long m1, long m2, int LD, int NP) {
   return 8.0 * ((double)NP * (MP1 + MP2) + (double)m1 * (double)m2 + (double)LD * std::max(MP1, MP2));
 }
 
-// LocalGP::predict (kernels_local.hip): how many queries one pass takes and how many persistent workgroups factor their local matrices.
+// The refusals LocalGP::predict, vecchia_neighbours and vecchia_loglik share (engine_local.hip); `who` is the prefix of the message.
+//   local_check_kernel  kt: 0 squared exponential, 1 Matern 5/2
+//   local_check_k       1 <= k <= LOCAL_MAX_K (launch.h: 126, passed in) and k <= N; vecchia: k <= N - 1, a point's neighbours come before it
+//   local_check_hyper   sigma^2, nugget and jitter, then the D scales (local_check_scales: all that vecchia_neighbours needs)
+inline void local_check_kernel(const std::string& who, int kt) {
+  if (kt != 0 && kt != 1) throw std::runtime_error(who + ": the kernel must be a function of one scaled distance (squared exponential or Matern 5/2)");
+}
+inline void local_check_k(const std::string& who, long N, int k, bool vecchia, int max_k) {
+  const long top = vecchia ? N - 1 : N;
+  if (top < 1 || k < 1 || k > max_k || k > top)
+    throw std::runtime_error(who + ": n_neighbours must be between 1 and " + std::to_string(std::min<long>(top, max_k)));
+}
+inline void local_check_scales(const std::string& who, int D, const double* scale) {
+  for (int d = 0; d < D; ++d)
+    if (!(scale[d] > 0.) || !std::isfinite(scale[d])) throw std::runtime_error(who + ": the scales must be positive and finite");
+}
+inline void local_check_hyper(const std::string& who, int D, const double* scale, double sigma2, double nugget, double jitter) {
+  if (!(sigma2 > 0.) || !std::isfinite(sigma2) || !(nugget >= 0.) || !std::isfinite(nugget) || !(jitter >= 0.) || !std::isfinite(jitter))
+    throw std::runtime_error(who + ": sigma^2 must be positive and finite, nugget and jitter finite and not negative");
+  local_check_scales(who, D, scale);
+}
+
+// The dynamic LDS of local_gp_kernel and vecchia_ll_kernel (kernels_local.hip), offsets in doubles: chol128_dev's own, the exponential's
+// table tab (256), the targets yv (128), with the gradient w and alpha (wv, av: 128 each) and the partial sums of a_d and b_d (reda, redb:
+// 256 each), the gathered points pts (128 rows of ld doubles) and chol128_dev's status word info (in the dynamic region: a static one
+// would misalign it).  constexpr, so that the kernels and the host read the same text.
+constexpr int LOCAL_CHOL_LDS_DOUBLES = 128 * 18 + 256 + 256;      // chol128_dev.h C128_LDS_DOUBLES (kernels_local.hip asserts it)
+struct LocalLds {
+  int tab, yv, wv, av, reda, redb, pts, ld, info, doubles;
+  constexpr LocalLds(int D, bool grad)
+      : tab(LOCAL_CHOL_LDS_DOUBLES), yv(tab + 256), wv(yv + 128), av(wv + (grad ? 128 : 0)), reda(av + (grad ? 128 : 0)),
+        redb(reda + (grad ? 256 : 0)), pts(redb + (grad ? 256 : 0)),
+        ld(D | 1),                                                 // odd row stride: rows a lane apart fall on different banks
+        info(pts + 128 * ld), doubles(info + 2) {}
+};
+inline std::size_t local_lds_bytes(int D, bool grad) { return sizeof(double) * (std::size_t)LocalLds(D, grad).doubles; }
+
+// LocalGP::predict (engine_local.hip): how many queries one pass takes and how many persistent workgroups factor their local matrices.
 // Bytes of one query of a pass (local_point_bytes): its raw and its scaled coordinates (2 D doubles), k neighbour indices and the ok flag
 // (ints), radius, mean and variance (doubles).  Every workgroup owns wg_bytes of scratch (launch.h LOCAL_WG_DOUBLES).
 //   grid    LOCAL_GRID_PER_CU workgroups per compute unit, never more than the queries of a pass, at least one
@@ -298,14 +336,19 @@ inline LocalPlan local_plan(long m, int D, int k, int n_cu, double free_bytes, i
   return {points, (int)std::min(points, full)};
 }
 
-// LocalGP::vecchia_loglik (kernels_local.hip): how many points one launch takes and how many persistent workgroups factor their local
+// LocalGP::vecchia_loglik (engine_local.hip): how many points one launch takes and how many persistent workgroups factor their local
 // matrices.  Held for the whole design, whatever the launches (vecchia_fixed_bytes): per point the term and, with the gradient, its D + 2
 // derivatives (doubles) and the ok flag (int); two buffers of ceil(N / 1024) partial sums per column.  Every workgroup owns wg_bytes of
 // scratch (launch.h LOCAL_WG_DOUBLES, VECCHIA_WG_DOUBLES with the gradient).
 //   points  max_points where given, else LOCAL_MAX_PASS; at most N, at least one
 //   grid    LOCAL_GRID_PER_CU workgroups per compute unit, never more than the points of a launch, at least one
 // Neither changes a bit of a result: a point's term depends on nothing but the point, and the sum runs over the whole design in blocks of 1024
-// afterwards.  Throws for a negative max_points and when the whole does not fit half of the free device memory.
+// afterwards.  Throws for a negative max_points and when the whole does not fit half of the free device memory.  What the handle holds
+// from earlier calls is not free any more but is reused: vecchia_held_bytes of its buffers (elements: out, red and scratch doubles, ok ints)
+// count as free.
+inline double vecchia_held_bytes(std::size_t out, std::size_t red, std::size_t scratch, std::size_t ok) {
+  return 8.0 * ((double)out + (double)red + (double)scratch) + 4.0 * (double)ok;
+}
 struct VecchiaPlan {
   long points;
   int grid;

@@ -13,8 +13,11 @@ M = 37
 D_ENDS_AND_EDGES = [1] + dc.D_EDGES[:-1] + [79, 80]        # 1, 16, 17, 32, 33, 79, 80
 SWEEP_K = 16
 SWEEP_KERNELS = KERNELS[:2]                                  # the per-dimension kernels
-ALL = [(N, D, k, kern) for (N, D, k) in SHAPES for kern in KERNELS] + [(dc.N_TILES, D, SWEEP_K, kern) for D in D_ENDS_AND_EDGES
-                                                                       for kern in SWEEP_KERNELS]
+# odd k: the tile's k + 2 rows are an odd count, whose middle row is its own partner in the kernel's mirrored row pairs; k = 1 is the least
+ODD_K = [(130, 3, 1), (130, 3, 7), (130, 3, 125)]
+ALL = ([(N, D, k, kern) for (N, D, k) in SHAPES for kern in KERNELS] + [(dc.N_TILES, D, SWEEP_K, kern) for D in D_ENDS_AND_EDGES
+                                                                        for kern in SWEEP_KERNELS]
+       + [(N, D, k, kern) for (N, D, k) in ODD_K for kern in SWEEP_KERNELS])
 SIGMA2 = float(np.exp(dc.LOG_COV))
 
 

@@ -63,6 +63,12 @@ def test_input_dimension(D, kernel):
     _check_neighbours_and_values(dc.N_TILES, D, lc.SWEEP_K, kernel)
 
 
+@pytest.mark.parametrize("kernel", lc.SWEEP_KERNELS)
+@pytest.mark.parametrize("N,D,k", lc.ODD_K)
+def test_odd_neighbour_counts(N, D, k, kernel):
+    _check_neighbours_and_values(N, D, k, kernel)
+
+
 @pytest.mark.parametrize("kernel", lc.KERNELS)
 def test_all_points_as_neighbours_is_the_dense_prediction(kernel):
     N, D, k = 126, 2, 126

@@ -1,7 +1,8 @@
 """Host-side checks of local approximate GP prediction (mogp_emulator_amd.LocalGP): the argument refusals that need no device, the
-bookkeeping of LocalPrediction, local_plan (csrc/predict_plan.h) against a hand-worked table through a sanitised stand-alone program, and
-the NumPy restatement (local_restate.py) in float64 against itself in long double on every shape of the GPU tests -- which proves that the
-bars the device is held to are not vacuous: the float64 error lies below them and above 0."""
+bookkeeping of LocalPrediction, local_plan (csrc/predict_plan.h) against a hand-worked table and the named refusals and the LDS layout of
+the handle (tests/c/local_args_check.cpp), each through a sanitised stand-alone program, and the NumPy restatement (local_restate.py) in
+float64 against itself in long double on every shape of the GPU tests -- which proves that the bars the device is held to are not vacuous:
+the float64 error lies below them and above 0."""
 import importlib
 import os
 import shutil
@@ -36,6 +37,11 @@ def _build_and_run(tmp_path, name):
 def test_local_plan_matches_the_hand_worked_table(tmp_path):
     out = _build_and_run(tmp_path, "local_plan_check")
     assert out.strip() == "ok 10 rows"
+
+
+def test_named_refusals_and_lds_layout_of_the_handle(tmp_path):
+    out = _build_and_run(tmp_path, "local_args_check")
+    assert out.strip() == "ok 805 checks"
 
 
 def test_exports():
