@@ -1,5 +1,6 @@
 // The active-learning entries of the C ABI, for DenseGP_GPU and MultiOutputGP_GPU: the posterior cross covariance of two point sets and the
-// ALC design criterion, one pick at a time or in greedy batches (Engine::predict_cov, Engine::alc, Engine::alc_batch / Engine::AlcBatch)
+// ALC design criterion, one pick at a time or in greedy batches (predict_cov, alc, alc_batch / AlcBatch of analysis.h)
+#include "analysis.h"
 #include "capi_internal.h"
 
 using namespace mogp;
@@ -27,7 +28,7 @@ int mogp_densegp_predict_cov(mogp_densegp* h, const double* X1, int m1, const do
   return on_engine_device(h, [&] {
     check_D(D, h->eng);
     check_fit(h);
-    h->eng->predict_cov({h->idx}, X1, m1, X2, m2, max_slots, cov_out);
+    predict_cov(*h->eng, {h->idx}, X1, m1, X2, m2, max_slots, cov_out);
   });
 }
 int mogp_densegp_alc(mogp_densegp* h, const double* candidates, int m_c, const double* reference, int m_r, int D, const double* weights,
@@ -36,11 +37,11 @@ int mogp_densegp_alc(mogp_densegp* h, const double* candidates, int m_c, const d
   return on_engine_device(h, [&] {
     check_D(D, h->eng);
     check_fit(h);
-    h->eng->alc({h->idx}, candidates, m_c, reference, m_r, weights, noise, max_slots, max_points, reduction_out, cand_var_out, ref_var_out,
+    alc(*h->eng, {h->idx}, candidates, m_c, reference, m_r, weights, noise, max_slots, max_points, reduction_out, cand_var_out, ref_var_out,
                 degenerate_out);
   });
 }
-// every part: its fitted emulators in one Engine::predict_cov, the rows of the others NaN
+// every part: its fitted emulators in one predict_cov, the rows of the others NaN
 int mogp_mogp_predict_cov(mogp_mogp* h, const double* X1, int m1, const double* X2, int m2, int D, int max_slots, double* cov_out) {
   return guarded([&] {
     check_model("predict_cov", h, D);
@@ -51,11 +52,11 @@ int mogp_mogp_predict_cov(mogp_mogp* h, const double* X1, int m1, const double* 
       Engine* e = p.eng.get();
       const std::vector<int> ids = fitted_ids(e);
       with_rows(e->B, ids, {Rows::out(cov_out + (size_t)p.lo * mm, mm, true)},
-                [&](const std::vector<Rows>& a) { e->predict_cov(ids, X1, m1, X2, m2, max_slots, a[0].d()); });
+                [&](const std::vector<Rows>& a) { predict_cov(*e, ids, X1, m1, X2, m2, max_slots, a[0].d()); });
     });
   });
 }
-// every part: its fitted emulators in one Engine::alc, the rows of the others NaN and degenerate = 0
+// every part: its fitted emulators in one alc, the rows of the others NaN and degenerate = 0
 int mogp_mogp_alc(mogp_mogp* h, const double* candidates, int m_c, const double* reference, int m_r, int D, const double* weights,
                   const double* noise, int max_slots, int max_points, double* reduction_out, double* cand_var_out, double* ref_var_out,
                   int* degenerate_out) {
@@ -73,7 +74,7 @@ int mogp_mogp_alc(mogp_mogp* h, const double* candidates, int m_c, const double*
                 {Rows::in(noise ? noise + lo : nullptr, 1), Rows::out(reduction_out + lo * mc, mc, true), Rows::out(cand_var_out + lo * mc, mc, true),
                  Rows::out(ref_var_out + lo * mr, mr, true), Rows::out(degenerate_out + lo * mc, mc, true)},
                 [&](const std::vector<Rows>& a) {
-                  e->alc(ids, candidates, m_c, reference, m_r, weights, a[0].d(), max_slots, max_points, a[1].d(), a[2].d(), a[3].d(), a[4].i());
+                  alc(*e, ids, candidates, m_c, reference, m_r, weights, a[0].d(), max_slots, max_points, a[1].d(), a[2].d(), a[3].d(), a[4].i());
                 });
     });
   });
@@ -85,12 +86,12 @@ int mogp_densegp_alc_batch(mogp_densegp* h, const double* candidates, int m, int
   return on_engine_device(h, [&] {
     check_D(D, h->eng);
     check_fit(h);
-    h->eng->alc_batch({h->idx}, candidates, m, n_forced, reference, m_r, weights, noise, n_points, max_slots,
+    alc_batch(*h->eng, {h->idx}, candidates, m, n_forced, reference, m_r, weights, noise, n_points, max_slots,
                       {picks_out, pick_red_out, red_out, deg_out, cand_var_out, ref_var_out, ref_var_after_out, iv_out});
   });
 }
 
-// select_total = 0: every part runs its fitted emulators through Engine::alc_batch.  select_total = 1: one Engine::AlcBatch per part stays
+// select_total = 0: every part runs its fitted emulators through alc_batch.  select_total = 1: one AlcBatch per part stays
 // open over the steps; per step every part downloads its score rows, this layer sums red_e / IV_e over the fitted emulators of ALL parts in
 // ascending emulator order (IV_e: the integrated variance before the step, from the same rows) and takes the arg-max -- ties to the lowest
 // index, a masked candidate never, a NaN never --, and every part applies that pick.  The sum depends on the rows alone, not on the parts.
@@ -122,14 +123,14 @@ int mogp_mogp_alc_batch(mogp_mogp* h, const double* candidates, int m, int n_for
                                Rows::out(iv_out + lo * (T + 1), (size_t)T + 1, true)};
     };
     const auto as_out = [](const std::vector<Rows>& a) {
-      return Engine::AlcBatchOut{a[1].i(), a[2].d(), a[3].d(), a[4].i(), a[5].d(), a[6].d(), a[7].d(), a[8].d()};
+      return AlcBatchOut{a[1].i(), a[2].d(), a[3].d(), a[4].i(), a[5].d(), a[6].d(), a[7].d(), a[8].d()};
     };
     if (!select_total) {
       for_parts(h, [&](mogp_part& p, int) {
         Engine* e = p.eng.get();
         const std::vector<int> ids = fitted_ids(e);
         with_rows(e->B, ids, part_rows((size_t)p.lo), [&](const std::vector<Rows>& a) {
-          e->alc_batch(ids, candidates, m, n_forced, reference, m_r, weights, a[0].d(), n_points, max_slots, as_out(a));
+          alc_batch(*e, ids, candidates, m, n_forced, reference, m_r, weights, a[0].d(), n_points, max_slots, as_out(a));
         });
       });
       return;
@@ -138,7 +139,7 @@ int mogp_mogp_alc_batch(mogp_mogp* h, const double* candidates, int m, int n_for
     struct PartRun {
       std::vector<int> ids, picks, deg, row_deg;
       std::vector<double> tau, pick_red, red, cand_var, ref_var, ref_var_after, iv, row_red, iv_now;
-      std::unique_ptr<Engine::AlcBatch> run;
+      std::unique_ptr<AlcBatch> run;
     };
     const int np = (int)h->parts.size();
     std::vector<PartRun> pr((size_t)np);
@@ -167,13 +168,13 @@ int mogp_mogp_alc_batch(mogp_mogp* h, const double* candidates, int m, int n_for
       std::vector<double> nz(nf);
       if (noise)
         for (size_t s = 0; s < nf; ++s) nz[s] = noise[(size_t)p.lo + r.ids[s]];
-      e->alc_batch_check(r.ids, candidates, m, n_forced, reference, m_r, weights, noise ? nz.data() : nullptr, n_points, 0, r.tau);
-      e->alc_batch_slots((long)nf, m, m_r, T, 0, true);
+      alc_batch_check(*e, r.ids, candidates, m, n_forced, reference, m_r, weights, noise ? nz.data() : nullptr, n_points, 0, r.tau);
+      alc_batch_slots(*e, (long)nf, m, m_r, T, 0, true);
       r.picks.assign(nf * T, -1), r.pick_red.assign(nf * T, 0.), r.cand_var.resize(nf * M), r.ref_var.resize(nf * mr);
       r.ref_var_after.resize(nf * mr), r.iv.resize(nf * (T + 1)), r.row_red.resize(nf * M), r.row_deg.resize(nf * M), r.iv_now.resize(nf);
       if (red_out) r.red.resize(nf * TM);
       if (deg_out) r.deg.resize(nf * TM);
-      r.run.reset(new Engine::AlcBatch(*e, r.ids, r.tau.data(), candidates, m, n_forced, reference, m_r, weights, n_points,
+      r.run.reset(new AlcBatch(*e, r.ids, r.tau.data(), candidates, m, n_forced, reference, m_r, weights, n_points,
                                        {r.picks.data(), r.pick_red.data(), red_out ? r.red.data() : nullptr, deg_out ? r.deg.data() : nullptr,
                                         r.cand_var.data(), r.ref_var.data(), r.ref_var_after.data(), r.iv.data()}));
       for (size_t s = 0; s < nf; ++s) {

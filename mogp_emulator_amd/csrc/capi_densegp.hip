@@ -1,4 +1,5 @@
 // DenseGP_GPU: one emulator, an engine of its own or a borrowed view into a MultiOutputGP_GPU's (capi_internal.h)
+#include "analysis.h"
 #include "capi_internal.h"
 
 using namespace mogp;
@@ -226,7 +227,7 @@ int mogp_densegp_predict_mixture(mogp_densegp* h, const double* thetas, int S, i
     if (S >= 1 && len != e->n_theta(h->idx)) throw std::runtime_error("Shape of new GPParams object does not match existing one");
     const GPState& g = e->gp[h->idx];
     if (!(g.has_data && g.factored)) throw std::runtime_error("Hyperparameters have not been fit for this Gaussian Process");
-    e->predict_mixture({h->idx}, thetas, S, len, weights, log_q, testing, m, include_nugget != 0, max_slots, max_points, mean_out, within_out,
+    predict_mixture(*e, {h->idx}, thetas, S, len, weights, log_q, testing, m, include_nugget != 0, max_slots, max_points, mean_out, within_out,
                        between_out, weights_out, logpost_out, ok_out, nullptr);
   });
 }
@@ -237,7 +238,7 @@ int mogp_densegp_cross_validate(mogp_densegp* h, const int* labels, int n_labels
     const GPState& g = e->gp[h->idx];
     if (!(g.has_data && g.factored)) throw std::runtime_error("Hyperparameters have not been fit for this Gaussian Process");
     if (n_labels != e->n) throw std::runtime_error("cross_validate: one fold label per training point is needed");
-    e->cross_validate({h->idx}, labels, k, include_nugget != 0, max_slots, mean_out, var_out, maha_out, log_score_out, ok_out);
+    cross_validate(*e, {h->idx}, labels, k, include_nugget != 0, max_slots, mean_out, var_out, maha_out, log_score_out, ok_out);
   });
 }
 int mogp_densegp_sample_posterior(mogp_densegp* h, const double* testing, int m, int D, int S, unsigned long long seed, unsigned int stream0,
@@ -249,7 +250,7 @@ int mogp_densegp_sample_posterior(mogp_densegp* h, const double* testing, int m,
     const GPState& g = e->gp[h->idx];
     if (!(g.has_data && g.factored)) throw std::runtime_error("Hyperparameters have not been fit for this Gaussian Process");
     (void)z_in_per_emulator;      // one emulator: (S, m) either way
-    e->sample_posterior({h->idx}, &stream0, testing, m, S, seed, z_in, false, include_nugget != 0, jitter, max_slots, max_draws, samples_out,
+    sample_posterior(*e, {h->idx}, &stream0, testing, m, S, seed, z_in, false, include_nugget != 0, jitter, max_slots, max_draws, samples_out,
                         mean_out, z_out, jitter_used_out, ok_out);
   });
 }

@@ -1,5 +1,6 @@
 // MultiOutputGP_GPU: the prediction family -- host predict, full covariance, Sobol indices, the mixture over hyperparameter samples,
 // implausibility with its cross-part merge, and the device-resident predict
+#include "analysis.h"
 #include "capi_internal.h"
 
 using namespace mogp;
@@ -76,7 +77,6 @@ static void engine_sobol(Engine* e, const double* A, const double* B, int N, boo
 }
 // device-resident prediction: d_means / d_vars (n_emulators, m) and d_derivs (n_emulators, m, D) are device buffers (d_vars, d_derivs may be
 // null); rows of emulators that are not fit are filled with NaN (MultiOutputGP_GPU.py:288-296)
-#define HIPCK(x) hip_check((x), #x)
 static void engine_predict_dev(Engine* e, const double* d_testing, int m, int D, double* d_means, double* d_vars, double* d_derivs) {
   std::vector<int> ids = fitted_ids(e);
   if ((int)ids.size() == e->B) {
@@ -213,7 +213,7 @@ int mogp_mogp_sobol(mogp_mogp* h, const double* A, const double* B, int N, int D
     });
   });
 }
-// every part: its fitted emulators in one Engine::predict_mixture, the rows of the others NaN
+// every part: its fitted emulators in one predict_mixture, the rows of the others NaN
 int mogp_mogp_predict_mixture(mogp_mogp* h, const double* thetas, int S, int n_cols, const double* weights, const double* log_q,
                               const double* testing, int m, int D, int include_nugget, int max_slots, int max_points, double* mean_out,
                               double* within_out, double* between_out, double* weights_out, double* logpost_out, int* ok_out,
@@ -236,13 +236,13 @@ int mogp_mogp_predict_mixture(mogp_mogp* h, const double* thetas, int S, int n_c
                         Rows::out(weights_out + lo * SS, SS, true), Rows::out(logpost_out + lo * SS, SS, true),
                         Rows::out(ok_out + lo * SS, SS, true), Rows::out(ok_all_out ? ok_all_out + lo : nullptr, 1, true)},
                        [&](const std::vector<int>& ids, const std::vector<Rows>& a) {
-                         e->predict_mixture(ids, a[0].d(), S, n_cols, a[1].d(), a[2].d(), testing, m, include_nugget != 0, max_slots, max_points,
+                         predict_mixture(*e, ids, a[0].d(), S, n_cols, a[1].d(), a[2].d(), testing, m, include_nugget != 0, max_slots, max_points,
                                             a[3].d(), a[4].d(), a[5].d(), a[6].d(), a[7].d(), a[8].i(), a[9].i());
                        });
     });
   });
 }
-// every part: its fitted emulators in one Engine::cross_validate, the rows of the others NaN and ok = 0
+// every part: its fitted emulators in one cross_validate, the rows of the others NaN and ok = 0
 int mogp_mogp_cross_validate(mogp_mogp* h, const int* labels, int n_labels, int k, int include_nugget, int max_slots, double* mean_out,
                              double* var_out, double* maha_out, double* log_score_out, int* ok_out) {
   return guarded([&] {
@@ -257,12 +257,12 @@ int mogp_mogp_cross_validate(mogp_mogp* h, const int* labels, int n_labels, int 
                        {Rows::out(mean_out + lo * nn, nn, true), Rows::out(var_out + lo * nn, nn, true), Rows::out(maha_out + lo * kk, kk, true),
                         Rows::out(log_score_out + lo * kk, kk, true), Rows::out(ok_out + lo * kk, kk, true)},
                        [&](const std::vector<int>& ids, const std::vector<Rows>& a) {
-                         e->cross_validate(ids, labels, k, include_nugget != 0, max_slots, a[0].d(), a[1].d(), a[2].d(), a[3].d(), a[4].i());
+                         cross_validate(*e, ids, labels, k, include_nugget != 0, max_slots, a[0].d(), a[1].d(), a[2].d(), a[3].d(), a[4].i());
                        });
     });
   });
 }
-// every part: its fitted emulators in one Engine::sample_posterior, each on stream stream0 + its index in the model; the rows of the
+// every part: its fitted emulators in one sample_posterior, each on stream stream0 + its index in the model; the rows of the
 // others NaN and ok = 0
 int mogp_mogp_sample_posterior(mogp_mogp* h, const double* testing, int m, int D, int S, unsigned long long seed, unsigned int stream0,
                                const double* z_in, int z_in_per_emulator, int include_nugget, double jitter, int max_slots, int max_draws,
@@ -285,7 +285,7 @@ int mogp_mogp_sample_posterior(mogp_mogp* h, const double* testing, int m, int D
                        [&](const std::vector<int>& ids, const std::vector<Rows>& a) {
                          std::vector<unsigned> streams(ids.size());
                          for (size_t k = 0; k < ids.size(); ++k) streams[k] = stream0 + (unsigned)(p.lo + ids[k]);
-                         e->sample_posterior(ids, streams.data(), testing, m, S, seed, per ? a[0].d() : z_in, per, include_nugget != 0, jitter,
+                         sample_posterior(*e, ids, streams.data(), testing, m, S, seed, per ? a[0].d() : z_in, per, include_nugget != 0, jitter,
                                              max_slots, max_draws, a[1].d(), a[2].d(), a[3].d(), a[4].d(), a[5].i());
                        });
     });

@@ -13,6 +13,7 @@
 namespace mogp {
 
 void hip_check(hipError_t e, const char* what);
+#define HIPCK(x) hip_check((x), #x)
 
 // device bytes currently held by DevBuf objects of this process (mogp_profile_counter "device_bytes_live")
 inline std::atomic<long long> g_device_bytes_live{0};

@@ -36,8 +36,6 @@ struct DeviceGuard {
   DeviceGuard& operator=(const DeviceGuard&) = delete;
 };
 
-struct CvBuffers;      // engine_analysis.hip
-struct CvFolds;        // predict_plan.h
 class ScratchFactor;   // engine_internal.h
 // what build_cov runs instead of the covariance build when a factorisation is given one (ScratchFactor::factor): it writes every slot's
 // matrix into the factor buffer, with the layout of the covariance build (launch.h)
@@ -110,127 +108,10 @@ class Engine {
   // entry, the leading n_theta x n_theta block filled; ok[k] = 0 and NaN where the factorisation fails.  Throws for what it does not
   // cover (nugget="pivot", analytic mean, mean parameters in theta, ProductMat52).  The cached state of a fitted emulator is kept.
   void hessian(const std::vector<int>& ids, const std::vector<const double*>& thetas, double* H, int ld, int* ok);
-  // Prediction averaged over S hyperparameter samples per emulator (kernels_mixture.hip).  thetas (E, S, ld): full vectors [mean | data]
-  // of emulator ids[e], the first n_theta of each row used; EXACTLY ONE of weights (E, S, non-negative) and log_q (E, S, the log proposal
-  // density up to a constant: self-normalised importance weights exp(-(F - F_min) - (log_q - log_q at the arg-min)), predict_plan.h
-  // mixture_weights); Xs host (m, D).  The (emulator, sample) pairs are factored on a replica engine (as fit_map's starts are), emulator-major
-  // and sample-ascending, `slots` at a time; THIS engine's emulators are not refitted -- factor, alpha, L^-1, K^-1, theta and logpost stay.
-  // Per emulator and point, with the PIVOT mu_0 = the mean of sample 0 -- whatever its weight -- or, where sample 0 failed to factorise,
-  // of the first sample that did, d_s = mu_s - mu_0 and v_s = max(variance + (include_nugget ? sample s's own nugget : 0), 0) as predict()
-  // reports it:   mean = mu_0 + sum w_s d_s,  within = sum w_s v_s,  between = max(sum w_s d_s^2 - (sum w_s d_s)^2, 0)     -- (E, m) each.
-  // Per sample (E, S): the normalised weights, F (the value eval returns, NaN where it failed) and ok.  A sample that fails gets weight 0;
-  // an emulator whose samples all fail or whose weights sum to 0 gets NaN rows and ok_all[e] = 0 (ok_all may be null) -- not an error.
-  // The sums are updated in sample order with one add per sample and no atomics: the same bits for every max_slots >= 1 (slots per pass)
-  // and max_points >= 1 (query points per chunk); 0 = the library's choice.  Throws for nugget="pivot" and the analytic mean.
-  void predict_mixture(const std::vector<int>& ids, const double* thetas, int S, int ld, const double* weights, const double* log_q,
-                       const double* Xs, int m, bool include_nugget, int max_slots, int max_points, double* mean_out, double* within_out,
-                       double* between_out, double* weights_out, double* logpost_out, int* ok_out, int* ok_all);
-  // Leave-one-out / k-fold predictive errors of emulators `ids` at their fitted hyperparameters, without refitting (kernels_cv.hip).
-  // labels (n): the fold of every training point, values 0 .. k-1, every fold non-empty, 2 <= k <= n.  With Q the factored matrix,
-  // alpha = Q^-1 r and S = (Q^-1)_FF of a fold F: the held-out error is e_F = S^-1 alpha_F and the held-out covariance of the
-  // observations S^-1.  mean / var (ids, n): mean_i = t_i - e_i and var_i = (S^-1)_ii -- with include_nugget false max(var_i - nugget
-  // used, 0) --, in training order.  maha / log_score / ok (ids, k): e_F^T S e_F, the log predictive density of the fold given the
-  // rest, and whether S factorised (0: NaN for the fold's points and scalars; no jitter, no exception).  Every fold a single point:
-  // one pass over L^-1.  Otherwise K^-1 is formed and the (emulator, fold) pairs go, emulator-major and fold-ascending, `slots` per
-  // pass (cv_plan of predict_plan.h; max_slots = 0: the library's choice) through a ScratchFactor of the call.  THIS engine is only
-  // read, apart from gaining alpha / L^-1 / K^-1: theta, factor and logpost stay.  No atomics: the same call returns the same bits.
-  // Throws for nugget="pivot", the analytic mean, an emulator that is not fit, bad k, a label outside [0, k) and an empty fold.
-  void cross_validate(const std::vector<int>& ids, const int* labels, int k, bool include_nugget, int max_slots, double* mean, double* var,
-                      double* maha, double* log_score, int* ok);
   // leave-one-out predictive variance of emulator i at its own training inputs (MICEFastGP.fast_predict for every index)
   void loo_variance(int i, double* out);
   // predict(full_cov=True), GaussianProcess.py:899-911: means (nb, m), covs (nb, m, m) host buffers, nugget NOT included
   void predict_full_cov(const std::vector<int>& ids, const double* Xs, int m, double* means, double* covs);
-  // Joint posterior draws of emulators `ids` at the m query points Xs (host, (m, D)) -- kernels_sample.hip, DESIGN.md section 3 "Sampling".
-  // With Sigma*_e, mu*_e what predict_full_cov returns (the same launches, the same bits; nugget not included):
-  //   Sigma~_e = Sigma*_e + ((include_nugget ? nugget used by the fit : 0) + jitter + delta_e) I = L_e L_e^T,
-  //   samples[e][s][:] = mu*_e + L_e z[e][s][:]                                              samples (ids, S, m), mean (ids, m).
-  // delta_e = 0 on the first try; an emulator whose Sigma~ does not factorise is tried again -- it alone -- with delta_e =
-  // sample_ladder_delta(t, mean diag Sigma*_e), t = 0 .. 4 (predict_plan.h); jitter_used[e] = jitter + delta_e; after the fifth failure
-  // ok[e] = 0 and its samples are NaN (no exception).  The factor's diagonal is finished from its rows with the correctly rounded square root.  z: z_in (S, m) shared by all emulators or, with z_per_emulator, (ids, S, m); null:
-  // generated on the device, value (e, s, j) from (seed, streams[e], s, j) alone (philox_dev.h).  z_out (ids, S, m) or null: the normals used.
-  // The emulators go `slots` per pass and the draws `draws` per chunk (sample_plan; max_slots / max_draws = 0: the library's choice)
-  // through a ScratchFactor of m rows; every buffer is scratch of the call.  THIS engine is only read, apart from gaining alpha / L^-1.  One writer
-  // per output, no atomics: the same call returns the same bits, and max_draws changes none.  Throws for nugget="pivot", the analytic mean,
-  // an emulator that is not fit, S < 1, jitter < 0, negative max_*, non-finite Xs / z_in and scratch beyond sample_plan's limits.
-  void sample_posterior(const std::vector<int>& ids, const unsigned* streams, const double* Xs, int m, int S, unsigned long long seed,
-                        const double* z_in, bool z_per_emulator, bool include_nugget, double jitter, int max_slots, int max_draws,
-                        double* samples, double* mean, double* z_out, double* jitter_used, int* ok);
-  // Posterior covariance of the latent function between two point sets, per emulator of `ids` (kernels_alc.hip, DESIGN.md section 3 "Active
-  // learning"): out (ids, m1, m2) = sigma^2 k(X1, X2) - V_1^T V_2 with V = L^-1 K*^T as predict_full_cov stores it; nugget not included.
-  // X2 == null: X2 = X1.  The emulators go in groups sized by the 64 GB rule of predict_full_cov (V_1, V_2, the output and the K* scratch
-  // counted) and half of the free device memory; every buffer is scratch of the call.  THIS engine is only read, apart from gaining L^-1.
-  // Throws for nugget="pivot", the analytic mean, an emulator that is not fit, m < 1, non-finite points, negative max_slots and one emulator
-  // beyond either memory rule.
-  void predict_cov(const std::vector<int>& ids, const double* X1, int m1, const double* X2, int m2, int max_slots, double* out);
-  // The ALC design criterion of emulators `ids` at fixed hyperparameters: with c the covariance above, s^2(x) = max(c(x, x), 0) as predict()
-  // reports it (the engine's own predictive-variance launches: the same bits) and tau[e] >= 0 the noise variance of one more run,
-  //   reduction[e][i] = sum_j w_j c_e(r_j, c_i)^2 / (s_e^2(c_i) + tau[e])           candidates Xc (mc, D), reference Xr (mr, D), weights w (mr) >= 0
-  // reduction / cand_var / degenerate (ids, mc), ref_var (ids, mr).  noise == null: tau[e] = nugget_size(ids[e]).  A candidate with
-  // s^2 + tau <= (n + 2) 2^-52 sigma^2 -- the rounding of sigma^2 minus a sum of n squares -- gets reduction 0 and degenerate 1; no NaN.
-  // The emulators go `slots` per group and the reference points `points` per chunk (alc_plan; max_slots / max_points = 0: the library's
-  // choice); the partial sums are kept per 128-point tile of the WHOLE reference set and added in ascending tile order, so the same call
-  // returns the same bits and neither number changes any.  Throws as predict_cov does, and for negative or non-finite weights or noise and
-  // weights that sum to 0.
-  void alc(const std::vector<int>& ids, const double* Xc, int mc, const double* Xr, int mr, const double* w, const double* noise, int max_slots,
-           int max_points, double* reduction, double* cand_var, double* ref_var, int* degenerate);
-  // Greedy ALC batches at fixed hyperparameters (kernels_alc.hip, DESIGN.md section 3 "Active learning: batches").  The predictive variance
-  // does not depend on the targets, so conditioning on a run at p with noise tau appends one row to the Cholesky factor and one entry
-  // u(x) = c(x, p) / sqrt(s^2(p) + tau) to every stored v(x): c_new(x, x') = c(x, x') - u(x) u(x'), s^2_new(x) = s^2(x) - u(x)^2.  V_c and V_r
-  // are built once, with room for the rows of all T = forced + q steps behind their roundup(n, 16) base rows, and step t is alc's product
-  // over n16 + t rows, alc_finish with the floor of n + t, the pick, and two rank-one updates: no n^3 and no (m_c + m_r) n^2 work per pick.
-  // X (M, D): the candidates; the first `forced` of them are taken in order in steps 0 .. forced - 1 (points already submitted), the other
-  // steps take the unmasked candidate with the largest score, ties to the lowest index.  A step whose best score is not above 0 or whose
-  // denominator is at or below (n + t + 2) 2^-52 sigma^2 picks -1 and conditions on nothing; a picked candidate is masked.
-  // AlcBatch is one group of emulators resident on the device for the whole batch; alc_batch runs the groups of alc_batch_plan one after
-  // another, every step enqueued without a host synchronisation (select = "each").  select = "total" drives one AlcBatch per part from the
-  // C ABI layer: scores() -> the host's sum and arg-max -> apply(pick).  THIS engine is only read, apart from gaining L^-1.
-  struct AlcBatchOut {       // host arrays, rows of the group's emulators; T = forced + q.  red / deg may be null (scores not kept)
-    int* picks;              // (E, T)   -1: nothing picked in that step
-    double* pick_red;        // (E, T)   the score of the pick, 0 where there is none
-    double* red;             // (E, T, M)
-    int* deg;                // (E, T, M)
-    double* cand_var;        // (E, M)   before any step: predict()'s own bits
-    double* ref_var;         // (E, mr)  likewise
-    double* ref_var_after;   // (E, mr)  after the last step, clipped at 0
-    double* iv;              // (E, T + 1)  iv[0] = sum_j w_j ref_var[j] in ascending j, iv[t + 1] = iv[t] - pick_red[t]
-    AlcBatchOut rows_from(size_t e0, int T, int M, int mr) const {
-      return {picks + e0 * T, pick_red + e0 * T, red ? red + e0 * T * M : nullptr, deg ? deg + e0 * T * M : nullptr, cand_var + e0 * M,
-              ref_var + e0 * mr, ref_var_after + e0 * mr, iv + e0 * (T + 1)};
-    }
-  };
-  class AlcBatch {
-   public:
-    // builds V_c, V_r and both variances of emulators grp (tau: their noise variances) and starts the downloads of out.cand_var / ref_var;
-    // out must outlive the object.  The caller has checked the arguments (alc_batch_check) and the memory (alc_batch_plan).
-    AlcBatch(Engine& eng, const std::vector<int>& grp, const double* tau, const double* X, int M, int forced, const double* Xr, int mr,
-             const double* w, int q, const AlcBatchOut& out);
-    int steps() const { return T; }
-    // the scores of step t on the device (product, finish); with out.red they are also on their way to the host
-    void scores(int t);
-    // the same, then waits: row_red / row_deg (E, M) of this step on the host
-    void scores_to_host(int t, double* row_red, int* row_deg);
-    // the pick of step t (forced >= 0: that candidate; -1: the arg-max on the device) and the conditioning on it
-    void apply(int t, int forced);
-    // waits for everything, fills the rest of out
-    void finish();
-
-   private:
-    Engine& e;
-    std::vector<int> ids;
-    AlcBatchOut o;
-    int cnt, M, mr, T, MPc, MPr, tiles_r, rows, n16;
-    std::vector<double> hw;
-    DevBuf<double> dXc, dXr, dW, dTau, dVc, dVr, dPart, dVarC, dVarR, dRed, dPickRed, dPickD;
-    DevBuf<int> dDeg, dMask, dPicks;
-  };
-  // the refusals of a batch, as `alc_batch`; tau (ids) receives the noise variances
-  void alc_batch_check(const std::vector<int>& ids, const double* X, int M, int forced, const double* Xr, int mr, const double* w,
-                       const double* noise, int q, int max_slots, std::vector<double>& tau) const;
-  long alc_batch_slots(long E, int M, int mr, int T, int max_slots, bool total) const;
-  // select = "each": out holds the rows of ids
-  void alc_batch(const std::vector<int>& ids, const double* X, int M, int forced, const double* Xr, int mr, const double* w, const double* noise,
-                 int q, int max_slots, const AlcBatchOut& out);
   void get_invQ(int i, double* out);
   void get_invQt(int i, double* out);
   void get_chol(int i, double* out);
@@ -260,6 +141,29 @@ class Engine {
   // matrix and every slot's pivot-ordered copy of the inputs
   void reset_inputs(const std::vector<double>& X);
 
+  // For the analyses (analysis.h): bring cached state into being, select a group, launch on it.
+  // what cross_validate, sample_posterior, predict_cov and alc refuse alike, as `who`: an emulator without a factor, the analytic mean
+  // (`analytic_reason`: why the caller cannot cover it) and nugget="pivot"
+  void require_plain_fit(const char* who, const std::vector<int>& ids, const char* analytic_reason) const;
+  // alpha of the emulators of ids that hold a factor but not yet alpha: the one-launch chain on `stream`, its time-out words read back
+  // (one small copy and synchronisation of its own), the repeat with the multi-launch path where a wait gave up
+  void ensure_alpha(const std::vector<int>& ids);
+  void ensure_linv(const std::vector<int>& ids);
+  void ensure_kinv(const std::vector<int>& ids, bool for_gradient = false);
+  void upload_idx(const std::vector<int>& ids);
+  BatchView view(int nb) const;
+  // free device memory in bytes; false: the runtime could not tell (the callers then keep their own fallback)
+  bool free_device_bytes(double& free_bytes) const;
+  // the same with the fallback of sample_posterior, predict_cov and alc: twice the prediction budget when the runtime cannot tell
+  double free_bytes_or_twice_budget() const;
+  // the two halves of predict_full_cov (engine_predict.hip), shared with sample_posterior.  fullcov_launches: the device part on `stream`
+  // for the emulators in dIdx -- dC (nb, m, m) = Sigma*, dDots (nb, R, m) the dot products; dKf (nb, MP, LD) and dV (nb, NP, MP) are scratch.
+  // fullcov_host_means: the means (nb, m) from the downloaded dot products, mean-function terms added; with the analytic mean its
+  // covariance term goes into covs (host, may be null without it).
+  void fullcov_launches(int nb, const double* dXf, int m, int MP, double* dKf, double* dV, double* dC, double* dDots);
+  void fullcov_host_means(const std::vector<int>& ids, const double* Xs, int m, const double* dots, double* means, double* covs);
+  int compute_units() const { return n_cu; }
+
   // (streams and events are declared in front of every buffer: members go in reverse order, so the streams are destroyed last)
   Stream stream;                     // main stream: covariance build, trailing updates, everything else
   Stream pstream;                    // look-ahead stream: panel factorisations
@@ -271,7 +175,6 @@ class Engine {
  private:
   friend class ScratchFactor;      // factors matrices of its caller's with an engine of its own (engine_internal.h)
   void upload_params(const std::vector<int>& ids);
-  void upload_idx(const std::vector<int>& ids);
   // defer_info: leave the status words on the device (the caller reads them together with its own results: one
   // synchronisation per evaluation instead of two)
   void factorize(const std::vector<int>& ids, std::vector<int>& info, bool defer_info = false);
@@ -311,19 +214,10 @@ class Engine {
   void unpermute(int i, double* vec) const;          // vec (n) from pivoted to training order, in place
   void restore_order(int i);                         // emulator i's inputs back to training order (after a pivoted fit)
   void panel(const BatchView& v, int o, int w, hipStream_t st);
-  // alpha of the emulators of ids that hold a factor but not yet alpha: the one-launch chain on `stream`, its time-out words read back
-  // (one small copy and synchronisation of its own), the repeat with the multi-launch path where a wait gave up
-  void ensure_alpha(const std::vector<int>& ids);
-  void ensure_linv(const std::vector<int>& ids);
-  void ensure_kinv(const std::vector<int>& ids, bool for_gradient = false);
-  BatchView view(int nb) const;
   void build_cov(const BatchView& v, const ZeroRanges& zero = ZeroRanges(), const CovFill* fill = nullptr);
   std::vector<char> z_armed;     // per emulator: its solution row holds the sentinel pattern of the one-launch back substitution
   void set_theta(int i, const double* theta);
   void require_factored(const std::vector<int>& ids) const;      // throws unless every emulator of ids holds a factor
-  // what cross_validate, sample_posterior, predict_cov and alc refuse alike, as `who`: an emulator without a factor, the analytic mean
-  // (`analytic_reason`: why the caller cannot cover it) and nugget="pivot"
-  void require_plain_fit(const char* who, const std::vector<int>& ids, const char* analytic_reason) const;
   // the steps of predict (engine_predict.hip).  PredictPlace: where means / variances / derivatives / dot products live on the device
   struct PredictPlace {
     double *fm, *fv, *fd, *dots;
@@ -340,11 +234,7 @@ class Engine {
   void implausibility_chunks(const std::vector<int>& ids, const double* Xs, int m, int MC, const double* obs, const double* obs_var,
                              const double* discrepancy, bool include_nugget, const std::function<void(const double*, int, int)>& tail);
   void ensure_predict_scratch(int nb, int MC);
-  // free device memory in bytes; false: the runtime could not tell (the callers then keep their own fallback)
-  bool free_device_bytes(double& free_bytes) const;
-  // the same with the fallback of sample_posterior, predict_cov and alc: twice the prediction budget when the runtime cannot tell
-  double free_bytes_or_twice_budget() const;
-  // the steps of hessian (engine_analysis.hip).  hessian_move_to: the emulators to their thetas -- fine[k] = 1 where ids[k] holds a factor
+  // the steps of hessian (engine_hessian.hip).  hessian_move_to: the emulators to their thetas -- fine[k] = 1 where ids[k] holds a factor
   // there, before[k] = the theta it has to be put back at (hessian_put_back).  hessian_group_sums: the device sums of one group of emulators
   // into their host copies (six launches behind the gradient's, six downloads, one synchronisation)
   struct HessianScratch;
@@ -353,29 +243,6 @@ class Engine {
                        std::vector<std::vector<double>>& before);
   void hessian_group_sums(const std::vector<int>& grp, HessianScratch& d, HessianSums& h);
   void hessian_put_back(const std::vector<int>& ids, const std::vector<std::vector<double>>& before);
-  // the two paths of cross_validate (engine_analysis.hip): every fold a single point / the folds of cf through a ScratchFactor
-  void cv_leave_one_out(const std::vector<int>& ids, const int* labels, bool include_nugget, CvBuffers& b, double* mean_out, double* var_out,
-                        double* maha_out, double* log_score_out, int* ok_out);
-  void cv_kfold(const std::vector<int>& ids, const CvFolds& cf, int k, bool include_nugget, int max_slots, CvBuffers& b, double* mean_out,
-                double* var_out, double* maha_out, double* log_score_out, int* ok_out);
-  // the two halves of predict_full_cov (engine_predict.hip), shared with sample_posterior.  fullcov_launches: the device part on `stream`
-  // for the emulators in dIdx -- dC (nb, m, m) = Sigma*, dDots (nb, R, m) the dot products; dKf (nb, MP, LD) and dV (nb, NP, MP) are scratch.
-  // fullcov_host_means: the means (nb, m) from the downloaded dot products, mean-function terms added; with the analytic mean its
-  // covariance term goes into covs (host, may be null without it).
-  void fullcov_launches(int nb, const double* dXf, int m, int MP, double* dKf, double* dV, double* dC, double* dDots);
-  void fullcov_host_means(const std::vector<int>& ids, const double* Xs, int m, const double* dots, double* means, double* covs);
-  // the steps of sample_posterior (engine_analysis.hip)
-  struct SamplePass;
-  void sample_build(const std::vector<int>& grp, const double* Xs, const double* dXq, int m, SamplePass& p, double* mean_out);
-  void sample_factor(ScratchFactor& sub, const std::vector<int>& grp, bool include_nugget, double jitter, SamplePass& p, double* jitter_used, int* ok);
-  void sample_draws(ScratchFactor& sub, long e0, long cnt, int m, int S, int Sc, unsigned long long seed, const double* z_in, bool z_per_emulator,
-                    SamplePass& p, double* samples, double* z_out);
-
-  // what alc and predict_cov share (engine_analysis.hip): the refusals; and, for the nb emulators in dIdx and the m points at dXq, K*
-  // (scratch), the predictive variance (dVar, rows var_ld apart; null: not wanted) and V = L^-1 K*^T, with predict()'s own launches
-  void check_cov_args(const char* who, const std::vector<int>& ids, const double* X1, int m1, const double* X2, int m2, int max_a, int max_b) const;
-  void points_v(int nb, const double* dXq, int m, int MP, double* dK, double* dDots, double* dPartial, double* dVar, int var_ld, double* dV);
-
   DevBuf<double> dX, dP, dT, dA, dLinv, dKinv, dAlpha;
   // signal word of the stream memory operations of the look-ahead schedule.  The one raw pointer of the engine: signal memory comes from
   // hipExtMallocWithFlags(hipMallocSignalMemory), not from the allocator behind DevBuf, and is freed in ~Engine.

@@ -1,9 +1,11 @@
-// What engine.hip, engine_chol.hip, engine_fit.hip, engine_predict.hip, engine_analysis.hip and engine_local.hip share and nobody else sees: the error-check
-// macro, small helpers and the process-wide diagnostic counters behind prof_counter (engine.hip).  What lives where: engine.hip the
+// What engine.hip, engine_chol.hip, engine_fit.hip, engine_predict.hip, engine_hessian.hip, engine_local.hip and the analysis_*.hip units share and
+// nobody else sees: small helpers and the process-wide diagnostic counters behind prof_counter (engine.hip).  What lives where: engine.hip the
 // construction, the cached state, eval's steps, L^-1 / K^-1 and the gradient; engine_chol.hip the factorisation schedules; engine_fit.hip
 // the optimiser, the slot pool, the replica engines and ScratchFactor; engine_predict.hip predict, full covariance, implausibility, Sobol and loo_variance;
-// engine_analysis.hip the Hessian, the mixture over hyperparameter samples, cross-validation, joint posterior draws and
-// active learning (alc, predict_cov); engine_local.hip the LocalGP handle, which is no Engine.  Whoever needs "factor a batch of matrices I wrote myself" and nothing else of an engine (gkdr_R,
+// engine_hessian.hip the Hessian; engine_local.hip the LocalGP handle, which is no Engine.  The analyses that only read a fitted engine are
+// free functions (analysis.h), one unit per subject: analysis_mixture.hip the mixture over hyperparameter samples, analysis_cv.hip
+// cross-validation, analysis_sample.hip joint posterior draws, analysis_active.hip active learning (predict_cov, alc, alc_batch).
+// Whoever needs "factor a batch of matrices I wrote myself" and nothing else of an engine (gkdr_R,
 // cross_validate's k-fold path, sample_posterior) takes a ScratchFactor, below.
 #pragma once
 #include "engine.h"
@@ -15,8 +17,6 @@
 #include <memory>
 
 namespace mogp {
-
-#define HIPCK(x) hip_check((x), #x)
 
 inline int roundup(int x, int m) { return (x + m - 1) / m * m; }
 
@@ -37,7 +37,7 @@ inline double ks_budget_bytes() {
 // cached one of the device when its shape matches (taken out of the cache, its inputs reset), else a new one -- whatever the cache held
 // is freed first.  When the scope is left normally the engine goes back into the cache (MOGP_REPLICA_CACHE=0: never); an exception
 // destroys it.  `targets` (slots, n), nug_type and nug_size only initialise a NEW engine: every slot is given its emulator by
-// Engine::retarget before it is used.  Shared by fit_map_from and predict_mixture (engine_analysis.hip).
+// Engine::retarget before it is used.  Shared by fit_map_from and predict_mixture (analysis_mixture.hip).
 class ReplicaLease {
  public:
   ReplicaLease(const Engine& src, long slots, const std::vector<double>& targets, int nug_type, double nug_size);

@@ -13,6 +13,14 @@ void Engine::require_factored(const std::vector<int>& ids) const {
     if (!gp[i].factored) throw std::runtime_error("emulator has not been fit");
 }
 
+void Engine::require_plain_fit(const char* who, const std::vector<int>& ids, const char* analytic_reason) const {
+  const std::string p = std::string(who) + ": not available with ";
+  require_factored(ids);
+  if (analytic) throw std::runtime_error(p + "analytic_mean=True (" + analytic_reason + ")");
+  for (int i : ids)
+    if (gp[i].nug_type == NUG_PIVOT || gp[i].permuted) throw std::runtime_error(p + "nugget=\"pivot\" (a pivoted, possibly rank-deficient factor)");
+}
+
 void Engine::ensure_predict_scratch(int nb, int MC) {
   dKs.reserve((size_t)nb * MC * LD);
   // partial sums per row tile

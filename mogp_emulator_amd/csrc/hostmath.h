@@ -287,7 +287,7 @@ inline void fullcov_mean_terms(int q, int m, const double* beta, const double* L
     }
 }
 
-// The host algebra of Engine::hessian (engine_analysis.hip) for one emulator: the P x P block of the Hessian of the negative log-posterior,
+// The host algebra of Engine::hessian (engine_hessian.hip) for one emulator: the P x P block of the Hessian of the negative log-posterior,
 // P = NC + 1 (+ 1 with a fitted nugget), theta order [corr (NC) | cov | nugget], from the device sums of kernels_hess.hip:
 //   o (D + 3)              the gradient's sums as launch_grad leaves them: 0.5 sum W o Q_p (p < D), 0.5 sum W o sigma^2 C, tr Q^-1, ., alpha^T alpha
 //   T ((D + 1) x (D + 2))  T[p][q] = sum_ab P_p[a,b] P_q[b,a] over the planes M_0 .. M_{D-1}, Q^-1, I (upper entries; T[D][D] = tr Q^-2)

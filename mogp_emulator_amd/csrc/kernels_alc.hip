@@ -1,24 +1,23 @@
-// Active learning (Engine::alc, Engine::predict_cov; DESIGN.md section 3 "Active learning"): the posterior covariance between two point sets,
+// Active learning (alc, predict_cov; DESIGN.md section 3 "Active learning"): the posterior covariance between two point sets,
 //     c(x, x') = sigma^2 k(x, x') - v(x)^T v(x'),   v(x) = L^-1 k(x),
 // and the ALC criterion built on it, ALC(c) = sum_j w_j c(r_j, c)^2 / (s^2(c) + tau).
 //   alc_cross_kernel<KT, STORE>  one 128 x 128 tile of V_1^T V_2 on fp64 MFMA (fullcov_kernel's loop on two different operands), then
 //                                sigma^2 k of the tile in the accumulator's own layout and x = sigma^2 k - acc;
 //                                STORE: x written out; otherwise w_j x^2 summed along the tile's columns into ONE partial per row
 //   alc_finish_kernel            the partials of a candidate in ascending reference-tile order, the division, the floor rule
-// and, for greedy batches (Engine::AlcBatch; DESIGN.md section 3 "Active learning: batches"), the conditioning on a pick: a run at p with noise
+// and, for greedy batches (AlcBatch; DESIGN.md section 3 "Active learning: batches"), the conditioning on a pick: a run at p with noise
 // tau gives every stored v(x) one more entry u(x) = c(x, p) / sqrt(s^2(p) + tau), so V carries room for those rows behind its base rows and
 // alc_cross_kernel takes the rows per slot and the end of its K range from its caller:
 //   alc_argmax_kernel            per slot the unmasked candidate with the largest score (ties: the lowest index), the stopping rule, the mask
 //   alc_condition_kernel<KT>     row n16 + t of V of one point set and its tracked variances; bandwidth bound, one owner per output
 // The m_1 x m_2 matrix of the criterion never exists.  One writer per output, fixed orders, no atomics: the same call returns the same bits,
 // and neither the chunk of reference points nor the group of emulators a tile is computed in changes any.
-#include "engine.h"
+#include "launch.h"
+#include "devmem.h"
 #include "cov_dev.h"
 #include "gemm_loop_dev.h"
 
 namespace mogp {
-
-#define HIPCK(x) hip_check((x), #x)
 
 namespace {
 

@@ -1,4 +1,4 @@
-// Cross-validation of a fitted emulator at its fitted hyperparameters (Engine::cross_validate): leave-one-out and k-fold predictive
+// Cross-validation of a fitted emulator at its fitted hyperparameters (cross_validate): leave-one-out and k-fold predictive
 // errors from what a fit leaves on the device, without refitting.  Q = sigma^2 C + eta I is the factored matrix, alpha = Q^-1 r.  For a
 // fold F (an index set) with S = (Q^-1)_FF = L_S L_S^T and y = L_S^-1 alpha_F:
 //   e_F = S^-1 alpha_F  (held-out error t_F - mu_-F(X_F)),   Sigma_F = S^-1  (held-out covariance of the observations, nugget included),
@@ -8,11 +8,10 @@
 // layout), the engine's batched Cholesky, trtri, log-determinant and L^-T y launchers run on it, and cv_finish_kernel scatters the results
 // to the caller-order rows.  Plain vector code: every output has one writer, the column sums are split over the four waves as in
 // loo_variance_kernel and added in a fixed order, nothing is atomic -- the same call returns the same bits.
-#include "engine.h"
+#include "launch.h"
+#include "devmem.h"
 
 namespace mogp {
-
-#define HIPCK(x) hip_check((x), #x)
 
 namespace {
 

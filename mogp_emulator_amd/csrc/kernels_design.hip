@@ -18,8 +18,6 @@
 
 namespace mogp {
 
-#define HIPCK(x) hip_check((x), #x)
-
 namespace {
 
 constexpr unsigned long long INF_BITS = 0x7FF0000000000000ull;      // +infinity: above every finite squared distance

@@ -1,4 +1,4 @@
-// Mixture prediction over hyperparameter samples (Engine::predict_mixture): the reduction over samples behind the batched prediction.
+// Mixture prediction over hyperparameter samples (predict_mixture): the reduction over samples behind the batched prediction.
 // With normalised weights w_s, predictive means mu_s and variances v_s of the S samples of one emulator at one query point, and the
 // pivot mu_0 (the mean of the first sample that factorised), d_s = mu_s - mu_0:
 //   mean = mu_0 + sum w_s d_s,   within = sum w_s v_s,   between = max(sum w_s d_s^2 - (sum w_s d_s)^2, 0)      (law of total variance)
@@ -7,11 +7,10 @@
 // threads on consecutive points, so every load and store of a wave is one contiguous 512-byte run; no LDS, no waits, no atomics.
 // A point's sums are updated in slot (= sample) order with one rounded multiply and one rounded add per sample: contraction to FMA is
 // off in this file, so the bits do not depend on what the compiler prefers, nor on the pass or chunk a sample or a point falls into.
-#include "engine.h"
+#include "launch.h"
+#include "devmem.h"
 
 namespace mogp {
-
-#define HIPCK(x) hip_check((x), #x)
 
 namespace {
 

@@ -1,4 +1,4 @@
-// Joint posterior draws f(X*) ~ N(mu*, Sigma~) of a fitted emulator (Engine::sample_posterior, DESIGN.md section 3 "Sampling"):
+// Joint posterior draws f(X*) ~ N(mu*, Sigma~) of a fitted emulator (sample_posterior, DESIGN.md section 3 "Sampling"):
 // Sigma~ = Sigma* + shift I = L L^T is factored by the engine's batched Cholesky in a scratch engine of m rows, and a draw is mu* + L z.
 //   sample_gather_kernel   Sigma* (m x m dense) -> the factor-matrix layout of a scratch-engine slot (launch.h), the shift on the diagonal
 //   sample_polish_kernel   the factor's diagonal recomputed from its finished rows with the correctly rounded square root
@@ -6,13 +6,12 @@
 //   sample_apply_kernel    Y^T tile (128 points x 64 draws) = L[tile rows, 0 .. end of the diagonal block] Z^T + mu on fp64 MFMA
 // Every output has one writer, the k sum of an output runs in a fixed order that depends on its row tile alone, nothing is atomic: the
 // same call returns the same bits, and cutting the draws into other chunks changes none.
-#include "engine.h"
+#include "launch.h"
+#include "devmem.h"
 #include "gemm_dev.h"
 #include "philox_dev.h"
 
 namespace mogp {
-
-#define HIPCK(x) hip_check((x), #x)
 
 namespace {
 

@@ -224,7 +224,7 @@ void launch_hess_pair(const BatchView& v, const double* Xs, double* partial, dou
 void launch_hess_vectors(const BatchView& v, const double* M, double* V, double* U, double* Zv, hipStream_t s);
 
 // --- mixture prediction over hyperparameter samples (kernels_mixture.hip) -------------------------
-// One pass of Engine::predict_mixture: mu / var (rows, ld) are the means and raw variances of the pass's slots that factorised, at the mc
+// One pass of predict_mixture: mu / var (rows, ld) are the means and raw variances of the pass's slots that factorised, at the mc
 // query points [c0, c0 + mc) of m.  The pass's slots are emulator-major, sample-ascending; emulator entry b < nemu of the pass is
 //   etab[4 b ..] = { emulator e, its first slot, its number of slots, the row of its pivot sample or -1 (the pivot is of an earlier pass) }
 // and slot k has rows[k] (its row of mu / var, -1: the sample failed and is skipped) and prm[2 k ..] = { weight, nugget to add }.
@@ -254,7 +254,7 @@ void launch_cv_finish(const int* folds, const int* tab, int nslots, const double
                       double* var, double* maha, double* log_score, int* ok, hipStream_t s);
 
 // --- joint posterior draws (kernels_sample.hip) -----------------------------------------------------
-// The scratch engine of Engine::sample_posterior has n' = m rows (NPs = roundup(m + 1, 128)); `sv` is ITS view, batch entry z of the launch
+// The scratch engine of sample_posterior has n' = m rows (NPs = roundup(m + 1, 128)); `sv` is ITS view, batch entry z of the launch
 // = its slot sv.idx[z].  gather: A[slot] <- the factor-matrix layout above with Sigma* = cov[src[slot]] (m x m dense, row stride m) plus
 // shift[slot] on its diagonal; the target row m is neutral (zeros, PAD_BIG on the diagonal), rows > m identity, src[slot] < 0 an identity
 // matrix.  Only the 64 x 64 tiles on and below the diagonal carry the matrix: the tiles above it are written as exact zeros (the
@@ -294,7 +294,7 @@ void launch_alc_cross(const BatchView& v, const double* V1, int MP1, int m1, con
 // red = (sum of the tiles_r partials, ascending) / d, deg = 0
 void launch_alc_finish(const BatchView& v, int nrows, int m1, int MP1, int tiles_r, const double* part, double* var, int var_ld, const double* tau,
                        double* red, int* deg, hipStream_t s);
-// Greedy ALC batches (Engine::AlcBatch; DESIGN.md section 3 "Active learning: batches").  Per slot, step t of T:
+// Greedy ALC batches (AlcBatch; DESIGN.md section 3 "Active learning: batches").  Per slot, step t of T:
 //   argmax   the pick of step t: forced >= 0 that candidate, else the candidate with mask == 0 and the largest red (ties: the lowest index;
 //            NaN never wins).  With d = max(var[pick], 0) + tau and the floor (n + t + 2) 2^-52 sigma^2: no candidate left, a best score
 //            that is not above 0 or d at or below the floor give picks[slot * T + t] = -1, pick_red = 0 (nothing is conditioned on);

@@ -1,4 +1,4 @@
-// The normal generator of Engine::sample_posterior, for the device (sample_normals_kernel, kernels_sample.hip) and for a host compiler
+// The normal generator of sample_posterior, for the device (sample_normals_kernel, kernels_sample.hip) and for a host compiler
 // (tests/c/philox_check.cpp), as exp_dev.h is.  Counter-based: value j of draw s of stream e under a 64-bit seed is a function of
 // (seed, e, s, j) alone, so how the work is cut into passes, chunks and workgroups changes no bit.
 //   block function   Philox4x32-10 (Salmon et al., SC'11; Random123): multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85

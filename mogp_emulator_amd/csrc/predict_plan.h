@@ -1,5 +1,5 @@
-// How the prediction family of Engine (engine_predict.hip) and the analysis family (engine_analysis.hip: hessian, predict_mixture,
-// cross_validate, sample_posterior, alc, alc_batch, predict_cov) cut their work to a byte budget, the index tables of their passes, and where the mean-function terms of a prediction are
+// How the prediction family of Engine (engine_predict.hip), its Hessian (engine_hessian.hip) and the analyses of analysis.h (analysis_*.hip:
+// predict_mixture, cross_validate, sample_posterior, alc, alc_batch, predict_cov) cut their work to a byte budget, the index tables of their passes, and where the mean-function terms of a prediction are
 // staged.  Plain host arithmetic with no HIP in it, so that a host compiler takes it and tests/c/predict_plan_check.cpp, mixture_plan_check.cpp,
 // cv_plan_check.cpp, sample_plan_check.cpp, alc_plan_check.cpp, alc_batch_plan_check.cpp, local_plan_check.cpp, vecchia_plan_check.cpp and local_args_check.cpp (the refusals
 // and the LDS layout of the LocalGP handle, engine_local.hip) can check it without a device.  The caps that need the device (MOGP_KS_BUDGET_GB, free memory) are passed in.
@@ -53,7 +53,7 @@ inline double replica_slot_bytes(std::size_t MS, int LD) { return 3.0 * (double)
 // replicas beyond what fills the device buy nothing: the batched kernels of a factorisation stay below 4096 tile rows per launch
 inline long replica_slot_bound(int NP, int TILE) { return 4095 / std::max(1, NP / TILE) + 1; }
 
-// Engine::predict_mixture: how many replica slots one pass takes and how many query points one chunk.  The E * S (emulator, sample) pairs
+// predict_mixture: how many replica slots one pass takes and how many query points one chunk.  The E * S (emulator, sample) pairs
 // are laid out emulator-major, sample-ascending, and pass g takes the pairs [g * slots, (g + 1) * slots): a slot always holds one whole
 // sample, and a contiguous cut of that order never puts a later sample of an emulator in front of an earlier one.  slots: at least one,
 // never more than the E * S pairs, the `device_slots` the device holds beside the source engine, or max_slots (0: the library's choice);
@@ -75,7 +75,7 @@ inline MixturePlan mixture_plan(long E, long S, int LD, long device_slots, int m
   return {slots, points};
 }
 
-// Engine::cross_validate: how many (emulator, fold) pairs one pass of the ScratchFactor takes.  The E * k pairs are laid out emulator-major,
+// cross_validate: how many (emulator, fold) pairs one pass of the ScratchFactor takes.  The E * k pairs are laid out emulator-major,
 // fold-ascending, and pass g takes the pairs [g * slots, (g + 1) * slots).  slots: at least one, never more than the E * k pairs, the
 // `device_slots` that half of the free memory holds at 3 NPsub^2 doubles per slot, NPsub = scratch_np(largest fold) (factor, L^-1 and its scratch; cv_slot_bytes), the batch
 // bound predict_mixture's replica engine observes (cv_slot_bound: the batched kernels of a factorisation stay in the range of tiles per
@@ -92,7 +92,7 @@ inline long cv_plan(long E, long k, int NPsub, long device_slots, int max_slots)
   return std::max<long>(1, slots);
 }
 
-// The folds of Engine::cross_validate from the labels (n) of the training points: size (k) = points per fold, nsub = the largest fold,
+// The folds of cross_validate from the labels (n) of the training points: size (k) = points per fold, nsub = the largest fold,
 // folds (k, nsub) = the points of every fold in ascending order, -1 behind the end of a short one.  Throws for a label outside [0, k)
 // and for an empty fold.
 struct CvFolds {
@@ -116,7 +116,7 @@ inline CvFolds cv_folds(const int* labels, int n, int k) {
   return c;
 }
 
-// The slot table (slots, 4) of the pass of Engine::cross_validate that starts at pair p0 and holds cnt pairs: per slot
+// The slot table (slots, 4) of the pass of cross_validate that starts at pair p0 and holds cnt pairs: per slot
 // [emulator of the engine, its position in ids, fold, size of the fold]; the slots behind cnt are [-1, 0, 0, 0] -- not used: an identity,
 // so that the batch factorises.
 inline void cv_pass_table(long p0, long cnt, long slots, long k, const int* ids, const int* size, int* tab) {
@@ -128,7 +128,7 @@ inline void cv_pass_table(long p0, long cnt, long slots, long k, const int* ids,
   }
 }
 
-// Engine::sample_posterior: how many emulators one pass takes and how many draws one chunk.  The emulators go in passes [p0, p0 + slots)
+// sample_posterior: how many emulators one pass takes and how many draws one chunk.  The emulators go in passes [p0, p0 + slots)
 // in caller order and, inside a pass, the S draws in chunks [s0, s0 + draws): every (emulator, draw) pair is computed exactly once.
 // Bytes of one slot (sample_slot_bytes):
 //   Sigma* and what predict_full_cov builds it from: K* (MP x LD), V (NP x MP), Sigma* (m x m), the R dot-product rows   (MP = roundup(m, 128))
@@ -184,7 +184,7 @@ inline double sample_ladder_delta(int t, double mean_diag) {
   return d;
 }
 
-// Engine::alc: how many emulators one group takes and how many reference points one chunk.  The emulators go in groups [e0, e0 + slots) in
+// alc: how many emulators one group takes and how many reference points one chunk.  The emulators go in groups [e0, e0 + slots) in
 // caller order and, inside a group, the m_r reference points in chunks [c0, c0 + points), points a multiple of 128: a chunk is a run of whole
 // 128-point tiles of the reference set, and the partial sums of the criterion are kept per GLOBAL tile, so neither number changes a bit of
 // the result.  Bytes of one slot (alc_slot_bytes), MP_c = roundup(m_c, 128), tiles_r = ceil(m_r / 128):
@@ -223,7 +223,7 @@ inline AlcPlan alc_plan(long E, long m_c, long m_r, int LD, int NP, double free_
   if (max_slots > 0) slots = std::min<long>(slots, max_slots);
   return {std::max<long>(1, slots), points};
 }
-// Engine::alc_batch: how many emulators one group takes.  V_r stays resident across the picks, so the reference set is ONE chunk, and both
+// alc_batch: how many emulators one group takes.  V_r stays resident across the picks, so the reference set is ONE chunk, and both
 // V carry ext = roundup(steps, 16) conditioning rows behind their base rows (steps = pending points + picks).  Bytes of one slot:
 //   alc_slot_bytes with NP + ext rows and points = MP_r = roundup(m_r, 128)
 //   + 8 NP max(MP_c, MP_r)                      the stored V as launch_predict_v_store leaves it, before it is copied into the wider buffer
@@ -259,7 +259,7 @@ inline long alc_batch_plan(long E, long m_c, long m_r, long steps, int LD, int N
   if (max_slots > 0) slots = std::min<long>(slots, max_slots);
   return std::max<long>(1, slots);
 }
-// Engine::predict_cov: V_1, V_2, the output and the K* scratch of one emulator against the 64 GB rule of predict_full_cov
+// predict_cov: V_1, V_2, the output and the K* scratch of one emulator against the 64 GB rule of predict_full_cov
 inline double predict_cov_rule_bytes(long m1, long m2, int LD, int NP) {
   const double MP1 = (double)alc_mp(m1), MP2 = (double)alc_mp(m2);
   return 8.0 * ((double)NP * (MP1 + MP2) + (double)m1 * (double)m2 + (double)LD * std::max(MP1, MP2));
@@ -372,7 +372,7 @@ inline VecchiaPlan vecchia_plan(long N, int D, bool grad, int n_cu, double free_
   return {points, (int)grid, vecchia_blocks(N)};
 }
 
-// Stage 2 of Engine::predict_mixture: the normalised weights of the S samples of one emulator, from their negative log-posteriors F and
+// Stage 2 of predict_mixture: the normalised weights of the S samples of one emulator, from their negative log-posteriors F and
 // ok flags and EITHER explicit weights w_in OR the log proposal density log_q (up to a constant).  With log_q:
 //   l_s = -(F_s - F_min) - (log_q_s - log_q_a),  a = the first ok sample with F_a = F_min over the ok samples,  w_s = exp(l_s - max l)
 // (the shift by max l changes nothing but the range of exp).  Samples that are not ok get weight 0; the rest is divided by its sum.
@@ -404,7 +404,7 @@ inline bool mixture_weights(int S, const double* F, const int* ok, const double*
   return true;
 }
 
-// The tables of the pass of Engine::predict_mixture that holds the pairs [p0, p0 + cnt) (ok, w, nug: per pair; alive, pivot_pair: per
+// The tables of the pass of predict_mixture that holds the pairs [p0, p0 + cnt) (ok, w, nug: per pair; alive, pivot_pair: per
 // emulator, pivot_pair = the first pair of the emulator that factorised or -1):
 //   okslots  the slots whose sample factorised, ascending -- what is predicted, row r of the prediction = slot okslots[r];
 //   rows     (cnt) the prediction row of a slot, -1 where its sample failed;
