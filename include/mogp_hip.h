@@ -476,6 +476,36 @@ int mogp_local_vecchia_neighbours(mogp_local* h, const double* scale, int k, int
    choice), and with or without terms_out / ok_out; value_out is the same bits with and without want_grad. */
 int mogp_local_vecchia_loglik(mogp_local* h, int emulator, int kernel_type, const double* scale, double sigma2, double nugget, double jitter, int k,
                               int want_grad, int max_points, double* value_out, double* grad_out, double* terms_out, int* ok_out);
+/* ---- exact prediction for large designs on the same handle: matrix-free preconditioned conjugate gradients (mogp_emulator_amd/IterativeGP.py) ----
+   A = sigma2 k(X, X) + nugget I over the WHOLE design is never stored: its entries are generated from the scaled design (x~ = x_d * s_d, r2 by
+   fused multiply-adds over d) as they are multiplied.  kernel_type and scale as above.  No atomics anywhere: every output is the same bits
+   for a repeated call, and column c of a result depends on column c of the right-hand sides alone.
+   mogp_local_kmatvec: out (M, r) = A V with queries == NULL (M = N), else sigma2 k(queries (m, D), X) V (M = m, no nugget); V (N, r), r >= 1. */
+int mogp_local_kmatvec(mogp_local* h, int kernel_type, const double* scale, double sigma2, double nugget, const double* queries, int m, int D,
+                       const double* V, int r, double* out);
+/* Builds and keeps the preconditioner P = L L^T + nugget I: L the partial pivoted Cholesky factor of sigma2 k(X, X) of rank
+   0 <= rank <= min(N, 1024) (0: none, plain conjugate gradients); nugget > 0.  Every step takes the largest remaining diagonal entry, ties to
+   the lowest index, and the factorisation stops early when that entry is <= 0: rank_out (1) = the rank reached.  pivots_out (rank) and
+   L_out (N, rank) or NULL; entries / columns behind the rank reached are zero. */
+int mogp_local_precondition(mogp_local* h, int kernel_type, const double* scale, double sigma2, double nugget, int rank, int* rank_out,
+                            int* pivots_out, double* L_out);
+/* Solves A x = b for the c columns of B (N, c) at the hyperparameters of the last mogp_local_precondition, in blocks of 32 columns that
+   share each product with A.  Column j stops as soon as its recurrence residual satisfies |r_j| <= rtol |b_j| (a zero column at iteration 0
+   with x = 0), or when p^T A p is not a positive finite number (converged_out 0), and is never touched again: its result does not depend
+   on the other columns.  0 < rtol < 1, max_iter >= 1.  iterations_out (c), converged_out (c): the criterion was met within max_iter;
+   residual_out (c) = |b - A x| / |b| from one further product with the returned x, as it is.  A column that did not converge is no error. */
+int mogp_local_solve(mogp_local* h, const double* B, int c, double rtol, int max_iter, double* x_out, int* iterations_out, int* converged_out,
+                     double* residual_out);
+/* Exact prediction of residual row `emulator`: alpha = A^-1 y (solved once and kept per emulator while the hyperparameters, rank, rtol and
+   max_iter stay), mean_out (m) = sigma2 k(testing, X) alpha and, with var_out != NULL, var_out (m) = max(sigma2 - k*^T A^-1 k* +
+   (include_nugget ? nugget : 0), 0) from solves with blocks of 32 cross columns.  The preconditioner of these hyperparameters is built when
+   it is not the one held.  stat_out (2) = iterations, converged and residual_out (1) of the alpha solve; var_stat_out (2 m) = iterations,
+   converged per query and var_residual_out (m) (needed with var_out); alpha_out (N) or NULL.  m = 0: alpha and its figures alone.
+   max_points: queries per device pass, 0 = sized by the free device memory; no result bit depends on it. */
+int mogp_local_predict_exact(mogp_local* h, int emulator, int kernel_type, const double* scale, double sigma2, double nugget, int rank, double rtol,
+                             int max_iter, int include_nugget, const double* testing, int m, int D, int max_points, double* mean_out,
+                             double* var_out, int* stat_out, double* residual_out, int* var_stat_out, double* var_residual_out,
+                             double* alpha_out);
 void mogp_local_destroy(mogp_local* h);
 /* device memory helpers so a host program can hand device-resident buffers to the *_dev calls */
 void* mogp_dev_malloc(unsigned long long bytes);

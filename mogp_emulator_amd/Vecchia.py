@@ -22,6 +22,7 @@ grouped Vecchia, ``ProductMat52``, ``nugget="adaptive"`` / ``"pivot"``, k > 126,
 """
 import numpy as np
 
+from .IterativeGP import IterativeGP as _IterativeGP
 from .LocalGP import MAX_D, MAX_NEIGHBOURS, _KERNELS, LocalGP as _LocalGP, _create_native as _create_local_native
 
 _FAILED = 1e30          # what the optimiser sees in place of a non-finite evaluation (with a zero gradient)
@@ -323,3 +324,31 @@ class VecchiaGP(object):
         if p.neighbours is not None:
             p.neighbours = self._order[p.neighbours]
         return p
+
+    def predict_exact(self, testing, theta=None, **kw):
+        """``IterativeGP.predict`` at the fitted theta (or ``theta``) on the same native handle: the exact posterior of all N points by
+        preconditioned conjugate gradients, where ``predict`` answers from the neighbours of a query.  ``precond_rank``, ``rtol`` and
+        ``max_iter`` of ``kw`` go to ``IterativeGP``, the rest to its ``predict``.  Returns an ``IterativePrediction``; the nugget must be
+        positive.  ``predict`` is unchanged."""
+        options = {k: kw.pop(k) for k in ("precond_rank", "rtol", "max_iter") if k in kw}
+        return self._exact_view("VecchiaGP.predict_exact", theta, options).predict(testing, **kw)
+
+    def exact_view(self, theta=None, **options):
+        """An ``IterativeGP`` on this object's native handle at the fitted theta (or ``theta``), for ``matvec`` / ``solve`` / ``weights``;
+        ``options``: ``precond_rank``, ``rtol``, ``max_iter``.  THE HANDLE HOLDS THE DESIGN IN THE VECCHIA ORDER: rows of what the view takes
+        and returns are in that order (``order``); ``weights_in_callers_order`` undoes it.  ``predict`` of the view has no such index."""
+        return self._exact_view("VecchiaGP.exact_view", theta, options)
+
+    def _exact_view(self, who, theta, options):
+        if theta is None:
+            if self._fit is None:
+                raise RuntimeError("%s: fit has not been called and no theta was given" % who)
+            theta = self._fit.theta
+        s, sigma2, nugget = self._hyper(who, theta)
+        return _IterativeGP._on_handle(self._open(who), [(self._kt, s, sigma2, nugget, None, np.zeros(0))], self._D, self._N, **options)
+
+    def weights_in_callers_order(self, view):
+        """alpha of ``view`` (an ``exact_view``) with entry i belonging to design point i of the caller"""
+        out = np.empty(self._N)
+        out[self._order] = view.weights()
+        return out

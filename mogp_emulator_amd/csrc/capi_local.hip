@@ -47,6 +47,44 @@ int mogp_local_vecchia_loglik(mogp_local* h, int emulator, int kernel_type, cons
   });
 }
 
+int mogp_local_kmatvec(mogp_local* h, int kernel_type, const double* scale, double sigma2, double nugget, const double* queries, int m, int D,
+                       const double* V, int r, double* out) {
+  return guarded([&] {
+    if (!h || !h->gp) throw std::runtime_error("kmatvec: null handle");
+    if (queries && D != h->gp->D) throw std::runtime_error("kmatvec: queries must have D columns");
+    h->gp->kmatvec(kernel_type, scale, sigma2, nugget, queries, m, V, r, out);
+  });
+}
+
+int mogp_local_precondition(mogp_local* h, int kernel_type, const double* scale, double sigma2, double nugget, int rank, int* rank_out,
+                            int* pivots_out, double* L_out) {
+  return guarded([&] {
+    if (!h || !h->gp) throw std::runtime_error("precondition: null handle");
+    if (!rank_out) throw std::runtime_error("precondition: null pointer");
+    *rank_out = h->gp->precondition(kernel_type, scale, sigma2, nugget, rank, pivots_out, L_out);
+  });
+}
+
+int mogp_local_solve(mogp_local* h, const double* B, int c, double rtol, int max_iter, double* x_out, int* iterations_out, int* converged_out,
+                     double* residual_out) {
+  return guarded([&] {
+    if (!h || !h->gp) throw std::runtime_error("solve: null handle");
+    h->gp->solve(B, c, rtol, max_iter, x_out, iterations_out, converged_out, residual_out);
+  });
+}
+
+int mogp_local_predict_exact(mogp_local* h, int emulator, int kernel_type, const double* scale, double sigma2, double nugget, int rank, double rtol,
+                             int max_iter, int include_nugget, const double* testing, int m, int D, int max_points, double* mean_out,
+                             double* var_out, int* stat_out, double* residual_out, int* var_stat_out, double* var_residual_out,
+                             double* alpha_out) {
+  return guarded([&] {
+    if (!h || !h->gp) throw std::runtime_error("predict_exact: null handle");
+    if (m > 0 && D != h->gp->D) throw std::runtime_error("predict_exact: testing points must have D columns");
+    h->gp->predict_exact(emulator, kernel_type, scale, sigma2, nugget, rank, rtol, max_iter, include_nugget != 0, testing, m, max_points, mean_out,
+                         var_out, stat_out, residual_out, var_stat_out, var_residual_out, alpha_out);
+  });
+}
+
 void mogp_local_destroy(mogp_local* h) {
   if (!h) return;
   (void)guarded([&] {

@@ -317,12 +317,53 @@ class LocalGP {
   void vecchia_neighbours(const double* scale, int k, int* nbr_out);
   void vecchia_loglik(int e, int kt, const double* scale, double sigma2, double nugget, double jitter, int k, bool want_grad, int max_points,
                       double* value_out, double* grad_out, double* terms_out, int* ok_out);
+  // Iterative exact prediction (engine_iter.hip; DESIGN.md section 3 "Iterative exact prediction"): conjugate gradients on A = sigma2 k(X, X)
+  // + nugget I of the WHOLE design, A never stored.  Host pointers; matrices with several columns are row-major as the caller holds them.
+  // kmatvec: out (M, r) = A V (N, r) with queries == null (M = N), else sigma2 k(queries (m, D), X) V (M = m, no nugget).
+  void kmatvec(int kt, const double* scale, double sigma2, double nugget, const double* queries, long m, const double* V, int r, double* out);
+  // Builds and keeps the preconditioner P = L L^T + nugget I of these hyperparameters, L (N, rank reached) the partial pivoted Cholesky
+  // factor of sigma2 k(X, X); returns the rank reached (it stops early when the largest remaining diagonal is <= 0).  piv_out (rank) and
+  // L_out (N, rank) row-major may be null; only the first `rank reached` entries / columns are written, the rest is zero.
+  int precondition(int kt, const double* scale, double sigma2, double nugget, int rank, int* piv_out, double* L_out);
+  // Column-wise preconditioned CG at the hyperparameters of the last precondition: x (N, c); per column iterations, converged (the recurrence
+  // residual met |r| <= rtol |b| within max_iter) and residual = |b - A x| / |b| from one further product, as it is.
+  void solve(const double* B, int c, double rtol, int max_iter, double* x, int* iterations, int* converged, double* residual);
+  // alpha = A^-1 (residual row e) -- solved once and kept per emulator while hyperparameters, rank, rtol and max_iter stay -- and
+  // mean (m) = sigma2 k(testing, X) alpha; with var: var (m) = max(sigma2 - k*^T A^-1 k* + (include_nugget ? nugget : 0), 0), the solves in
+  // blocks of 32 queries.  stat_i (2) = iterations, converged and stat_r (1) = residual of the alpha solve; var_stat_i (2 m) and
+  // var_stat_r (m) the same per query; alpha_out (N) may be null.  m = 0: alpha alone.
+  void predict_exact(int e, int kt, const double* scale, double sigma2, double nugget, int rank, double rtol, int max_iter, bool include_nugget,
+                     const double* testing, long m, int max_points, double* mean, double* var, int* stat_i, double* stat_r, int* var_stat_i,
+                     double* var_stat_r, double* alpha_out);
   int device_id() const { return device; }
   const long N;
   const int D, E;
 
  private:
   void ensure_scaled(const double* scale, hipStream_t st);      // dXs = dX * scale, formed again only when the scales change
+  struct IterKey {                   // what a preconditioner or a kept alpha belongs to
+    int kt = -1, rank = -1, max_iter = 0;
+    double sigma2 = 0., nugget = 0., rtol = 0.;
+    std::vector<double> scale;
+    bool operator==(const IterKey& o) const {
+      return kt == o.kt && rank == o.rank && max_iter == o.max_iter && sigma2 == o.sigma2 && nugget == o.nugget && rtol == o.rtol && scale == o.scale;
+    }
+  };
+  struct IterAlpha {                 // the kept alpha of one emulator
+    IterKey key;
+    std::vector<double> alpha;
+    int iterations = 0, converged = 0;
+    double residual = 0.;
+  };
+  void iter_reserve(const char* who, int rank);                               // the panels and the preconditioner's buffers (refused by name when they do not fit)
+  void iter_build(const IterKey& k, hipStream_t st);            // the preconditioner of k, unless it is the one held
+  // CG on the panel itB (N x 32, kept; columns >= cols are zero) into itX; it / cv / rs: 32 entries each
+  void iter_cg(int cols, double rtol, int max_iter, int* it, int* cv, double* rs, hipStream_t st);
+  IterKey itKey;                     // of the preconditioner held (rtol and max_iter unused: 0)
+  int itRank = 0;                    // the rank it reached
+  DevBuf<double> itL, itG, itDiag, itDmax, itPval, itB, itX, itXl, itR, itP, itQ, itZ, itV, itWpart, itW, itW2, itPart, itSc;
+  DevBuf<int> itPiv, itState, itPidx, itFl;
+  std::vector<IterAlpha> itAlpha;    // per emulator
   int device = 0, n_cu = 1;
   DevBuf<double> dX, dY, dXs, dScale;
   std::vector<double> hScale;        // the scales dXs was formed with (empty: not formed yet)

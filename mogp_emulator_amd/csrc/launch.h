@@ -343,6 +343,46 @@ void launch_vecchia_ll(const double* Xs, const double* Y, long N, int D, long p0
 // returns the one of them whose first cols entries are the sums
 double* launch_vecchia_reduce(const double* in, long n, int cols, double* a, double* b, hipStream_t st);
 
+// --- iterative exact prediction (kernels_iter.hip) ----------------------------------------------------
+// Matrix-free preconditioned conjugate gradients on the whole design (DESIGN.md section 3 "Iterative exact prediction").  A PANEL is a set
+// of columns stored one after another: entry (i, c) at [c * ld + i].  No kernel of the unit waits on another workgroup and none uses an
+// atomic: every result is the same bits for a repeated call, and column c of a result depends on column c of its inputs alone.
+constexpr int ITER_COLS = 32;           // columns of a CG panel (two MFMA blocks of 16 right-hand sides)
+constexpr int ITER_SEG = 4096;          // rows per workgroup of the tall-skinny product L^T V (its partial sums are added in ascending order)
+constexpr int ITER_DOT_BLOCK = 1024;    // rows per workgroup of a column-wise dot
+// Out (M rows, 16 nb columns, ld ldo) = [sigma2 k(r2(As_i, Bs_j)) + nug * (same && i == j)] V (N rows, 16 nb columns, ld ldv); nb = 1 or 2.
+// As (M, D), Bs (N, D) scaled coordinates; the entries are generated per lane (r2 with FMAs, kern_val with the staged table) as the A
+// operand of v_mfma_f64_16x16x4_f64 and never stored.  A workgroup owns 64 rows and sweeps the columns j in ascending tiles of 64.
+void launch_kmatvec(const double* As, long M, const double* Bs, long N, int D, int kt, double sigma2, double nug, bool same, const double* V,
+                    long ldv, int nb, double* Out, long ldo, hipStream_t st);
+// Partial pivoted Cholesky of sigma2 k(Xs, Xs), one step per call of launch_pchol_step: state[0] = the rank reached, state[1] = 1 once the
+// largest remaining diagonal was <= 0 (later steps then do nothing); piv (rank) and the pivot's diagonal dmax (rank) stay on the device.
+// L (N rows, `rank` columns, ld N); diag (N) the remaining diagonal; part: 2 * ceil(N / 1024) doubles and as many ints.
+void launch_pchol_init(double* diag, long N, double sigma2, int* state, hipStream_t st);
+void launch_pchol_step(const double* Xs, long N, int D, int kt, double sigma2, int t, double* L, double* diag, int* piv, double* dmax,
+                       int* state, double* pval, int* pidx, hipStream_t st);
+// G (p, p) = eta I + L^T L, every entry summed over the rows in ascending order
+void launch_pchol_gram(const double* L, long N, int p, double eta, double* G, hipStream_t st);
+// Z = (R - L Ginv L^T R) / eta on panels of ITER_COLS columns (ld N); wpart: ceil(N / ITER_SEG) * p * ITER_COLS doubles, w and w2: p * ITER_COLS
+void launch_precond_apply(const double* L, long N, int p, const double* Ginv, double eta, const double* R, double* Z, double* wpart, double* w,
+                          double* w2, hipStream_t st);
+// column-wise <A_c, B_c> of two panels (ld N): part (ITER_COLS, ceil(N / ITER_DOT_BLOCK)), then launch_cg_scalars(mode) adds them in ascending
+// order and does the step's scalar work on the device.  sc: 5 * ITER_COLS doubles (bb, rz, alpha, beta, out), fl: 3 * ITER_COLS ints (frozen,
+// converged, iterations).
+//   mode 0  bb = s; a column with s == 0 is frozen as converged at iteration 0      mode 1  rz = s
+//   mode 2  s = p^T A p: alpha = rz / s, or frozen as not converged when s is not a positive finite number
+//   mode 3  s = |r|^2: frozen as converged at iteration it + 1 when sqrt(s) <= rtol sqrt(bb)
+//   mode 4  s = r^T z: beta = s / rz, rz = s                                        mode 5  out = s
+// Modes 2 .. 4 leave a frozen column alone.
+void launch_cg_dot(const double* A, const double* B, long N, double* part, hipStream_t st);
+void launch_cg_scalars(int mode, const double* part, long N, double* sc, int* fl, int it, double rtol, hipStream_t st);
+// x += alpha p with the roundings of that sum collected in xl (x + xl is the iterate), r -= alpha q;  p = z + beta p (first: p = z);
+// out = a - b;  x += xl: panels of ITER_COLS columns (ld N).  The two updates leave frozen columns untouched.
+void launch_cg_update(double* x, double* xl, double* r, const double* p, const double* q, long N, const double* sc, const int* fl, hipStream_t st);
+void launch_panel_add(double* x, const double* xl, long N, hipStream_t st);
+void launch_cg_direction(double* p, const double* z, long N, bool first, const double* sc, const int* fl, hipStream_t st);
+void launch_panel_sub(const double* a, const double* b, long N, double* out, hipStream_t st);
+
 // --- utilities -------------------------------------------------------------------------------
 // out (n,n) <- tile of src (NP,NP): mode 0 copy, mode 1 transpose of the lower triangle (zeros below the diagonal of out), mode 2 symmetrise from lower
 void launch_extract(const double* src, int NP, int n, double* out, int mode, hipStream_t s);

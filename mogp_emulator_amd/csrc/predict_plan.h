@@ -1,7 +1,7 @@
 // How the prediction family of Engine (engine_predict.hip), its Hessian (engine_hessian.hip) and the analyses of analysis.h (analysis_*.hip:
 // predict_mixture, cross_validate, sample_posterior, alc, alc_batch, predict_cov) cut their work to a byte budget, the index tables of their passes, and where the mean-function terms of a prediction are
 // staged.  Plain host arithmetic with no HIP in it, so that a host compiler takes it and tests/c/predict_plan_check.cpp, mixture_plan_check.cpp,
-// cv_plan_check.cpp, sample_plan_check.cpp, alc_plan_check.cpp, alc_batch_plan_check.cpp, local_plan_check.cpp, vecchia_plan_check.cpp and local_args_check.cpp (the refusals
+// cv_plan_check.cpp, sample_plan_check.cpp, alc_plan_check.cpp, alc_batch_plan_check.cpp, local_plan_check.cpp, vecchia_plan_check.cpp, iter_plan_check.cpp and local_args_check.cpp (the refusals
 // and the LDS layout of the LocalGP handle, engine_local.hip) can check it without a device.  The caps that need the device (MOGP_KS_BUDGET_GB, free memory) are passed in.
 #pragma once
 #include <algorithm>
@@ -370,6 +370,63 @@ inline VecchiaPlan vecchia_plan(long N, int D, bool grad, int n_cu, double free_
     throw std::runtime_error("vecchia_loglik: " + std::to_string((long long)need) + " bytes of device scratch for " + std::to_string(N) +
                              " points are more than half of the free device memory");
   return {points, (int)grid, vecchia_blocks(N)};
+}
+
+// Iterative exact prediction on the LocalGP handle (engine_iter.hip): the refusals, the device memory it holds and the query passes.
+//   iter_check_hyper   the hyperparameters of local_check_hyper, and a nugget that is positive: the preconditioner divides by it
+//   iter_check_rank    0 <= rank <= min(N, ITER_MAX_RANK); 0 is plain conjugate gradients
+//   iter_check_solve   at least one right-hand side, rtol inside (0, 1), max_iter >= 1
+//   iter_held_bytes    L (8 N rank), G and its inverse, ITER_PANELS panels of ITER_PLAN_COLS columns, the remaining diagonal, the partial sums
+//                      of the tall-skinny product (ceil(N / ITER_PLAN_SEG) rank ITER_PLAN_COLS, and two rank x ITER_PLAN_COLS blocks behind
+//                      them), of the dots (ceil(N / 1024) ITER_PLAN_COLS) and of the pivot search (2 ceil(N / 1024))
+//   iter_check_memory  refuses, before anything is allocated, what does not fit half of the free device memory (what the handle holds of
+//                      it already counts as free: it is reused)
+//   iter_plan          queries per pass: max_points where given, else what the rest of that half holds at iter_point_bytes per query (raw and
+//                      scaled coordinates and the 16 output columns of the rectangular product), at most m and LOCAL_MAX_PASS, at least one;
+//                      blocks = the variance's solves per pass, ITER_PLAN_COLS queries each.  No bit of a result depends on either.
+constexpr int ITER_MAX_RANK = 1024, ITER_PLAN_COLS = 32, ITER_PANELS = 8, ITER_PLAN_SEG = 4096, ITER_PLAN_DOT = 1024;
+inline void iter_check_hyper(const std::string& who, int D, const double* scale, double sigma2, double nugget) {
+  local_check_hyper(who, D, scale, sigma2, nugget, 0.);
+  if (!(nugget > 0.)) throw std::runtime_error(who + ": the nugget must be positive (the preconditioner divides by it)");
+}
+inline void iter_check_rank(const std::string& who, long N, int rank) {
+  const long top = std::min<long>(N, ITER_MAX_RANK);
+  if (rank < 0 || rank > top) throw std::runtime_error(who + ": precond_rank must be between 0 and min(N, 1024) = " + std::to_string(top));
+}
+inline void iter_check_solve(const std::string& who, long cols, double rtol, int max_iter) {
+  if (cols < 1) throw std::runtime_error(who + ": at least one right-hand side is needed");
+  if (!(rtol > 0.) || !(rtol < 1.)) throw std::runtime_error(who + ": rtol must lie between 0 and 1 (both excluded)");
+  if (max_iter < 1) throw std::runtime_error(who + ": max_iter must be at least 1");
+}
+inline double iter_held_bytes(long N, int rank) {
+  const double n = (double)N, p = (double)rank, segs = std::ceil(n / ITER_PLAN_SEG), dots = std::ceil(n / ITER_PLAN_DOT);
+  return 8.0 * (n * p + 2.0 * p * p + ((double)ITER_PANELS * ITER_PLAN_COLS + 1.0) * n + ITER_PLAN_COLS * (segs * p + 2.0 * p + dots) + 2.0 * dots);
+}
+inline void iter_check_memory(const std::string& who, long N, int rank, double free_bytes, double already_held) {
+  const double need = iter_held_bytes(N, rank);
+  if (need > 0.5 * (free_bytes + already_held))
+    throw std::runtime_error(who + ": " + std::to_string((long long)need) + " bytes of device memory for " + std::to_string(N) +
+                             " points at preconditioner rank " + std::to_string(rank) + " are more than half of the free device memory");
+}
+struct IterPlan {
+  long points;      // queries per pass
+  long blocks;      // solves of ITER_PLAN_COLS cross columns per pass (with the variance)
+};
+inline double iter_point_bytes(int D) { return 8.0 * (2.0 * D + 16.0); }
+inline IterPlan iter_plan(const std::string& who, long m, int D, double free_bytes, int max_points) {
+  if (max_points < 0) throw std::runtime_error(who + ": max_points must not be negative");
+  const double budget = 0.5 * free_bytes, per = iter_point_bytes(D);
+  const long want = std::max<long>(1, std::min<long>(m, LOCAL_MAX_PASS));
+  long points;
+  if (max_points > 0) {
+    points = std::min<long>(want, max_points);
+    if ((double)points * per > budget)
+      throw std::runtime_error(who + ": " + std::to_string(points) + " queries per pass need more than half of the free device memory; use a smaller max_points");
+  } else {
+    if (budget < per) throw std::runtime_error(who + ": one query does not fit half of the free device memory");
+    points = std::min<long>(want, (long)std::floor(budget / per));
+  }
+  return {points, (points + ITER_PLAN_COLS - 1) / ITER_PLAN_COLS};
 }
 
 // Stage 2 of predict_mixture: the normalised weights of the S samples of one emulator, from their negative log-posteriors F and

@@ -1395,6 +1395,64 @@ class LocalGP_GPU(object):
                                              int(bool(grad)), int(max_points), dptr(value), dptr(g), dptr(terms), iptr(ok)))
         return float(value[0]), g, terms, ok.astype(bool)
 
+    # ---- iterative exact prediction (csrc/engine_iter.hip, csrc/kernels_iter.hip) ----
+    def kmatvec(self, kern, scale, sigma2, nugget, V, queries=None):
+        """(sigma2 k(X, X) + nugget I) V, or sigma2 k(queries, X) V with ``queries`` (m, D); V (N, r)"""
+        if not self._h:
+            raise RuntimeError("kmatvec: the handle has been closed")
+        scale, V = _f64(scale, 1, "scale"), _f64(V, 2, "V")
+        q = None if queries is None else _f64(queries, 2, "queries")
+        out = np.empty((self.N if q is None else q.shape[0], V.shape[1]))
+        check(_lib.mogp_local_kmatvec(self._h, int(kern), dptr(scale), float(sigma2), float(nugget), dptr(q), 0 if q is None else q.shape[0],
+                                      self.D if q is None else q.shape[1], dptr(V), V.shape[1], dptr(out)))
+        return out
+
+    def precondition(self, kern, scale, sigma2, nugget, rank, return_factor=False):
+        """Builds and keeps the preconditioner; (rank reached, pivots (rank reached) int64 or None, L (N, rank reached) or None)"""
+        if not self._h:
+            raise RuntimeError("precondition: the handle has been closed")
+        scale, rank = _f64(scale, 1, "scale"), int(rank)
+        got = np.zeros(1, dtype=np.int32)
+        piv = np.zeros(max(rank, 1), dtype=np.int32) if return_factor else None
+        L = np.zeros((self.N, max(rank, 1))) if return_factor else None
+        check(_lib.mogp_local_precondition(self._h, int(kern), dptr(scale), float(sigma2), float(nugget), rank, iptr(got), iptr(piv), dptr(L)))
+        r = int(got[0])
+        if not return_factor:
+            return r, None, None
+        return r, piv[:r].astype(np.int64), np.ascontiguousarray(L[:, :r])
+
+    def solve(self, B, rtol, max_iter):
+        """(x (N, c), iterations (c) int64, converged (c) bool, residual (c)) at the hyperparameters of the last ``precondition``"""
+        if not self._h:
+            raise RuntimeError("solve: the handle has been closed")
+        B = _f64(B, 2, "B")
+        c = B.shape[1]
+        x, res = np.empty_like(B), np.empty(c)
+        it, cv = np.empty(c, dtype=np.int32), np.empty(c, dtype=np.int32)
+        check(_lib.mogp_local_solve(self._h, dptr(B), c, float(rtol), int(max_iter), dptr(x), iptr(it), iptr(cv), dptr(res)))
+        return x, it.astype(np.int64), cv.astype(bool), res
+
+    def predict_exact(self, emulator, kern, scale, sigma2, nugget, rank, rtol, max_iter, include_nugget, testing, unc=False, max_points=0,
+                      return_alpha=False):
+        """(mean (m), unc (m) or None, (iterations, converged, residual) of the alpha solve, (iterations (m), converged (m), residual (m)) of the
+        variance solves or None, alpha (N) or None); ``testing`` None: alpha alone"""
+        if not self._h:
+            raise RuntimeError("predict_exact: the handle has been closed")
+        scale = _f64(scale, 1, "scale")
+        t = None if testing is None else _f64(testing, 2, "testing")
+        m = 0 if t is None else t.shape[0]
+        want = bool(unc) and m > 0
+        mean = np.empty(m) if m else None
+        var, vres = (np.empty(m), np.empty(m)) if want else (None, None)
+        vst = np.empty((m, 2), dtype=np.int32) if want else None
+        st, res = np.empty(2, dtype=np.int32), np.empty(1)
+        alpha = np.empty(self.N) if return_alpha else None
+        check(_lib.mogp_local_predict_exact(self._h, int(emulator), int(kern), dptr(scale), float(sigma2), float(nugget), int(rank), float(rtol),
+                                            int(max_iter), int(bool(include_nugget)), dptr(t), m, self.D if t is None else t.shape[1],
+                                            int(max_points), dptr(mean), dptr(var), iptr(st), dptr(res), iptr(vst), dptr(vres), dptr(alpha)))
+        vstats = (vst[:, 0].astype(np.int64), vst[:, 1].astype(bool), vres) if want else None
+        return mean, var, (int(st[0]), bool(st[1]), float(res[0])), vstats, alpha
+
 
 # --------------------------------------------------------------------------------------
 # stand-alone kernel objects (bindings.cu:340-361; flat layouts of kernel.hpp:47-107), evaluated on the
