@@ -506,6 +506,30 @@ int mogp_local_predict_exact(mogp_local* h, int emulator, int kernel_type, const
                              int max_iter, int include_nugget, const double* testing, int m, int D, int max_points, double* mean_out,
                              double* var_out, int* stat_out, double* residual_out, int* var_stat_out, double* var_residual_out,
                              double* alpha_out);
+/* The pieces of the EXACT log-likelihood of residual row `emulator` and of its gradient, by one preconditioned CG solve and stochastic
+   Lanczos quadrature (mogp_emulator_amd/IterativeGP.py log_likelihood assembles them):
+     log p(y) = -1/2 y^T alpha - 1/2 log|A| - N/2 log 2 pi,   log|A| = log|G| + (N - r) log nugget + tr log(P^-1/2 A P^-1/2)
+   with P = L L^T + nugget I the preconditioner of mogp_local_precondition, r the rank it reaches and G = nugget I + L^T L.  The probes are
+   z_t = L g1_t + sqrt(nugget) g2_t for t < n_probes (1 .. 31): g1 (g1_rows, n_probes) with g1_rows = r -- call mogp_local_precondition
+   first to learn it; another value is refused -- and g2 (N, n_probes), row-major standard normals of the caller.  At rank 0 the solver's
+   preconditioner is the identity: then P = I, z_t = g2_t, log|G| = 0 and the term (N - r) log nugget is absent.  One solve of the panel
+   [y | z_1 .. z_T] (C = 1 + n_probes columns) as mogp_local_solve runs it gives alpha (kept as mogp_local_predict_exact keeps it),
+   u_t = A^-1 z_t, w_t = P^-1 z_t (the first preconditioned residual) and the step coefficients.
+     scalars_out (4)      y^T alpha, alpha^T alpha, log|G|, r
+     stat_out (2 C)       iterations, converged per column; residual_out (C) as mogp_local_solve reports it
+     rho_out, uw_out (n_probes)   z_t^T w_t and u_t^T w_t
+     coef_out (max_iter, 2, C)    the CG coefficients alpha_j, beta_j of column c at iteration j while the column was live, 0 elsewhere: the
+                          Lanczos matrix of column c has T_jj = 1 / alpha_j + beta_(j-1) / alpha_(j-1) and T_j,j+1 = sqrt(beta_j) / alpha_j
+     forms_out (2 D)      with want_grad != 0: alpha^T (dA/dtheta_d) alpha for d < D, then sum_t u_t^T (dA/dtheta_d) w_t, where
+                          dA_ij/dtheta_d = sigma2 k'(r2_ij) (x~_id - x~_jd)^2, theta_d = log s_d^2 (one entry per dimension whatever the
+                          kernel), from ONE sweep over the generated matrix; forms_each_out (n_probes, D) or NULL: the second group per
+                          probe, from one sweep each
+     z_out (N, n_probes), x_out (N, C), w_out (N, C) or NULL: the probes, the solutions [alpha | u_t] and the panel [alpha | w_t]
+   No atomics: the same bits for a repeated call; the first D entries of forms_out do not depend on the probes. */
+int mogp_local_loglik_exact(mogp_local* h, int emulator, int kernel_type, const double* scale, double sigma2, double nugget, int rank, double rtol,
+                            int max_iter, const double* g1, int g1_rows, const double* g2, int n_probes, int want_grad, double* scalars_out,
+                            int* stat_out, double* residual_out, double* rho_out, double* uw_out, double* coef_out, double* forms_out,
+                            double* forms_each_out, double* z_out, double* x_out, double* w_out);
 void mogp_local_destroy(mogp_local* h);
 /* device memory helpers so a host program can hand device-resident buffers to the *_dev calls */
 void* mogp_dev_malloc(unsigned long long bytes);

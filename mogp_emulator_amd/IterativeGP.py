@@ -18,14 +18,28 @@ so a result depends neither on the columns it shares a block with nor on ``max_p
 same bits.  What is reported as ``residual`` is |b - A x| / |b| recomputed with one further product, as it is: a column that did not
 converge within ``max_iter`` is not an error, it comes back with ``converged`` False and its honest residual.
 
-Not covered: estimating theta or the log-determinant iteratively, cheap approximate variances (every variance is a solve), the symmetry of A
-in the product, several devices per handle, ``ProductMat52``, ``analytic_mean=True``, ``nugget="pivot"``.
+The exact log-likelihood at those hyperparameters and its gradient come from ONE such solve (``log_likelihood``; ``VecchiaGP.loglik_exact`` and
+``VecchiaGP.fit_exact`` evaluate and maximise it at any theta): the panel [y | z_1 .. z_T] with probes z_t = L g1_t + sqrt(nugget) g2_t ~ N(0, P),
+
+    log p(y) = -1/2 y^T alpha - 1/2 log|A| - N/2 log 2 pi,        log|A| = log|P| + tr log(P^-1/2 A P^-1/2)
+    tr log(.) ~ 1/T sum_t rho_t e_1^T log(T_t) e_1                rho_t = z_t^T P^-1 z_t, T_t the Lanczos matrix of column t's CG coefficients
+    d/dtheta_q = 1/2 alpha^T dA_q alpha - 1/2 tr(A^-1 dA_q),      tr(A^-1 dA_q) ~ 1/T sum_t (A^-1 z_t)^T dA_q (P^-1 z_t)      (E[z z^T] = P)
+
+(stochastic Lanczos quadrature in its CG form).  The forms with the length-scale derivatives are one further sweep over the generated matrix
+for all probes together; those of log sigma^2 (dA = A - nugget I) and log nugget (dA = nugget I) are dots.  With ``precond_rank=0`` the
+solver's preconditioner is the identity: P = I and z_t = g2_t.  The estimate is a deterministic function of (theta, probes).
+
+Not covered: cheap approximate variances (every variance is a solve), more than 31 probes per evaluation (average over seeds), derivatives
+with respect to mean-function parameters, the symmetry of A in the product, several devices per handle, ``ProductMat52``,
+``analytic_mean=True``, ``nugget="pivot"``.
 """
 import numpy as np
 
-from .LocalGP import MAX_D, _create_native, _emulator_type, _fit_state, _hyperparameters, _mean_at, _points
+from .LocalGP import MAX_D, _KERNELS, _create_native, _emulator_type, _fit_state, _hyperparameters, _mean_at, _points
 
 MAX_RANK = 1024
+MAX_PROBES = 31          # the data column and the probes share one panel of 32 columns
+_PROBE_STREAM = 0x10c    # the Philox stream of the default probes (g1 from it, g2 from the next)
 
 
 class IterativeSolve(object):
@@ -47,6 +61,107 @@ class IterativePrediction(object):
     def __init__(self, mean, unc, converged, residual, iterations, var_converged, var_residual):
         self.mean, self.unc, self.converged, self.residual, self.iterations = mean, unc, converged, residual, iterations
         self.var_converged, self.var_residual = var_converged, var_residual
+
+
+class ExactLogLik(object):
+    """What ``IterativeGP.log_likelihood`` and ``VecchiaGP.loglik_exact`` return:
+
+    * ``value``           -fit_term / 2 - logdet / 2 - N log(2 pi) / 2; NaN when ``ok`` is False
+    * ``grad``            (P,) in ``VecchiaLogLik.grad``'s layout -- the correlation parameters (D, or 1 for the uniform kernels), log sigma^2,
+                          and log nugget when the nugget is fitted -- with ``grad=True``, else None
+    * ``fit_term``        y^T alpha;   ``logdet`` the estimate of log|A|;   ``logdet_precond`` log|P|, its exact part
+    * ``logdet_se``       the standard error of ``logdet`` over the probes (NaN with one probe)
+    * ``trace``, ``trace_se``   (P,) the estimates of tr(A^-1 dA/dtheta_q) and their standard errors; the length-scale entries of
+                          ``trace_se`` are NaN unless ``probe_terms=True``.  None without ``grad``
+    * ``data_forms``      (P,) alpha^T (dA/dtheta_q) alpha, None without ``grad``
+    * ``rho``, ``uw``     (T,) z_t^T P^-1 z_t and (A^-1 z_t)^T (P^-1 z_t) as the device returned them; ``quadrature`` (T,) rho_t e_1^T log(T_t) e_1
+    * ``iterations``, ``converged``, ``residual``   per column of the solve, the data column first
+    * ``precond_rank``    the rank the preconditioner reached
+    * ``ok``              every column converged and every quadrature was finite"""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+
+def _lanczos_quadrature(a, b):
+    """e_1^T log(T) e_1 of the Lanczos matrix of one column's CG coefficients a_0 .. a_(m-1), b_0 .. b_(m-2)"""
+    from scipy.linalg import eigh_tridiagonal
+    m = a.shape[0]
+    if m < 1 or not (np.all(np.isfinite(a)) and np.all(a > 0.) and np.all(np.isfinite(b[:m - 1])) and np.all(b[:m - 1] >= 0.)):
+        return np.nan
+    diag = 1. / a
+    diag[1:] += b[:m - 1] / a[:m - 1]
+    if m == 1:
+        return float(np.log(diag[0])) if diag[0] > 0. else np.nan
+    lam, vec = eigh_tridiagonal(diag, np.sqrt(b[:m - 1]) / a[:m - 1], lapack_driver="stev")      # (QR: the default MRRR driver can fail on these)
+    if not np.all(lam > 0.):
+        return np.nan
+    return float(np.sum(vec[0] ** 2 * np.log(lam)))
+
+
+def _check_probes(who, n_probes, seed, probes, N):
+    """(T, seed, g2 or None, g1 or None) -- g1's row count is checked once the rank is known"""
+    if probes is None:
+        T = int(n_probes)
+        if T != n_probes or T < 1 or T > MAX_PROBES:
+            raise ValueError("%s: n_probes must be between 1 and %d" % (who, MAX_PROBES))
+        if int(seed) != seed or int(seed) < 0:
+            raise ValueError("%s: seed must be a non-negative integer" % who)
+        return T, int(seed), None, None
+    try:
+        g1, g2 = probes
+        g1, g2 = np.ascontiguousarray(g1, dtype=np.float64), np.ascontiguousarray(g2, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("%s: probes must be a pair (g1 (rank reached, T), g2 (N, T)) of arrays" % who)
+    if g2.ndim != 2 or g1.ndim != 2 or g2.shape[0] != N or g1.shape[1] != g2.shape[1]:
+        raise ValueError("%s: probes must be a pair (g1 (rank reached, T), g2 (N, T)) of arrays with N = %d" % (who, N))
+    if g2.shape[1] < 1 or g2.shape[1] > MAX_PROBES:
+        raise ValueError("%s: n_probes must be between 1 and %d" % (who, MAX_PROBES))
+    if not (np.all(np.isfinite(g1)) and np.all(np.isfinite(g2))):
+        raise ValueError("%s: probes must be finite" % who)
+    return g2.shape[1], 0, g2, g1
+
+
+def _exact_loglik(who, native, e, hyper, layout, D, N, p, rtol, max_iter, grad, T, seed, g1, g2, probe_terms):
+    """the device call and the assembly of an ``ExactLogLik``; every argument has been checked"""
+    kt, s, sigma2, eta = hyper[:4]
+    uniform, fit_nugget = layout
+    rank = native.precondition(kt, s, sigma2, eta, p)[0]
+    if g2 is None:
+        from .Sampling import philox_normals
+        g1 = np.ascontiguousarray(philox_normals(seed, _PROBE_STREAM, T, rank).T) if rank else np.zeros((0, T))
+        g2 = np.ascontiguousarray(philox_normals(seed, _PROBE_STREAM + 1, T, N).T)
+    elif g1.shape[0] != rank:
+        raise ValueError("%s: g1 of probes must have as many rows as the rank the preconditioner reaches, %d" % (who, rank))
+    r = native.loglik_exact(e, kt, s, sigma2, eta, p, rtol, max_iter, g1, g2, grad=grad, probe_terms=probe_terms)
+    rho, uw, its = r["rho"], r["uw"], r["iterations"]
+    quad = np.array([rho[t] * _lanczos_quadrature(r["coef"][:its[1 + t], 0, 1 + t], r["coef"][:its[1 + t], 1, 1 + t]) for t in range(T)])
+    ok = bool(r["converged"].all() and np.all(np.isfinite(quad)) and np.isfinite(r["y_alpha"]))
+    root = np.sqrt(T)
+    se = (lambda v: float(np.std(v, ddof=1)) / root) if T > 1 else (lambda v: np.nan)
+    logdet_p = r["logdet_g"] + (N - rank) * np.log(eta) if rank else 0.
+    logdet = logdet_p + float(np.mean(quad))
+    value = -0.5 * r["y_alpha"] - 0.5 * logdet - 0.5 * N * np.log(2. * np.pi) if ok else np.nan
+    out_g = trace = trace_se = data = None
+    if grad:
+        def corr(v):                              # (.., D) per dimension -> the layout of theta: the uniform kernels share one parameter
+            if not uniform:
+                return v
+            tot = 0. * v[..., 0]
+            for d in range(D):                    # ascending in d
+                tot = tot + v[..., d]
+            return tot[..., None]
+        tr_eta, tr_s2 = eta * np.mean(uw), np.mean(rho) - eta * np.mean(uw)
+        trace = np.concatenate([corr(r["forms_probe"]) / T, [tr_s2], [tr_eta] if fit_nugget else []])
+        each = corr(r["forms_each"]) if probe_terms else None
+        nc = trace.shape[0] - 1 - (1 if fit_nugget else 0)
+        trace_se = np.concatenate([[se(each[:, q]) for q in range(nc)] if probe_terms else np.full(nc, np.nan), [se(rho - eta * uw)],
+                                   [se(eta * uw)] if fit_nugget else []])
+        data = np.concatenate([corr(r["forms_data"]), [r["y_alpha"] - eta * r["alpha_alpha"]], [eta * r["alpha_alpha"]] if fit_nugget else []])
+        out_g = 0.5 * data - 0.5 * trace if ok else np.full(trace.shape[0], np.nan)
+    return ExactLogLik(value=float(value), grad=out_g, fit_term=r["y_alpha"], logdet=logdet if ok else np.nan, logdet_precond=float(logdet_p),
+                       logdet_se=se(quad), trace=trace, trace_se=trace_se, data_forms=data, rho=rho, uw=uw, quadrature=quad,
+                       iterations=its, converged=r["converged"], residual=r["residual"], precond_rank=rank, ok=ok)
 
 
 def _check_options(who, N, precond_rank, rtol, max_iter):
@@ -104,15 +219,18 @@ class IterativeGP(object):
         if device is not None and (int(device) != device or int(device) < 0):
             raise ValueError("%s: device must be a device ordinal or None" % who)
         self._hyper = [_hyperparameters(em, D) for em in natives]
+        fit_nugget = (gp.nugget_type if single else gp._nugget_name) == "fit"
+        self._layout = [(_KERNELS[str(em.get_kernel_type()).split(".")[1]][1], fit_nugget) for em in natives]
         _check_nuggets(who, self._hyper)
         self._single, self._D, self._N, self._E = single, D, N, E
         resid = np.stack([targets[e] - _mean_at(h[4], h[5], inputs) for e, h in enumerate(self._hyper)])
         self._native = _create_native(inputs, np.ascontiguousarray(resid), None if device is None else int(device))
 
     @classmethod
-    def _on_handle(cls, native, hyper, D, N, precond_rank=256, rtol=1e-8, max_iter=1000):
+    def _on_handle(cls, native, hyper, D, N, precond_rank=256, rtol=1e-8, max_iter=1000, layout=None):
         """Internal: a single-output view on a native handle that somebody else owns (``VecchiaGP.predict_exact``), at the hyperparameters
         ``hyper`` = [(kernel 0 / 1, s (D,), sigma^2, nugget, mean function or None, its parameters)] in place of a fitted ``gp``.
+        ``layout`` = [(uniform kernel, fitted nugget)]: what ``log_likelihood`` lays its gradient out by (default: per-dimension, fitted).
         ``close()`` of the view leaves the handle open."""
         who = "IterativeGP"
         self = cls.__new__(cls)
@@ -120,6 +238,7 @@ class IterativeGP(object):
         _check_nuggets(who, hyper)
         self._single, self._D, self._N, self._E = True, int(D), int(N), 1
         self._hyper, self._native, self._borrowed = list(hyper), native, True
+        self._layout = list(layout) if layout is not None else [(False, True)] * len(self._hyper)
         return self
 
     n = property(lambda self: self._N)
@@ -191,6 +310,22 @@ class IterativeGP(object):
         who = "IterativeGP.weights"
         e, (kt, s, sigma2, nugget, _, _) = self._emulator(who, emulator)
         return self._native.predict_exact(e, kt, s, sigma2, nugget, self._p, self._rtol, self._max_iter, True, None, return_alpha=True)[4]
+
+    # ---- the exact likelihood ---------------------------------------------------------------------------------------------------------------
+    def log_likelihood(self, emulator=0, grad=False, n_probes=15, seed=0, probes=None, probe_terms=False):
+        """The exact log-likelihood of the whole design at the hyperparameters of ``emulator`` (its log-determinant estimated by stochastic
+        Lanczos quadrature) and, with ``grad=True``, its gradient; returns an ``ExactLogLik``.  The mean function is held fixed.
+
+        ``n_probes`` 1 .. 31 (the default 15 makes 16 columns with the data: the product then runs on one block of 16); the normals come
+        from ``philox_normals(seed, .)`` of ``Sampling.py`` unless ``probes=(g1 (rank reached, T), g2 (N, T))`` gives the caller's (common
+        random numbers; ``preconditioner()`` tells the rank).  ``probe_terms=True`` also gives the length-scale traces a standard error,
+        by one sweep per probe: T times the cost of the sweep.  A column that does not converge is reported (``ok`` False, ``value``
+        NaN), never raised.  The weights of the solve are kept as ``weights()`` / ``predict`` keep them."""
+        who = "IterativeGP.log_likelihood"
+        T, seed, g2, g1 = _check_probes(who, n_probes, seed, probes, self._N)
+        e, hyper = self._emulator(who, emulator)
+        return _exact_loglik(who, self._native, e, hyper, self._layout[e], self._D, self._N, self._p, self._rtol, self._max_iter, bool(grad),
+                             T, seed, g1, g2, bool(probe_terms) and bool(grad))
 
     # ---- prediction ----------------------------------------------------------------------------------------------------------------------
     def predict(self, testing, unc=False, include_nugget=True, max_points=0):

@@ -17,12 +17,15 @@ log nugget with ``nugget="fit"``.  The neighbour search follows the contract of 
 ascending in d without fused multiply-add, the smallest (r2, index) pairs, ties to the lowest position), so NumPy reproduces every list.
 Value and gradient are summed without atomics in an order that depends on N alone: the same bits for a repeated call and any ``max_points``.
 
+``loglik_exact`` and ``fit_exact`` evaluate and maximise the EXACT likelihood of the whole design on the same handle (``IterativeGP.py``:
+one matrix-free CG solve and stochastic Lanczos quadrature per evaluation), typically started from the Vecchia optimum.
+
 Not covered: priors, mean functions (the mean is zero), several outputs or several theta per call, a maximin ordering on the device,
 grouped Vecchia, ``ProductMat52``, ``nugget="adaptive"`` / ``"pivot"``, k > 126, several devices.
 """
 import numpy as np
 
-from .IterativeGP import IterativeGP as _IterativeGP
+from .IterativeGP import IterativeGP as _IterativeGP, _check_options, _check_probes, _exact_loglik
 from .LocalGP import MAX_D, MAX_NEIGHBOURS, _KERNELS, LocalGP as _LocalGP, _create_native as _create_local_native
 
 _FAILED = 1e30          # what the optimiser sees in place of a non-finite evaluation (with a zero gradient)
@@ -56,6 +59,16 @@ class VecchiaFit(object):
         self.theta, self.value, self.grad = best["theta"], best["value"], best["grad"]
         self.n_evaluations, self.n_refreshes, self.converged = best["n_evaluations"], best["n_refreshes"], best["converged"]
         self.tries = tries
+
+
+class ExactFit(object):
+    """What ``VecchiaGP.fit_exact`` returns: ``theta``, ``value`` (the estimated exact log-likelihood there, on the probes of the run), ``grad``
+    (its gradient there), ``n_evaluations``, ``converged`` (L-BFGS-B ended by one of its own rules), ``message`` and ``loglik``, the
+    ``ExactLogLik`` at ``theta``."""
+
+    def __init__(self, theta, value, grad, n_evaluations, converged, message, loglik):
+        self.theta, self.value, self.grad, self.n_evaluations = theta, value, grad, n_evaluations
+        self.converged, self.message, self.loglik = converged, message, loglik
 
 
 def _kernel_name(who, kernel):
@@ -126,7 +139,7 @@ class VecchiaGP(object):
         self._kernel, (self._kt, self._uniform) = name, _KERNELS[name]
         self._N, self._D, self._k, self._nugget = N, D, k, nugget
         self._nc = 1 if self._uniform else D
-        self._scales = self._nbr = self._fit = None
+        self._scales = self._nbr = self._fit = self._theta = None      # _theta: what predict uses, of the last fit or fit_exact
         self._range, self._tvar = inputs.max(axis=0) - inputs.min(axis=0), float(np.var(targets))
         self._native = _create_native(np.ascontiguousarray(inputs[self._order]), np.ascontiguousarray(targets[self._order][None, :]),
                                       None if device is None else int(device))
@@ -137,7 +150,7 @@ class VecchiaGP(object):
     n_params = property(lambda self: self._nc + 1 + (1 if self._nugget == "fit" else 0))
     kernel = property(lambda self: self._kernel)
     order = property(lambda self: self._order.copy())
-    theta = property(lambda self: None if self._fit is None else self._fit.theta.copy())
+    theta = property(lambda self: None if self._theta is None else self._theta.copy())
 
     def close(self):
         native, self._native = getattr(self, "_native", None), None
@@ -305,6 +318,7 @@ class VecchiaGP(object):
         if best is not tries[-1]:
             self.set_neighbours(theta=best["lists_theta"])     # the lists on the device are those the kept value was computed on
         self._fit = VecchiaFit(best, tries)
+        self._theta = self._fit.theta
         return self._fit
 
     # ---- prediction ---------------------------------------------------------------------------------------------------------------------
@@ -314,9 +328,9 @@ class VecchiaGP(object):
         Returns a ``LocalPrediction`` whose neighbour indices are in the caller's numbering."""
         who = "VecchiaGP.predict"
         if theta is None:
-            if self._fit is None:
+            if self._theta is None:
                 raise RuntimeError("%s: fit has not been called and no theta was given" % who)
-            theta = self._fit.theta
+            theta = self._theta
         s, sigma2, nugget = self._hyper(who, theta)
         k = self._k if n_neighbours is None else n_neighbours
         view = _LocalGP._on_handle(self._open(who), [(self._kt, s, sigma2, nugget, None, np.zeros(0))], self._D, self._N, k)
@@ -341,11 +355,69 @@ class VecchiaGP(object):
 
     def _exact_view(self, who, theta, options):
         if theta is None:
-            if self._fit is None:
+            if self._theta is None:
                 raise RuntimeError("%s: fit has not been called and no theta was given" % who)
-            theta = self._fit.theta
+            theta = self._theta
         s, sigma2, nugget = self._hyper(who, theta)
-        return _IterativeGP._on_handle(self._open(who), [(self._kt, s, sigma2, nugget, None, np.zeros(0))], self._D, self._N, **options)
+        return _IterativeGP._on_handle(self._open(who), [(self._kt, s, sigma2, nugget, None, np.zeros(0))], self._D, self._N,
+                                       layout=[(self._uniform, self._nugget == "fit")], **options)
+
+    # ---- the exact likelihood -----------------------------------------------------------------------------------------------------------
+    def loglik_exact(self, theta, grad=False, n_probes=15, seed=0, probes=None, precond_rank=256, rtol=1e-8, max_iter=1000, probe_terms=False):
+        """The EXACT log-likelihood of the whole design at ``theta`` (laid out as for ``loglik``) and, with ``grad=True``, its gradient, by
+        ``IterativeGP.log_likelihood`` on this object's native handle: one preconditioned CG solve of [y | probes] and stochastic Lanczos
+        quadrature.  Returns an ``ExactLogLik``; the nugget must be positive.  ``probes=(g1, g2)``: the caller's normals, g2's rows in the
+        Vecchia order of the handle (``order``).  Needs no neighbour lists."""
+        who = "VecchiaGP.loglik_exact"
+        s, sigma2, nugget = self._hyper(who, theta)
+        if not nugget > 0.:
+            raise ValueError("%s: the nugget must be positive (the preconditioner divides by it)" % who)
+        p, rtol, max_iter = _check_options(who, self._N, precond_rank, rtol, max_iter)
+        T, seed, g2, g1 = _check_probes(who, n_probes, seed, probes, self._N)
+        return _exact_loglik(who, self._open(who), 0, (self._kt, s, sigma2, nugget), (self._uniform, self._nugget == "fit"), self._D, self._N, p,
+                             rtol, max_iter, bool(grad), T, seed, g1, g2, bool(probe_terms) and bool(grad))
+
+    def fit_exact(self, theta0=None, n_probes=15, seed=0, precond_rank=256, rtol=1e-8, max_iter=1000, **lbfgs_options):
+        """Maximise the exact log-likelihood: ``scipy.optimize.minimize(method="L-BFGS-B", jac=True)`` on ``-loglik_exact``; no priors.
+
+        The normals of the probes are those of ``seed`` for the whole run -- the probes z = L g1 + sqrt(nugget) g2 follow theta through L
+        and the nugget -- so the objective is a deterministic function of theta.  ``theta0`` (P,) or None: the Vecchia fit (``fit()`` is run
+        when it has not been).  ``lbfgs_options`` go to the optimiser's ``options`` (defaults as ``fit``).  An evaluation that is not finite
+        or whose solve did not converge is handed to the optimiser as a large finite value with a zero gradient.  Returns an ``ExactFit``;
+        the theta is also kept (``theta``; ``predict`` / ``predict_exact`` use it), the record of the Vecchia fit is left as it is."""
+        from scipy.optimize import minimize
+        who = "VecchiaGP.fit_exact"
+        if theta0 is not None:
+            theta0 = np.array(theta0, dtype=np.float64)
+            if not self._hyper(who, theta0)[2] > 0.:
+                raise ValueError("%s: the nugget must be positive (the preconditioner divides by it)" % who)
+        elif not (self._nugget == "fit" or self._nugget > 0.):
+            raise ValueError("%s: the nugget must be positive (the preconditioner divides by it)" % who)
+        _check_options(who, self._N, precond_rank, rtol, max_iter)
+        _check_probes(who, n_probes, seed, None, self._N)
+        self._open(who)
+        if theta0 is None:
+            theta0 = (self._fit if self._fit is not None else self.fit()).theta
+        options = dict(gtol=1e-5 * self._N, ftol=1e-13, maxiter=200)
+        options.update(lbfgs_options)
+        kw = dict(n_probes=n_probes, seed=seed, precond_rank=precond_rank, rtol=rtol, max_iter=max_iter)
+        count = [0]
+
+        def objective(th):
+            count[0] += 1
+            try:
+                ll = self.loglik_exact(th, grad=True, **kw)
+            except ValueError:                   # theta outside what exp() holds
+                return _FAILED, np.zeros(self.n_params)
+            if not (ll.ok and np.isfinite(ll.value) and np.all(np.isfinite(ll.grad))):
+                return _FAILED, np.zeros(self.n_params)
+            return -ll.value, -ll.grad
+
+        res = minimize(objective, theta0, method="L-BFGS-B", jac=True, options=options)
+        theta = np.array(res.x, dtype=np.float64)
+        final = self.loglik_exact(theta, grad=True, **kw)
+        self._theta = theta
+        return ExactFit(theta, final.value, final.grad, count[0], bool(res.success), str(res.message), final)
 
     def weights_in_callers_order(self, view):
         """alpha of ``view`` (an ``exact_view``) with entry i belonging to design point i of the caller"""

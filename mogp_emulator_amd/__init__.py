@@ -22,7 +22,8 @@ mogp_emulator_amd -- MI355X (gfx950) native fit + predict backend for mogp_emula
                    posterior covariance between two point sets and the ALC (integrated-variance) design criterion, reduced on the device
   LocalGP.py       local approximate GP prediction for designs beyond the dense path: k nearest neighbours and one small GP per query, on the device
   Vecchia.py       hyperparameters from the whole of a large design: the Vecchia likelihood and its analytic gradient on the device, L-BFGS fit
-  IterativeGP.py   exact prediction for designs beyond the dense path: matrix-free preconditioned conjugate gradients on the whole design, on the device
+  IterativeGP.py   exact prediction for designs beyond the dense path: matrix-free preconditioned conjugate gradients on the whole design, on the device;
+                   the exact log-likelihood and its gradient by stochastic Lanczos quadrature from one such solve
   dist.py          one-process-per-GPU sharding of emulators + single gather (torch.distributed/RCCL)
 """
 from .LibGPGPU import HAVE_LIBGPGPU, gpu_usable            # noqa: F401
@@ -33,8 +34,8 @@ from .Marginal import predict_marginal, MarginalPredictResult, mixture_weights  
 from .Sampling import sample_posterior, PosteriorSamples, philox_normals   # noqa: F401
 from .ActiveLearning import predict_cov, alc_criterion, ALCResult, alc_batch, ALCBatchResult   # noqa: F401
 from .LocalGP import LocalGP, LocalPrediction, predict_local   # noqa: F401
-from .Vecchia import VecchiaGP, VecchiaLogLik, VecchiaFit   # noqa: F401
-from .IterativeGP import IterativeGP, IterativeSolve, IterativePrediction   # noqa: F401
+from .Vecchia import VecchiaGP, VecchiaLogLik, VecchiaFit, ExactFit   # noqa: F401
+from .IterativeGP import IterativeGP, IterativeSolve, IterativePrediction, ExactLogLik   # noqa: F401
 
 if HAVE_LIBGPGPU:
     from .GaussianProcessGPU import GaussianProcessGPU, PredictResult   # noqa: F401

@@ -85,6 +85,17 @@ int mogp_local_predict_exact(mogp_local* h, int emulator, int kernel_type, const
   });
 }
 
+int mogp_local_loglik_exact(mogp_local* h, int emulator, int kernel_type, const double* scale, double sigma2, double nugget, int rank, double rtol,
+                            int max_iter, const double* g1, int g1_rows, const double* g2, int n_probes, int want_grad, double* scalars_out,
+                            int* stat_out, double* residual_out, double* rho_out, double* uw_out, double* coef_out, double* forms_out,
+                            double* forms_each_out, double* z_out, double* x_out, double* w_out) {
+  return guarded([&] {
+    if (!h || !h->gp) throw std::runtime_error("loglik_exact: null handle");
+    h->gp->loglik_exact(emulator, kernel_type, scale, sigma2, nugget, rank, rtol, max_iter, g1, g1_rows, g2, n_probes, want_grad != 0, scalars_out,
+                        stat_out, residual_out, rho_out, uw_out, coef_out, forms_out, forms_each_out, z_out, x_out, w_out);
+  });
+}
+
 void mogp_local_destroy(mogp_local* h) {
   if (!h) return;
   (void)guarded([&] {

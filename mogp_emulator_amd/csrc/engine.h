@@ -335,6 +335,21 @@ class LocalGP {
   void predict_exact(int e, int kt, const double* scale, double sigma2, double nugget, int rank, double rtol, int max_iter, bool include_nugget,
                      const double* testing, long m, int max_points, double* mean, double* var, int* stat_i, double* stat_r, int* var_stat_i,
                      double* var_stat_r, double* alpha_out);
+  // The pieces of the exact log-likelihood of residual row e and of its gradient (engine_iter_lik.hip; DESIGN.md section 3 "Iterative exact
+  // likelihood"): the preconditioner, the probes z_t = L g1_t + sqrt(nugget) g2_t (g1 (g1_rows, T) with g1_rows the rank the preconditioner
+  // reaches, g2 (N, T), row-major standard normals; at rank 0 the preconditioner is the identity and z_t = g2_t), ONE solve of the panel
+  // [y | z_1 .. z_T] with the step coefficients logged, the dots and -- with want_grad -- the sweep of launch_kgrad_forms.  C = 1 + T.
+  //   scalars (4)     y^T alpha, alpha^T alpha, log|G| (G = nugget I + L^T L; 0 at rank 0), the rank reached
+  //   stat_i (2 C)    iterations, converged per column;  residual (C)
+  //   rho (T), uw (T) z_t^T w_t with w_t = P^-1 z_t, and u_t^T w_t with u_t = A^-1 z_t
+  //   coef (max_iter, 2, C)  the CG step coefficients alpha_j, beta_j of every column while it was live, zero elsewhere
+  //   forms (2 D)     with want_grad: alpha^T (dA/dtheta_d) alpha, then sum_t u_t^T (dA/dtheta_d) w_t; forms_each (T, D) or null: the
+  //                   latter per probe, from one sweep each
+  //   z_out (N, T), x_out (N, C), w_out (N, C) or null: the probes, the solutions [alpha | u_t] and the other side of the forms
+  //                   [alpha | w_t], row-major.  alpha is kept as predict_exact keeps it.
+  void loglik_exact(int e, int kt, const double* scale, double sigma2, double nugget, int rank, double rtol, int max_iter, const double* g1,
+                    int g1_rows, const double* g2, int T, bool want_grad, double* scalars, int* stat_i, double* residual, double* rho, double* uw,
+                    double* coef, double* forms, double* forms_each, double* z_out, double* x_out, double* w_out);
   int device_id() const { return device; }
   const long N;
   const int D, E;
@@ -358,9 +373,13 @@ class LocalGP {
   void iter_reserve(const char* who, int rank);                               // the panels and the preconditioner's buffers (refused by name when they do not fit)
   void iter_build(const IterKey& k, hipStream_t st);            // the preconditioner of k, unless it is the one held
   // CG on the panel itB (N x 32, kept; columns >= cols are zero) into itX; it / cv / rs: 32 entries each
-  void iter_cg(int cols, double rtol, int max_iter, int* it, int* cv, double* rs, hipStream_t st);
+  // first_z (a panel) receives the first z = P^-1 r of every column, coef_log (2 * 32 * max_iter) the step coefficients; both may be null
+  // and change no bit of anything else
+  void iter_cg(int cols, double rtol, int max_iter, int* it, int* cv, double* rs, hipStream_t st, double* first_z = nullptr, double* coef_log = nullptr);
   IterKey itKey;                     // of the preconditioner held (rtol and max_iter unused: 0)
   int itRank = 0;                    // the rank it reached
+  double itLogdetG = 0.;             // log|nugget I + L^T L| of it (0 at rank 0)
+  DevBuf<double> lkW, lkLog, lkG1, lkPart, lkOut;    // the exact likelihood's own buffers (loglik_exact alone allocates them)
   DevBuf<double> itL, itG, itDiag, itDmax, itPval, itB, itX, itXl, itR, itP, itQ, itZ, itV, itWpart, itW, itW2, itPart, itSc;
   DevBuf<int> itPiv, itState, itPidx, itFl;
   std::vector<IterAlpha> itAlpha;    // per emulator

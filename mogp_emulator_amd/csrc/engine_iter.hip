@@ -17,8 +17,8 @@ static_assert(ITER_COLS == ITER_PLAN_COLS && ITER_SEG == ITER_PLAN_SEG && ITER_D
 constexpr int ITER_LOOK = 8;      // iterations between two looks of the host at the frozen flags (no result depends on it)
 
 // Ginv = G^-1 of the symmetric positive definite G (p x p, row-major), in place and exactly symmetric: G = C C^T, U = C^-T (row j of U is
-// column j of C^-1), Ginv = U U^T.  Plain loops over contiguous rows; p <= 1024.
-void spd_inverse(std::vector<double>& G, int p) {
+// column j of C^-1), Ginv = U U^T.  Plain loops over contiguous rows; p <= 1024.  Returns log|G| = 2 sum_i log C_ii.
+double spd_inverse(std::vector<double>& G, int p) {
   std::vector<double> C((size_t)p * p, 0.0), U((size_t)p * p, 0.0);
   for (int i = 0; i < p; ++i) {
     const double* gi = &G[(size_t)i * p];
@@ -51,6 +51,9 @@ void spd_inverse(std::vector<double>& G, int p) {
       for (int k = a; k < p; ++k) s += ua[k] * ub[k];
       G[(size_t)a * p + b] = G[(size_t)b * p + a] = s;
     }
+  double logdet = 0.0;
+  for (int i = 0; i < p; ++i) logdet += std::log(C[(size_t)i * p + i]);
+  return 2.0 * logdet;
 }
 
 }  // namespace
@@ -96,13 +99,14 @@ void LocalGP::iter_build(const IterKey& k, hipStream_t st) {
     HIPCK(hipStreamSynchronize(st));
   }
   const int p = state[0];
+  itLogdetG = 0.;
   if (p > 0) {
     launch_pchol_gram(itL, N, p, k.nugget, itG, st);
     HIPCK(hipGetLastError());
     std::vector<double> G((size_t)p * p);
     HIPCK(hipMemcpyAsync(G.data(), itG, G.size() * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCK(hipStreamSynchronize(st));
-    spd_inverse(G, p);
+    itLogdetG = spd_inverse(G, p);
     HIPCK(hipMemcpyAsync(itG, G.data(), G.size() * sizeof(double), hipMemcpyHostToDevice, st));
     HIPCK(hipStreamSynchronize(st));
   }
@@ -110,7 +114,8 @@ void LocalGP::iter_build(const IterKey& k, hipStream_t st) {
   itKey = k;
 }
 
-void LocalGP::iter_cg(int cols, double rtol, int max_iter, int* it_out, int* cv_out, double* rs_out, hipStream_t st) {
+void LocalGP::iter_cg(int cols, double rtol, int max_iter, int* it_out, int* cv_out, double* rs_out, hipStream_t st, double* first_z,
+                      double* coef_log) {
   const size_t panel_bytes = (size_t)N * ITER_COLS * sizeof(double);
   const IterKey& k = itKey;
   const bool pre = itRank > 0;
@@ -124,13 +129,14 @@ void LocalGP::iter_cg(int cols, double rtol, int max_iter, int* it_out, int* cv_
   };
   auto dot = [&](int mode, const double* a, const double* b, int it) {
     launch_cg_dot(a, b, N, itPart, st);
-    launch_cg_scalars(mode, itPart, N, itSc, itFl, it, rtol, st);
+    launch_cg_scalars(mode, itPart, N, itSc, itFl, it, rtol, st, coef_log);
   };
   HIPCK(hipMemsetAsync(itX, 0, panel_bytes, st));
   HIPCK(hipMemsetAsync(itXl, 0, panel_bytes, st));
   HIPCK(hipMemcpyAsync(itR, itB, panel_bytes, hipMemcpyDeviceToDevice, st));
   dot(0, itB, itB, 0);
   apply();
+  if (first_z) HIPCK(hipMemcpyAsync(first_z, z, panel_bytes, hipMemcpyDeviceToDevice, st));
   dot(1, itR, z, 0);
   launch_cg_direction(itP, z, N, true, itSc, itFl, st);
   int fl[3 * ITER_COLS];

@@ -19,6 +19,10 @@
 //   cg_*_kernel          column-wise dots (x carried as a compensated sum; blocks of ITER_DOT_BLOCK rows in a fixed tree, the blocks added in ascending order by one thread
 //                        per column, which also does the step's scalar work: the step scalars and the frozen flags never leave the
 //                        device) and the fused updates, which leave a frozen column alone
+//   probe_kernel         the probes of the exact likelihood (engine_iter_lik.hip), Z = L g1 + sqrt(eta) g2, one row per thread
+//   kgrad_forms_kernel   sum_ij U_ic W_jc dA_ij/dtheta_d for the data column and for the sum over the probe columns, in one sweep over the
+//                        generated matrix on kmatvec_kernel's tiling: the MFMA forms S_ij = sum_c U_ic W_jc, the lane that holds S_ij
+//                        generates sigma2 k'(r2_ij) and adds per dimension; one partial per workgroup, added in ascending order
 // Every launch is a plain grid that ends by itself: nothing here waits on another workgroup.
 #include <algorithm>
 #include <climits>
@@ -331,7 +335,7 @@ __global__ __launch_bounds__(256) void cg_dot_kernel(const double* __restrict__ 
 
 // sc: bb | rz | alpha | beta | out, ITER_COLS each; fl: frozen | converged | iterations
 __global__ __launch_bounds__(64) void cg_scalars_kernel(int mode, const double* __restrict__ part, int nblk, double* __restrict__ sc,
-                                                        int* __restrict__ fl, int it, double rtol) {
+                                                        int* __restrict__ fl, int it, double rtol, double* __restrict__ lg) {
   const int c = threadIdx.x;
   if (c >= ITER_COLS) return;
   double s = 0.0;
@@ -352,6 +356,7 @@ __global__ __launch_bounds__(64) void cg_scalars_kernel(int mode, const double* 
     if (mode == 2) {
       if (good) {
         alpha[c] = rz[c] / s;
+        if (lg) lg[(size_t)(2 * it) * ITER_COLS + c] = alpha[c];
       } else {
         frozen[c] = 1;
         conv[c] = 0;
@@ -366,6 +371,7 @@ __global__ __launch_bounds__(64) void cg_scalars_kernel(int mode, const double* 
     } else {
       beta[c] = s / rz[c];
       rz[c] = s;
+      if (lg) lg[(size_t)(2 * it + 1) * ITER_COLS + c] = beta[c];
     }
   }
 }
@@ -414,6 +420,135 @@ __global__ __launch_bounds__(256) void panel_add_kernel(double* __restrict__ x, 
   if (i >= N) return;
   const size_t o = (size_t)blockIdx.y * N + i;
   x[o] = x[o] + xl[o];
+}
+
+// ---- the exact likelihood: probes and the forms of the derivative matrices ---------------------------------------------------------------------
+// column c_lo + blockIdx.y of the panel Z, one row per thread: the normals g2 it holds become L g1 + root g2
+__global__ __launch_bounds__(256) void probe_kernel(const double* __restrict__ L, int N, int p, const double* __restrict__ g1, double root, int c_lo,
+                                                    double* __restrict__ Z) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= N) return;
+  const int c = c_lo + blockIdx.y;
+  const size_t ld = (size_t)N;
+  double acc = 0.0;
+  for (int s = 0; s < p; ++s) acc = __builtin_fma(L[(size_t)s * ld + i], g1[s * ITER_COLS + c], acc);
+  Z[(size_t)c * ld + i] = __builtin_fma(root, Z[(size_t)c * ld + i], acc);
+}
+
+constexpr int KG_LDP = ITER_COLS + 1;   // odd row stride of the staged panel rows
+
+// Workgroup (x, y): rows [64 x, 64 x + 64), dimensions [KGRAD_DC y, KGRAD_DC y + KGRAD_DC).  A wave owns 16 rows; per tile of 64 columns and
+// block g of 16 of them the wave forms S (16 x 16) = sum over the probe columns of U_ic W_jc by MFMA (operands: row / column lane & 15,
+// panel column 4 s + (lane >> 4); the lane then holds S of rows (lane >> 4) + 4 reg and column lane & 15), generates r2 of its four entries over
+// ALL dimensions and sigma2 k', and adds (S sigma2 k') (x~_id - x~_jd)^2 -- and the same with the data pair's U_i0 W_j0, one plain product,
+// in place of S -- into the accumulators of its slice of dimensions.  A slice repeats the generation: KGRAD_DC accumulator pairs are
+// what a lane holds in registers.  The sum of one output runs over tiles, blocks and reg in one fixed order whatever the slice, then over the
+// lanes by a fixed shuffle tree, the waves and (kgrad_reduce_kernel) the workgroups in ascending order.  Rows and columns >= N enter with
+// zero panel rows, the diagonal with a zero difference.
+// LDS: tab (256) | sa (D x 64) | sb (D x 64) | su (64 x 33) | sw (64 x 33) | su0 (64) | sw0 (64) | red (4 x 2 KGRAD_DC)
+template <int KT>
+__global__ __launch_bounds__(256) void kgrad_forms_kernel(const double* __restrict__ Xs, int N, int D, double sigma2, const double* __restrict__ U,
+                                                          const double* __restrict__ W, size_t ld, int c_lo, int c_hi, double* __restrict__ part) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  double* tab = sm;
+  double* sa = tab + 256;
+  double* sb = sa + (size_t)KM_ROWS * D;
+  double* su = sb + (size_t)KM_ROWS * D;
+  double* sw = su + KM_ROWS * KG_LDP;
+  double* su0 = sw + KM_ROWS * KG_LDP;
+  double* sw0 = su0 + KM_ROWS;
+  double* red = sw0 + KM_ROWS;
+  const int t = threadIdx.x, lane = t & 63;
+  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int i0 = blockIdx.x * KM_ROWS, d0 = blockIdx.y * KGRAD_DC;
+  const int jq = lane >> 4, cl = lane & 15;
+  const int s_lo = c_lo >> 2, s_hi = (c_hi + 3) >> 2;        // the MFMA steps that hold a probe column (the others would add exact zeros)
+  stage_exp_tab(tab);
+  stage_rows(Xs, N, D, i0, sa);
+  for (int e = t; e < KM_ROWS * ITER_COLS; e += 256) {
+    const int i = e & 63, c = e >> 6;
+    su[i * KG_LDP + c] = (c >= c_lo && c < c_hi && i0 + i < N) ? U[(size_t)c * ld + (size_t)(i0 + i)] : 0.0;
+  }
+  if (t < KM_ROWS) su0[t] = (i0 + t < N) ? U[(size_t)(i0 + t)] : 0.0;
+  double accp[KGRAD_DC], accd[KGRAD_DC];
+#pragma unroll
+  for (int dd = 0; dd < KGRAD_DC; ++dd) accp[dd] = accd[dd] = 0.0;
+  for (int j0 = 0; j0 < N; j0 += KM_ROWS) {
+    __syncthreads();                                         // the previous tile has been read (first pass: nothing to wait for)
+    stage_rows(Xs, N, D, j0, sb);
+    for (int e = t; e < KM_ROWS * ITER_COLS; e += 256) {
+      const int j = e & 63, c = e >> 6;
+      sw[j * KG_LDP + c] = (c >= c_lo && c < c_hi && j0 + j < N) ? W[(size_t)c * ld + (size_t)(j0 + j)] : 0.0;
+    }
+    if (t < KM_ROWS) sw0[t] = (j0 + t < N) ? W[(size_t)(j0 + t)] : 0.0;
+    __syncthreads();
+#pragma unroll 1
+    for (int g = 0; g < 4; ++g) {
+      const int jl = g * 16 + cl;
+      v4d S = v4d{0.0, 0.0, 0.0, 0.0};
+      for (int s = s_lo; s < s_hi; ++s)
+        S = __builtin_amdgcn_mfma_f64_16x16x4f64(su[(w * 16 + cl) * KG_LDP + 4 * s + jq], sw[jl * KG_LDP + 4 * s + jq], S, 0, 0, 0);
+      double r2[4] = {0.0, 0.0, 0.0, 0.0};
+      for (int d = 0; d < D; ++d) {
+        const double b = sb[d * 64 + jl];
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+          const double df = sa[d * 64 + w * 16 + jq + 4 * reg] - b;
+          r2[reg] = __builtin_fma(df, df, r2[reg]);
+        }
+      }
+      const double w0 = sw0[jl];
+      double cp[4], cd[4];
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const double kd = sigma2 * kern_dr2<KT>(r2[reg], tab);
+        cp[reg] = S[reg] * kd;
+        cd[reg] = (su0[w * 16 + jq + 4 * reg] * w0) * kd;
+      }
+#pragma unroll
+      for (int dd = 0; dd < KGRAD_DC; ++dd) {
+        const int d = d0 + dd;
+        if (d < D) {
+          const double b = sb[d * 64 + jl];
+#pragma unroll
+          for (int reg = 0; reg < 4; ++reg) {
+            const double df = sa[d * 64 + w * 16 + jq + 4 * reg] - b;
+            const double q = df * df;
+            accp[dd] = __builtin_fma(cp[reg], q, accp[dd]);
+            accd[dd] = __builtin_fma(cd[reg], q, accd[dd]);
+          }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int dd = 0; dd < KGRAD_DC; ++dd) {
+    double a = accd[dd], b = accp[dd];
+    for (int off = 32; off > 0; off >>= 1) {
+      a += __shfl_down(a, off, 64);
+      b += __shfl_down(b, off, 64);
+    }
+    if (lane == 0) {
+      red[w * 2 * KGRAD_DC + dd] = a;
+      red[w * 2 * KGRAD_DC + KGRAD_DC + dd] = b;
+    }
+  }
+  __syncthreads();
+  if (t < 2 * KGRAD_DC) {
+    const int grp = t / KGRAD_DC, d = d0 + (t - grp * KGRAD_DC);
+    double s = red[t];
+    for (int v = 1; v < 4; ++v) s += red[v * 2 * KGRAD_DC + t];
+    if (d < D) part[((size_t)blockIdx.x * 2 + grp) * D + d] = s;
+  }
+}
+
+// out[e] = the partials of the workgroups in ascending order; part (nblk, n)
+__global__ __launch_bounds__(256) void kgrad_reduce_kernel(const double* __restrict__ part, int nblk, int n, double* __restrict__ out) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= n) return;
+  double s = 0.0;
+  for (int b = 0; b < nblk; ++b) s += part[(size_t)b * n + e];
+  out[e] = s;
 }
 
 inline unsigned blocks_of(long n, int per) { return (unsigned)((n + per - 1) / per); }
@@ -469,8 +604,26 @@ void launch_cg_dot(const double* A, const double* B, long N, double* part, hipSt
   hipLaunchKernelGGL(cg_dot_kernel, dim3(blocks_of(N, ITER_DOT_BLOCK), ITER_COLS), dim3(256), 0, st, A, B, (int)N, part);
 }
 
-void launch_cg_scalars(int mode, const double* part, long N, double* sc, int* fl, int it, double rtol, hipStream_t st) {
-  hipLaunchKernelGGL(cg_scalars_kernel, dim3(1), dim3(64), 0, st, mode, part, (int)blocks_of(N, ITER_DOT_BLOCK), sc, fl, it, rtol);
+void launch_cg_scalars(int mode, const double* part, long N, double* sc, int* fl, int it, double rtol, hipStream_t st, double* lg) {
+  hipLaunchKernelGGL(cg_scalars_kernel, dim3(1), dim3(64), 0, st, mode, part, (int)blocks_of(N, ITER_DOT_BLOCK), sc, fl, it, rtol, lg);
+}
+
+void launch_probes(const double* L, long N, int p, const double* g1, double root, int c_lo, int c_hi, double* Z, hipStream_t st) {
+  if (c_hi <= c_lo) return;
+  hipLaunchKernelGGL(probe_kernel, dim3(blocks_of(N, 256), c_hi - c_lo), dim3(256), 0, st, L, (int)N, p, g1, root, c_lo, Z);
+}
+
+void launch_kgrad_forms(const double* Xs, long N, int D, int kt, double sigma2, const double* U, const double* W, int c_lo, int c_hi, double* part,
+                        double* out, hipStream_t st) {
+  const unsigned nblk = blocks_of(N, KM_ROWS), nch = blocks_of(D, KGRAD_DC);
+  const size_t lds = sizeof(double) * (256 + (size_t)2 * KM_ROWS * D + 2 * KM_ROWS * KG_LDP + 2 * KM_ROWS + 4 * 2 * KGRAD_DC);
+  prof_begin("kgrad_forms", st);
+  hipLaunchKernelGGL(kt == 0 ? kgrad_forms_kernel<0> : kgrad_forms_kernel<1>, dim3(nblk, nch), dim3(256), lds, st, Xs, (int)N, D, sigma2, U, W,
+                     (size_t)N, c_lo, c_hi, part);
+  hipLaunchKernelGGL(kgrad_reduce_kernel, dim3(blocks_of(2 * D, 256)), dim3(256), 0, st, part, (int)nblk, 2 * D, out);
+  // algorithmic: a slice of KGRAD_DC dimensions generates r2 (3 D) and k' (~20) again; 2 per probe column for S, 6 per dimension and entry
+  prof_end("kgrad_forms", st, (double)N * (double)N * (nch * (3.0 * D + 20.0 + 2.0 * (c_hi - c_lo)) + 6.0 * D),
+           8.0 * (double)nblk * (double)N * nch * (D + 32.0));
 }
 
 void launch_cg_update(double* x, double* xl, double* r, const double* p, const double* q, long N, const double* sc, const int* fl, hipStream_t st) {

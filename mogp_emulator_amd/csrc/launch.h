@@ -375,13 +375,28 @@ void launch_precond_apply(const double* L, long N, int p, const double* Ginv, do
 //   mode 4  s = r^T z: beta = s / rz, rz = s                                        mode 5  out = s
 // Modes 2 .. 4 leave a frozen column alone.
 void launch_cg_dot(const double* A, const double* B, long N, double* part, hipStream_t st);
-void launch_cg_scalars(int mode, const double* part, long N, double* sc, int* fl, int it, double rtol, hipStream_t st);
+// lg (or null): the coefficient log of the exact likelihood, lg[(2 it + 0) * ITER_COLS + c] = alpha of iteration it (mode 2) and
+// lg[(2 it + 1) * ITER_COLS + c] = beta (mode 4), stored for the columns that are live at that point; no other result depends on it.
+void launch_cg_scalars(int mode, const double* part, long N, double* sc, int* fl, int it, double rtol, hipStream_t st, double* lg = nullptr);
 // x += alpha p with the roundings of that sum collected in xl (x + xl is the iterate), r -= alpha q;  p = z + beta p (first: p = z);
 // out = a - b;  x += xl: panels of ITER_COLS columns (ld N).  The two updates leave frozen columns untouched.
 void launch_cg_update(double* x, double* xl, double* r, const double* p, const double* q, long N, const double* sc, const int* fl, hipStream_t st);
 void launch_panel_add(double* x, const double* xl, long N, hipStream_t st);
 void launch_cg_direction(double* p, const double* z, long N, bool first, const double* sc, const int* fl, hipStream_t st);
 void launch_panel_sub(const double* a, const double* b, long N, double* out, hipStream_t st);
+// The probes of the exact likelihood, in place on a panel (ld N): Z[c][i] = sum_s L[s][i] g1[s * ITER_COLS + c] (ascending s, FMAs)
+// + root * Z[c][i] for the columns c_lo <= c < c_hi, which hold the normals g2 on entry.  g1: p * ITER_COLS doubles.
+void launch_probes(const double* L, long N, int p, const double* g1, double root, int c_lo, int c_hi, double* Z, hipStream_t st);
+// The bilinear forms of the derivative matrices dA/dtheta_d = sigma2 k'(r2_ij) (x~_id - x~_jd)^2 in one sweep over the generated matrix:
+//   out[d]     = sum_ij U[0][i] W[0][j] dA_ij/dtheta_d                               (the data pair: column 0 of the panels alone)
+//   out[D + d] = sum over the columns c_lo <= c < c_hi (1 <= c_lo, c_hi <= ITER_COLS) of sum_ij U[c][i] W[c][j] dA_ij/dtheta_d
+// U, W: panels of ITER_COLS columns (ld N).  A workgroup owns 64 rows and KGRAD_DC dimensions, forms S_ij = sum_c U_ic W_jc of a 16 x 16
+// block with v_mfma_f64_16x16x4_f64, generates r2 and k' in the lane that holds S_ij and adds in a fixed order; part: ceil(N / 64) * 2 * D
+// doubles, one partial per workgroup and output, added in ascending order by a second kernel.  No atomics; no bit of out[0 .. D) depends on
+// the probe columns, and none of out on KGRAD_DC.
+constexpr int KGRAD_DC = 16;
+void launch_kgrad_forms(const double* Xs, long N, int D, int kt, double sigma2, const double* U, const double* W, int c_lo, int c_hi, double* part,
+                        double* out, hipStream_t st);
 
 // --- utilities -------------------------------------------------------------------------------
 // out (n,n) <- tile of src (NP,NP): mode 0 copy, mode 1 transpose of the lower triangle (zeros below the diagonal of out), mode 2 symmetrise from lower

@@ -408,6 +408,23 @@ inline void iter_check_memory(const std::string& who, long N, int rank, double f
     throw std::runtime_error(who + ": " + std::to_string((long long)need) + " bytes of device memory for " + std::to_string(N) +
                              " points at preconditioner rank " + std::to_string(rank) + " are more than half of the free device memory");
 }
+// The exact likelihood (engine_iter_lik.hip) holds, beside iter_held_bytes: one further panel (the first preconditioned residuals), the
+// coefficient log (2 ITER_PLAN_COLS max_iter), the normals g1 (rank x ITER_PLAN_COLS) and the partial sums and results of the sweep
+// ((ceil(N / 64) + ITER_PLAN_COLS) 2 D).  1 <= T <= ITER_PLAN_COLS - 1 probes: one panel with the data column.
+inline double iter_lik_bytes(long N, int D, int rank, int max_iter) {
+  const double n = (double)N;
+  return 8.0 * (ITER_PLAN_COLS * n + 2.0 * ITER_PLAN_COLS * (double)max_iter + (double)ITER_PLAN_COLS * std::max(rank, 1) +
+                (std::ceil(n / 64.0) + ITER_PLAN_COLS) * 2.0 * D);
+}
+inline void iter_lik_check_probes(const std::string& who, int T) {
+  if (T < 1 || T > ITER_PLAN_COLS - 1) throw std::runtime_error(who + ": n_probes must be between 1 and " + std::to_string(ITER_PLAN_COLS - 1));
+}
+inline void iter_lik_check_memory(const std::string& who, long N, int D, int rank, int max_iter, double free_bytes, double already_held) {
+  const double need = iter_lik_bytes(N, D, rank, max_iter);
+  if (need > 0.5 * (free_bytes + already_held))
+    throw std::runtime_error(who + ": " + std::to_string((long long)need) + " bytes of device memory for the probe panel and the coefficient log of " +
+                             std::to_string(N) + " points and " + std::to_string(max_iter) + " iterations are more than half of the free device memory");
+}
 struct IterPlan {
   long points;      // queries per pass
   long blocks;      // solves of ITER_PLAN_COLS cross columns per pass (with the variance)

@@ -1453,6 +1453,28 @@ class LocalGP_GPU(object):
         vstats = (vst[:, 0].astype(np.int64), vst[:, 1].astype(bool), vres) if want else None
         return mean, var, (int(st[0]), bool(st[1]), float(res[0])), vstats, alpha
 
+    def loglik_exact(self, emulator, kern, scale, sigma2, nugget, rank, rtol, max_iter, g1, g2, grad=False, probe_terms=False,
+                     return_panels=False):
+        """The pieces of the exact log-likelihood (``mogp_local_loglik_exact``) as a dict: ``y_alpha``, ``alpha_alpha``, ``logdet_g``,
+        ``rank``, per column (the data column first) ``iterations``, ``converged``, ``residual``, per probe ``rho`` and ``uw``, ``coef``
+        (max_iter, 2, 1 + T), ``forms_data`` / ``forms_probe`` (D,) with ``grad``, ``forms_each`` (T, D) with ``probe_terms``, and ``z`` (N, T),
+        ``x`` = [alpha | u_t] and ``w`` = [alpha | w_t] (N, 1 + T) with ``return_panels``.  g1 (rank reached, T), g2 (N, T)."""
+        if not self._h:
+            raise RuntimeError("loglik_exact: the handle has been closed")
+        scale, g1, g2 = _f64(scale, 1, "scale"), _f64(g1, 2, "g1"), _f64(g2, 2, "g2")
+        T, C, D = g2.shape[1], g2.shape[1] + 1, self.D
+        sc, st, res = np.zeros(4), np.zeros((C, 2), dtype=np.int32), np.zeros(C)
+        rho, uw, coef = np.zeros(T), np.zeros(T), np.zeros((int(max_iter), 2, C))
+        forms = np.zeros(2 * D) if grad else None
+        each = np.zeros((T, D)) if grad and probe_terms else None
+        z, x, w = (np.zeros((self.N, T)), np.zeros((self.N, C)), np.zeros((self.N, C))) if return_panels else (None, None, None)
+        check(_lib.mogp_local_loglik_exact(self._h, int(emulator), int(kern), dptr(scale), float(sigma2), float(nugget), int(rank), float(rtol),
+                                           int(max_iter), dptr(g1) if g1.size else None, g1.shape[0], dptr(g2), T, int(bool(grad)), dptr(sc),
+                                           iptr(st), dptr(res), dptr(rho), dptr(uw), dptr(coef), dptr(forms), dptr(each), dptr(z), dptr(x), dptr(w)))
+        return dict(y_alpha=float(sc[0]), alpha_alpha=float(sc[1]), logdet_g=float(sc[2]), rank=int(sc[3]), iterations=st[:, 0].astype(np.int64),
+                    converged=st[:, 1].astype(bool), residual=res, rho=rho, uw=uw, coef=coef, forms_data=None if forms is None else forms[:D],
+                    forms_probe=None if forms is None else forms[D:], forms_each=each, z=z, x=x, w=w)
+
 
 # --------------------------------------------------------------------------------------
 # stand-alone kernel objects (bindings.cu:340-361; flat layouts of kernel.hpp:47-107), evaluated on the
