@@ -530,6 +530,20 @@ int mogp_local_loglik_exact(mogp_local* h, int emulator, int kernel_type, const 
                             int max_iter, const double* g1, int g1_rows, const double* g2, int n_probes, int want_grad, double* scalars_out,
                             int* stat_out, double* residual_out, double* rho_out, double* uw_out, double* coef_out, double* forms_out,
                             double* forms_each_out, double* z_out, double* x_out, double* w_out);
+/* A conservative bound of the predictive variance at the price of one rectangular product per batch of queries, with no solve:
+     var_out (m) = max(sigma2 + (include_nugget ? nugget : 0) - |R^T k*|^2, 0) >= the exact predictive variance,
+   R (N, r) with span R = span L (L the factor of mogp_local_precondition at precond_rank >= 1, built when it is not the one held) and
+   R^T A R = I: R R^T is the Galerkin inverse of A on that subspace, and Q (Q^T A Q)^-1 Q^T never exceeds A^-1.  The bound tightens as
+   the rank grows and is the exact variance at rank N.  R is built once per (hyperparameters, precond_rank) and kept on the handle, from two
+   prefix Cholesky factorisations in natural column order (L^T L, stopped where the columns of L become dependent to 1e-10 of the first, then
+   Q^T A Q): its rank may lie below the rank the preconditioner reached, and its leading r' columns are the cache of rank r'.
+   var_rank_request: 0 for all of them, else 1 .. the rank the preconditioner reached (another value is refused); var_rank_out (1) = the
+   columns that entered, min(request, rank of the cache).  R_out (N, precond_rank) row-major or NULL: the cache, zero behind its rank.
+   m = 0: the cache alone.  No atomics: the same bits for a repeated call, whatever max_points (queries per pass, 0 = sized by the free
+   device memory) and whatever the other queries; for r1 < r2 the bound at r2 never exceeds the bound at r1. */
+int mogp_local_variance_bound(mogp_local* h, int kernel_type, const double* scale, double sigma2, double nugget, int precond_rank,
+                              int var_rank_request, int include_nugget, const double* testing, int m, int D, int max_points, double* var_out,
+                              int* var_rank_out, double* R_out);
 void mogp_local_destroy(mogp_local* h);
 /* device memory helpers so a host program can hand device-resident buffers to the *_dev calls */
 void* mogp_dev_malloc(unsigned long long bytes);

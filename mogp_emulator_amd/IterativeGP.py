@@ -6,6 +6,7 @@ design, matrix-free and preconditioned (Gardner et al. 2018; Wang et al. 2019).
     A = sigma^2 k(r2(x_i s, x_j s)) + nugget I            N x N, never stored: its entries are generated as they are multiplied
     alpha = A^-1 (y - m(X))                               preconditioned CG, P = L L^T + nugget I, L a rank-p pivoted Cholesky factor
     mean = m(q) + k*^T alpha,    unc = max(sigma^2 - k*^T A^-1 k* + nugget, 0)
+    bound = max(sigma^2 - |R^T k*|^2 + nugget, 0) >= unc  R (N, r), span R = span L, R^T A R = I: no solve, one product with the generated k*
 
 ``LocalGP`` answers from at most 126 neighbours of a query; this class gives what the dense ``predict`` would give at the same
 hyperparameters -- the posterior of all N points -- at the price of one product with A (N^2 generated entries) per iteration.  The
@@ -29,7 +30,15 @@ The exact log-likelihood at those hyperparameters and its gradient come from ONE
 for all probes together; those of log sigma^2 (dA = A - nugget I) and log nugget (dA = nugget I) are dots.  With ``precond_rank=0`` the
 solver's preconditioner is the identity: P = I and z_t = g2_t.  The estimate is a deterministic function of (theta, probes).
 
-Not covered: cheap approximate variances (every variance is a solve), more than 31 probes per evaluation (average over seeds), derivatives
+An exact variance is one solve per query.  ``variance_bound`` (``predict(unc="bound")``) gives, at the price of the mean, a variance that is
+never below the exact one: for any full-column-rank Q the Galerkin inverse Q (Q^T A Q)^-1 Q^T never exceeds A^-1, and with span Q = span L
+-- the factor the handle holds already -- it is R R^T for a cache R that is built once per (hyperparameters, rank): G0 = L^T L,
+a prefix Cholesky of it in natural column order (stopped where L's columns become dependent), Q = L C0^-T, H = Q^T A Q by ``rank / 32``
+products with A, a prefix Cholesky of H, R = Q C^-T.  Both factors are prefixes, so the leading r columns of R are the cache of rank r:
+the bound tightens monotonically with the rank, bit for bit, and is the exact variance at rank N.  How far it lies above the exact variance
+depends on the design, the kernel and the rank; ``variance_gap`` measures it on the caller's own queries.
+
+Not covered: bounds of cross-covariances, a lower bound, more than 31 probes per evaluation (average over seeds), derivatives
 with respect to mean-function parameters, the symmetry of A in the product, several devices per handle, ``ProductMat52``,
 ``analytic_mean=True``, ``nugget="pivot"``.
 """
@@ -40,6 +49,8 @@ from .LocalGP import MAX_D, _KERNELS, _create_native, _emulator_type, _fit_state
 MAX_RANK = 1024
 MAX_PROBES = 31          # the data column and the probes share one panel of 32 columns
 _PROBE_STREAM = 0x10c    # the Philox stream of the default probes (g1 from it, g2 from the next)
+VAR_CHUNK = 64           # columns of the variance cache per workgroup of the bound's kernel (csrc/predict_plan.h ITER_VAR_CHUNK)
+_NEEDS_FACTOR = "%s: the variance bound is built from the preconditioner's factor: precond_rank must be at least 1"
 
 
 class IterativeSolve(object):
@@ -56,11 +67,14 @@ class IterativePrediction(object):
 
     * ``mean``, ``unc``                 predictive mean and variance; ``unc`` is None with ``unc=False``
     * ``converged``, ``residual``, ``iterations``   of the solve for the weights alpha (scalars, or (E,))
-    * ``var_converged``, ``var_residual``           per query, of the solve behind its variance; None with ``unc=False``"""
+    * ``var_converged``, ``var_residual``           per query, of the solve behind its variance; None with ``unc=False`` and ``unc="bound"``
+    * ``unc_kind``                      None, "exact" or "bound": what ``unc`` holds
+    * ``var_rank``                      with ``unc="bound"``: the columns of the variance cache that entered (a scalar, or (E,)); else None"""
 
-    def __init__(self, mean, unc, converged, residual, iterations, var_converged, var_residual):
+    def __init__(self, mean, unc, converged, residual, iterations, var_converged, var_residual, var_rank=None, unc_kind=None):
         self.mean, self.unc, self.converged, self.residual, self.iterations = mean, unc, converged, residual, iterations
         self.var_converged, self.var_residual = var_converged, var_residual
+        self.var_rank, self.unc_kind = var_rank, ("exact" if unc is not None else None) if unc_kind is None else unc_kind
 
 
 class ExactLogLik(object):
@@ -241,6 +255,7 @@ class IterativeGP(object):
         self._layout = list(layout) if layout is not None else [(False, True)] * len(self._hyper)
         return self
 
+    VAR_CHUNK = VAR_CHUNK              # ranks on both sides of a multiple of it take one more workgroup column in ``variance_bound``
     n = property(lambda self: self._N)
     D = property(lambda self: self._D)
     n_emulators = property(lambda self: self._E)
@@ -331,11 +346,21 @@ class IterativeGP(object):
     def predict(self, testing, unc=False, include_nugget=True, max_points=0):
         """Predict at ``testing`` (m, D) from the whole design; returns an ``IterativePrediction``.
 
-        ``unc=True`` solves one system per query (in blocks of 32): exact, and as expensive as that sounds.  ``include_nugget``: add the
+        ``unc=True`` solves one system per query (in blocks of 32): exact, and as expensive as that sounds.  ``unc="bound"`` puts
+        ``variance_bound(testing)`` there instead, bit for bit -- never below the exact variance, no solve; ``var_converged`` and
+        ``var_residual`` are then None, ``var_rank`` tells the columns of the cache and ``unc_kind`` is "bound".  Any other string is a
+        ``ValueError``.  The mean is the same bits whatever ``unc``.  ``include_nugget``: add the
         nugget to ``unc`` as ``predict`` of the emulator does.  ``max_points`` caps the queries per device pass (0: sized by the free device
         memory) and changes no bit of the result.  Emulator e of a ``MultiOutputGP_GPU`` uses its own hyperparameters and its own
         preconditioner; the emulators run one after another on the same handle, and row e equals the single-emulator call bit for bit."""
         who = "IterativeGP.predict"
+        if isinstance(unc, str):
+            if unc != "bound":
+                raise ValueError('%s: unc must be False, True or "bound"' % who)
+            if self._p == 0:
+                raise ValueError(_NEEDS_FACTOR % who)
+        bound = isinstance(unc, str)
+        exact = bool(unc) and not bound
         testing = _points("testing", who, testing, self._D)
         if int(max_points) != max_points or int(max_points) < 0:
             raise ValueError("%s: max_points must not be negative" % who)
@@ -346,11 +371,64 @@ class IterativeGP(object):
         rows = []
         for e, (kt, s, sigma2, nugget, meanfunc, mparams) in enumerate(self._hyper):
             mean, var, (it, cv, res), vstats, _ = self._native.predict_exact(e, kt, s, sigma2, nugget, self._p, self._rtol, self._max_iter,
-                                                                             include_nugget, testing, unc=bool(unc), max_points=int(max_points))
+                                                                             include_nugget, testing, unc=exact, max_points=int(max_points))
             mean += _mean_at(meanfunc, mparams, testing)
-            rows.append((mean, var, cv, res, it, vstats[1] if unc else None, vstats[2] if unc else None))
+            vr = None
+            if bound:
+                var, vr, _ = self._native.variance_bound(kt, s, sigma2, nugget, self._p, include_nugget, testing, max_points=int(max_points))
+            rows.append((mean, var, cv, res, it, vstats[1] if exact else None, vstats[2] if exact else None, vr))
+        kind = "bound" if bound else "exact" if exact else None
         if self._single:
-            return IterativePrediction(*rows[0])
+            return IterativePrediction(*rows[0], unc_kind=kind)
         cols = list(zip(*rows))
         return IterativePrediction(np.stack(cols[0]), np.stack(cols[1]) if unc else None, np.array(cols[2]), np.array(cols[3]), np.array(cols[4]),
-                                   np.stack(cols[5]) if unc else None, np.stack(cols[6]) if unc else None)
+                                   np.stack(cols[5]) if exact else None, np.stack(cols[6]) if exact else None,
+                                   np.array(cols[7]) if bound else None, kind)
+
+    # ---- the variance bound -----------------------------------------------------------------------------------------------------------------
+    def variance_bound(self, testing, emulator=0, include_nugget=True, rank=None, max_points=0):
+        """(m,) max(sigma^2 [+ nugget] - |R^T k*|^2, 0) at ``testing`` (m, D): never below the exact predictive variance of ``emulator``, and
+        no solve -- one product of the generated cross covariance with the cache R (built at the first call and kept while the
+        hyperparameters and ``precond_rank`` stay; ``variance_cache``).  ``rank`` (default: all of the cache) 1 .. the rank the
+        preconditioner reached: the bound of that many leading columns, which is the bound a handle of that ``precond_rank`` gives (to
+        rounding); a larger rank never gives a larger value, bit for bit.  A value depends on its query alone, not on ``max_points``
+        (queries per device pass, 0: sized by the free device memory) nor on the other queries.  Needs ``precond_rank`` >= 1."""
+        who = "IterativeGP.variance_bound"
+        r = self._bound_rank(who, rank)
+        testing = _points("testing", who, testing, self._D)
+        if int(max_points) != max_points or int(max_points) < 0:
+            raise ValueError("%s: max_points must not be negative" % who)
+        if testing.shape[0] >= 2 ** 31:
+            raise ValueError("%s: at most 2^31 - 1 testing points per call" % who)
+        e, (kt, s, sigma2, nugget, _, _) = self._emulator(who, emulator)
+        return self._native.variance_bound(kt, s, sigma2, nugget, self._p, include_nugget, testing, var_rank=r, max_points=int(max_points))[0]
+
+    def variance_cache(self, emulator=0):
+        """(R (N, var_rank), var_rank) of ``emulator``: R^T A R = I and span R = span of the leading columns of ``preconditioner()[0]``.
+        ``var_rank`` lies below the rank the preconditioner reached when the trailing columns of L are linearly dependent to rounding."""
+        who = "IterativeGP.variance_cache"
+        self._bound_rank(who, None)
+        e, (kt, s, sigma2, nugget, _, _) = self._emulator(who, emulator)
+        _, r, R = self._native.variance_bound(kt, s, sigma2, nugget, self._p, True, None, return_cache=True)
+        return R, r
+
+    def variance_gap(self, testing, emulator=0):
+        """(m,) bound - exact variance at ``testing``, from one exact pass (a solve per query: meant for a few queries), both with the
+        nugget: how much the bound gives away here.  Negative entries are rounding, or a variance solve that did not converge."""
+        who = "IterativeGP.variance_gap"
+        self._bound_rank(who, None)
+        testing = _points("testing", who, testing, self._D)
+        e, (kt, s, sigma2, nugget, _, _) = self._emulator(who, emulator)
+        exact = self._native.predict_exact(e, kt, s, sigma2, nugget, self._p, self._rtol, self._max_iter, True, testing, unc=True)[1]
+        return self._native.variance_bound(kt, s, sigma2, nugget, self._p, True, testing)[0] - exact
+
+    def _bound_rank(self, who, rank):
+        """the ``var_rank`` request of the native call: 0 for all; every refusal that needs no device"""
+        if self._p == 0:
+            raise ValueError(_NEEDS_FACTOR % who)
+        if rank is None:
+            return 0
+        r = int(rank)
+        if r != rank or r < 1 or r > self._p:
+            raise ValueError("%s: rank must be between 1 and precond_rank = %d" % (who, self._p))
+        return r

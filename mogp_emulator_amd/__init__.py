@@ -23,7 +23,8 @@ mogp_emulator_amd -- MI355X (gfx950) native fit + predict backend for mogp_emula
   LocalGP.py       local approximate GP prediction for designs beyond the dense path: k nearest neighbours and one small GP per query, on the device
   Vecchia.py       hyperparameters from the whole of a large design: the Vecchia likelihood and its analytic gradient on the device, L-BFGS fit
   IterativeGP.py   exact prediction for designs beyond the dense path: matrix-free preconditioned conjugate gradients on the whole design, on the device;
-                   the exact log-likelihood and its gradient by stochastic Lanczos quadrature from one such solve
+                   the exact log-likelihood and its gradient by stochastic Lanczos quadrature from one such solve; variance_bound: a
+                   conservative predictive variance from a cached low-rank factor, one product per batch of queries and no solve
   dist.py          one-process-per-GPU sharding of emulators + single gather (torch.distributed/RCCL)
 """
 from .LibGPGPU import HAVE_LIBGPGPU, gpu_usable            # noqa: F401

@@ -96,6 +96,17 @@ int mogp_local_loglik_exact(mogp_local* h, int emulator, int kernel_type, const 
   });
 }
 
+int mogp_local_variance_bound(mogp_local* h, int kernel_type, const double* scale, double sigma2, double nugget, int precond_rank,
+                              int var_rank_request, int include_nugget, const double* testing, int m, int D, int max_points, double* var_out,
+                              int* var_rank_out, double* R_out) {
+  return guarded([&] {
+    if (!h || !h->gp) throw std::runtime_error("variance_bound: null handle");
+    if (m > 0 && D != h->gp->D) throw std::runtime_error("variance_bound: testing points must have D columns");
+    h->gp->variance_bound(kernel_type, scale, sigma2, nugget, precond_rank, var_rank_request, include_nugget != 0, testing, m, max_points, var_out,
+                          var_rank_out, R_out);
+  });
+}
+
 void mogp_local_destroy(mogp_local* h) {
   if (!h) return;
   (void)guarded([&] {

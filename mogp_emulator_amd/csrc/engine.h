@@ -350,6 +350,13 @@ class LocalGP {
   void loglik_exact(int e, int kt, const double* scale, double sigma2, double nugget, int rank, double rtol, int max_iter, const double* g1,
                     int g1_rows, const double* g2, int T, bool want_grad, double* scalars, int* stat_i, double* residual, double* rho, double* uw,
                     double* coef, double* forms, double* forms_each, double* z_out, double* x_out, double* w_out);
+  // A conservative bound of the predictive variance from the preconditioner's factor (DESIGN.md section 3 "Variance bound"): with R (N, r)
+  // such that R^T A R = I and span R = span L, var (m) = max(sigma2 + (include_nugget ? nugget : 0) - |R^T k*|^2, 0) >= the exact variance,
+  // because R R^T is a Galerkin inverse of A.  R is built once per (hyperparameters, rank) and kept; no solve is involved.  rank >= 1;
+  // var_rank_request: 0 for every column of the cache, else 1 .. the rank the preconditioner reached (the leading columns: R is nested).
+  // *var_rank_out = the columns that entered.  R_out (N, rank) row-major or null: the cache, columns behind its rank zero.  m = 0: the cache alone.
+  void variance_bound(int kt, const double* scale, double sigma2, double nugget, int rank, int var_rank_request, bool include_nugget,
+                      const double* testing, long m, int max_points, double* var, int* var_rank_out, double* R_out);
   int device_id() const { return device; }
   const long N;
   const int D, E;
@@ -376,6 +383,11 @@ class LocalGP {
   // first_z (a panel) receives the first z = P^-1 r of every column, coef_log (2 * 32 * max_iter) the step coefficients; both may be null
   // and change no bit of anything else
   void iter_cg(int cols, double rtol, int max_iter, int* it, int* cv, double* rs, hipStream_t st, double* first_z = nullptr, double* coef_log = nullptr);
+  double iter_held() const;          // the bytes of the buffers of iter_reserve as they are now
+  void iter_var_build(const IterKey& k, hipStream_t st);        // the variance cache of k from the preconditioner held (iter_build(k) first), unless it is the one held
+  IterKey itVarKey;                  // of the variance cache held
+  int itVarRank = 0, itVarReached = 0;      // its rank, and the rank the preconditioner it was built from had reached
+  DevBuf<double> itVR, itVT;         // R (N, the rank in whole panels of 32 columns) and the triangular factor that is being applied
   IterKey itKey;                     // of the preconditioner held (rtol and max_iter unused: 0)
   int itRank = 0;                    // the rank it reached
   double itLogdetG = 0.;             // log|nugget I + L^T L| of it (0 at rank 0)

@@ -4,6 +4,7 @@
 // tests/c/iter_plan_check.cpp), then the launches and the copies.  The iteration is a host loop of plain launches bounded by max_iter; the
 // step scalars and the frozen flags live on the device and the host looks at the flags every ITER_LOOK iterations.
 #include "engine_internal.h"
+#include "iter_var_host.h"
 
 #include <algorithm>
 #include <climits>
@@ -58,13 +59,18 @@ double spd_inverse(std::vector<double>& G, int p) {
 
 }  // namespace
 
-void LocalGP::iter_reserve(const char* who, int rank) {
-  size_t free_b = 0, total_b = 0;
-  HIPCK(hipMemGetInfo(&free_b, &total_b));
-  double held = 0.;                                          // what the handle holds of it already is reused, hence counts as free
+double LocalGP::iter_held() const {
+  double held = 0.;
   for (const DevBuf<double>* b : {&itL, &itG, &itDiag, &itDmax, &itPval, &itB, &itX, &itXl, &itR, &itP, &itQ, &itZ, &itV, &itWpart, &itW, &itW2, &itPart, &itSc})
     held += 8.0 * (double)b->size();
   for (const DevBuf<int>* b : {&itPiv, &itState, &itPidx, &itFl}) held += 4.0 * (double)b->size();
+  return held;
+}
+
+void LocalGP::iter_reserve(const char* who, int rank) {
+  size_t free_b = 0, total_b = 0;
+  HIPCK(hipMemGetInfo(&free_b, &total_b));
+  const double held = iter_held();                           // what the handle holds of it already is reused, hence counts as free
   iter_check_memory(who, N, rank, (double)free_b, held);
   const size_t n = (size_t)N, panel = n * ITER_COLS, p = (size_t)std::max(rank, 1);
   const size_t segs = (n + ITER_SEG - 1) / ITER_SEG, dots = (n + ITER_DOT_BLOCK - 1) / ITER_DOT_BLOCK, blk = (n + 1023) / 1024;
@@ -360,6 +366,119 @@ void LocalGP::predict_exact(int e, int kt, const double* scale, double sigma2, d
         var_stat_r[c0 + b0 + q] = rs[q];
       }
     }
+  }
+}
+
+// The cache of the variance bound: R (N, r) with span R = span L and R^T A R = I, in two orthonormalisations so that no matrix worse
+// conditioned than A is factorised (chol(L^T A L) directly would meet cond(A) cond(L)^2):
+//   G0 = L^T L,  G0[:r0, :r0] = C0 C0^T (a prefix, stopped where L's columns become dependent),  Q = L[:, :r0] C0^-T   (Q^T Q = I)
+//   H = Q^T (A Q) one panel of 32 columns at a time,  H = C C^T (a prefix, stopped at a pivot <= 0),  R = Q[:, :r] C^-T
+// Both triangular factors are prefixes, so R[:, :r'] is the cache of every smaller rank r'.
+void LocalGP::iter_var_build(const IterKey& k, hipStream_t st) {
+  if (k == itVarKey) return;
+  itVarKey = IterKey();
+  itVarRank = 0;
+  const int p = itRank;
+  const int pad = (int)iter_var_pad(std::max(p, 1));
+  int r = 0;
+  if (p > 0) {
+    HIPCK(hipMemsetAsync(itVR, 0, (size_t)N * pad * sizeof(double), st));       // (the product with A reads whole panels of 32 columns)
+    launch_pchol_gram(itL, N, p, 0., itVT, st);
+    HIPCK(hipGetLastError());
+    std::vector<double> G((size_t)p * p), C, T;
+    HIPCK(hipMemcpyAsync(G.data(), itVT, G.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCK(hipStreamSynchronize(st));
+    const int r0 = prefix_cholesky(G.data(), p, ITER_VAR_TAU * G[0], C);
+    if (r0 > 0) {
+      upper_inverse(C.data(), p, r0, T, pad);
+      HIPCK(hipMemcpyAsync(itVT, T.data(), (size_t)r0 * pad * sizeof(double), hipMemcpyHostToDevice, st));
+      for (int c0 = 0; c0 < r0; c0 += ITER_COLS) launch_tri_right(itL, N, r0, itVT, pad, c0, itVR, st);
+      HIPCK(hipGetLastError());
+      std::vector<double> H((size_t)r0 * r0), w((size_t)r0 * ITER_COLS);
+      for (int b0 = 0; b0 < r0; b0 += ITER_COLS) {
+        launch_kmatvec(dXs, N, dXs, N, D, k.kt, k.sigma2, k.nugget, true, itVR.get() + (size_t)b0 * N, N, 2, itQ, N, st);
+        launch_ltv(itVR, N, r0, itQ, itWpart, itW, st);
+        HIPCK(hipGetLastError());
+        HIPCK(hipMemcpyAsync(w.data(), itW, w.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCK(hipStreamSynchronize(st));
+        for (int a = 0; a < r0; ++a)
+          for (int c = 0; c < ITER_COLS && b0 + c < r0; ++c) H[(size_t)a * r0 + b0 + c] = w[(size_t)a * ITER_COLS + c];
+      }
+      for (int a = 0; a < r0; ++a)
+        for (int b = 0; b < a; ++b) H[(size_t)a * r0 + b] = H[(size_t)b * r0 + a] = 0.5 * (H[(size_t)a * r0 + b] + H[(size_t)b * r0 + a]);
+      r = prefix_cholesky(H.data(), r0, 0., C);
+      if (r > 0) {
+        upper_inverse(C.data(), r0, r, T, pad);
+        HIPCK(hipMemcpyAsync(itVT, T.data(), (size_t)r * pad * sizeof(double), hipMemcpyHostToDevice, st));
+        for (int c0 = ((r - 1) / ITER_COLS) * ITER_COLS; c0 >= 0; c0 -= ITER_COLS) launch_tri_right(itVR, N, r, itVT, pad, c0, itVR, st);   // in place: descending
+        HIPCK(hipGetLastError());
+        HIPCK(hipStreamSynchronize(st));                     // (T is a local)
+      }
+    }
+  }
+  itVarRank = r;
+  itVarReached = p;
+  itVarKey = k;
+}
+
+void LocalGP::variance_bound(int kt, const double* scale, double sigma2, double nugget, int rank, int var_rank_request, bool include_nugget,
+                             const double* testing, long m, int max_points, double* var, int* var_rank_out, double* R_out) {
+  const char* who = "variance_bound";
+  if (!scale || !var_rank_out || (m > 0 && (!testing || !var))) throw std::runtime_error("variance_bound: null pointer");
+  local_check_kernel(who, kt);
+  iter_check_hyper(who, D, scale, sigma2, nugget);
+  iter_check_rank(who, N, rank);
+  iter_var_check_precond(who, rank);
+  iter_var_check_rank(who, var_rank_request, rank);
+  if (m < 0 || m > INT_MAX) throw std::runtime_error("variance_bound: the number of testing points must not be negative");
+  DeviceGuard guard(device);
+  hipStream_t st = nullptr;
+  IterKey k;
+  k.kt = kt, k.rank = rank, k.sigma2 = sigma2, k.nugget = nugget;
+  k.scale.assign(scale, scale + D);
+  size_t free_b = 0, total_b = 0;
+  HIPCK(hipMemGetInfo(&free_b, &total_b));
+  iter_var_check_memory(who, N, rank, (double)free_b, iter_held() + 8.0 * ((double)itVR.size() + (double)itVT.size()));
+  iter_reserve(who, rank);
+  const size_t pad = (size_t)iter_var_pad(rank);
+  if (itVR.size() < (size_t)N * pad || itVT.size() < pad * pad) itVarKey = IterKey();      // (the cache is about to be freed)
+  itVR.reserve((size_t)N * pad);
+  itVT.reserve(pad * pad);
+  HIPCK(hipMemGetInfo(&free_b, &total_b));
+  const IterPlan plan = iter_plan(who, std::max<long>(m, 1), D, (double)free_b, max_points);
+  const size_t P = (size_t)plan.points;
+  DevBuf<double> dQ(P * D), dQs(P * D), dPart(P * 16);
+  SyncOnUnwind sync{st};
+  if (k == itVarKey) {
+    ensure_scaled(k.scale.data(), st);                       // the cache stands for itself: the preconditioner held may be another's
+  } else {
+    iter_build(k, st);
+    iter_var_build(k, st);
+  }
+  iter_var_check_rank(who, var_rank_request, itVarReached);
+  const int r = var_rank_request > 0 ? std::min(var_rank_request, itVarRank) : itVarRank;
+  *var_rank_out = r;
+  if (R_out) {
+    std::fill(R_out, R_out + (size_t)N * rank, 0.0);
+    std::vector<double> col((size_t)N);
+    for (int t = 0; t < itVarRank; ++t) {
+      HIPCK(hipMemcpy(col.data(), itVR.get() + (size_t)t * N, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
+      for (long i = 0; i < N; ++i) R_out[(size_t)i * rank + t] = col[i];
+    }
+  }
+  const double base = include_nugget ? sigma2 + nugget : sigma2;
+  for (long c0 = 0; c0 < m; c0 += plan.points) {
+    const long mc = std::min<long>(plan.points, m - c0);
+    if (r < 1) {                                             // an empty cache: the prior variance
+      std::fill(var + c0, var + c0 + mc, base);
+      continue;
+    }
+    HIPCK(hipMemcpyAsync(dQ, testing + (size_t)c0 * D, (size_t)mc * D * sizeof(double), hipMemcpyHostToDevice, st));
+    launch_local_scale(dQ, mc, D, dScale, dQs, st);
+    launch_kvar(dQs, mc, dXs, N, D, kt, sigma2, itVR, N, r, base, dPart, st);
+    HIPCK(hipGetLastError());
+    HIPCK(hipMemcpyAsync(var + c0, dPart, (size_t)mc * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCK(hipStreamSynchronize(st));
   }
 }
 

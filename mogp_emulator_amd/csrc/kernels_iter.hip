@@ -23,6 +23,10 @@
 //   kgrad_forms_kernel   sum_ij U_ic W_jc dA_ij/dtheta_d for the data column and for the sum over the probe columns, in one sweep over the
 //                        generated matrix on kmatvec_kernel's tiling: the MFMA forms S_ij = sum_c U_ic W_jc, the lane that holds S_ij
 //                        generates sigma2 k'(r2_ij) and adds per dimension; one partial per workgroup, added in ascending order
+//   tri_right_kernel     a tall panel times an upper triangular matrix, 32 columns per launch: the two orthonormalisations of the variance
+//                        bound's cache (engine_iter.hip iter_var_build)
+//   kvar_kernel          sum_c (sum_j sigma2 k(r2(q_i, x_j)) R_jc)^2 on kmatvec_kernel's tiling, the grid split over chunks of ITER_VAR_CHUNK
+//                        columns of R; kvar_reduce_kernel adds the chunks in ascending order and forms max(base - sum, 0)
 // Every launch is a plain grid that ends by itself: nothing here waits on another workgroup.
 #include <algorithm>
 #include <climits>
@@ -551,9 +555,141 @@ __global__ __launch_bounds__(256) void kgrad_reduce_kernel(const double* __restr
   out[e] = s;
 }
 
+// ---- the variance bound: the cache's triangular products and the sum of squares over the generated cross covariance --------------------------
+// Out[:, c0 + c] = sum over s <= c0 + c of In[:, s] T[s][c0 + c] for the 32 columns of block c0, one row per thread, s ascending (T is upper
+// triangular with zeros stored below its diagonal: those terms leave the accumulator as it is).  Only columns < r are written.  In == Out is
+// allowed when the blocks are launched in descending order: a thread reads its own row of the columns <= c0 + 31 and writes that row alone.
+__global__ __launch_bounds__(256) void tri_right_kernel(const double* In, int N, int r, const double* __restrict__ T, int ldt, int c0, double* Out) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= N) return;
+  const size_t ld = (size_t)N;
+  double acc[ITER_COLS];
+#pragma unroll
+  for (int c = 0; c < ITER_COLS; ++c) acc[c] = 0.0;
+  const int send = c0 + ITER_COLS < r ? c0 + ITER_COLS : r;
+  for (int s = 0; s < send; ++s) {
+    const double l = In[(size_t)s * ld + i];
+#pragma unroll
+    for (int c = 0; c < ITER_COLS; ++c) acc[c] = __builtin_fma(l, T[(size_t)s * ldt + c0 + c], acc[c]);
+  }
+#pragma unroll
+  for (int c = 0; c < ITER_COLS; ++c)
+    if (c0 + c < r) Out[(size_t)(c0 + c) * ld + i] = acc[c];
+}
+
+// part[chunk * ldp + i] = sum over the columns c of chunk blockIdx.y (16 NB of them, those >= rank as exact zeros) of
+// (sum_j sigma2 k(r2(Q_i, X_j)) R_jc)^2.  The sweep is kmatvec_kernel's: a workgroup owns 64 queries, a wave 16, the design columns j come
+// in ascending tiles of 64, every lane generates its entry of k* once and feeds it as the A operand to the NB blocks of 16 columns of R staged
+// in LDS.  A lane then holds the sums of rows (lane >> 4) + 4 reg and column lane & 15: it squares them, the 16 column lanes are added by a
+// fixed butterfly (both partners form the same sum), the blocks in ascending order.  One writer per entry of part, no atomics.
+// LDS: tab (256) | sa (D x 64) | sb (D x 64) | sv (64 x km_ldv)
+template <int KT, int NB>
+__global__ __launch_bounds__(256) void kvar_kernel(const double* __restrict__ Qs, int M, const double* __restrict__ Xs, int N, int D, double sigma2,
+                                                   const double* __restrict__ R, size_t ldr, int rank, double* __restrict__ part, size_t ldp) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  constexpr int LDV = km_ldv<NB>();
+  double* tab = sm;
+  double* sa = tab + 256;
+  double* sb = sa + (size_t)KM_ROWS * D;
+  double* sv = sb + (size_t)KM_ROWS * D;
+  const int t = threadIdx.x, lane = t & 63;
+  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int i0 = blockIdx.x * KM_ROWS, c0 = blockIdx.y * 16 * NB;
+  const int il = w * 16 + (lane & 15), jq = lane >> 4, cl = lane & 15;
+  const int gi = i0 + il;
+  stage_exp_tab(tab);
+  stage_rows(Qs, M, D, i0, sa);
+  v4d acc[NB];
+#pragma unroll
+  for (int b = 0; b < NB; ++b) acc[b] = v4d{0.0, 0.0, 0.0, 0.0};
+  for (int j0 = 0; j0 < N; j0 += KM_ROWS) {
+    __syncthreads();                                         // the previous tile has been read
+    stage_rows(Xs, N, D, j0, sb);
+    for (int e = t; e < KM_ROWS * 16 * NB; e += 256) {
+      const int j = e & 63, c = e >> 6;
+      sv[j * LDV + c] = (j0 + j < N && c0 + c < rank) ? R[(size_t)(c0 + c) * ldr + (size_t)(j0 + j)] : 0.0;
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int g = 0; g < 4; ++g) {
+      double r2[4] = {0.0, 0.0, 0.0, 0.0};
+      for (int d = 0; d < D; ++d) {
+        const double a = sa[d * 64 + il];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const double df = a - sb[d * 64 + (g * 4 + u) * 4 + jq];
+          r2[u] = __builtin_fma(df, df, r2[u]);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int jl = (g * 4 + u) * 4 + jq;
+        double kv = sigma2 * kern_val<KT>(r2[u], tab);
+        if (j0 + jl >= N || gi >= M) kv = 0.0;
+#pragma unroll
+        for (int b = 0; b < NB; ++b) acc[b] = __builtin_amdgcn_mfma_f64_16x16x4f64(kv, sv[jl * LDV + b * 16 + cl], acc[b], 0, 0, 0);
+      }
+    }
+  }
+  double q[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int b = 0; b < NB; ++b)
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+      double s = acc[b][reg] * acc[b][reg];
+      for (int off = 8; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+      q[reg] += s;
+    }
+  if (cl == 0) {
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+      const int i = i0 + w * 16 + jq + 4 * reg;
+      if (i < M) part[(size_t)blockIdx.y * ldp + (size_t)i] = q[reg];
+    }
+  }
+}
+
+// part[i] = max(base - (the partial sums of query i over the chunks, added in ascending order), 0): the floor of predict(), NaN stays
+__global__ __launch_bounds__(256) void kvar_reduce_kernel(double* __restrict__ part, int M, size_t ldp, int nchunk, double base) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= M) return;
+  double q = 0.0;
+  for (int c = 0; c < nchunk; ++c) q += part[(size_t)c * ldp + (size_t)i];
+  const double v = base - q;
+  part[i] = v < 0.0 ? 0.0 : v;
+}
+
 inline unsigned blocks_of(long n, int per) { return (unsigned)((n + per - 1) / per); }
 
 }  // namespace
+
+static_assert(ITER_VAR_CHUNK == 16 * ITER_VAR_NB, "a chunk of the variance kernel is ITER_VAR_NB MFMA blocks of 16 columns");
+
+void launch_ltv(const double* L, long N, int p, const double* R, double* wpart, double* w, hipStream_t st) {
+  const unsigned nseg = blocks_of(N, ITER_SEG);
+  hipLaunchKernelGGL(ltv_kernel, dim3(blocks_of(p, 16), nseg), dim3(256), 0, st, L, (int)N, p, R, wpart);
+  hipLaunchKernelGGL(ltv_reduce_kernel, dim3(blocks_of((long)p * ITER_COLS, 256)), dim3(256), 0, st, wpart, (int)nseg, p, w);
+}
+
+void launch_tri_right(const double* In, long N, int r, const double* T, int ldt, int c0, double* Out, hipStream_t st) {
+  if (N < 1 || r < 1) return;
+  hipLaunchKernelGGL(tri_right_kernel, dim3(blocks_of(N, 256)), dim3(256), 0, st, In, (int)N, r, T, ldt, c0, Out);
+}
+
+void launch_kvar(const double* Qs, long M, const double* Xs, long N, int D, int kt, double sigma2, const double* R, long ldr, int rank, double base,
+                 double* part, hipStream_t st) {
+  if (M < 1 || N < 1 || rank < 1) return;
+  const unsigned nchunk = blocks_of(rank, ITER_VAR_CHUNK);
+  const auto kern = kt == 0 ? kvar_kernel<0, ITER_VAR_NB> : kvar_kernel<1, ITER_VAR_NB>;
+  const size_t lds = sizeof(double) * (256 + (size_t)2 * KM_ROWS * D + (size_t)KM_ROWS * (ITER_VAR_CHUNK + 1));
+  prof_begin("kvar", st);
+  hipLaunchKernelGGL(kern, dim3(blocks_of(M, KM_ROWS), nchunk), dim3(256), lds, st, Qs, (int)M, Xs, (int)N, D, sigma2, R, (size_t)ldr, rank, part,
+                     (size_t)M);
+  hipLaunchKernelGGL(kvar_reduce_kernel, dim3(blocks_of(M, 256)), dim3(256), 0, st, part, (int)M, (size_t)M, (int)nchunk, base);
+  // algorithmic: every chunk generates its entries again (3 D of the distance, ~20 of the kernel function), then 2 per column of R
+  prof_end("kvar", st, (double)M * (double)N * (nchunk * (3.0 * D + 20.0) + 2.0 * ITER_VAR_CHUNK * nchunk),
+           8.0 * (double)blocks_of(M, KM_ROWS) * (double)N * nchunk * (D + (double)ITER_VAR_CHUNK));
+}
 
 void launch_kmatvec(const double* As, long M, const double* Bs, long N, int D, int kt, double sigma2, double nug, bool same, const double* V,
                     long ldv, int nb, double* Out, long ldo, hipStream_t st) {

@@ -397,6 +397,25 @@ void launch_probes(const double* L, long N, int p, const double* g1, double root
 constexpr int KGRAD_DC = 16;
 void launch_kgrad_forms(const double* Xs, long N, int D, int kt, double sigma2, const double* U, const double* W, int c_lo, int c_hi, double* part,
                         double* out, hipStream_t st);
+// The variance bound (DESIGN.md section 3 "Variance bound").  w (p, ITER_COLS) = L^T R for a panel R of ITER_COLS columns: the first two
+// steps of launch_precond_apply on their own (wpart: ceil(N / ITER_SEG) * p * ITER_COLS doubles).
+void launch_ltv(const double* L, long N, int p, const double* R, double* wpart, double* w, hipStream_t st);
+// Out[:, c0 .. c0 + 31] = In[:, :r] T[:, c0 .. c0 + 31] for panels In, Out (ld N) and an upper triangular T (r rows of ldt >= c0 + 32
+// doubles, zeros below the diagonal), every entry summed over s in ascending order; columns >= r are not written.  In == Out is allowed when
+// the blocks c0 are launched in descending order on one stream.
+void launch_tri_right(const double* In, long N, int r, const double* T, int ldt, int c0, double* Out, hipStream_t st);
+// part[i] = max(base - sum_{c < rank} (sum_j sigma2 k(r2(Qs_i, Xs_j)) R[c][j])^2, 0) for the M queries Qs (scaled coordinates); R a panel
+// (ld ldr) of at least `rank` columns.  The grid is (ceil(M / 64), ceil(rank / ITER_VAR_CHUNK)): a workgroup owns 64 queries and ITER_VAR_NB
+// MFMA blocks of 16 columns of R, generates its entries of k* as kmatvec_kernel does and adds the squares in a fixed order; the chunks'
+// partial sums part[chunk * M + i] are added in ascending order by a second kernel, in place.  part: M * ceil(rank / ITER_VAR_CHUNK) doubles.
+// No atomics; a query's result depends on that query alone, and on `rank` only through the columns that enter.
+// ITER_VAR_NB = 4: a generated entry (3 D + ~20 operations of the lane) then feeds four MFMAs, twice what it feeds in the solver's product,
+// with 32 accumulator registers per lane and 33 KB of LDS for the staged columns beside the 1 KB per dimension of the two coordinate tiles
+// (117 KB of the CU's 160 at D = 80, three workgroups per CU at D = 10); a wider chunk would leave m / 64 x chunks too few workgroups for
+// the 256 CUs at the ranks below 256.
+constexpr int ITER_VAR_NB = 4;
+void launch_kvar(const double* Qs, long M, const double* Xs, long N, int D, int kt, double sigma2, const double* R, long ldr, int rank, double base,
+                 double* part, hipStream_t st);
 
 // --- utilities -------------------------------------------------------------------------------
 // out (n,n) <- tile of src (NP,NP): mode 0 copy, mode 1 transpose of the lower triangle (zeros below the diagonal of out), mode 2 symmetrise from lower

@@ -445,6 +445,32 @@ inline IterPlan iter_plan(const std::string& who, long m, int D, double free_byt
   }
   return {points, (points + ITER_PLAN_COLS - 1) / ITER_PLAN_COLS};
 }
+// The variance bound (engine_iter.hip variance_bound) holds, beside iter_held_bytes, the cache R (N rows, the rank rounded up to whole
+// panels of ITER_PLAN_COLS columns) and one triangular factor of that padded order.  Its query passes are those of iter_plan: the 16 doubles
+// per query that iter_point_bytes counts hold the partial sums of the at most ITER_MAX_RANK / ITER_VAR_CHUNK = 16 column chunks.
+//   iter_var_check_precond   the bound is built from the preconditioner's factor: rank 0 is refused
+//   iter_var_check_memory    refuses, before anything is allocated, what does not fit half of the free device memory with the solver's buffers
+//   iter_var_check_rank      the rank asked for: 0 (all the cache has) or 1 .. the rank the preconditioner reached
+constexpr int ITER_VAR_CHUNK = 64;      // columns of R per workgroup of the variance kernel (four MFMA blocks of 16)
+static_assert(ITER_MAX_RANK / ITER_VAR_CHUNK <= 16, "the partial sums of a query live in the 16 doubles of iter_point_bytes");
+inline long iter_var_pad(int rank) { return (long)ITER_PLAN_COLS * ((rank + ITER_PLAN_COLS - 1) / ITER_PLAN_COLS); }
+inline double iter_var_bytes(long N, int rank) {
+  const double pad = (double)iter_var_pad(rank);
+  return 8.0 * ((double)N * pad + pad * pad);
+}
+inline void iter_var_check_precond(const std::string& who, int rank) {
+  if (rank == 0) throw std::runtime_error(who + ": the variance bound is built from the preconditioner's factor: precond_rank must be at least 1");
+}
+inline void iter_var_check_memory(const std::string& who, long N, int rank, double free_bytes, double already_held) {
+  const double need = iter_held_bytes(N, rank) + iter_var_bytes(N, rank);
+  if (need > 0.5 * (free_bytes + already_held))
+    throw std::runtime_error(who + ": " + std::to_string((long long)need) + " bytes of device memory for the solver and the variance cache of " +
+                             std::to_string(N) + " points at rank " + std::to_string(rank) + " are more than half of the free device memory");
+}
+inline void iter_var_check_rank(const std::string& who, int request, int reached) {
+  if (request < 0 || request > reached)
+    throw std::runtime_error(who + ": rank must be between 1 and the rank the preconditioner reached, " + std::to_string(reached));
+}
 
 // Stage 2 of predict_mixture: the normalised weights of the S samples of one emulator, from their negative log-posteriors F and
 // ok flags and EITHER explicit weights w_in OR the log proposal density log_q (up to a constant).  With log_q:

@@ -1453,6 +1453,23 @@ class LocalGP_GPU(object):
         vstats = (vst[:, 0].astype(np.int64), vst[:, 1].astype(bool), vres) if want else None
         return mean, var, (int(st[0]), bool(st[1]), float(res[0])), vstats, alpha
 
+    def variance_bound(self, kern, scale, sigma2, nugget, rank, include_nugget, testing, var_rank=0, max_points=0, return_cache=False):
+        """(bound (m) or None, the columns of the cache that entered, R (N, rank of the cache) or None) of ``mogp_local_variance_bound``;
+        ``testing`` None: the cache alone.  ``var_rank`` 0: every column of the cache"""
+        if not self._h:
+            raise RuntimeError("variance_bound: the handle has been closed")
+        scale, rank = _f64(scale, 1, "scale"), int(rank)
+        t = None if testing is None else _f64(testing, 2, "testing")
+        m = 0 if t is None else t.shape[0]
+        var = np.empty(m) if m else None
+        got = np.zeros(1, dtype=np.int32)
+        R = np.zeros((self.N, max(rank, 1))) if return_cache else None
+        check(_lib.mogp_local_variance_bound(self._h, int(kern), dptr(scale), float(sigma2), float(nugget), rank, int(var_rank),
+                                             int(bool(include_nugget)), dptr(t), m, self.D if t is None else t.shape[1], int(max_points), dptr(var),
+                                             iptr(got), dptr(R)))
+        r = int(got[0])
+        return var, r, None if R is None else np.ascontiguousarray(R[:, :r])
+
     def loglik_exact(self, emulator, kern, scale, sigma2, nugget, rank, rtol, max_iter, g1, g2, grad=False, probe_terms=False,
                      return_panels=False):
         """The pieces of the exact log-likelihood (``mogp_local_loglik_exact``) as a dict: ``y_alpha``, ``alpha_alpha``, ``logdet_g``,
