@@ -1,7 +1,8 @@
 """Iterative exact prediction on the MI355X (mogp_emulator_amd.IterativeGP, csrc/kernels_iter.hip, csrc/engine_iter.hip) against the NumPy
 restatement (iterative_restate.py) and the dense GaussianProcessGPU.predict, at the smallest shapes where the code can go another way: one,
 a partial and several blocks of 16 right-hand sides, a second panel of 32 (r = 33), designs of two to sixteen row tiles with a partial last
-one, every kernel, both ends of the input dimension, both query counts of dimension_cases, preconditioner ranks from none to 256.
+one, every kernel, both ends of the input dimension, both query counts of dimension_cases, preconditioner ranks from none to 256.  Every design here fits one block of 1024 rows of the dots and of
+the pivot search and one segment of 4096 rows of the preconditioner: N > 1024 (1030 and 4100) is in test_gpu_large_design.py.
 
 The shapes, the right-hand sides and the product's bar are those of test_iterative_host.py, which shows on the CPU that the restatement
 converges within 600 iterations where these tests allow 1000, and that the bar is neither vacuous nor missed by float64.  Hyperparameters
