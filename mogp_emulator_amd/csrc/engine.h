@@ -14,6 +14,7 @@
 #include "devmem.h"
 #include "gp_state.h"
 #include "hostmath.h"
+#include "iter_solver.h"
 #include "launch.h"
 
 namespace mogp {
@@ -319,6 +320,7 @@ class LocalGP {
                       double* value_out, double* grad_out, double* terms_out, int* ok_out);
   // Iterative exact prediction (engine_iter.hip; DESIGN.md section 3 "Iterative exact prediction"): conjugate gradients on A = sigma2 k(X, X)
   // + nugget I of the WHOLE design, A never stored.  Host pointers; matrices with several columns are row-major as the caller holds them.
+  // The state of all of it is one IterSolver (iter_solver.h); the methods below are the entry points: refusals, plan, calls on the solver, copies.
   // kmatvec: out (M, r) = A V (N, r) with queries == null (M = N), else sigma2 k(queries (m, D), X) V (M = m, no nugget).
   void kmatvec(int kt, const double* scale, double sigma2, double nugget, const double* queries, long m, const double* V, int r, double* out);
   // Builds and keeps the preconditioner P = L L^T + nugget I of these hyperparameters, L (N, rank reached) the partial pivoted Cholesky
@@ -363,38 +365,8 @@ class LocalGP {
 
  private:
   void ensure_scaled(const double* scale, hipStream_t st);      // dXs = dX * scale, formed again only when the scales change
-  struct IterKey {                   // what a preconditioner or a kept alpha belongs to
-    int kt = -1, rank = -1, max_iter = 0;
-    double sigma2 = 0., nugget = 0., rtol = 0.;
-    std::vector<double> scale;
-    bool operator==(const IterKey& o) const {
-      return kt == o.kt && rank == o.rank && max_iter == o.max_iter && sigma2 == o.sigma2 && nugget == o.nugget && rtol == o.rtol && scale == o.scale;
-    }
-  };
-  struct IterAlpha {                 // the kept alpha of one emulator
-    IterKey key;
-    std::vector<double> alpha;
-    int iterations = 0, converged = 0;
-    double residual = 0.;
-  };
-  void iter_reserve(const char* who, int rank);                               // the panels and the preconditioner's buffers (refused by name when they do not fit)
-  void iter_build(const IterKey& k, hipStream_t st);            // the preconditioner of k, unless it is the one held
-  // CG on the panel itB (N x 32, kept; columns >= cols are zero) into itX; it / cv / rs: 32 entries each
-  // first_z (a panel) receives the first z = P^-1 r of every column, coef_log (2 * 32 * max_iter) the step coefficients; both may be null
-  // and change no bit of anything else
-  void iter_cg(int cols, double rtol, int max_iter, int* it, int* cv, double* rs, hipStream_t st, double* first_z = nullptr, double* coef_log = nullptr);
-  double iter_held() const;          // the bytes of the buffers of iter_reserve as they are now
-  void iter_var_build(const IterKey& k, hipStream_t st);        // the variance cache of k from the preconditioner held (iter_build(k) first), unless it is the one held
-  IterKey itVarKey;                  // of the variance cache held
-  int itVarRank = 0, itVarReached = 0;      // its rank, and the rank the preconditioner it was built from had reached
-  DevBuf<double> itVR, itVT;         // R (N, the rank in whole panels of 32 columns) and the triangular factor that is being applied
-  IterKey itKey;                     // of the preconditioner held (rtol and max_iter unused: 0)
-  int itRank = 0;                    // the rank it reached
-  double itLogdetG = 0.;             // log|nugget I + L^T L| of it (0 at rank 0)
-  DevBuf<double> lkW, lkLog, lkG1, lkPart, lkOut;    // the exact likelihood's own buffers (loglik_exact alone allocates them)
-  DevBuf<double> itL, itG, itDiag, itDmax, itPval, itB, itX, itXl, itR, itP, itQ, itZ, itV, itWpart, itW, itW2, itPart, itSc;
-  DevBuf<int> itPiv, itState, itPidx, itFl;
-  std::vector<IterAlpha> itAlpha;    // per emulator
+  void precondition_for(const IterKey& k, hipStream_t st);     // the scaled design of k's scales, then the solver's preconditioner of k
+  IterSolver iter;                   // the whole state of the iterative solver (iter_solver.h); it sees dXs and dY through const pointers
   int device = 0, n_cu = 1;
   DevBuf<double> dX, dY, dXs, dScale;
   std::vector<double> hScale;        // the scales dXs was formed with (empty: not formed yet)

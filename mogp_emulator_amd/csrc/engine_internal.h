@@ -1,8 +1,10 @@
-// What engine.hip, engine_chol.hip, engine_fit.hip, engine_predict.hip, engine_hessian.hip, engine_local.hip and the analysis_*.hip units share and
+// What engine.hip, engine_chol.hip, engine_fit.hip, engine_predict.hip, engine_hessian.hip, engine_local.hip, engine_iter*.hip and the analysis_*.hip units share and
 // nobody else sees: small helpers and the process-wide diagnostic counters behind prof_counter (engine.hip).  What lives where: engine.hip the
 // construction, the cached state, eval's steps, L^-1 / K^-1 and the gradient; engine_chol.hip the factorisation schedules; engine_fit.hip
 // the optimiser, the slot pool, the replica engines and ScratchFactor; engine_predict.hip predict, full covariance, implausibility, Sobol and loo_variance;
-// engine_hessian.hip the Hessian; engine_local.hip the LocalGP handle, which is no Engine.  The analyses that only read a fitted engine are
+// engine_hessian.hip the Hessian; engine_local.hip the LocalGP handle, which is no Engine: its design, local prediction and the Vecchia
+// likelihood; engine_iter.hip the state of its iterative solver (IterSolver, iter_solver.h: the groups' reserve, the builds, the iteration)
+// and the entry points kmatvec, precondition, solve, predict_exact and variance_bound; engine_iter_lik.hip loglik_exact.  The analyses that only read a fitted engine are
 // free functions (analysis.h), one unit per subject: analysis_mixture.hip the mixture over hyperparameter samples, analysis_cv.hip
 // cross-validation, analysis_sample.hip joint posterior draws, analysis_active.hip active learning (predict_cov, alc, alc_batch).
 // Whoever needs "factor a batch of matrices I wrote myself" and nothing else of an engine (gkdr_R,
@@ -80,6 +82,24 @@ class ScratchFactor {
  private:
   ScratchFactor(int rows, long slots, const std::vector<double>& zeros);
   Engine eng;
+};
+
+// One pass of queries of a LocalGP entry point (local prediction, the rectangular product, exact prediction, the variance bound): the
+// raw and the scaled rows of up to `points` queries of D coordinates on the device.  points = 0: nothing is allocated.
+struct QueryPass {
+  QueryPass(size_t points, int D_) : D(D_) {
+    if (points) raw.reserve(points * D), scaled.reserve(points * D);
+  }
+  // uploads rows [c0, c0 + mc) of `testing` (host, row-major) and scales them with dScale on st; the scaled rows
+  const double* load(const double* testing, long c0, long mc, const double* dScale, hipStream_t st) {
+    HIPCK(hipMemcpyAsync(raw, testing + (size_t)c0 * D, (size_t)mc * D * sizeof(double), hipMemcpyHostToDevice, st));
+    launch_local_scale(raw, mc, D, dScale, scaled, st);
+    return scaled;
+  }
+
+ private:
+  const int D;
+  DevBuf<double> raw, scaled;
 };
 
 // throws std::runtime_error(message) unless the `count` values at p are all finite

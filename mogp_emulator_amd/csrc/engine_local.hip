@@ -23,6 +23,7 @@ LocalGP::LocalGP(const double* inputs, long N_, int D_, const double* resid, int
   dScale.reserve(D);
   HIPCK(hipMemcpy(dX, inputs, nd * sizeof(double), hipMemcpyHostToDevice));
   HIPCK(hipMemcpy(dY, resid, (size_t)E * N * sizeof(double), hipMemcpyHostToDevice));
+  iter.design = IterDesign{dXs, dY, N, D, E};      // (dXs and dY are reserved once, above, and never again: the pointers stay)
 }
 
 void LocalGP::ensure_scaled(const double* scale, hipStream_t st) {
@@ -110,7 +111,8 @@ void LocalGP::predict(int e, int kt, const double* scale, double sigma2, double 
   HIPCK(hipMemGetInfo(&free_b, &total_b));
   const LocalPlan plan = local_plan(m, D, k, n_cu, (double)free_b, max_points, (double)LOCAL_WG_DOUBLES * sizeof(double));
   const size_t P = (size_t)plan.points;
-  DevBuf<double> dQ(P * D), dQs(P * D), dRad(P), dMean(P), dVar(P), dScratch((size_t)plan.grid * LOCAL_WG_DOUBLES);
+  QueryPass pass(P, D);
+  DevBuf<double> dRad(P), dMean(P), dVar(P), dScratch((size_t)plan.grid * LOCAL_WG_DOUBLES);
   DevBuf<int> dNbr(P * k), dOk(P);
   SyncOnUnwind sync{st};
   ensure_scaled(scale, st);
@@ -118,8 +120,7 @@ void LocalGP::predict(int e, int kt, const double* scale, double sigma2, double 
   for (long c0 = 0; c0 < m; c0 += plan.points) {
     const int mc = (int)std::min<long>(plan.points, m - c0);
     const int grid = std::min(plan.grid, mc);
-    HIPCK(hipMemcpyAsync(dQ, testing + (size_t)c0 * D, (size_t)mc * D * sizeof(double), hipMemcpyHostToDevice, st));
-    launch_local_scale(dQ, mc, D, dScale, dQs, st);
+    const double* dQs = pass.load(testing, c0, mc, dScale, st);
     launch_local_knn(dXs, N, D, dQs, mc, k, dNbr, dRad, st);
     launch_local_gp(dXs, dYe, N, D, dQs, mc, k, dNbr, kt, sigma2, nugget + jitter, include_nugget ? nugget : 0., dScratch, grid, dMean, dVar, dOk, st);
     HIPCK(hipGetLastError());

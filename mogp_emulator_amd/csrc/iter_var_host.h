@@ -1,4 +1,4 @@
-// The small dense arithmetic of the variance bound's cache (engine_iter.hip iter_var_build), on the host: matrices of the order of the
+// The small dense arithmetic of the variance bound's cache (engine_iter.hip IterSolver::var_build), on the host: matrices of the order of the
 // preconditioner's rank (<= 1024), row-major, plain loops in one fixed order.  Host code only; tests/c/iter_var_host_check.cpp checks it.
 //
 //   prefix_cholesky      G[:r, :r] = C C^T in NATURAL column order, stopped at the first column whose pivot is not above `floor`: the rank

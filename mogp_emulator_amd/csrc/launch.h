@@ -366,18 +366,21 @@ void launch_pchol_gram(const double* L, long N, int p, double eta, double* G, hi
 // Z = (R - L Ginv L^T R) / eta on panels of ITER_COLS columns (ld N); wpart: ceil(N / ITER_SEG) * p * ITER_COLS doubles, w and w2: p * ITER_COLS
 void launch_precond_apply(const double* L, long N, int p, const double* Ginv, double eta, const double* R, double* Z, double* wpart, double* w,
                           double* w2, hipStream_t st);
-// column-wise <A_c, B_c> of two panels (ld N): part (ITER_COLS, ceil(N / ITER_DOT_BLOCK)), then launch_cg_scalars(mode) adds them in ascending
-// order and does the step's scalar work on the device.  sc: 5 * ITER_COLS doubles (bb, rz, alpha, beta, out), fl: 3 * ITER_COLS ints (frozen,
-// converged, iterations).
-//   mode 0  bb = s; a column with s == 0 is frozen as converged at iteration 0      mode 1  rz = s
-//   mode 2  s = p^T A p: alpha = rz / s, or frozen as not converged when s is not a positive finite number
-//   mode 3  s = |r|^2: frozen as converged at iteration it + 1 when sqrt(s) <= rtol sqrt(bb)
-//   mode 4  s = r^T z: beta = s / rz, rz = s                                        mode 5  out = s
-// Modes 2 .. 4 leave a frozen column alone.
+// column-wise <A_c, B_c> of two panels (ld N): part (ITER_COLS, ceil(N / ITER_DOT_BLOCK)), then launch_cg_scalars(step) adds them in ascending
+// order and does that step's scalar work on the device.  sc: 5 * ITER_COLS doubles (bb, rz, alpha, beta, out), fl: 3 * ITER_COLS ints (frozen,
+// converged, iterations).  CG_ALPHA, CG_TEST and CG_BETA leave a frozen column alone.
+enum CgStep {
+  CG_BB,      // bb = s; a column with s == 0 is frozen as converged at iteration 0
+  CG_RZ,      // rz = s
+  CG_ALPHA,   // s = p^T A p: alpha = rz / s, or frozen as not converged when s is not a positive finite number
+  CG_TEST,    // s = |r|^2: frozen as converged at iteration it + 1 when sqrt(s) <= rtol sqrt(bb)
+  CG_BETA,    // s = r^T z: beta = s / rz, rz = s
+  CG_OUT      // out = s
+};
 void launch_cg_dot(const double* A, const double* B, long N, double* part, hipStream_t st);
-// lg (or null): the coefficient log of the exact likelihood, lg[(2 it + 0) * ITER_COLS + c] = alpha of iteration it (mode 2) and
-// lg[(2 it + 1) * ITER_COLS + c] = beta (mode 4), stored for the columns that are live at that point; no other result depends on it.
-void launch_cg_scalars(int mode, const double* part, long N, double* sc, int* fl, int it, double rtol, hipStream_t st, double* lg = nullptr);
+// lg (or null): the coefficient log of the exact likelihood, lg[(2 it + 0) * ITER_COLS + c] = alpha of iteration it (CG_ALPHA) and
+// lg[(2 it + 1) * ITER_COLS + c] = beta (CG_BETA), stored for the columns that are live at that point; no other result depends on it.
+void launch_cg_scalars(CgStep step, const double* part, long N, double* sc, int* fl, int it, double rtol, hipStream_t st, double* lg = nullptr);
 // x += alpha p with the roundings of that sum collected in xl (x + xl is the iterate), r -= alpha q;  p = z + beta p (first: p = z);
 // out = a - b;  x += xl: panels of ITER_COLS columns (ld N).  The two updates leave frozen columns untouched.
 void launch_cg_update(double* x, double* xl, double* r, const double* p, const double* q, long N, const double* sc, const int* fl, hipStream_t st);
@@ -392,13 +395,13 @@ void launch_probes(const double* L, long N, int p, const double* g1, double root
 //   out[D + d] = sum over the columns c_lo <= c < c_hi (1 <= c_lo, c_hi <= ITER_COLS) of sum_ij U[c][i] W[c][j] dA_ij/dtheta_d
 // U, W: panels of ITER_COLS columns (ld N).  A workgroup owns 64 rows and KGRAD_DC dimensions, forms S_ij = sum_c U_ic W_jc of a 16 x 16
 // block with v_mfma_f64_16x16x4_f64, generates r2 and k' in the lane that holds S_ij and adds in a fixed order; part: ceil(N / 64) * 2 * D
-// doubles, one partial per workgroup and output, added in ascending order by a second kernel.  No atomics; no bit of out[0 .. D) depends on
+// doubles, one partial per workgroup and output, added in ascending order by a second kernel (the one that adds the segments of launch_ltv).  No atomics; no bit of out[0 .. D) depends on
 // the probe columns, and none of out on KGRAD_DC.
 constexpr int KGRAD_DC = 16;
 void launch_kgrad_forms(const double* Xs, long N, int D, int kt, double sigma2, const double* U, const double* W, int c_lo, int c_hi, double* part,
                         double* out, hipStream_t st);
 // The variance bound (DESIGN.md section 3 "Variance bound").  w (p, ITER_COLS) = L^T R for a panel R of ITER_COLS columns: the first two
-// steps of launch_precond_apply on their own (wpart: ceil(N / ITER_SEG) * p * ITER_COLS doubles).
+// steps of launch_precond_apply, which calls it (wpart: ceil(N / ITER_SEG) * p * ITER_COLS doubles).
 void launch_ltv(const double* L, long N, int p, const double* R, double* wpart, double* w, hipStream_t st);
 // Out[:, c0 .. c0 + 31] = In[:, :r] T[:, c0 .. c0 + 31] for panels In, Out (ld N) and an upper triangular T (r rows of ldt >= c0 + 32
 // doubles, zeros below the diagonal), every entry summed over s in ascending order; columns >= r are not written.  In == Out is allowed when
@@ -406,7 +409,7 @@ void launch_ltv(const double* L, long N, int p, const double* R, double* wpart, 
 void launch_tri_right(const double* In, long N, int r, const double* T, int ldt, int c0, double* Out, hipStream_t st);
 // part[i] = max(base - sum_{c < rank} (sum_j sigma2 k(r2(Qs_i, Xs_j)) R[c][j])^2, 0) for the M queries Qs (scaled coordinates); R a panel
 // (ld ldr) of at least `rank` columns.  The grid is (ceil(M / 64), ceil(rank / ITER_VAR_CHUNK)): a workgroup owns 64 queries and ITER_VAR_NB
-// MFMA blocks of 16 columns of R, generates its entries of k* as kmatvec_kernel does and adds the squares in a fixed order; the chunks'
+// MFMA blocks of 16 columns of R, generates its entries of k* by the sweep kmatvec_kernel runs and adds the squares in a fixed order; the chunks'
 // partial sums part[chunk * M + i] are added in ascending order by a second kernel, in place.  part: M * ceil(rank / ITER_VAR_CHUNK) doubles.
 // No atomics; a query's result depends on that query alone, and on `rank` only through the columns that enter.
 // ITER_VAR_NB = 4: a generated entry (3 D + ~20 operations of the lane) then feeds four MFMAs, twice what it feeds in the solver's product,

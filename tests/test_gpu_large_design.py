@@ -2,7 +2,7 @@
 persistent grid has workgroups (every workgroup takes a second problem and some a third: csrc/kernels_local.hip local_gp_kernel and
 vecchia_ll_kernel), the second pass of the Vecchia sum (launch_vecchia_reduce), and IterativeGP at N = 1030 and N = 4100: a second, partial
 block of 1024 rows in the dots (cg_dot_kernel, cg_scalars_kernel) and in the pivot search (pchol_argmax1/2_kernel), a second, partial segment
-of 4096 rows in the preconditioner's L^T R (ltv_kernel, ltv_reduce_kernel; csrc/kernels_iter.hip).  Every other GPU test of these features
+of 4096 rows in the preconditioner's L^T R (ltv_kernel, sum_parts_kernel; csrc/kernels_iter.hip).  Every other GPU test of these features
 stays below those sizes: there the second stage of every reduction adds one summand and no workgroup takes a second problem.
 
 The grid is not written down here: it is LOCAL_GRID_PER_CU = 4 workgroups per compute unit of the device the tests run on (the rule of

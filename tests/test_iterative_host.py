@@ -82,6 +82,13 @@ def test_plan_memory_refusal_and_refusal_texts(tmp_path):
     assert out.strip() == "ok 53 checks"
 
 
+def test_panel_transposes_follow_the_index_formula_and_stay_inside_their_window(tmp_path):
+    """tests/c/iter_panel_check.cpp: csrc/iter_panel.h both ways at (N, r) = (1, 1), (5, 33), (130, 7), the windows of the passes of 32 and of
+    the probe columns, leading dimensions beyond the counts, canaries around the destination"""
+    out = _build_and_run(tmp_path, "iter_panel_check")
+    assert out.strip() == "ok 48 checks"
+
+
 def test_exports():
     assert M.IterativeGP is IG.IterativeGP and M.IterativeSolve is IG.IterativeSolve and M.IterativePrediction is IG.IterativePrediction
     assert hasattr(M.VecchiaGP, "predict_exact")
