@@ -544,6 +544,26 @@ int mogp_local_loglik_exact(mogp_local* h, int emulator, int kernel_type, const 
 int mogp_local_variance_bound(mogp_local* h, int kernel_type, const double* scale, double sigma2, double nugget, int precond_rank,
                               int var_rank_request, int include_nugget, const double* testing, int m, int D, int max_points, double* var_out,
                               int* var_rank_out, double* R_out);
+/* Pathwise posterior draws (Matheron's rule with a random-Fourier-feature prior; Wilson et al. 2020): a draw is the function
+     f_s(.) = g_s(.) + sigma2 k(., X) v_s,   g_s(x) = amp sum_f W[s][f] cos(phase[f] + omega[f] . (x * scale)),   v_s = A^-1 (y - g_s(X) - sqrt(nugget) eps_s).
+   Matrices of draws are (S, .) row-major.
+   mogp_local_rff: out (S, M) = g at the design's rows (queries NULL, M = N) or at queries (m, D); omega (F, D) in scaled coordinates, phase (F),
+   W (S, F), 1 <= F <= 65536.  The feature matrix is generated and never stored: one cosine per lane as the A operand of the fp64 MFMA, the
+   features summed in one fixed ascending order, amp applied once at the end.  No atomics: entry (s, i) is the same bits for a repeated
+   call, whatever the other draws, the other points and max_points (points per pass, 0 = sized by the free device memory). */
+int mogp_local_rff(mogp_local* h, const double* scale, const double* queries, int m, int D, const double* omega, const double* phase, int n_features,
+                   const double* W, int n_draws, double amp, int max_points, double* out);
+/* mogp_local_sample_paths: the updates v_s of n_draws paths of residual row `emulator`: the preconditioner of mogp_local_precondition at
+   precond_rank (built when it is not the one held), the right-hand sides formed on the device, the solver of mogp_local_solve in blocks of 32
+   columns.  W_in (S, F) / noise_in (S, N) or NULL: then the standard normals of draw first_draw + s of the streams stream + 3 / stream + 4
+   of the generator of mogp_*_sample_posterior under `seed`, generated on the device.  W_out (S, F): the weights' normals used; v_out (S, N);
+   stat_out (2 S) iterations and converged per draw; residual_out (S) = |b - A v| / |b| recomputed; rank_out (1) the rank the preconditioner
+   reached.  A draw that does not converge within max_iter is returned as it is with converged 0.  Draw s depends on (seed, stream,
+   first_draw + s) and the features alone: no bit of it depends on the other draws of the call. */
+int mogp_local_sample_paths(mogp_local* h, int emulator, int kernel_type, const double* scale, double sigma2, double nugget, int precond_rank,
+                            double rtol, int max_iter, const double* omega, const double* phase, int n_features, int n_draws, double amp,
+                            unsigned long long seed, unsigned stream, int first_draw, const double* W_in, const double* noise_in, double* W_out,
+                            double* v_out, int* stat_out, double* residual_out, int* rank_out);
 void mogp_local_destroy(mogp_local* h);
 /* device memory helpers so a host program can hand device-resident buffers to the *_dev calls */
 void* mogp_dev_malloc(unsigned long long bytes);

@@ -38,15 +38,25 @@ products with A, a prefix Cholesky of H, R = Q C^-T.  Both factors are prefixes,
 the bound tightens monotonically with the rank, bit for bit, and is the exact variance at rank N.  How far it lies above the exact variance
 depends on the design, the kernel and the rank; ``variance_gap`` measures it on the caller's own queries.
 
-Not covered: bounds of cross-covariances, a lower bound, more than 31 probes per evaluation (average over seeds), derivatives
-with respect to mean-function parameters, the symmetry of A in the product, several devices per handle, ``ProductMat52``,
-``analytic_mean=True``, ``nugget="pivot"``.
+Joint draws of the posterior at these sizes are functions (``sample_paths``, ``PosteriorPaths``): pathwise conditioning, that is Matheron's rule
+on a random-Fourier-feature prior (Wilson et al. 2020),
+
+    f_s(.) = m(.) + g_s(.) + sigma^2 k(., X) v_s,    v_s = A^-1 (y - m(X) - g_s(X) - sqrt(nugget) eps_s)
+    g_s(x) = sqrt(2 sigma^2 / F) sum_f W_sf cos(omega_f . (x * s) + b_f)
+
+with the v_s as further columns of the solver, the feature matrix generated and never stored (``csrc/kernels_rff.hip``) and every random
+input a named Philox sub-stream, so that a path is a deterministic function of (seed, stream, emulator, draw index, n_features).
+
+Not covered: joint draws of paths over hyperparameters, input derivatives of a path, bounds of cross-covariances, a lower bound, more
+than 31 probes per evaluation (average over seeds), derivatives with respect to mean-function parameters, the symmetry of A in the
+product, several devices per handle, ``ProductMat52``, ``analytic_mean=True``, ``nugget="pivot"``.
 """
 import numpy as np
 
 from .LocalGP import MAX_D, _KERNELS, _create_native, _emulator_type, _fit_state, _hyperparameters, _mean_at, _points
 
 MAX_RANK = 1024
+MAX_FEATURES = 65536     # random Fourier features of a path (csrc/predict_plan.h RFF_MAX_FEATURES)
 MAX_PROBES = 31          # the data column and the probes share one panel of 32 columns
 _PROBE_STREAM = 0x10c    # the Philox stream of the default probes (g1 from it, g2 from the next)
 VAR_CHUNK = 64           # columns of the variance cache per workgroup of the bound's kernel (csrc/predict_plan.h ITER_VAR_CHUNK)
@@ -188,6 +198,89 @@ def _check_options(who, N, precond_rank, rtol, max_iter):
     if int(max_iter) != max_iter or int(max_iter) < 1:
         raise ValueError("%s: max_iter must be at least 1" % who)
     return p, rtol, int(max_iter)
+
+
+def path_features(seed, stream, n_features, D, kt):
+    """(omega (F, D), phase (F,)) of the random Fourier features of a path, from ``philox_normals`` under the sub-streams ``stream + j``:
+    j = 0 (F, D) normals z; j = 1 (F, 5) normals g for the Matern-5/2 kernels (``kt`` 1), omega_f = z_f sqrt(5 / sum_i g_fi^2) -- the
+    kernel's multivariate-t spectral measure; omega = z for the squared exponential (``kt`` 0) --; j = 2 (F, 2) normals h,
+    phase_f = arctan2(h_f0, h_f1), uniform on (-pi, pi].  In the scaled coordinates x * s of the handle."""
+    from .Sampling import philox_normals
+    F = int(n_features)
+    omega = philox_normals(seed, stream, F, D)
+    if kt == 1:
+        g = philox_normals(seed, stream + 1, F, 5)
+        chi = np.zeros(F)
+        for i in range(5):                        # ascending in i
+            chi = chi + g[:, i] * g[:, i]
+        omega = omega * np.sqrt(5. / chi)[:, None]
+    h = philox_normals(seed, stream + 2, F, 2)
+    return np.ascontiguousarray(omega), np.ascontiguousarray(np.arctan2(h[:, 0], h[:, 1]))
+
+
+class PosteriorPaths(object):
+    """What ``IterativeGP.sample_paths`` returns: ``n_draws`` functions drawn from the posterior of one emulator,
+
+        f_s(x) = m(x) + g_s(x) + sigma^2 k(x, X) update[:, s],      g_s(x) = sqrt(2 sigma^2 / F) sum_f feature_normals[s, f] cos(omega_f . (x * s) + phase_f)
+
+    Each may be evaluated at any query set, any number of times, consistently: ``evaluate(testing)`` (or calling the object) gives
+    (n_draws, m) values of the latent f -- no nugget is added --, ``prior(testing)`` m + g_s alone.  Fields: ``n_draws``, ``n_features``,
+    ``omega`` (F, D) in scaled coordinates, ``phase`` (F,), ``feature_normals`` (S, F), ``update`` (N, S), per draw ``iterations``,
+    ``converged``, ``residual`` (|b - A v| / |b| recomputed) and ``ok`` (converged and finite), ``precond_rank`` (the rank reached),
+    ``seed``, ``stream`` (of the emulator: the caller's plus 8 times its index), ``first_draw``, ``emulator``.  The paths hold on to the
+    ``IterativeGP`` they came from and refuse by name once it is closed."""
+
+    def __init__(self, gp, hyper, **fields):
+        self._gp, self._hyper = gp, hyper
+        self.__dict__.update(fields)
+
+    def _native(self, who):
+        if self._gp._native is None:
+            raise RuntimeError("%s: the handle has been closed" % who)
+        return self._gp._native
+
+    def _queries(self, who, testing, max_points):
+        testing = _points("testing", who, testing, self._gp._D)
+        if int(max_points) != max_points or int(max_points) < 0:
+            raise ValueError("%s: max_points must not be negative" % who)
+        if testing.shape[0] >= 2 ** 31:
+            raise ValueError("%s: at most 2^31 - 1 testing points per call" % who)
+        return testing, int(max_points), self._native(who)
+
+    def _prior(self, native, testing, max_points):
+        kt, s, sigma2, nugget, meanfunc, mparams = self._hyper
+        g = native.rff(s, self.omega, self.phase, self.feature_normals, np.sqrt(2. * sigma2 / self.n_features), queries=testing,
+                       max_points=max_points)
+        return g + _mean_at(meanfunc, mparams, testing)[None, :]
+
+    def prior(self, testing, max_points=0):
+        """(n_draws, m) m(x) + g_s(x): the prior draws the paths are conditioned from"""
+        testing, max_points, native = self._queries("PosteriorPaths.prior", testing, max_points)
+        return self._prior(native, testing, max_points)
+
+    def evaluate(self, testing, max_points=0):
+        """(n_draws, m) f_s at ``testing`` (m, D).  ``max_points`` caps the queries per device pass (0: sized by the free device memory) and
+        changes no bit; neither do the other queries or a repeated call."""
+        testing, max_points, native = self._queries("PosteriorPaths.evaluate", testing, max_points)
+        kt, s, sigma2, nugget, _, _ = self._hyper
+        out = self._prior(native, testing, max_points)
+        step = max_points if max_points else testing.shape[0]
+        for c0 in range(0, testing.shape[0], step):
+            out[:, c0:c0 + step] += native.kmatvec(kt, s, sigma2, nugget, self.update, queries=testing[c0:c0 + step]).T
+        return out
+
+    __call__ = evaluate
+
+
+def _check_normals(who, name, z, S, cols, what):
+    if z is None:
+        return None
+    z = np.ascontiguousarray(z, dtype=np.float64)
+    if z.shape != (S, cols):
+        raise ValueError("%s: %s must have shape (n_draws, %s) = (%d, %d)" % (who, name, what, S, cols))
+    if not np.all(np.isfinite(z)):
+        raise ValueError("%s: %s must be finite" % (who, name))
+    return z
 
 
 def _check_nuggets(who, hyper):
@@ -341,6 +434,46 @@ class IterativeGP(object):
         e, hyper = self._emulator(who, emulator)
         return _exact_loglik(who, self._native, e, hyper, self._layout[e], self._D, self._N, self._p, self._rtol, self._max_iter, bool(grad),
                              T, seed, g1, g2, bool(probe_terms) and bool(grad))
+
+    # ---- pathwise posterior draws ------------------------------------------------------------------------------------------------------------
+    def sample_paths(self, n_draws=1, emulator=0, n_features=2048, seed=0, stream=0x200, first_draw=0, feature_normals=None, noise_normals=None):
+        """``n_draws`` functions from the posterior of ``emulator`` by pathwise conditioning (Matheron's rule on a random-Fourier-feature
+        prior; Wilson et al. 2020); returns a ``PosteriorPaths``.  Conditional on the features the draws are Gaussian with the exact data
+        term and a prior covariance that is off by O(sigma^2 / sqrt(n_features)).
+
+        The random inputs are ``philox_normals(seed, stream + 8 emulator + j, ...)`` of ``Sampling.py``: j = 0, 1, 2 the frequencies and
+        phases (``path_features``), j = 3 the (n_draws, n_features) weights' normals and j = 4 the (n_draws, N) noise normals, both at
+        draw rows ``first_draw + s`` and generated on the device unless ``feature_normals`` / ``noise_normals`` give the caller's (common
+        random numbers, antithetic pairs, exact tests; on a view of a ``VecchiaGP`` the columns of ``noise_normals`` are in the handle's
+        order).  A path depends on (seed, stream, emulator, draw index, n_features) alone: ``sample_paths(4)`` equals ``sample_paths(2)``
+        followed by ``sample_paths(2, first_draw=2)`` bit for bit, and a repeated call returns the same bits.  The updates are ``n_draws``
+        further columns of the solver of ``solve`` (``precond_rank``, ``rtol``, ``max_iter`` of this object); a draw whose solve did not
+        converge comes back with ``converged`` False, nothing is raised.  Every argument is checked before the device is touched."""
+        who = "IterativeGP.sample_paths"
+        S = int(n_draws)
+        if S != n_draws or S < 1:
+            raise ValueError("%s: n_draws must be at least 1" % who)
+        F = int(n_features)
+        if F != n_features or F < 1 or F > MAX_FEATURES:
+            raise ValueError("%s: n_features must be between 1 and %d" % (who, MAX_FEATURES))
+        if int(first_draw) != first_draw or int(first_draw) < 0 or int(first_draw) + S >= 2 ** 31:
+            raise ValueError("%s: first_draw must not be negative (and first_draw + n_draws below 2^31)" % who)
+        if int(seed) != seed or int(seed) < 0 or int(seed) >= 2 ** 64:
+            raise ValueError("%s: seed must be an integer in [0, 2^64)" % who)
+        if int(stream) != stream or int(stream) < 0 or int(stream) + 8 * self._E >= 2 ** 32:
+            raise ValueError("%s: stream must be an integer in [0, 2^32 - 8 n_emulators)" % who)
+        W = _check_normals(who, "feature_normals", feature_normals, S, F, "n_features")
+        eps = _check_normals(who, "noise_normals", noise_normals, S, self._N, "N")
+        e, hyper = self._emulator(who, emulator)
+        kt, s, sigma2, nugget, _, _ = hyper
+        sub = int(stream) + 8 * e
+        omega, phase = path_features(int(seed), sub, F, self._D, kt)
+        W, v, it, cv, res, rank = self._native.sample_paths(e, kt, s, sigma2, nugget, self._p, self._rtol, self._max_iter, omega, phase, S,
+                                                            np.sqrt(2. * sigma2 / F), int(seed), sub, int(first_draw), W, eps)
+        update = np.ascontiguousarray(v.T)
+        return PosteriorPaths(self, hyper, n_draws=S, n_features=F, omega=omega, phase=phase, feature_normals=W, update=update, iterations=it,
+                              converged=cv, residual=res, ok=cv & np.all(np.isfinite(update), axis=0), precond_rank=rank, seed=int(seed),
+                              stream=sub, first_draw=int(first_draw), emulator=e)
 
     # ---- prediction ----------------------------------------------------------------------------------------------------------------------
     def predict(self, testing, unc=False, include_nugget=True, max_points=0):

@@ -348,6 +348,14 @@ class VecchiaGP(object):
         options = {k: kw.pop(k) for k in ("precond_rank", "rtol", "max_iter") if k in kw}
         return self._exact_view("VecchiaGP.predict_exact", theta, options).predict(testing, **kw)
 
+    def sample_paths(self, n_draws=1, theta=None, **kw):
+        """``IterativeGP.sample_paths`` at the fitted theta (or ``theta``) on the same native handle: ``n_draws`` functions from the exact
+        posterior of all N points, each to be evaluated at any query set.  ``precond_rank``, ``rtol`` and ``max_iter`` of ``kw`` go to
+        ``IterativeGP``, the rest to its ``sample_paths``.  Returns a ``PosteriorPaths``; its ``update`` -- and the columns of a
+        ``noise_normals`` given -- are in the Vecchia order of the handle (``order``), what it evaluates to has no such index."""
+        options = {k: kw.pop(k) for k in ("precond_rank", "rtol", "max_iter") if k in kw}
+        return self._exact_view("VecchiaGP.sample_paths", theta, options).sample_paths(n_draws, **kw)
+
     def exact_view(self, theta=None, **options):
         """An ``IterativeGP`` on this object's native handle at the fitted theta (or ``theta``), for ``matvec`` / ``solve`` / ``weights``;
         ``options``: ``precond_rank``, ``rtol``, ``max_iter``.  THE HANDLE HOLDS THE DESIGN IN THE VECCHIA ORDER: rows of what the view takes

@@ -24,7 +24,8 @@ mogp_emulator_amd -- MI355X (gfx950) native fit + predict backend for mogp_emula
   Vecchia.py       hyperparameters from the whole of a large design: the Vecchia likelihood and its analytic gradient on the device, L-BFGS fit
   IterativeGP.py   exact prediction for designs beyond the dense path: matrix-free preconditioned conjugate gradients on the whole design, on the device;
                    the exact log-likelihood and its gradient by stochastic Lanczos quadrature from one such solve; variance_bound: a
-                   conservative predictive variance from a cached low-rank factor, one product per batch of queries and no solve
+                   conservative predictive variance from a cached low-rank factor, one product per batch of queries and no solve;
+                   sample_paths: posterior draws as functions (pathwise conditioning on a random-Fourier-feature prior)
   dist.py          one-process-per-GPU sharding of emulators + single gather (torch.distributed/RCCL)
 """
 from .LibGPGPU import HAVE_LIBGPGPU, gpu_usable            # noqa: F401
@@ -36,7 +37,7 @@ from .Sampling import sample_posterior, PosteriorSamples, philox_normals   # noq
 from .ActiveLearning import predict_cov, alc_criterion, ALCResult, alc_batch, ALCBatchResult   # noqa: F401
 from .LocalGP import LocalGP, LocalPrediction, predict_local   # noqa: F401
 from .Vecchia import VecchiaGP, VecchiaLogLik, VecchiaFit, ExactFit   # noqa: F401
-from .IterativeGP import IterativeGP, IterativeSolve, IterativePrediction, ExactLogLik   # noqa: F401
+from .IterativeGP import IterativeGP, IterativeSolve, IterativePrediction, ExactLogLik, PosteriorPaths, path_features   # noqa: F401
 
 if HAVE_LIBGPGPU:
     from .GaussianProcessGPU import GaussianProcessGPU, PredictResult   # noqa: F401

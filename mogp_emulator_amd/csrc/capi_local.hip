@@ -107,6 +107,26 @@ int mogp_local_variance_bound(mogp_local* h, int kernel_type, const double* scal
   });
 }
 
+int mogp_local_rff(mogp_local* h, const double* scale, const double* queries, int m, int D, const double* omega, const double* phase, int n_features,
+                   const double* W, int n_draws, double amp, int max_points, double* out) {
+  return guarded([&] {
+    if (!h || !h->gp) throw std::runtime_error("rff: null handle");
+    if (D != h->gp->D) throw std::runtime_error("rff: queries and frequencies must have D columns");
+    h->gp->rff(scale, queries, m, omega, phase, n_features, W, n_draws, amp, max_points, out);
+  });
+}
+
+int mogp_local_sample_paths(mogp_local* h, int emulator, int kernel_type, const double* scale, double sigma2, double nugget, int precond_rank,
+                            double rtol, int max_iter, const double* omega, const double* phase, int n_features, int n_draws, double amp,
+                            unsigned long long seed, unsigned stream, int first_draw, const double* W_in, const double* noise_in, double* W_out,
+                            double* v_out, int* stat_out, double* residual_out, int* rank_out) {
+  return guarded([&] {
+    if (!h || !h->gp) throw std::runtime_error("sample_paths: null handle");
+    h->gp->sample_paths(emulator, kernel_type, scale, sigma2, nugget, precond_rank, rtol, max_iter, omega, phase, n_features, n_draws, amp, seed,
+                        stream, first_draw, W_in, noise_in, W_out, v_out, stat_out, residual_out, rank_out);
+  });
+}
+
 void mogp_local_destroy(mogp_local* h) {
   if (!h) return;
   (void)guarded([&] {

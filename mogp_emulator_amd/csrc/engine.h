@@ -359,6 +359,20 @@ class LocalGP {
   // *var_rank_out = the columns that entered.  R_out (N, rank) row-major or null: the cache, columns behind its rank zero.  m = 0: the cache alone.
   void variance_bound(int kt, const double* scale, double sigma2, double nugget, int rank, int var_rank_request, bool include_nugget,
                       const double* testing, long m, int max_points, double* var, int* var_rank_out, double* R_out);
+  // Pathwise posterior draws (engine_rff.hip; DESIGN.md section 3 "Pathwise posterior draws").  Matrices of draws are (S, .) row-major.
+  // rff: out (S, M) = (amp Phi(P) W^T)^T with Phi_if = cos(phase_f + omega_f . P_i) over the scaled rows P of the design (queries == null,
+  // M = N) or of queries (m, D); omega (F, D), phase (F), W (S, F).  Column s depends on row s of W alone, entry (s, i) on point i alone;
+  // max_points caps the points per pass (0: sized by the free memory) and changes no bit.
+  void rff(const double* scale, const double* queries, long m, const double* omega, const double* phase, int F, const double* W, int S, double amp,
+           int max_points, double* out);
+  // The updates v_s = A^-1 (y_e - g_s(X) - sqrt(nugget) eps_s) of S paths, g_s = amp Phi(X) W_s: the preconditioner of these hyperparameters
+  // (built unless held), the right-hand sides formed on the device, IterSolver::solve in blocks of 32.  W_in (S, F) / noise_in (S, N) or null:
+  // then the normals of draw first_draw + s of the streams stream + 3 / stream + 4 under `seed` (philox_dev.h), generated on the device.
+  // W_out (S, F) the weights' normals used, v_out (S, N), stat_i (2 S) iterations and converged, residual (S) = |b - A v| / |b|, *rank_out
+  // the rank the preconditioner reached.  A column that does not converge is reported, not refused.
+  void sample_paths(int e, int kt, const double* scale, double sigma2, double nugget, int rank, double rtol, int max_iter, const double* omega,
+                    const double* phase, int F, int S, double amp, unsigned long long seed, unsigned stream, int first_draw, const double* W_in,
+                    const double* noise_in, double* W_out, double* v_out, int* stat_i, double* residual, int* rank_out);
   int device_id() const { return device; }
   const long N;
   const int D, E;

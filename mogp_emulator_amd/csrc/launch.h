@@ -420,6 +420,21 @@ constexpr int ITER_VAR_NB = 4;
 void launch_kvar(const double* Qs, long M, const double* Xs, long N, int D, int kt, double sigma2, const double* R, long ldr, int rank, double base,
                  double* part, hipStream_t st);
 
+// --- pathwise posterior draws (kernels_rff.hip) ---------------------------------------------------------
+// Random Fourier features that are generated and never stored (DESIGN.md section 3 "Pathwise posterior draws").
+// Out (M rows, 16 nb columns, ld ldo) = amp Phi W with Phi_if = cos(t_if), t_if = phase[f] then fma(omega[f][d], Ps[i][d], t) over d ascending;
+// Ps (M, D) scaled coordinates, omega (F, D), phase (F), W a panel of F rows and 16 nb columns (ld ldw); nb = 1 or 2.  kmatvec_kernel's
+// tiling and lane layout: one cosine per lane as the A operand of v_mfma_f64_16x16x4_f64, the features in ascending tiles of 64, one
+// fixed order of the sum, no atomics; column c of Out depends on column c of W alone, row i on point i alone.
+void launch_rff(const double* Ps, long M, const double* omega, const double* phase, int F, int D, const double* W, long ldw, int nb, double amp,
+                double* Out, long ldo, hipStream_t st);
+// W[c * ldw + j] = the normal j of draw draw0 + c of (seed, stream) (philox_dev.h) for c < cols, j < n
+void launch_rff_normals(unsigned long long seed, unsigned stream, unsigned draw0, int cols, long n, double* W, long ldw, hipStream_t st);
+// The right-hand sides of the paths, panels of ITER_COLS columns (ld N): B[c][i] = fma(-root, noise, y[i] - g[c][i]) for c < cols, exact zeros
+// behind them; the noise is E[c][i] or, with E null, the normal i of draw draw0 + c of (seed, stream).
+void launch_rff_rhs(const double* y, const double* g, const double* E, long N, int cols, double root, unsigned long long seed, unsigned stream,
+                    unsigned draw0, double* B, hipStream_t st);
+
 // --- utilities -------------------------------------------------------------------------------
 // out (n,n) <- tile of src (NP,NP): mode 0 copy, mode 1 transpose of the lower triangle (zeros below the diagonal of out), mode 2 symmetrise from lower
 void launch_extract(const double* src, int NP, int n, double* out, int mode, hipStream_t s);

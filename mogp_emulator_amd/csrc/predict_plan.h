@@ -472,6 +472,46 @@ inline void iter_var_check_rank(const std::string& who, int request, int reached
     throw std::runtime_error(who + ": rank must be between 1 and the rank the preconditioner reached, " + std::to_string(reached));
 }
 
+// Pathwise posterior draws (engine_rff.hip): the feature product amp Phi W and the solves of the paths' updates.
+//   rff_check_counts   1 <= n_features <= RFF_MAX_FEATURES, n_draws >= 1, first_draw >= 0 and first_draw + n_draws within 2^31 - 1 (the
+//                      generator's draw index)
+//   rff_fixed_bytes    held whatever the points: the frequencies (F D), the phases (F) and one panel of ITER_PLAN_COLS columns of W (F each)
+//   rff_point_bytes    per point of a pass: raw and scaled coordinates and the ITER_PLAN_COLS output columns
+//   rff_plan           points per pass: max_points where given, else what the rest of half of the free memory holds, at most m and
+//                      LOCAL_MAX_PASS, at least one; passes = blocks of ITER_PLAN_COLS draws.  No bit of a result depends on either.
+constexpr int RFF_MAX_FEATURES = 65536;
+inline void rff_check_counts(const std::string& who, long n_features, long n_draws, long first_draw) {
+  if (n_features < 1 || n_features > RFF_MAX_FEATURES)
+    throw std::runtime_error(who + ": n_features must be between 1 and " + std::to_string(RFF_MAX_FEATURES));
+  if (n_draws < 1) throw std::runtime_error(who + ": n_draws must be at least 1");
+  if (first_draw < 0) throw std::runtime_error(who + ": first_draw must not be negative");
+  if (first_draw + n_draws > 2147483647L) throw std::runtime_error(who + ": first_draw + n_draws must stay below 2^31");
+}
+inline double rff_fixed_bytes(int D, int F) { return 8.0 * (double)F * ((double)D + 1.0 + ITER_PLAN_COLS); }
+inline double rff_point_bytes(int D) { return 8.0 * (2.0 * D + ITER_PLAN_COLS); }
+struct RffPlan {
+  long points;      // points per pass
+  long passes;      // blocks of ITER_PLAN_COLS draws
+};
+inline RffPlan rff_plan(const std::string& who, long m, int D, int F, long S, double free_bytes, int max_points) {
+  if (max_points < 0) throw std::runtime_error(who + ": max_points must not be negative");
+  rff_check_counts(who, F, S, 0);
+  const double fixed = rff_fixed_bytes(D, F), budget = 0.5 * free_bytes - fixed, per = rff_point_bytes(D);
+  if (budget < per)
+    throw std::runtime_error(who + ": " + std::to_string((long long)(fixed + per)) + " bytes of device memory for " + std::to_string(F) +
+                             " features and one point are more than half of the free device memory");
+  const long want = std::max<long>(1, std::min<long>(m, LOCAL_MAX_PASS));
+  long points;
+  if (max_points > 0) {
+    points = std::min<long>(want, max_points);
+    if ((double)points * per > budget)
+      throw std::runtime_error(who + ": " + std::to_string(points) + " points per pass need more than half of the free device memory; use a smaller max_points");
+  } else {
+    points = std::min<long>(want, (long)std::floor(budget / per));
+  }
+  return {points, (S + ITER_PLAN_COLS - 1) / ITER_PLAN_COLS};
+}
+
 // Stage 2 of predict_mixture: the normalised weights of the S samples of one emulator, from their negative log-posteriors F and
 // ok flags and EITHER explicit weights w_in OR the log proposal density log_q (up to a constant).  With log_q:
 //   l_s = -(F_s - F_min) - (log_q_s - log_q_a),  a = the first ok sample with F_a = F_min over the ok samples,  w_s = exp(l_s - max l)

@@ -1470,6 +1470,35 @@ class LocalGP_GPU(object):
         r = int(got[0])
         return var, r, None if R is None else np.ascontiguousarray(R[:, :r])
 
+    # ---- pathwise posterior draws (csrc/engine_rff.hip, csrc/kernels_rff.hip) ----
+    def rff(self, scale, omega, phase, W, amp, queries=None, max_points=0):
+        """(S, M) amp sum_f W[s][f] cos(phase[f] + omega[f] . (x * scale)) at the design's rows, or at ``queries`` (m, D); omega (F, D), W (S, F)"""
+        if not self._h:
+            raise RuntimeError("rff: the handle has been closed")
+        scale, omega, phase, W = _f64(scale, 1, "scale"), _f64(omega, 2, "omega"), _f64(phase, 1, "phase"), _f64(W, 2, "W")
+        q = None if queries is None else _f64(queries, 2, "queries")
+        out = np.empty((W.shape[0], self.N if q is None else q.shape[0]))
+        check(_lib.mogp_local_rff(self._h, dptr(scale), dptr(q), 0 if q is None else q.shape[0], omega.shape[1], dptr(omega), dptr(phase),
+                                  omega.shape[0], dptr(W), W.shape[0], float(amp), int(max_points), dptr(out)))
+        return out
+
+    def sample_paths(self, emulator, kern, scale, sigma2, nugget, rank, rtol, max_iter, omega, phase, n_draws, amp, seed, stream, first_draw,
+                     feature_normals=None, noise_normals=None):
+        """(W (S, F) the weights' normals used, v (S, N), iterations (S) int64, converged (S) bool, residual (S), the rank the preconditioner
+        reached) of ``mogp_local_sample_paths``"""
+        if not self._h:
+            raise RuntimeError("sample_paths: the handle has been closed")
+        scale, omega, phase = _f64(scale, 1, "scale"), _f64(omega, 2, "omega"), _f64(phase, 1, "phase")
+        Win = None if feature_normals is None else _f64(feature_normals, 2, "feature_normals")
+        Ein = None if noise_normals is None else _f64(noise_normals, 2, "noise_normals")
+        S, F = int(n_draws), omega.shape[0]
+        W, v, res = np.empty((S, F)), np.empty((S, self.N)), np.empty(S)
+        st, got = np.empty((S, 2), dtype=np.int32), np.zeros(1, dtype=np.int32)
+        check(_lib.mogp_local_sample_paths(self._h, int(emulator), int(kern), dptr(scale), float(sigma2), float(nugget), int(rank), float(rtol),
+                                           int(max_iter), dptr(omega), dptr(phase), F, S, float(amp), int(seed), int(stream), int(first_draw),
+                                           dptr(Win), dptr(Ein), dptr(W), dptr(v), iptr(st), dptr(res), iptr(got)))
+        return W, v, st[:, 0].astype(np.int64), st[:, 1].astype(bool), res, int(got[0])
+
     def loglik_exact(self, emulator, kern, scale, sigma2, nugget, rank, rtol, max_iter, g1, g2, grad=False, probe_terms=False,
                      return_panels=False):
         """The pieces of the exact log-likelihood (``mogp_local_loglik_exact``) as a dict: ``y_alpha``, ``alpha_alpha``, ``logdet_g``,
