@@ -564,6 +564,24 @@ int mogp_local_sample_paths(mogp_local* h, int emulator, int kernel_type, const 
                             double rtol, int max_iter, const double* omega, const double* phase, int n_features, int n_draws, double amp,
                             unsigned long long seed, unsigned stream, int first_draw, const double* W_in, const double* noise_in, double* W_out,
                             double* v_out, int* stat_out, double* residual_out, int* rank_out);
+/* Input derivatives at large designs, with respect to the RAW coordinates of the queries (x~ = x * scale, r2_ij = sum_d (q~_id - x~_jd)^2):
+     mogp_local_kmatvec_inputderiv: out (m, D, r) row-major,
+       out[i][d][c] = d/dx_d [sigma2 k(q_i, X) V]_c = 2 s_d sum_j sigma2 k'(r2_ij) (q~_id - x~_jd) V_jc,   k' = dk/dr2,
+     for queries (m, D) and V (N, r), r >= 1; there is no nugget term.  With V = alpha of mogp_local_predict_exact it is the derivative of the
+     exact mean, with V = v_s of mogp_local_sample_paths that of a path's update.
+     mogp_local_rff_inputderiv: out (S, m, D) row-major, the derivative of the entry (s, i) of mogp_local_rff at queries (m, D),
+       out[s][i][d] = -amp s_d sum_f W[s][f] omega[f][d] sin(phase[f] + omega[f] . q~_i).
+   Neither matrix is stored: a lane generates sigma2 k'(r2) -- or the sine of the argument mogp_local_rff builds, by the same operations in
+   the same order -- once per entry and feeds it to the fp64 MFMAs of a group of 8 dimensions, as k' times the DIFFERENCE q~_id - x~_jd (one
+   rounded subtraction: the form does not cancel on designs away from the origin) against the rows of V, or as the sine against the
+   rounded products omega_fd W_sf.  2 s_d and -amp s_d multiply once, at the end.  No atomics, and the summed index is not split: entry
+   (i, d, c) is the same bits for a repeated call, whatever the other queries, the other columns of V (rows of W) and max_points (queries
+   per pass, 0 = sized by the free device memory); a bit does depend on N, D, the kernel and the hyperparameters, nothing else.  A query
+   that coincides with a design point gets an exact zero from that point (k' is finite at r2 = 0 for both kernels). */
+int mogp_local_kmatvec_inputderiv(mogp_local* h, int kernel_type, const double* scale, double sigma2, const double* queries, int m, int D,
+                                  const double* V, int r, int max_points, double* out);
+int mogp_local_rff_inputderiv(mogp_local* h, const double* scale, const double* queries, int m, int D, const double* omega, const double* phase,
+                              int n_features, const double* W, int n_draws, double amp, int max_points, double* out);
 void mogp_local_destroy(mogp_local* h);
 /* device memory helpers so a host program can hand device-resident buffers to the *_dev calls */
 void* mogp_dev_malloc(unsigned long long bytes);

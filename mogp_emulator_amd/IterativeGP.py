@@ -47,13 +47,31 @@ on a random-Fourier-feature prior (Wilson et al. 2020),
 with the v_s as further columns of the solver, the feature matrix generated and never stored (``csrc/kernels_rff.hip``) and every random
 input a named Philox sub-stream, so that a path is a deterministic function of (seed, stream, emulator, draw index, n_features).
 
-Not covered: joint draws of paths over hyperparameters, input derivatives of a path, bounds of cross-covariances, a lower bound, more
-than 31 probes per evaluation (average over seeds), derivatives with respect to mean-function parameters, the symmetry of A in the
-product, several devices per handle, ``ProductMat52``, ``analytic_mean=True``, ``nugget="pivot"``.
+Input derivatives come from one further sweep over the same generated matrices (``csrc/kernels_iter.hip`` kinderiv_kernel,
+``csrc/kernels_rff.hip`` rff_inderiv_kernel), with respect to the RAW coordinates of a query:
+
+    G_c(x)_d = d/dx_d [sigma^2 k(x, X) V]_c = 2 s_d sum_j sigma^2 k'(r2_j) (x~_d - x~_jd) V_jc      ``matvec_inputderiv``; k' = dk/dr2, no nugget term
+    d mean / dx_d = dm/dx_d + G(x)_d at V = alpha                                                   ``predict(deriv=True)``
+    d g_s / dx_d  = -sqrt(2 sigma^2 / F) s_d sum_f W_sf omega_fd sin(omega_f . x~ + b_f)            ``PosteriorPaths.prior_gradient`` (with dm/dx_d)
+    d f_s / dx_d  = dm/dx_d + d g_s / dx_d + G_s(x)_d at V = v                                      ``PosteriorPaths.gradient``
+
+The entry is k' times the DIFFERENCE of the scaled coordinates: the expanded form x~_d sum g V - sum g x~_jd V cancels on designs away
+from the origin.
+
+Not covered: joint draws of paths over hyperparameters, second derivatives and derivatives of the variance, bounds of
+cross-covariances, a lower bound, more than 31 probes per evaluation (average over seeds), derivatives with respect to mean-function
+parameters, the symmetry of A in the product, several devices per handle, ``ProductMat52``, ``analytic_mean=True``, ``nugget="pivot"``.
 """
 import numpy as np
 
 from .LocalGP import MAX_D, _KERNELS, _create_native, _emulator_type, _fit_state, _hyperparameters, _mean_at, _points
+
+
+def _mean_inputderiv_at(meanfunc, params, x):
+    """(m, D) d m(x) / d x of the fixed mean function; exact zeros for the zero mean"""
+    if meanfunc is None or (meanfunc.get_n_params() == 0 and type(meanfunc).__name__ == "ZeroMeanFunc"):
+        return np.zeros(x.shape)
+    return np.ascontiguousarray(np.asarray(meanfunc.mean_inputderiv(x, params), dtype=np.float64).reshape(x.shape[1], x.shape[0]).T)
 
 MAX_RANK = 1024
 MAX_FEATURES = 65536     # random Fourier features of a path (csrc/predict_plan.h RFF_MAX_FEATURES)
@@ -79,10 +97,12 @@ class IterativePrediction(object):
     * ``converged``, ``residual``, ``iterations``   of the solve for the weights alpha (scalars, or (E,))
     * ``var_converged``, ``var_residual``           per query, of the solve behind its variance; None with ``unc=False`` and ``unc="bound"``
     * ``unc_kind``                      None, "exact" or "bound": what ``unc`` holds
-    * ``var_rank``                      with ``unc="bound"``: the columns of the variance cache that entered (a scalar, or (E,)); else None"""
+    * ``var_rank``                      with ``unc="bound"``: the columns of the variance cache that entered (a scalar, or (E,)); else None
+    * ``deriv``                         with ``deriv=True``: d mean / d x, (m, D) or (E, m, D), as the dense ``predict`` lays it out; else None"""
 
-    def __init__(self, mean, unc, converged, residual, iterations, var_converged, var_residual, var_rank=None, unc_kind=None):
+    def __init__(self, mean, unc, converged, residual, iterations, var_converged, var_residual, var_rank=None, unc_kind=None, deriv=None):
         self.mean, self.unc, self.converged, self.residual, self.iterations = mean, unc, converged, residual, iterations
+        self.deriv = deriv
         self.var_converged, self.var_residual = var_converged, var_residual
         self.var_rank, self.unc_kind = var_rank, ("exact" if unc is not None else None) if unc_kind is None else unc_kind
 
@@ -271,6 +291,33 @@ class PosteriorPaths(object):
 
     __call__ = evaluate
 
+    def _prior_gradient(self, native, testing, max_points):
+        kt, s, sigma2, nugget, meanfunc, mparams = self._hyper
+        g = native.rff_inputderiv(s, self.omega, self.phase, self.feature_normals, np.sqrt(2. * sigma2 / self.n_features), testing,
+                                  max_points=max_points)
+        return g + _mean_inputderiv_at(meanfunc, mparams, testing)[None, :, :]
+
+    def prior_gradient(self, testing, max_points=0):
+        """(n_draws, m, D) d(m + g_s) / dx at ``testing`` (m, D): the input derivative of ``prior``, analytic, from one product with the
+        sines of the features (never stored)"""
+        testing, max_points, native = self._queries("PosteriorPaths.prior_gradient", testing, max_points)
+        return self._prior_gradient(native, testing, max_points)
+
+    def gradient(self, testing, max_points=0):
+        """(n_draws, m, D) df_s / dx at ``testing`` (m, D), with respect to the raw coordinates: ``prior_gradient`` plus the derivative of
+        sigma^2 k(x, X) ``update``, one sweep over the generated cross covariance for all dimensions and draws.  ``max_points`` caps the
+        queries per device pass (0: sized by the free device memory) and changes no bit; neither do the other queries, the other draws or a
+        repeated call."""
+        testing, max_points, native = self._queries("PosteriorPaths.gradient", testing, max_points)
+        kt, s, sigma2, nugget, _, _ = self._hyper
+        out = self._prior_gradient(native, testing, max_points)
+        out += np.transpose(native.kmatvec_inputderiv(kt, s, sigma2, self.update, testing, max_points=max_points), (2, 0, 1))
+        return out
+
+    def value_and_gradient(self, testing, max_points=0):
+        """``(evaluate(testing), gradient(testing))``, bit for bit: two sweeps"""
+        return self.evaluate(testing, max_points), self.gradient(testing, max_points)
+
 
 def _check_normals(who, name, z, S, cols, what):
     if z is None:
@@ -395,6 +442,22 @@ class IterativeGP(object):
         out = self._native.kmatvec(kt, s, sigma2, nugget, V, queries=testing)
         return out[:, 0] if vector else out
 
+    def matvec_inputderiv(self, V, testing, emulator=0, max_points=0):
+        """d/dx [sigma^2 k(testing, X) V] with respect to the raw coordinates of ``testing`` (m, D) at the hyperparameters of ``emulator``:
+        (m, D, c) for V (N, c), (m, D) for a vector V (N,); entry (i, d, c) = 2 s_d sum_j sigma^2 k'(r2_ij) (q~_id - x~_jd) V_jc, no nugget
+        term.  Column c depends on column c of V alone and row i on query i alone, bit for bit; ``max_points`` caps the queries per device
+        pass (0: sized by the free device memory) and changes no bit."""
+        who = "IterativeGP.matvec_inputderiv"
+        V, vector = self._columns(who, "V", V)
+        testing = _points("testing", who, testing, self._D)
+        if int(max_points) != max_points or int(max_points) < 0:
+            raise ValueError("%s: max_points must not be negative" % who)
+        if testing.shape[0] >= 2 ** 31:
+            raise ValueError("%s: at most 2^31 - 1 testing points per call" % who)
+        e, (kt, s, sigma2, nugget, _, _) = self._emulator(who, emulator)
+        out = self._native.kmatvec_inputderiv(kt, s, sigma2, V, testing, max_points=int(max_points))
+        return out[:, :, 0] if vector else out
+
     def preconditioner(self, emulator=0):
         """(L (N, rank reached), pivots (rank reached,) int64) of the partial pivoted Cholesky factor the solves of ``emulator`` are
         preconditioned with; the rank reached is below ``precond_rank`` when the remaining diagonal ran out."""
@@ -476,7 +539,7 @@ class IterativeGP(object):
                               stream=sub, first_draw=int(first_draw), emulator=e)
 
     # ---- prediction ----------------------------------------------------------------------------------------------------------------------
-    def predict(self, testing, unc=False, include_nugget=True, max_points=0):
+    def predict(self, testing, unc=False, include_nugget=True, max_points=0, deriv=False):
         """Predict at ``testing`` (m, D) from the whole design; returns an ``IterativePrediction``.
 
         ``unc=True`` solves one system per query (in blocks of 32): exact, and as expensive as that sounds.  ``unc="bound"`` puts
@@ -485,7 +548,9 @@ class IterativeGP(object):
         ``ValueError``.  The mean is the same bits whatever ``unc``.  ``include_nugget``: add the
         nugget to ``unc`` as ``predict`` of the emulator does.  ``max_points`` caps the queries per device pass (0: sized by the free device
         memory) and changes no bit of the result.  Emulator e of a ``MultiOutputGP_GPU`` uses its own hyperparameters and its own
-        preconditioner; the emulators run one after another on the same handle, and row e equals the single-emulator call bit for bit."""
+        preconditioner; the emulators run one after another on the same handle, and row e equals the single-emulator call bit for bit.
+        ``deriv=True``: ``deriv`` (m, D), or (E, m, D), the derivative of the mean with respect to the inputs as the dense ``predict``
+        returns it -- the mean function's plus ``matvec_inputderiv`` at the kept weights --; every other field keeps its bits."""
         who = "IterativeGP.predict"
         if isinstance(unc, str):
             if unc != "bound":
@@ -503,20 +568,25 @@ class IterativeGP(object):
             raise RuntimeError("%s: the handle has been closed" % who)
         rows = []
         for e, (kt, s, sigma2, nugget, meanfunc, mparams) in enumerate(self._hyper):
-            mean, var, (it, cv, res), vstats, _ = self._native.predict_exact(e, kt, s, sigma2, nugget, self._p, self._rtol, self._max_iter,
-                                                                             include_nugget, testing, unc=exact, max_points=int(max_points))
+            mean, var, (it, cv, res), vstats, alpha = self._native.predict_exact(e, kt, s, sigma2, nugget, self._p, self._rtol, self._max_iter,
+                                                                                 include_nugget, testing, unc=exact, max_points=int(max_points),
+                                                                                 return_alpha=bool(deriv))
             mean += _mean_at(meanfunc, mparams, testing)
+            dm = None
+            if deriv:
+                dm = _mean_inputderiv_at(meanfunc, mparams, testing)
+                dm += self._native.kmatvec_inputderiv(kt, s, sigma2, alpha.reshape(-1, 1), testing, max_points=int(max_points))[:, :, 0]
             vr = None
             if bound:
                 var, vr, _ = self._native.variance_bound(kt, s, sigma2, nugget, self._p, include_nugget, testing, max_points=int(max_points))
-            rows.append((mean, var, cv, res, it, vstats[1] if exact else None, vstats[2] if exact else None, vr))
+            rows.append((mean, var, cv, res, it, vstats[1] if exact else None, vstats[2] if exact else None, vr, dm))
         kind = "bound" if bound else "exact" if exact else None
         if self._single:
-            return IterativePrediction(*rows[0], unc_kind=kind)
+            return IterativePrediction(*rows[0][:8], unc_kind=kind, deriv=rows[0][8])
         cols = list(zip(*rows))
         return IterativePrediction(np.stack(cols[0]), np.stack(cols[1]) if unc else None, np.array(cols[2]), np.array(cols[3]), np.array(cols[4]),
                                    np.stack(cols[5]) if exact else None, np.stack(cols[6]) if exact else None,
-                                   np.array(cols[7]) if bound else None, kind)
+                                   np.array(cols[7]) if bound else None, kind, np.stack(cols[8]) if deriv else None)
 
     # ---- the variance bound -----------------------------------------------------------------------------------------------------------------
     def variance_bound(self, testing, emulator=0, include_nugget=True, rank=None, max_points=0):

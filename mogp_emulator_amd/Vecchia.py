@@ -343,8 +343,9 @@ class VecchiaGP(object):
         """``IterativeGP.predict`` at the fitted theta (or ``theta``) on the same native handle: the exact posterior of all N points by
         preconditioned conjugate gradients, where ``predict`` answers from the neighbours of a query.  ``precond_rank``, ``rtol`` and
         ``max_iter`` of ``kw`` go to ``IterativeGP``, the rest to its ``predict`` (``unc="bound"`` among them: the conservative variance of
-        ``IterativeGP.variance_bound`` in place of one solve per query).  Returns an ``IterativePrediction``; the nugget must be
-        positive.  ``predict`` is unchanged."""
+        ``IterativeGP.variance_bound`` in place of one solve per query; ``deriv=True``: the derivative of the mean with respect to the
+        inputs, ``IterativePrediction.deriv`` (m, D)).  Returns an ``IterativePrediction``; the nugget must be positive.  ``predict``
+        is unchanged."""
         options = {k: kw.pop(k) for k in ("precond_rank", "rtol", "max_iter") if k in kw}
         return self._exact_view("VecchiaGP.predict_exact", theta, options).predict(testing, **kw)
 

@@ -25,7 +25,8 @@ mogp_emulator_amd -- MI355X (gfx950) native fit + predict backend for mogp_emula
   IterativeGP.py   exact prediction for designs beyond the dense path: matrix-free preconditioned conjugate gradients on the whole design, on the device;
                    the exact log-likelihood and its gradient by stochastic Lanczos quadrature from one such solve; variance_bound: a
                    conservative predictive variance from a cached low-rank factor, one product per batch of queries and no solve;
-                   sample_paths: posterior draws as functions (pathwise conditioning on a random-Fourier-feature prior)
+                   sample_paths: posterior draws as functions (pathwise conditioning on a random-Fourier-feature prior);
+                   predict(deriv=True), matvec_inputderiv and PosteriorPaths.gradient: input derivatives of the mean and of the paths
   dist.py          one-process-per-GPU sharding of emulators + single gather (torch.distributed/RCCL)
 """
 from .LibGPGPU import HAVE_LIBGPGPU, gpu_usable            # noqa: F401

@@ -181,6 +181,10 @@ SIGNATURES = {
     "mogp_local_sample_paths": (c_int, [c_void_p, c_int, c_int, c_double_p, c_double, c_double, c_int, c_double, c_int, c_double_p, c_double_p, c_int,
                                         c_int, c_double, c_ulonglong, c_uint, c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_int_p,
                                         c_double_p, c_int_p]),
+    "mogp_local_kmatvec_inputderiv": (c_int, [c_void_p, c_int, c_double_p, c_double, c_double_p, c_int, c_int, c_double_p, c_int, c_int,
+                                              c_double_p]),
+    "mogp_local_rff_inputderiv": (c_int, [c_void_p, c_double_p, c_double_p, c_int, c_int, c_double_p, c_double_p, c_int, c_double_p, c_int, c_double,
+                                          c_int, c_double_p]),
     "mogp_local_destroy": (None, [c_void_p]),
     "mogp_profile_enable": (c_int, [c_int]),
     "mogp_profile_reset": (c_int, []),

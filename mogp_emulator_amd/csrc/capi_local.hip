@@ -127,6 +127,24 @@ int mogp_local_sample_paths(mogp_local* h, int emulator, int kernel_type, const 
   });
 }
 
+int mogp_local_kmatvec_inputderiv(mogp_local* h, int kernel_type, const double* scale, double sigma2, const double* queries, int m, int D,
+                                  const double* V, int r, int max_points, double* out) {
+  return guarded([&] {
+    if (!h || !h->gp) throw std::runtime_error("kmatvec_inputderiv: null handle");
+    if (D != h->gp->D) throw std::runtime_error("kmatvec_inputderiv: queries must have D columns");
+    h->gp->kmatvec_inputderiv(kernel_type, scale, sigma2, queries, m, V, r, max_points, out);
+  });
+}
+
+int mogp_local_rff_inputderiv(mogp_local* h, const double* scale, const double* queries, int m, int D, const double* omega, const double* phase,
+                              int n_features, const double* W, int n_draws, double amp, int max_points, double* out) {
+  return guarded([&] {
+    if (!h || !h->gp) throw std::runtime_error("rff_inputderiv: null handle");
+    if (D != h->gp->D) throw std::runtime_error("rff_inputderiv: queries and frequencies must have D columns");
+    h->gp->rff_inputderiv(scale, queries, m, omega, phase, n_features, W, n_draws, amp, max_points, out);
+  });
+}
+
 void mogp_local_destroy(mogp_local* h) {
   if (!h) return;
   (void)guarded([&] {

@@ -373,6 +373,15 @@ class LocalGP {
   void sample_paths(int e, int kt, const double* scale, double sigma2, double nugget, int rank, double rtol, int max_iter, const double* omega,
                     const double* phase, int F, int S, double amp, unsigned long long seed, unsigned stream, int first_draw, const double* W_in,
                     const double* noise_in, double* W_out, double* v_out, int* stat_i, double* residual, int* rank_out);
+  // Input derivatives at large designs (DESIGN.md section 3 "Input derivatives at large designs"), with respect to the RAW query coordinates.
+  // kmatvec_inputderiv: out (m, D, r) row-major, out[i][d][c] = d/dx_d [sigma2 k(q_i, X) V]_c = 2 s_d sum_j sigma2 k'(r2_ij) (q~_id - x~_jd) V_jc
+  // for queries (m, D) and V (N, r); no nugget term.  rff_inputderiv: out (S, m, D), out[s][i][d] = d/dx_d of rff's entry (s, i)
+  // = -amp s_d sum_f W_sf omega_fd sin(phase_f + omega_f . q~_i).  Column c / draw s depends on column c of V / row s of W alone, row i on
+  // query i alone; max_points caps the queries per pass (0: sized by the free memory) and changes no bit.
+  void kmatvec_inputderiv(int kt, const double* scale, double sigma2, const double* queries, long m, const double* V, int r, int max_points,
+                          double* out);
+  void rff_inputderiv(const double* scale, const double* queries, long m, const double* omega, const double* phase, int F, const double* W, int S,
+                      double amp, int max_points, double* out);
   int device_id() const { return device; }
   const long N;
   const int D, E;

@@ -326,6 +326,44 @@ void LocalGP::kmatvec(int kt, const double* scale, double sigma2, double nugget,
   }
 }
 
+void LocalGP::kmatvec_inputderiv(int kt, const double* scale, double sigma2, const double* queries, long m, const double* V, int r, int max_points,
+                                 double* out) {
+  const std::string who = "kmatvec_inputderiv";
+  if (!scale || !queries || !V || !out) throw std::runtime_error("kmatvec_inputderiv: null pointer");
+  local_check_kernel(who, kt);
+  local_check_hyper(who, D, scale, sigma2, 0., 0.);
+  if (r < 1) throw std::runtime_error("kmatvec_inputderiv: at least one column is needed");
+  if (m < 1 || m > INT_MAX) throw std::runtime_error("kmatvec_inputderiv: at least one query is needed");
+  DeviceGuard guard(device);
+  hipStream_t st = nullptr;
+  size_t free_b = 0, total_b = 0;
+  HIPCK(hipMemGetInfo(&free_b, &total_b));
+  const InderivPlan plan = kinderiv_plan(who, m, D, N, r, (double)free_b, max_points);
+  const size_t P = (size_t)plan.points, n = (size_t)N, wide = (size_t)D * ITER_COLS;
+  DevBuf<double> dV(n * ITER_COLS), dO(P * wide);
+  QueryPass pass(P, D);
+  SyncOnUnwind sync{st};
+  ensure_scaled(scale, st);
+  std::vector<double> hv(n * ITER_COLS), ho(P * wide);
+  for (int c0 = 0; c0 < r; c0 += ITER_COLS) {
+    const int cols = std::min(ITER_COLS, r - c0), nb = cols > 16 ? 2 : 1;
+    std::fill(hv.begin(), hv.end(), 0.0);                    // the columns behind `cols` of the last block are exact zeros
+    rows_to_panel(V, n, (size_t)r, (size_t)c0, (size_t)cols, hv.data(), n, 0);
+    HIPCK(hipMemcpyAsync(dV, hv.data(), n * 16 * nb * sizeof(double), hipMemcpyHostToDevice, st));
+    for (long p0 = 0; p0 < m; p0 += plan.points) {
+      const long mc = std::min<long>(plan.points, m - p0);
+      const double* rows = pass.load(queries, p0, mc, dScale, st);
+      launch_kinderiv(rows, mc, dXs, N, D, kt, sigma2, dScale, dV, N, nb, dO, mc, st);
+      HIPCK(hipGetLastError());
+      HIPCK(hipMemcpyAsync(ho.data(), dO, (size_t)mc * D * 16 * nb * sizeof(double), hipMemcpyDeviceToHost, st));
+      HIPCK(hipStreamSynchronize(st));
+      // dimension d is the panel of the columns [16 nb d, 16 nb d + cols) and the window [c0, c0 + cols) of the rows out[p0 + i][d][.]
+      for (int d = 0; d < D; ++d)
+        panel_to_rows(out + ((size_t)p0 * D + d) * r, (size_t)mc, (size_t)D * r, (size_t)c0, (size_t)cols, ho.data(), (size_t)mc, (size_t)d * 16 * nb);
+    }
+  }
+}
+
 int LocalGP::precondition(int kt, const double* scale, double sigma2, double nugget, int rank, int* piv_out, double* L_out) {
   const char* who = "precondition";
   if (!scale) throw std::runtime_error("precondition: null pointer");

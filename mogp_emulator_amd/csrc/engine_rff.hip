@@ -1,8 +1,10 @@
 // Pathwise posterior draws on the LocalGP handle (engine.h; DESIGN.md section 3 "Pathwise posterior draws"): a draw of the posterior is the
 // function  f_s(.) = g_s(.) + sigma2 k(., X) v_s  with a random-Fourier-feature prior draw g_s = amp Phi(.) W_s and the update
-// v_s = A^-1 (y - g_s(X) - sqrt(nugget) e_s)  (Matheron's rule; Wilson et al. 2020).  Two entry points, each as its steps: null pointers, the
-// named refusals and the plan (predict_plan.h: plain arithmetic, checked on the host by tests/c/rff_plan_check.cpp), the launches, the copies.
+// v_s = A^-1 (y - g_s(X) - sqrt(nugget) e_s)  (Matheron's rule; Wilson et al. 2020).  Three entry points, each as its steps: null pointers, the
+// named refusals and the plan (predict_plan.h: plain arithmetic, checked on the host by tests/c/rff_plan_check.cpp and
+// inputderiv_plan_check.cpp), the launches, the copies.
 //   rff            the feature product at the design or at queries, in passes of points and of ITER_COLS draws
+//   rff_inputderiv its derivative with respect to the raw coordinates of the queries, (draws, points, D), in the same passes
 //   sample_paths   the weights' normals, g_s(X), the right-hand sides and the solves, ITER_COLS draws at a time through IterSolver::solve as it is
 // Nothing of the design-sized work crosses the bus but v and, where the device generated them, the weights' normals.
 #include "engine_internal.h"
@@ -57,6 +59,50 @@ void LocalGP::rff(const double* scale, const double* queries, long m, const doub
       for (int c = 0; c < cols; ++c)
         HIPCK(hipMemcpyAsync(out + (size_t)(c0 + c) * M + p0, dO.get() + (size_t)c * mc, (size_t)mc * sizeof(double), hipMemcpyDeviceToHost, st));
       HIPCK(hipStreamSynchronize(st));
+    }
+  }
+}
+
+void LocalGP::rff_inputderiv(const double* scale, const double* queries, long m, const double* omega, const double* phase, int F, const double* W,
+                             int S, double amp, int max_points, double* out) {
+  const std::string who = "rff_inputderiv";
+  if (!scale || !queries || !omega || !phase || !W || !out) throw std::runtime_error("rff_inputderiv: null pointer");
+  local_check_scales(who, D, scale);
+  rff_check_counts(who, F, S, 0);
+  if (m < 1 || m > INT_MAX) throw std::runtime_error("rff_inputderiv: at least one query is needed");
+  rff_check_inputs(who, D, F, omega, phase, amp);
+  require_finite(W, (size_t)S * F, "rff_inputderiv: the weights must be finite");
+  DeviceGuard guard(device);
+  hipStream_t st = nullptr;
+  size_t free_b = 0, total_b = 0;
+  HIPCK(hipMemGetInfo(&free_b, &total_b));
+  const InderivPlan plan = rff_inderiv_plan(who, m, D, F, S, (double)free_b, max_points);
+  const size_t P = (size_t)plan.points, f = (size_t)F, wide = (size_t)D * ITER_COLS;
+  DevBuf<double> dOm(f * D), dPh(f), dW(f * ITER_COLS), dO(P * wide);
+  QueryPass pass(P, D);
+  SyncOnUnwind sync{st};
+  ensure_scaled(scale, st);
+  HIPCK(hipMemcpyAsync(dOm, omega, f * D * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCK(hipMemcpyAsync(dPh, phase, f * sizeof(double), hipMemcpyHostToDevice, st));
+  std::vector<double> ho(P * wide);
+  for (long p0 = 0; p0 < m; p0 += plan.points) {
+    const long mc = std::min<long>(plan.points, m - p0);
+    const double* rows = pass.load(queries, p0, mc, dScale, st);
+    for (int c0 = 0; c0 < S; c0 += ITER_COLS) {
+      const int cols = std::min(ITER_COLS, S - c0), nb = cols > 16 ? 2 : 1;
+      // (S, F) row-major is a panel of S columns already; the columns behind `cols` of the last block are exact zeros
+      HIPCK(hipMemsetAsync(dW, 0, f * 16 * nb * sizeof(double), st));
+      HIPCK(hipMemcpyAsync(dW, W + (size_t)c0 * f, f * cols * sizeof(double), hipMemcpyHostToDevice, st));
+      launch_rff_inderiv(rows, mc, dOm, dPh, F, D, dW, F, nb, amp, dScale, dO, mc, st);
+      HIPCK(hipGetLastError());
+      HIPCK(hipMemcpyAsync(ho.data(), dO, (size_t)mc * D * 16 * nb * sizeof(double), hipMemcpyDeviceToHost, st));
+      HIPCK(hipStreamSynchronize(st));
+      // out[c0 + c][p0 + i][d] = the panel's column 16 nb d + c
+      for (int c = 0; c < cols; ++c)
+        for (long i = 0; i < mc; ++i) {
+          double* dst = out + ((size_t)(c0 + c) * m + (size_t)(p0 + i)) * D;
+          for (int d = 0; d < D; ++d) dst[d] = ho[((size_t)d * 16 * nb + c) * mc + i];
+        }
     }
   }
 }

@@ -9,6 +9,8 @@
 //                        by that lane -- and 4 rows of W x 16 columns as its B operand.  No atomics and no split of f across workgroups: the
 //                        sum of a row runs over f in one fixed order, and the MFMA keeps its columns apart.  Entries of rows >= M and of
 //                        features >= F are exact zeros; amp multiplies once, in the store.
+//   rff_inderiv_kernel   Out = d/dx_d [amp Phi(P) W] = -amp s_d sum_f sin(t_if) omega_fd W_f for a group of INDERIV_DG dimensions per workgroup: the
+//                        same tiling and the same argument, the sine as the A operand shared by the dimensions, omega_fd W_fc as the B operand
 //   rff_normals_kernel   W[c][f] = normal(seed, stream, draw0 + c, f) of philox_dev.h, one thread per pair of features
 //   rff_rhs_kernel       B[c][i] = y_i - g[c][i] - root * noise, one row per thread; the noise is the panel E or, without one,
 //                        normal(seed, stream, draw0 + c, i); columns >= cols are exact zeros
@@ -86,6 +88,86 @@ __global__ __launch_bounds__(256) void rff_kernel(const double* __restrict__ Ps,
     }
 }
 
+// Out[(d * 16 NB + c) * ldo + i] = -amp s_d sum_f sin(t_if) (omega_fd W_fc): rff_kernel with the sine of the same argument -- t_if built by the
+// same FMAs in the same order -- as the A operand, which the DG dimensions of group blockIdx.y share: the columns (d, c) of the operand
+// omega_fd W_fc are just more column blocks.  The operand's entry is one rounded product of the staged frequency and the staged weight, formed
+// by the lane that feeds it to the MFMA (staging the products would take 64 x 16 NB DG doubles of LDS, 131 KB, for the same bits); the
+// sines are never stored.  A group repeats the arguments and the sines.  -amp s_d multiplies once, in the store.  LDS: rff_lds_bytes(D, NB).
+template <int NB, int DG>
+__global__ __launch_bounds__(256, 2) void rff_inderiv_kernel(const double* __restrict__ Ps, int M, const double* __restrict__ Om,
+                                                          const double* __restrict__ Ph, int F, int D, const double* __restrict__ W, size_t ldw,
+                                                          double amp, const double* __restrict__ scale, double* __restrict__ Out, size_t ldo) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  constexpr int LDV = 16 * NB + 1;
+  double* sa = sm;
+  double* so = sa + (size_t)RF_ROWS * D;
+  double* sp = so + (size_t)RF_ROWS * D;
+  double* sv = sp + RF_ROWS;
+  const int t = threadIdx.x, lane = t & 63;
+  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int i0 = blockIdx.x * RF_ROWS, d0 = blockIdx.y * DG;
+  const int il = w * 16 + (lane & 15), jq = lane >> 4, cl = lane & 15;
+  const int gi = i0 + il;
+  stage_rows(Ps, M, D, i0, sa);
+  v4d acc[DG][NB];
+#pragma unroll
+  for (int dd = 0; dd < DG; ++dd)
+#pragma unroll
+    for (int b = 0; b < NB; ++b) acc[dd][b] = v4d{0.0, 0.0, 0.0, 0.0};
+  for (int f0 = 0; f0 < F; f0 += RF_ROWS) {
+    __syncthreads();                                         // the previous tile has been read
+    stage_rows(Om, F, D, f0, so);
+    if (t < RF_ROWS) sp[t] = (f0 + t < F) ? Ph[f0 + t] : 0.0;
+    for (int e = t; e < RF_ROWS * 16 * NB; e += 256) {
+      const int f = e & 63, c = e >> 6;
+      sv[f * LDV + c] = (f0 + f < F) ? W[(size_t)c * ldw + (size_t)(f0 + f)] : 0.0;
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int g = 0; g < 4; ++g) {                            // 16 features: four MFMA steps of four
+      double ph[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) ph[u] = sp[(g * 4 + u) * 4 + jq];
+      for (int d = 0; d < D; ++d) {
+        const double a = sa[d * 64 + il];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) ph[u] = __builtin_fma(so[d * 64 + (g * 4 + u) * 4 + jq], a, ph[u]);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int fl = (g * 4 + u) * 4 + jq;
+        double sn = sin(ph[u]);
+        if (f0 + fl >= F || gi >= M) sn = 0.0;
+        double wv[NB];
+#pragma unroll
+        for (int b = 0; b < NB; ++b) wv[b] = sv[fl * LDV + b * 16 + cl];
+#pragma unroll
+        for (int dd = 0; dd < DG; ++dd) {
+          if (d0 + dd < D) {                                 // (the same for the whole workgroup)
+            const double om = so[(d0 + dd) * 64 + fl];
+#pragma unroll
+            for (int b = 0; b < NB; ++b) acc[dd][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(sn, om * wv[b], acc[dd][b], 0, 0, 0);
+          }
+        }
+      }
+    }
+  }
+  // register reg of a C fragment is row i0 + 16 w + jq + 4 reg, column cl
+#pragma unroll
+  for (int dd = 0; dd < DG; ++dd) {
+    if (d0 + dd < D) {
+      const double coef = -(amp * scale[d0 + dd]);
+#pragma unroll
+      for (int b = 0; b < NB; ++b)
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+          const int i = i0 + w * 16 + jq + 4 * reg;
+          if (i < M) Out[((size_t)(d0 + dd) * (16 * NB) + (size_t)(b * 16 + cl)) * ldo + (size_t)i] = coef * acc[dd][b][reg];
+        }
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void rff_normals_kernel(unsigned long long seed, unsigned stream, unsigned draw0, int n, double* __restrict__ W,
                                                           size_t ldw) {
   const long p = (long)blockIdx.x * 256 + threadIdx.x;
@@ -131,6 +213,18 @@ void launch_rff(const double* Ps, long M, const double* omega, const double* pha
                      F, D, W, (size_t)ldw, amp, Out, (size_t)ldo);
   // algorithmic: per entry 2 D operations of the argument and ~40 of the cosine, then 2 per column; the staged tiles are read once per workgroup
   prof_end("rff", st, (double)M * (double)F * (2.0 * D + 40.0 + 32.0 * nb), 8.0 * (double)rf_blocks(M, RF_ROWS) * (double)F * (D + 1.0 + 16.0 * nb));
+}
+
+void launch_rff_inderiv(const double* Ps, long M, const double* omega, const double* phase, int F, int D, const double* W, long ldw, int nb, double amp,
+                        const double* scale, double* Out, long ldo, hipStream_t st) {
+  if (M < 1 || F < 1) return;
+  const unsigned groups = rf_blocks(D, INDERIV_DG);
+  prof_begin("rff_inderiv", st);
+  const auto kern = nb == 1 ? rff_inderiv_kernel<1, INDERIV_DG> : rff_inderiv_kernel<2, INDERIV_DG>;
+  hipLaunchKernelGGL(kern, dim3(rf_blocks(M, RF_ROWS), groups), dim3(256), rff_lds_bytes(D, nb), st, Ps, (int)M, omega, phase, F, D, W, (size_t)ldw, amp, scale, Out, (size_t)ldo);
+  // algorithmic: every group of dimensions forms its arguments and sines again (2 D and ~40), then per dimension and column 1 of the operand and 2
+  prof_end("rff_inderiv", st, (double)M * (double)F * (groups * (2.0 * D + 40.0) + D * 48.0 * nb),
+           8.0 * (double)rf_blocks(M, RF_ROWS) * (double)F * groups * (D + 1.0 + 16.0 * nb));
 }
 
 void launch_rff_normals(unsigned long long seed, unsigned stream, unsigned draw0, int cols, long n, double* W, long ldw, hipStream_t st) {

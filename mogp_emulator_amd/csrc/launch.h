@@ -355,6 +355,17 @@ constexpr int ITER_DOT_BLOCK = 1024;    // rows per workgroup of a column-wise d
 // operand of v_mfma_f64_16x16x4_f64 and never stored.  A workgroup owns 64 rows and sweeps the columns j in ascending tiles of 64.
 void launch_kmatvec(const double* As, long M, const double* Bs, long N, int D, int kt, double sigma2, double nug, bool same, const double* V,
                     long ldv, int nb, double* Out, long ldo, hipStream_t st);
+// The input derivative of the rectangular product (DESIGN.md section 3 "Input derivatives at large designs"):
+//   Out[(d * 16 nb + c) * ldo + i] = 2 scale[d] sum_j sigma2 k'(r2(Qs_i, Xs_j)) (Qs_id - Xs_jd) V[c * ldv + j]      d < D, c < 16 nb, i < M
+// the derivative of sum_j sigma2 k(r2(q_i * scale, Xs_j)) V_jc with respect to the RAW coordinate d of query i (no nugget: it has no
+// derivative).  Qs (M, D), Xs (N, D) scaled coordinates, scale (D) on the device, V a panel of 16 nb columns; nb = 1 or 2.  launch_kmatvec's
+// tiling: the grid is (ceil(M / 64), ceil(D / INDERIV_DG)), a workgroup owns 64 queries and INDERIV_DG dimensions and sweeps the design in
+// ascending tiles of 64; the lane generates r2 and sigma2 k' once per entry and feeds k' times the DIFFERENCE of the staged coordinates
+// to the MFMAs of every dimension of its group against one staged B operand.  No atomics and no split of j: one fixed order of the sum; column
+// c depends on column c of V alone, row i on query i alone; rows >= M and columns >= N are exact zeros, a query on a design point gets an
+// exact zero from that point.
+void launch_kinderiv(const double* Qs, long M, const double* Xs, long N, int D, int kt, double sigma2, const double* scale, const double* V, long ldv,
+                     int nb, double* Out, long ldo, hipStream_t st);
 // Partial pivoted Cholesky of sigma2 k(Xs, Xs), one step per call of launch_pchol_step: state[0] = the rank reached, state[1] = 1 once the
 // largest remaining diagonal was <= 0 (later steps then do nothing); piv (rank) and the pivot's diagonal dmax (rank) stay on the device.
 // L (N rows, `rank` columns, ld N); diag (N) the remaining diagonal; part: 2 * ceil(N / 1024) doubles and as many ints.
@@ -428,6 +439,13 @@ void launch_kvar(const double* Qs, long M, const double* Xs, long N, int D, int 
 // fixed order of the sum, no atomics; column c of Out depends on column c of W alone, row i on point i alone.
 void launch_rff(const double* Ps, long M, const double* omega, const double* phase, int F, int D, const double* W, long ldw, int nb, double amp,
                 double* Out, long ldo, hipStream_t st);
+// The input derivative of the feature product:
+//   Out[(d * 16 nb + c) * ldo + i] = -(amp scale[d]) sum_f sin(t_if) (omega[f][d] W[c * ldw + f])      d < D, c < 16 nb, i < M
+// with t_if built as launch_rff builds it (the same FMAs in the same order).  The grid is (ceil(M / 64), ceil(D / INDERIV_DG)): the sine is the
+// A operand of the MFMAs of every dimension of the group, the B operand is one rounded product of the staged frequency and weight.  The
+// sines are never stored; no atomics, one fixed order of the sum; column c depends on column c of W alone, row i on point i alone.
+void launch_rff_inderiv(const double* Ps, long M, const double* omega, const double* phase, int F, int D, const double* W, long ldw, int nb, double amp,
+                        const double* scale, double* Out, long ldo, hipStream_t st);
 // W[c * ldw + j] = the normal j of draw draw0 + c of (seed, stream) (philox_dev.h) for c < cols, j < n
 void launch_rff_normals(unsigned long long seed, unsigned stream, unsigned draw0, int cols, long n, double* W, long ldw, hipStream_t st);
 // The right-hand sides of the paths, panels of ITER_COLS columns (ld N): B[c][i] = fma(-root, noise, y[i] - g[c][i]) for c < cols, exact zeros

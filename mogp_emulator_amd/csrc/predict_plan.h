@@ -512,6 +512,49 @@ inline RffPlan rff_plan(const std::string& who, long m, int D, int F, long S, do
   return {points, (S + ITER_PLAN_COLS - 1) / ITER_PLAN_COLS};
 }
 
+// Input derivatives at large designs (engine_iter.hip kmatvec_inputderiv, engine_rff.hip rff_inputderiv): d/dx_d of the rectangular product and
+// of the feature product, (points, D, columns) outputs.
+//   INDERIV_DG              dimensions per workgroup of the two kernels: INDERIV_DG x 2 accumulator fragments of 4 doubles per lane
+//   inderiv_point_bytes     per point of a pass: raw and scaled coordinates and the D x ITER_PLAN_COLS output columns
+//   kinderiv_fixed_bytes    held whatever the points: one panel of ITER_PLAN_COLS columns of V (N each); the feature product holds rff_fixed_bytes
+//   kinderiv_plan / rff_inderiv_plan   points per pass: max_points where given, else what the rest of half of the free memory holds, at most m and
+//                           LOCAL_MAX_PASS, at least one; blocks = blocks of ITER_PLAN_COLS columns; groups = ceil(D / INDERIV_DG), the second
+//                           grid dimension.  No bit of a result depends on any of them.
+constexpr int INDERIV_DG = 8;
+struct InderivPlan {
+  long points;      // points per pass
+  long blocks;      // blocks of ITER_PLAN_COLS columns
+  int groups;       // groups of INDERIV_DG dimensions
+};
+inline double inderiv_point_bytes(int D) { return 8.0 * (double)D * (2.0 + ITER_PLAN_COLS); }
+inline double kinderiv_fixed_bytes(long N) { return 8.0 * ITER_PLAN_COLS * (double)N; }
+inline InderivPlan inderiv_plan_of(const std::string& who, long m, int D, long cols, double fixed, const std::string& held, double free_bytes,
+                                   int max_points) {
+  if (max_points < 0) throw std::runtime_error(who + ": max_points must not be negative");
+  const double budget = 0.5 * free_bytes - fixed, per = inderiv_point_bytes(D);
+  if (budget < per)
+    throw std::runtime_error(who + ": " + std::to_string((long long)(fixed + per)) + " bytes of device memory for " + held +
+                             " and one point are more than half of the free device memory");
+  const long want = std::max<long>(1, std::min<long>(m, LOCAL_MAX_PASS));
+  long points;
+  if (max_points > 0) {
+    points = std::min<long>(want, max_points);
+    if ((double)points * per > budget)
+      throw std::runtime_error(who + ": " + std::to_string(points) + " points per pass need more than half of the free device memory; use a smaller max_points");
+  } else {
+    points = std::min<long>(want, (long)std::floor(budget / per));
+  }
+  return {points, (cols + ITER_PLAN_COLS - 1) / ITER_PLAN_COLS, (D + INDERIV_DG - 1) / INDERIV_DG};
+}
+inline InderivPlan kinderiv_plan(const std::string& who, long m, int D, long N, long r, double free_bytes, int max_points) {
+  if (r < 1) throw std::runtime_error(who + ": at least one column is needed");
+  return inderiv_plan_of(who, m, D, r, kinderiv_fixed_bytes(N), "a panel of " + std::to_string(N) + " rows", free_bytes, max_points);
+}
+inline InderivPlan rff_inderiv_plan(const std::string& who, long m, int D, int F, long S, double free_bytes, int max_points) {
+  rff_check_counts(who, F, S, 0);
+  return inderiv_plan_of(who, m, D, S, rff_fixed_bytes(D, F), std::to_string(F) + " features", free_bytes, max_points);
+}
+
 // Stage 2 of predict_mixture: the normalised weights of the S samples of one emulator, from their negative log-posteriors F and
 // ok flags and EITHER explicit weights w_in OR the log proposal density log_q (up to a constant).  With log_q:
 //   l_s = -(F_s - F_min) - (log_q_s - log_q_a),  a = the first ok sample with F_a = F_min over the ok samples,  w_s = exp(l_s - max l)

@@ -1482,6 +1482,32 @@ class LocalGP_GPU(object):
                                   omega.shape[0], dptr(W), W.shape[0], float(amp), int(max_points), dptr(out)))
         return out
 
+    # ---- input derivatives at large designs (csrc/kernels_iter.hip kinderiv_kernel, csrc/kernels_rff.hip rff_inderiv_kernel) ----
+    def kmatvec_inputderiv(self, kern, scale, sigma2, V, queries, max_points=0):
+        """(m, D, r) d/dx_d [sigma2 k(queries, X) V] with respect to the raw coordinates of ``queries`` (m, D); V (N, r)"""
+        if not self._h:
+            raise RuntimeError("kmatvec_inputderiv: the handle has been closed")
+        scale, V, q = _f64(scale, 1, "scale"), _f64(V, 2, "V"), _f64(queries, 2, "queries")
+        if V.shape[0] != self.N:
+            raise RuntimeError("kmatvec_inputderiv: V must have N rows")
+        out = np.empty((q.shape[0], q.shape[1], V.shape[1]))
+        check(_lib.mogp_local_kmatvec_inputderiv(self._h, int(kern), dptr(scale), float(sigma2), dptr(q), q.shape[0], q.shape[1], dptr(V),
+                                                 V.shape[1], int(max_points), dptr(out)))
+        return out
+
+    def rff_inputderiv(self, scale, omega, phase, W, amp, queries, max_points=0):
+        """(S, m, D) the derivative of ``rff`` with respect to the raw coordinates of ``queries`` (m, D)"""
+        if not self._h:
+            raise RuntimeError("rff_inputderiv: the handle has been closed")
+        scale, omega, phase, W = _f64(scale, 1, "scale"), _f64(omega, 2, "omega"), _f64(phase, 1, "phase"), _f64(W, 2, "W")
+        q = _f64(queries, 2, "queries")
+        if q.shape[1] != omega.shape[1] or W.shape[1] != omega.shape[0] or phase.shape[0] != omega.shape[0]:
+            raise RuntimeError("rff_inputderiv: queries (m, D), omega (F, D), phase (F,) and W (S, F) do not fit together")
+        out = np.empty((W.shape[0], q.shape[0], q.shape[1]))
+        check(_lib.mogp_local_rff_inputderiv(self._h, dptr(scale), dptr(q), q.shape[0], omega.shape[1], dptr(omega), dptr(phase), omega.shape[0],
+                                             dptr(W), W.shape[0], float(amp), int(max_points), dptr(out)))
+        return out
+
     def sample_paths(self, emulator, kern, scale, sigma2, nugget, rank, rtol, max_iter, omega, phase, n_draws, amp, seed, stream, first_draw,
                      feature_normals=None, noise_normals=None):
         """(W (S, F) the weights' normals used, v (S, N), iterations (S) int64, converged (S) bool, residual (S), the rank the preconditioner
