@@ -268,3 +268,311 @@ def exact_mean_bar(ref, r, alpha):
     rt, at = dc.BARS["mean"]
     res = np.asarray(r.t, dtype=LD) - ref["A"] @ np.asarray(alpha, dtype=LD)
     return ref["amp"] * (at + rt * np.abs(ref["mean"])) + ref["wnorm"] * np.sqrt(res @ res)
+
+
+# ---- the analyses (test_regime_analyses_host.py, test_gpu_regime_analyses.py) ------------------------------------------------------------------
+# Ulps (of 2^-52) an entry 2 s_d sigma^2 k'(r2) (q~_d - x~_d) of the input-derivative sweep (kinderiv_kernel behind a unit vector: the MFMA adds
+# one product with 1 and zeros, which is exact) may be off by apart from the error of r2, read off kern_dr2 and the kernel's text: the table
+# exponential 1.3; the product with sigma^2, the rounded difference q~_d - x~_d, its product with g, and the product with 2 s_d in the store
+# (2 s_d itself is exact) half an ulp each: 3.3.  The squared exponential's -0.5 is a power of two.  For the Matern 1 + t, the constant 5/6,
+# its product with 1 + t and the product with the exponential add half an ulp each: 5.3.  (The two roundings of t = sqrt(5 r2) enter through
+# the gain and sit in the (D + 1) of the bar, as for k.)
+FIXED_ULPS_DR2 = {"SquaredExponential": 3.3, "Matern52": 5.3}
+ANALYSIS_SEED = 20264                                 # candidates and reference points: the first seed from 20261 on at which every candidate of `underflow` lies close enough to a
+                                                      # reference point for alc_bar / ALC < 0.05 there (a premise about the inputs, checked on the CPU: test_regime_analyses_host.py)
+N_CAND, N_REF, N_FAR_B, FAR_LENGTHS = 129, 130, 64, 300.
+N_SHARED = 5                                          # reference points appended to the candidates in `needle`
+
+
+def entries_dr2(U1, U2, kind):
+    """(k' (n1, n2) = dk / dr2 without sigma^2, gain' = |d log|k'| / d r2| r2, the differences (D, n1, n2), the exponential alone) in long double
+    from float64 scaled coordinates"""
+    U1, U2 = np.asarray(U1, dtype=LD), np.asarray(U2, dtype=LD)
+    diff = np.stack([U1[:, d][:, None] - U2[:, d][None, :] for d in range(U1.shape[1])])
+    r2 = np.zeros(diff.shape[1:], dtype=LD)
+    for d in range(diff.shape[0]):
+        r2 = r2 + diff[d] * diff[d]
+    if kind == "Matern52":
+        a = np.sqrt(LD(5) * r2)
+        return -(LD(5) / LD(6)) * (LD(1) + a) * np.exp(-a), LD(5) * r2 / (LD(2) * (LD(1) + a)), diff, np.exp(-a)
+    assert kind == "SquaredExponential", kind
+    return -np.exp(-r2 / LD(2)) / LD(2), r2 / LD(2), diff, np.exp(-r2 / LD(2))
+
+
+@functools.lru_cache(maxsize=None)
+def deriv_entries(name, kernel, Dn, on_design):
+    """(want (m, D, N) long double, bar, literal bar): G[i, d, j] = 2 s_d sigma^2 k'(r2_ij) (q~_id - x~_jd) at the 37 queries or at the design
+    itself.  The literal bar is 2^-52 (FIXED_ULPS_DR2 + (D + 1) gain') |want|, two subnormal steps more where |want| lies below the smallest
+    normal double.  It cannot be met by float64 arithmetic that forms g = sigma^2 k' before the product with the difference and with 2 s_d, as
+    the kernel and the restatement both do: where the exponential, its half or g is itself subnormal, each of the three carries half a step
+    of the subnormal grid, and the later factors multiply that: with e the exponential, h = e / 2 (the Matern: (5/6)(1 + t) e, bounded the
+    same way with sigma^2 (5/6)(1 + t) in sigma^2's place) and g = sigma^2 h the errors in steps are 0.5, 0.75, 0.75 sigma^2 + 0.5, then
+    |q~_d - x~_d| times that plus 0.5 for the product, and 2 s_d times that plus 0.5 for the store.  In `underflow` 2 s_d |q~_d - x~_d| reaches
+    5e3, and the float64 restatement sits at 2e3 times the literal bar (test_regime_analyses_host.py asserts that it does, so that this
+    paragraph cannot go stale).  The bar used is therefore the literal one with, where e / 2 or g lies below the smallest normal double,
+    the carried steps in place of the two:  2^-1074 [2 s_d (|q~_d - x~_d| (0.75 c + 0.5) + 0.5) + 0.5],  c = sigma^2 (Matern: sigma^2 (5/6)(1 + t))."""
+    r = regime(name, kernel, Dn)
+    U = staged(r, r.X)
+    kd, gain, diff, expo = entries_dr2(U if on_design else staged(r, r.Xs), U, kernel)
+    s, s2 = scales(r), LD(sigma2(r))
+    want = np.stack([LD(2) * LD(s[d]) * s2 * kd * diff[d] for d in range(Dn)], axis=1)
+    rel = (LD(EPS) * (LD(FIXED_ULPS_DR2[kernel]) + LD(Dn + 1) * gain))[:, None, :] * np.abs(want)
+    literal = rel + np.where(np.abs(want) < LD(TINY), LD(2 * STEP), LD(0))
+    c = s2 * np.abs(kd) / np.where(expo > 0, expo, LD(1)) * (LD(2) if kernel == "SquaredExponential" else LD(1))
+    low = np.minimum(expo / 2, s2 * np.abs(kd)) < LD(TINY)
+    carried = np.stack([LD(STEP) * (LD(2) * LD(s[d]) * (np.abs(diff[d]) * (LD(0.75) * c + LD(0.5)) + LD(0.5)) + LD(0.5)) for d in range(Dn)], axis=1)
+    bar = np.where(low[:, None, :], rel + np.maximum(carried, LD(2 * STEP)), literal)
+    for a in (want, bar, literal):
+        a.setflags(write=False)
+    return want, bar, literal
+
+
+def excess(got, want, bar):
+    """largest |got - want| / bar, the difference in long double; an exact agreement counts as 0 whatever the bar"""
+    got = np.asarray(got, dtype=np.float64)
+    assert got.shape == want.shape, (got.shape, want.shape)
+    err = np.abs(got.astype(LD) - want)
+    bar = np.asarray(bar, dtype=LD)
+    return float(np.max(np.where(err == 0, LD(0), err / np.where(bar > 0, bar, LD(STEP) * LD(STEP)))))
+
+
+@functools.lru_cache(maxsize=None)
+def point_sets(name, kernel, Dn=D):
+    """dict(cand (129, D), ref (130, D): the 37 queries and 93 more, far_a (37, D), far_b (64, D)): candidates and reference points uniform in
+    the design's bounding box; the far sets are the queries and the first 64 candidates moved by 300 correlation lengths in every coordinate"""
+    r = regime(name, kernel, Dn)
+    rng = np.random.default_rng(ANALYSIS_SEED)
+    lo, hi = r.X.min(axis=0), r.X.max(axis=0)
+    cand = lo + (hi - lo) * rng.random((N_CAND, Dn))
+    more = lo + (hi - lo) * rng.random((N_REF - r.Xs.shape[0], Dn))
+    shift = FAR_LENGTHS / scales(r)
+    return _freeze(dict(cand=cand, ref=np.vstack([r.Xs, more]), far_a=r.Xs + shift, far_b=cand[:N_FAR_B] + shift))
+
+
+@functools.lru_cache(maxsize=None)
+def far_reference(name, kernel, Dn=D):
+    """dict(kstar: the largest long-double entry of k between the far sets and the design; ab, aa: (want, gain) of sigma^2 k(far_a, far_b) and
+    sigma^2 k(far_a, far_a) from the staged coordinates)"""
+    r, ps = regime(name, kernel, Dn), point_sets(name, kernel, Dn)
+    U, A, B = staged(r, r.X), staged(r, ps["far_a"]), staged(r, ps["far_b"])
+    kstar = max(entries(A, U, kernel)[0].max(), entries(B, U, kernel)[0].max())          # long double: 2^-1080 is no float64
+    out = dict(kstar=kstar)
+    for tag, V in (("ab", B), ("aa", A)):
+        k, gain = entries(A, V, kernel)
+        out[tag] = (LD(sigma2(r)) * k, gain)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def posterior(name, kernel, Dn=D, dtype=LD):
+    """alc_restate.Posterior of the regime, the nugget a parameter of theta or fixed: the same model"""
+    import alc_restate as ar
+    r = regime(name, kernel, Dn)
+    return ar.Posterior(r.X, theta(r, False), kernel, r.nugget, dtype)
+
+
+@functools.lru_cache(maxsize=None)
+def alc_reference(name, kernel, Dn=D, dtype=LD):
+    """dict(C (129, 130), cbar, alc (129,), abar, deg, sc, sr) of the general case, uniform weights, tau = the nugget"""
+    import alc_restate as ar
+    r, ps, p = regime(name, kernel, Dn), point_sets(name, kernel, Dn), posterior(name, kernel, Dn, dtype)
+    w = np.full(N_REF, 1. / N_REF)
+    a, sc, sr, deg, C, d = ar.alc(p, ps["cand"], ps["ref"], w, r.nugget)
+    return _freeze(dict(C=C, cbar=p.cov_bar(ps["cand"], ps["ref"]), alc=a, abar=ar.alc_bar(p, ps["cand"], ps["ref"], w, C, d), deg=deg, sc=sc, sr=sr))
+
+
+PATH_SEED, PATH_STREAM, PATH_F, PATH_S = 11, 0x200, 130, 3
+
+
+@functools.lru_cache(maxsize=None)
+def feature_reference(name, kernel, Dn=D):
+    """dict(omega, phase, W, amp, arg: the largest |argument|, val (37, 3), vbar, grad (37, D, 3), gbar, scale: amp sum_f |W_sf| (3,)) of the feature
+    product and its derivative at the staged queries in long double"""
+    import inputderiv_restate as idr
+    import pathwise_restate as pw
+    from mogp_emulator_amd.Sampling import philox_normals
+    r = regime(name, kernel, Dn)
+    omega, phase = pw.features(PATH_SEED, PATH_STREAM, PATH_F, Dn, kernel)
+    W = philox_normals(PATH_SEED, PATH_STREAM + 3, PATH_S, PATH_F)
+    Pt, s, s2 = staged(r, r.Xs), scales(r), sigma2(r)
+    amp = float(np.sqrt(2. * s2 / PATH_F))
+    return _freeze(dict(omega=omega, phase=phase, W=W, amp=amp, arg=float(np.abs(pw.arguments(Pt, omega, phase)).max()),
+                        val=pw.rff(Pt, omega, phase, W, s2, LD), vbar=pw.rff_bar(Pt, omega, phase, W, s2),
+                        grad=idr.rff_grad(Pt, s, omega, phase, W, s2, LD), gbar=idr.rffgrad_bar(Pt, s, omega, phase, W, s2),
+                        scale=amp * np.abs(W).sum(axis=1)))
+
+
+BATCH_Q = 6
+TIGHT = ("tail", "underflow", "noise_only", "big_nugget")            # the regimes in which alc_bar is a few ulps of the score
+GAP = 20.                                             # top-two gap, in bars, from which a greedy pick is pinned
+
+
+@functools.lru_cache(maxsize=None)
+def batch_reference(name, kernel, Dn=D):
+    """alc_batch_restate.greedy(route="fresh") of the regime: q = 6, select "each", uniform weights, tau = the nugget, no pending points"""
+    import alc_batch_restate as br
+    r, ps = regime(name, kernel, Dn), point_sets(name, kernel, Dn)
+    return br.greedy(r.X, [theta(r, False)], kernel, [r.nugget], ps["cand"], ps["ref"], np.full(N_REF, 1. / N_REF), [r.nugget], BATCH_Q)
+
+
+@functools.lru_cache(maxsize=None)
+def batch_steps(name, kernel, Dn, picks):
+    """the fresh route on a GIVEN history (picks: a tuple of candidate indices): dict(alc (q, m_c), bar (q, m_c): step t scored on the posterior
+    of the design with picks[:t] appended at noise tau; iv (q + 1,), iv_bar (q + 1,))"""
+    import alc_batch_restate as br
+    import alc_restate as ar
+    r, ps = regime(name, kernel, Dn), point_sets(name, kernel, Dn)
+    w, q = np.full(N_REF, 1. / N_REF), len(picks)
+    out = dict(alc=np.zeros((q, N_CAND)), bar=np.zeros((q, N_CAND)), iv=np.zeros(q + 1), iv_bar=np.zeros(q + 1))
+    for t in range(q + 1):
+        post = br.Augmented(r.X, theta(r, False), kernel, r.nugget, ps["cand"][list(picks[:t])], r.nugget)
+        a, _, sr, _, C, d = ar.alc(post, ps["cand"], ps["ref"], w, r.nugget)
+        out["iv"][t], out["iv_bar"][t] = float(sr @ w), float(post.var_bar(ps["ref"]) @ w)
+        if t < q:
+            out["alc"][t], out["bar"][t] = a, ar.alc_bar(post, ps["cand"], ps["ref"], w, C, d)
+    return _freeze(out)
+
+
+def path_normals():
+    """(W (3, 130), eps (3, N)) of the paths: the caller's normals, the same in every regime"""
+    rng = np.random.default_rng([PATH_SEED, N, PATH_S, PATH_F])
+    return rng.standard_normal((PATH_S, PATH_F)), rng.standard_normal((PATH_S, N))
+
+
+def path_truth(r, omega, phase, W, update, dtype=LD):
+    """(value (S, m), its bar, gradient (S, m, D), its bar) of paths at the 37 queries from the fields a PosteriorPaths holds -- the frequencies,
+    phases and weights of the prior and the update v (N, S) as they are: no solve here.  Values in `dtype`; the bars are those of
+    test_gpu_pathwise.py and test_gpu_inputderiv.py: the two products' (rff_bar; a fixed-order sum of N generated entries times v:
+    2^-52 [(N + 4) |K| |v| + (4 D + 32) sigma^2 sum |v|], test_iterative_host.matvec_bar with this regime's sigma^2; rffgrad_bar, kgrad_bar)
+    and the rounding of the sums"""
+    import inputderiv_restate as idr
+    import iterative_restate as ir
+    import pathwise_restate as pw
+    s, s2, Dn = scales(r), sigma2(r), r.X.shape[1]
+    Qt, Xt = staged(r, r.Xs), staged(r, r.X)
+    K = ir.covariance(r.Xs, r.X, s, r.kernel, s2, dtype)
+    val = (pw.rff(Qt, omega, phase, W, s2, dtype) + K @ np.asarray(update, dtype=np.float64).astype(dtype)).T
+    K64, v64 = np.abs(np.asarray(K, dtype=np.float64)), np.abs(np.asarray(update, dtype=np.float64))
+    vbar = (pw.rff_bar(Qt, omega, phase, W, s2) + EPS * ((N + 4) * (K64 @ v64) + (4 * Dn + 32) * s2 * v64.sum(axis=0)[None, :])).T \
+        + EPS * np.abs(np.asarray(val, dtype=np.float64))
+    prior = np.transpose(idr.rff_grad(Qt, s, omega, phase, W, s2, dtype), (2, 0, 1))
+    grad = idr.path_gradient(r.X, r.Xs, s, r.kernel, s2, omega, phase, W, update, dtype=dtype)
+    gbar = (np.transpose(idr.rffgrad_bar(Qt, s, omega, phase, W, s2), (2, 0, 1)) + EPS * np.abs(np.asarray(prior, dtype=np.float64))
+            + np.transpose(idr.kgrad_bar(Qt, Xt, s, r.kernel, s2, update), (2, 0, 1)) + EPS * np.abs(np.asarray(grad, dtype=np.float64)))
+    return val, vbar, grad, gbar
+
+
+def deriv_bar(ref, r, alpha, name, kernel, Dn):
+    """the bar of test_gpu_inputderiv.py for d mean / dx of an iterative solve: BARS["deriv"] and, for an inexact alpha,
+    |A^-1 d_d k*| |y - A alpha| (exact algebra), d_d k* the entries of deriv_entries; as exact_mean_bar"""
+    rt, at = dc.BARS["deriv"]
+    res = np.asarray(r.t, dtype=LD) - ref["A"] @ np.asarray(alpha, dtype=LD)
+    dk = np.asarray(deriv_entries(name, kernel, Dn, False)[0], dtype=np.float64)                   # (m, D, N)
+    W = np.linalg.solve(np.asarray(ref["A"], dtype=np.float64), dk.reshape(-1, dk.shape[2]).T)      # (N, m D)
+    wn = np.sqrt(np.sum(W * W, axis=0)).reshape(dk.shape[:2])
+    return ref["amp"] * (at + rt * np.abs(ref["deriv"])) + wn * float(np.sqrt(res @ res))
+
+
+# ---- mixtures and joint draws ------------------------------------------------------------------------------------------------------------------
+MIX_NAMES = tuple(n for n in NAMES if n != "twin")    # the regimes on the shared design: the samples of one emulator
+MIX_MARGIN, MIX_WEIGHTS = 100., ("uniform", "dirichlet")
+DRAWS = 3
+
+
+def mixture_thetas(kernel):
+    """(10, D + 2): theta(regime(name), fit=True) of every regime but `twin` -- samples of one emulator that differ by 36 in log sigma^2 and
+    by a factor e^36.4 (sixteen orders of magnitude) in the nugget"""
+    return np.stack([theta(regime(n, kernel), True) for n in MIX_NAMES])
+
+
+def mixture_weights(kind):
+    S = len(MIX_NAMES)
+    return np.ones(S) if kind == "uniform" else np.random.default_rng(ANALYSIS_SEED).dirichlet(np.ones(S))
+
+
+@functools.lru_cache(maxsize=None)
+def mixture_reference(kernel, wkind):
+    """(float64 restatement, bars, disagreements) of marginal_restate.mixture on the `base` design and targets with caller weights, by the
+    convention of test_gpu_marginal.py: the device is allowed 100 x the float64 / long double disagreement, floored at 2^-52, relative to
+    max|mean|, max within and the largest d_s^2; a disagreement above 1e-8 is refused"""
+    import marginal_restate as mr
+    r = regime("base", kernel)
+    args = (r.X, r.t, mixture_thetas(kernel), r.Xs, kernel, "zero", True, None, mixture_weights(wkind), None, True)
+    a, b = mr.mixture(*args), mr.mixture(*args, dtype=LD)
+    assert np.array_equal(a["ok"], b["ok"]) and a["ok"].all()
+    scale = {"mean": float(np.abs(b["mean"]).max()), "within": float(b["within"].max()), "between": float(b["d2max"])}
+    dis = {k: float(np.abs(a[k] - b[k]).max()) / sc for k, sc in scale.items()}
+    bars = {k: MIX_MARGIN * max(dis[k], EPS) * scale[k] for k in scale}
+    return a, bars, dis
+
+
+@functools.lru_cache(maxsize=None)
+def draw_normals(m=M):
+    z = np.random.default_rng([ANALYSIS_SEED, m]).standard_normal((DRAWS, m))
+    z.setflags(write=False)
+    return z
+
+
+def ladder_rung(cov, shift):
+    """the rung of sample_restate's jitter ladder at which cov + shift I factorises in float64: 0 none needed, t >= 1 the t-th, -1 none does"""
+    import sample_restate as sr
+    dbar = float(np.mean(np.diag(cov)))
+    for t, delta in enumerate([0.] + [sr.ladder_delta(k, dbar) for k in range(sr.LADDER_RUNGS)]):
+        try:
+            np.linalg.cholesky(cov + (shift + delta) * np.eye(cov.shape[0]))
+            return t
+        except np.linalg.LinAlgError:
+            pass
+    return -1
+
+
+# ---- the variance bound -------------------------------------------------------------------------------------------------------------------------
+VAR_RANKS = (32, 130)
+
+
+@functools.lru_cache(maxsize=None)
+def bound_inputs(name, kernel, Dn=D):
+    """(K (N, N) without the nugget, cross covariances of the 37 queries (N, 37), K from long double rounded once) in float64"""
+    import iterative_restate as ir
+    r = regime(name, kernel, Dn)
+    s, s2 = scales(r), sigma2(r)
+    K, ks = ir.covariance(r.X, r.X, s, kernel, s2), ir.covariance(r.X, r.Xs, s, kernel, s2)
+    K2 = np.asarray(ir.covariance(r.X, r.X, s, kernel, s2, dtype=LD), dtype=np.float64)
+    for a in (K, ks, K2):
+        a.setflags(write=False)
+    return K, ks, K2
+
+
+OWN_TRIALS = 6                                        # evaluations of K moved by an ulp per entry, next to the one rounded from long double
+
+
+@functools.lru_cache(maxsize=None)
+def bound_cache(name, kernel, Dn, rank, pivots=None):
+    """(variance_bound_restate.cache on the given pivots (a tuple; None: its own), bar, cond(H), amp, own, first): the bar of
+    test_gpu_variance_bound.py -- BARS["var"] at the scale of the prior variance sigma^2 + eta the bound is a difference from, amplified by
+    cond(H) --; own: per column of R the LARGEST excess over the "fullcov" bar of the restatement on the same pivots of K rounded another
+    way -- K from long double rounded once, and OWN_TRIALS copies of K with every entry moved one ulp up or down (symmetrically, seeded) --;
+    first: the index of the first column with own > 1 (var_rank if none).  A column above 1 is not determined by float64 arithmetic:
+    where the first prefix runs towards its cut by tau the pivots fall to 1e-10 of the first and a column is what is left of a column of L
+    after the ones before it are projected out.  Column j of R combines the columns <= j of the factor, so the columns before `first` are
+    held one by one and the ones behind it by R^T A R = I and the two-sided bound alone."""
+    import variance_bound_restate as vr
+    r = regime(name, kernel, Dn)
+    K, ks, K2 = bound_inputs(name, kernel, Dn)
+    ch = vr.cache(K, r.nugget, rank, pivots=pivots)
+    rtol, atol = dc.BARS["var"]
+    cond, amp = dc.amplification(ch.H)
+    rng = np.random.default_rng([ANALYSIS_SEED, rank])
+    own = np.zeros(ch.var_rank)
+    for t in range(OWN_TRIALS + 1):
+        Kp = K2
+        if t:
+            up = np.triu(rng.random(K.shape) < 0.5)
+            up = up | up.T
+            Kp = np.where(up, np.nextafter(K, np.inf), np.nextafter(K, -np.inf))
+        other = vr.cache(Kp, r.nugget, ch.L.shape[1], pivots=ch.pivots)
+        k = min(ch.var_rank, other.var_rank)
+        own[k:] = np.inf
+        own[:k] = np.maximum(own[:k], [dc.excess("fullcov", other.R[:, j], ch.R[:, j], amp) for j in range(k)])
+    first = int(np.argmax(own > 1.)) if np.any(own > 1.) else ch.var_rank
+    return ch, amp * (atol + rtol * (sigma2(r) + r.nugget)), cond, amp, own, first
