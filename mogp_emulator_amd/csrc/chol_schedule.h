@@ -38,4 +38,15 @@ inline int choose_cholesky_schedule(int nb, int NP, std::size_t matrix_bytes, in
   return schedule;
 }
 
+// Rows of the tile [row0, row0 + rows) that lie above the identity padding, in whole 16-row MFMA sub-tiles: n_real = n + R rows of an
+// emulator's matrix carry data (K, then the right-hand-side rows), everything below is identity up to NP.  0, 16, .. rows.  The ONE rule
+// of the factorisation's row tiles (kernels_mchol.hip), the triangular inverse (kernels_gemm.hip, kernels_chol.hip) and
+// tests/c/real_rows_check.cpp: a skipped sub-tile holds no data row, so its products are exact zeros.
+constexpr int real_rows(int n_real, int row0, int rows) {
+  const int left = n_real - row0;
+  if (left <= 0) return 0;
+  const int up = (left + 15) / 16 * 16;
+  return up < rows ? up : rows;
+}
+
 }  // namespace mogp

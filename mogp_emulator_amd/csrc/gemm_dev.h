@@ -298,11 +298,16 @@ __device__ __forceinline__ void sched_half() {       // MFMA M of NM, then its s
 }
 
 // kmask: as in mainloop_pf.  SCHED: 0 the compiler's order, 1 the barrier pinned behind the step's last MFMAs, 2 also the interleave above.
-template <int BM, int BN, int WR, int WC, int G, int SCHED = 0>
+// TIA < TI (the one-launch Cholesky's row tiles that end in identity padding): the row sub-tiles are dealt to the wave rows ROUND-ROBIN
+// (sub-tile a = i * WR + wr, as in mainloop_w<.., TRIA>) and a wave multiplies its first TIA of them only -- acc[i], i >= TIA, is not touched.
+// The operand tiles move through LDS whole; every accumulator entry that is computed receives the products of today's loop in today's order.
+template <int BM, int BN, int WR, int WC, int G, int SCHED = 0, int TIA = WCfg<BM, BN, WR, WC>::TI>
 __device__ __forceinline__ void mainloop_q(const double* __restrict__ Ag, int lda, const double* __restrict__ Bg, int ldb, int nk,
                                            v4d (&acc)[WCfg<BM, BN, WR, WC>::TI][WCfg<BM, BN, WR, WC>::TJ], double* smem, int kmask = -1) {
   using C = WCfg<BM, BN, WR, WC>;
   constexpr int STAGE = QCfg<BM, BN>::STAGE;
+  constexpr bool RR = TIA < C::TI;
+  static_assert(TIA >= 1 && TIA <= C::TI, "active row sub-tiles per wave");
   const int t = mogp_tid(), lane = t & 63, wave = t >> 6;
   const int wr = wave / WC, wc = wave % WC;
   const int fr = lane & 15, fk = lane >> 4;
@@ -329,11 +334,11 @@ __device__ __forceinline__ void mainloop_q(const double* __restrict__ Ag, int ld
   };
   // fragment of half step h: the lane's k = 4 fk + 2 h, + 1 of row fr of a 16-row block
   const int fo0 = fr * BK + (((2 * fk) ^ q_swz(fr)) << 1);
-  v2d fa[2][C::TI], fb[2][C::TJ];
+  v2d fa[2][TIA], fb[2][C::TJ];
   auto frag = [&](int set, const double* st, int h) {
     const int fo = fo0 ^ (h << 1);
 #pragma unroll
-    for (int i = 0; i < C::TI; ++i) fa[set][i] = *reinterpret_cast<const v2d*>(st + (wr * C::TI + i) * 16 * BK + fo);
+    for (int i = 0; i < TIA; ++i) fa[set][i] = *reinterpret_cast<const v2d*>(st + (RR ? i * WR + wr : wr * C::TI + i) * 16 * BK + fo);
 #pragma unroll
     for (int j = 0; j < C::TJ; ++j) fb[set][j] = *reinterpret_cast<const v2d*>(st + BM * BK + (wc * C::TJ + j) * 16 * BK + fo);
   };
@@ -341,7 +346,7 @@ __device__ __forceinline__ void mainloop_q(const double* __restrict__ Ag, int ld
 #pragma unroll
     for (int e = 0; e < 2; ++e)
 #pragma unroll
-      for (int i = 0; i < C::TI; ++i)
+      for (int i = 0; i < TIA; ++i)
 #pragma unroll
         for (int j = 0; j < C::TJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[set][i][e], fb[set][j][e], acc[i][j], 0, 0, 0);
   };
@@ -373,12 +378,12 @@ __device__ __forceinline__ void mainloop_q(const double* __restrict__ Ag, int ld
       frag(0, smem + nxt * STAGE, 0);                      // written during step kt - 1: visible since the barrier that ended it
       mfmas(1);
       if (SCHED == 2) {
-        constexpr int NM = 2 * C::TI * C::TJ, NR = C::TI + C::TJ, NW = C::CHA + C::CHB;
+        constexpr int NM = 2 * TIA * C::TJ, NR = TIA + C::TJ, NW = C::CHA + C::CHB;
         sched_half<0, NM, NR, NW, NW>();                   // first half step: frag(1) reads, the stage's writes, the next global loads
         sched_half<0, NM, NR, 0, 0>();                     // second: the first fragments of the next step
       }
       if (SCHED == 3) {                                    // (probe: the next step's fragments early in the second half, two behind each MFMA)
-        constexpr int NM = 2 * C::TI * C::TJ, NR = C::TI + C::TJ, NW = C::CHA + C::CHB;
+        constexpr int NM = 2 * TIA * C::TJ, NR = TIA + C::TJ, NW = C::CHA + C::CHB;
         sched_half<0, NM, NR, NW, NW>();
         sched_half<0, NR / 2, NR, 0, 0>();
         sched_group<0x008, NM - NR / 2>();

@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include "launch.h"
+#include "chol_schedule.h"
 #include "chol128_dev.h"
 
 namespace mogp {
@@ -686,6 +687,14 @@ __global__ __launch_bounds__(64) void trtri_leaf_kernel(BatchView v, const doubl
   const double* __restrict__ L = Lmat + (size_t)emu * v.MS + (size_t)d0 * ld + d0;
   double* Li = v.Linv + (size_t)emu * v.MS;
   const int t = threadIdx.x;
+  if (real_rows(v.n + v.R, d0, 64) == 0) {
+    // a leaf wholly in the identity padding (chol_schedule.h): its inverse is the identity -- written, as are the zeros beside it, without the
+    // substitution
+    for (int i = 0; i < 64; ++i) Li[(size_t)(d0 + i) * ld + d0 + t] = (i == t) ? 1.0 : 0.0;
+    if ((blockIdx.x & 1) == 0 && d0 + 64 < ld)
+      for (int i = 0; i < 64; ++i) Li[(size_t)(d0 + i) * ld + d0 + 64 + t] = 0.0;
+    return;
+  }
 #pragma unroll 8
   for (int r = 0; r < 64; ++r) Ls[r * 65 + t] = L[(size_t)r * ld + t];
   __builtin_amdgcn_wave_barrier();

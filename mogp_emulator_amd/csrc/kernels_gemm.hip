@@ -22,6 +22,7 @@
 #include <algorithm>
 #include <type_traits>
 #include "launch.h"
+#include "chol_schedule.h"
 #include "trsm_dev.h"
 #include "gemm_dev.h"
 #include "gemm_loop_dev.h"
@@ -85,9 +86,13 @@ __global__ __launch_bounds__(256, 3) void trsm128_lds_kernel(BatchView v, int c0
 // MODE 1 (Linv21 = -Linv22 T, k up to i0 + BM): the LAST nd steps are the diagonal block of Linv22 [i][k]: row sub-tile a has non-zeros up
 //         to step a of that block -- the set of active row sub-tiles [S, WT) SHRINKS (nk_full = steps in front of the block).
 // The k loop is cut into consecutive loops, one per set; skipped products are exact zeros (entries unchanged bit for bit).
+// a_rows (real_rows, chol_schedule.h): the rows of the output tile above the identity padding.  A padding row of L21 is zero and a padding row
+// of Linv22 is a unit vector that picks a zero row of T, so in both products the row sub-tiles at or below a_rows are exact zeros: a wave
+// multiplies its first RA row sub-tiles only (the deal is round-robin, so the waves stay balanced) and the accumulators of the others keep
+// their zeros.  The k ranges are unchanged.
 template <int WT, int MODE>
 __device__ __forceinline__ void merge_mainloop(const double* __restrict__ Ag, int lda, const double* __restrict__ Bg, int ldb, int nk, int nk_full,
-                                               v4d (&acc)[WT][WT], double* smem, int wr, int wc) {
+                                               v4d (&acc)[WT][WT], double* smem, int wr, int wc, int a_rows) {
   using C = Cfg<WT>;
   const int lane = threadIdx.x & 63;
   const int fr = lane & 15, fk = lane >> 4;
@@ -104,9 +109,9 @@ __device__ __forceinline__ void merge_mainloop(const double* __restrict__ Ag, in
   r2s<WT, true>(smem, ra);
   r2s<WT, false>(smem + C::OPSZ, rb);
   __syncthreads();
-  // one k-step with the row sub-tiles [S, WT) and the column sub-tiles [0, E)
-  auto step = [&](int kt, auto S_, auto E_) {
-    constexpr int S = decltype(S_)::value, E = decltype(E_)::value;
+  // one k-step with the row sub-tiles [S, RA) and the column sub-tiles [0, E)
+  auto step = [&](int kt, auto S_, auto RA_, auto E_) {
+    constexpr int S = decltype(S_)::value, RA = decltype(RA_)::value, E = decltype(E_)::value;
     const double* sA = smem + (kt & 1) * 2 * C::OPSZ;
     const double* sB = sA + C::OPSZ;
     const bool more = (kt + 1 < nk);
@@ -116,17 +121,17 @@ __device__ __forceinline__ void merge_mainloop(const double* __restrict__ Ag, in
       g2r<WT, true>(Ag, lda, offA, ra);
       g2r<WT, false>(Bg, ldb, offB, rb);
     }
-    if (S < WT && E > 0) {
+    if constexpr (S < RA && E > 0) {
 #pragma unroll
       for (int kk = 0; kk < 4; ++kk) {
         double a[WT], b[WT];
         const int k = kk * 4 + fk;
 #pragma unroll
-        for (int i = S; i < WT; ++i) a[i] = sA[((2 * i + wr) * 16 + fr) * LDK + k];
+        for (int i = S; i < RA; ++i) a[i] = sA[((2 * i + wr) * 16 + fr) * LDK + k];
 #pragma unroll
         for (int j = 0; j < E; ++j) b[j] = sB[k * C::LDM + (2 * j + wc) * 16 + fr];
 #pragma unroll
-        for (int i = S; i < WT; ++i)
+        for (int i = S; i < RA; ++i)
 #pragma unroll
           for (int j = 0; j < E; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], b[j], acc[i][j], 0, 0, 0);
       }
@@ -142,25 +147,36 @@ __device__ __forceinline__ void merge_mainloop(const double* __restrict__ Ag, in
   using IW = std::integral_constant<int, WT>;
   int kt = 0;
   static_assert(WT == 2 || WT == 4, "phase lists are written for two or four sub-tiles per wave");
-  if (MODE == 0) {
-    // column sub-tile 2 j + wc is active from step 2 j + wc on
-    for (const int end = min(nk, wc); kt < end; ++kt) step(kt, I0(), I0());
-    for (const int end = min(nk, 2 + wc); kt < end; ++kt) step(kt, I0(), std::integral_constant<int, 1>());
-    if (WT == 4) {
-      for (const int end = min(nk, 4 + wc); kt < end; ++kt) step(kt, I0(), std::integral_constant<int, 2>());
-      for (const int end = min(nk, 6 + wc); kt < end; ++kt) step(kt, I0(), std::integral_constant<int, 3>());
+  // the phase lists for a wave with RA real row sub-tiles
+  auto run = [&](auto RA_) {
+    if (MODE == 0) {
+      // column sub-tile 2 j + wc is active from step 2 j + wc on
+      for (const int end = min(nk, wc); kt < end; ++kt) step(kt, I0(), RA_, I0());
+      for (const int end = min(nk, 2 + wc); kt < end; ++kt) step(kt, I0(), RA_, std::integral_constant<int, 1>());
+      if (WT == 4) {
+        for (const int end = min(nk, 4 + wc); kt < end; ++kt) step(kt, I0(), RA_, std::integral_constant<int, 2>());
+        for (const int end = min(nk, 6 + wc); kt < end; ++kt) step(kt, I0(), RA_, std::integral_constant<int, 3>());
+      }
+      for (; kt < nk; ++kt) step(kt, I0(), RA_, IW());
+    } else {
+      // row sub-tile 2 i + wr is active up to step nk_full + 2 i + wr
+      for (const int end = min(nk, nk_full + wr + 1); kt < end; ++kt) step(kt, I0(), RA_, IW());
+      for (const int end = min(nk, nk_full + 2 + wr + 1); kt < end; ++kt) step(kt, std::integral_constant<int, 1>(), RA_, IW());
+      if (WT == 4) {
+        for (const int end = min(nk, nk_full + 4 + wr + 1); kt < end; ++kt) step(kt, std::integral_constant<int, 2>(), RA_, IW());
+        for (const int end = min(nk, nk_full + 6 + wr + 1); kt < end; ++kt) step(kt, std::integral_constant<int, 3>(), RA_, IW());
+      }
+      for (; kt < nk; ++kt) step(kt, IW(), RA_, IW());
     }
-    for (; kt < nk; ++kt) step(kt, I0(), IW());
-  } else {
-    // row sub-tile 2 i + wr is active up to step nk_full + 2 i + wr
-    for (const int end = min(nk, nk_full + wr + 1); kt < end; ++kt) step(kt, I0(), IW());
-    for (const int end = min(nk, nk_full + 2 + wr + 1); kt < end; ++kt) step(kt, std::integral_constant<int, 1>(), IW());
-    if (WT == 4) {
-      for (const int end = min(nk, nk_full + 4 + wr + 1); kt < end; ++kt) step(kt, std::integral_constant<int, 2>(), IW());
-      for (const int end = min(nk, nk_full + 6 + wr + 1); kt < end; ++kt) step(kt, std::integral_constant<int, 3>(), IW());
-    }
-    for (; kt < nk; ++kt) step(kt, IW(), IW());
-  }
+  };
+  int n_act = 0;     // row sub-tiles of this wave that contain real rows
+#pragma unroll
+  for (int i = 0; i < WT; ++i) n_act += ((2 * i + wr) * 16 < a_rows) ? 1 : 0;
+  if (n_act == WT) run(IW());
+  else if (WT == 4 && n_act == 3) run(std::integral_constant<int, WT == 4 ? 3 : 0>());
+  else if (WT == 4 && n_act == 2) run(std::integral_constant<int, WT == 4 ? 2 : 0>());
+  else if (n_act == 1) run(std::integral_constant<int, 1>());
+  else run(I0());                    // (only moves the wave's share of the operand tiles)
 }
 
 template <int WT, int STEP>
@@ -191,6 +207,8 @@ __global__ __launch_bounds__(256, 2) void trtri_merge_kernel(BatchView v, int h,
   }
   const int i0 = ti * C::BM, j0 = tj * C::BM;          // node-local
   if (i0 >= m2) return;
+  // rows of this output tile above the identity padding (0: the tile is written with its zeros and nothing is multiplied)
+  const int a_rows = real_rows(v.n + v.R, base + h + i0, C::BM);
   const double* L = v.A + (size_t)emu * v.MS;
   double* Li = v.Linv + (size_t)emu * v.MS;
   double* S = v.Kinv + (size_t)emu * v.MS;
@@ -211,14 +229,14 @@ __global__ __launch_bounds__(256, 2) void trtri_merge_kernel(BatchView v, int h,
     // T[i,j] = sum_{k >= j0} L21[i,k] Linv11[k,j]
     const double* Ag = L + (size_t)(base + h + i0) * ld + base + j0;       // K-major, k from j0
     const double* Bg = Li + (size_t)(base + j0) * ld + base + j0;          // M-major: [k][j], k from j0
-    merge_mainloop<WT, 0>(Ag, ld, Bg, ld, (h - j0) / BK, 0, acc, smem, wr, wc);
+    merge_mainloop<WT, 0>(Ag, ld, Bg, ld, a_rows > 0 ? (h - j0) / BK : 0, 0, acc, smem, wr, wc, a_rows);
     store(S + (size_t)(base + h + i0) * ld + base + j0, 1.0);
   } else {
     // Linv21[i,j] = - sum_{k < i0+BM} Linv22[i,k] T[k,j]
     const double* Ag = Li + (size_t)(base + h + i0) * ld + base + h;       // K-major, k from 0
     const double* Bg = S + (size_t)(base + h) * ld + base + j0;            // M-major: T[k][j]
     const int kend = min(i0 + C::BM, m2);
-    merge_mainloop<WT, 1>(Ag, ld, Bg, ld, kend / BK, i0 / BK, acc, smem, wr, wc);
+    merge_mainloop<WT, 1>(Ag, ld, Bg, ld, a_rows > 0 ? kend / BK : 0, i0 / BK, acc, smem, wr, wc, a_rows);
     store(Li + (size_t)(base + h + i0) * ld + base + j0, -1.0);
   }
 }

@@ -41,6 +41,7 @@
 #define MOGP_OPAQUE_TID 1
 #include "launch.h"
 #include "devmem.h"
+#include "chol_schedule.h"
 #include "chol128_dev.h"
 #include "trsm_dev.h"
 #include "gemm_dev.h"
@@ -68,10 +69,11 @@ constexpr int MC_SCHED = MOGP_MC_SCHED;
 // the GEMM main loop of the tasks (gemm_dev.h): mainloop_q, two global-load steps ahead of its three LDS stages
 // (PIN: the step's barrier stays behind its last MFMAs -- probe 2.13 -> 2.08 us per k-step with two workgroups per CU, 8 x n=2000 0.707 -> 0.693 ms,
 // level elsewhere; profiles/r05_loop_pin_ab.txt)
-template <int BM, int BN>
+// TIA = 1: the half-height form for a row tile with at most 32 real rows (real_rows, chol_schedule.h) -- wave row wr multiplies row sub-tile wr alone
+template <int BM, int BN, int TIA = BM / 32>
 __device__ __forceinline__ void MC_GEMM(const double* __restrict__ Ag, int lda, const double* __restrict__ Bg, int ldb, int nk, v4d (&acc)[BM / 32][BN / 32],
                                         double* smem, int kmask) {
-  mainloop_q<BM, BN, 2, 2, 2, MC_SCHED>(Ag, lda, Bg, ldb, nk, acc, smem, kmask);
+  mainloop_q<BM, BN, 2, 2, 2, MC_SCHED, TIA>(Ag, lda, Bg, ldb, nk, acc, smem, kmask);
 }
 constexpr size_t MC_GEMM_LDS = QCfg<64, 128>::SMEM_DOUBLES;
 
@@ -300,6 +302,29 @@ __global__ __launch_bounds__(256, SOLO ? 1 : 2) void mchol_kernel(BatchView v, u
       }
       // ---- T: 64 rows x 128 columns receive the panels 0 .. c-1 -----------------------------------------------------
       const int r0 = 64 * r;
+      // Identity padding (rows >= n + R): real = the rows of this tile above it, in whole 16-row sub-tiles.  The padding rows of a tile below
+      // the diagonal block are zeros, stay zeros through the GEMM and the solve, and no real entry depends on them.
+      const int real = real_rows(v.n + v.R, r0, 64);
+      if (real == 0) {
+        // no real row: no arithmetic.  rowprog / rowdone are plain stores, so the task still takes its turn behind the row's previous column
+        // (which a full task meets as the last wait of its GEMM), writes the zeros the solve would have written, and publishes as ever.
+        if (c > 0 && mc_wait_min3(cx, rowprog + r, rowprog + r, rowprog + r, 8u * (unsigned)c, tr) < 0) return;
+        // (a rolled loop on a laundered thread index: unrolled, its sixteen addresses are hoisted out of the task loop and spill)
+        const int tz = mogp_tid();
+        v2d* z0 = reinterpret_cast<v2d*>(A + (size_t)(r0 + (tz >> 6)) * ld + c0) + (tz & 63);
+#pragma clang loop unroll(disable)
+        for (int q = 0; q < 16; ++q) z0[(size_t)q * 2 * ld] = (v2d){0., 0.};
+        drain_stores();
+        __syncthreads();
+        if (t == 0) {
+          stu(rowprog + r, 8u * (unsigned)(c + 1));
+          stu(rowdone + r, (unsigned)(c + 1));
+        }
+        mc_stamp<TRACE>(tr, 5);
+        continue;
+      }
+      // at most 32 real rows: the row sub-tiles are dealt round-robin (acc[i] = sub-tile 2 i + wr) and only acc[0] is multiplied (MC_GEMM<.., 1>)
+      const bool half = real <= 32;
       // tasks of the dependent chain (diagonal tiles, the two row blocks of the next diagonal block) issue ahead of the
       // workgroup they share the CU with
       // (opts bits 8, 9: 4 + 2 x rows below the diagonal block are chain tasks -- chain-bound launches take three pairs)
@@ -312,13 +337,14 @@ __global__ __launch_bounds__(256, SOLO ? 1 : 2) void mchol_kernel(BatchView v, u
         // the solve then takes x = -acc.  Throughput-bound launches read C after the GEMM as before: there the early read costs 1 % (its
         // latency is covered by the CU partner anyway, and the first MFMAs wait for it).  Round 5, profiles/r05_negc_ab.txt.
         v4d acc[2][4];
-        const double* pcT = A + (size_t)(r0 + (t >> 7) * 32 + ((t & 63) >> 4)) * ld + (c0 + ((t >> 6) & 1) * 64 + (t & 15));
+        const double* pcT = A + (size_t)(r0 + (t >> 7) * (half ? 16 : 32) + ((t & 63) >> 4)) * ld + (c0 + ((t >> 6) & 1) * 64 + (t & 15));
+        const int istr = half ? 32 : 16;            // rows between acc[0] and acc[1]
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
           for (int j = 0; j < 4; ++j)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) acc[i][j][q] = SOLO ? -pcT[(size_t)(i * 16 + 4 * q) * ld + j * 16] : 0.0;
+            for (int q = 0; q < 4; ++q) acc[i][j][q] = SOLO ? -pcT[(size_t)(i * istr + 4 * q) * ld + j * 16] : 0.0;
         // x = C - (sum of products), whichever way acc started
         auto finish_x = [&]() {
           if (SOLO) {
@@ -333,7 +359,7 @@ __global__ __launch_bounds__(256, SOLO ? 1 : 2) void mchol_kernel(BatchView v, u
 #pragma unroll
               for (int j = 0; j < 4; ++j)
 #pragma unroll
-                for (int q = 0; q < 4; ++q) cv[i][j][q] = pcT[(size_t)(i * 16 + 4 * q) * ld + j * 16];
+                for (int q = 0; q < 4; ++q) cv[i][j][q] = pcT[(size_t)(i * istr + 4 * q) * ld + j * 16];
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -359,8 +385,8 @@ __global__ __launch_bounds__(256, SOLO ? 1 : 2) void mchol_kernel(BatchView v, u
             // (opts bit 1 is never set: the launcher lost its traffic-measurement switch, MOGP_MC_NOTRAFFIC, in round 7.  The operand stays
             // because without it the register allocation of this kernel changes -- two-per-CU build: 65 -> 157 SGPR spills, +572
             // instructions; SOLO build: one more VGPR.  The planned rewrite of the Cholesky chain can drop it.)
-            MC_GEMM<64, 128>(A + (size_t)r0 * ld + 16 * ks, ld, A + (size_t)c0 * ld + 16 * ks, ld, have - ks, acc, lds,
-                             (opts & 2) ? 3 : -1);
+            if (half) MC_GEMM<64, 128, 1>(A + (size_t)r0 * ld + 16 * ks, ld, A + (size_t)c0 * ld + 16 * ks, ld, have - ks, acc, lds, (opts & 2) ? 3 : -1);
+            else MC_GEMM<64, 128>(A + (size_t)r0 * ld + 16 * ks, ld, A + (size_t)c0 * ld + 16 * ks, ld, have - ks, acc, lds, (opts & 2) ? 3 : -1);
             ks = have;
           }
         }
@@ -376,7 +402,7 @@ __global__ __launch_bounds__(256, SOLO ? 1 : 2) void mchol_kernel(BatchView v, u
           mc_stamp<TRACE>(tr, 4);
           mc_stamp<TRACE>(tr, 8);
           __builtin_amdgcn_s_setprio(1);
-          trsm128_tile2_dev<true>(v, c0, r0, pk, emu, lds, acc, SP, TRACE ? tr + 10 : nullptr);
+          trsm128_tile2_dev<true>(v, c0, r0, pk, emu, lds, acc, SP, TRACE ? tr + 10 : nullptr, real);
           drain_stores();
           mc_stamp<TRACE>(tr, 13);
           __syncthreads();
@@ -407,8 +433,8 @@ __global__ __launch_bounds__(256, SOLO ? 1 : 2) void mchol_kernel(BatchView v, u
           if (prog < 0) return;
           if (prog >= 8) {
             mc_stamp<TRACE>(tr, 8);
-            trsm128_tile2_chain_dev<true, true>(v, c0, r0, pk, emu, lds, acc, TrsmNoWait(), pub);
-          } else if (!trsm128_tile2_chain_dev<true, false>(v, c0, r0, pk, emu, lds, acc, wait, pub)) return;
+            trsm128_tile2_chain_dev<true, true>(v, c0, r0, pk, emu, lds, acc, TrsmNoWait(), pub, real);
+          } else if (!trsm128_tile2_chain_dev<true, false>(v, c0, r0, pk, emu, lds, acc, wait, pub, real)) return;
           drain_stores();
           __syncthreads();
           if (t == 0) {
@@ -442,14 +468,14 @@ __global__ __launch_bounds__(256, SOLO ? 1 : 2) void mchol_kernel(BatchView v, u
         if (prog < 0) return;
         if (prog >= 8) {
           mc_stamp<TRACE>(tr, 8);
-          trsm128_lds_dev<true, true, false>(v, c0, r0, pk, emu, 0, lds, TrsmNoWait(), pub);
-        } else if (!trsm128_lds_dev<true, false, true>(v, c0, r0, pk, emu, 0, lds, wait, pub)) return;
+          trsm128_lds_dev<true, true, false>(v, c0, r0, pk, emu, 0, lds, TrsmNoWait(), pub, real);
+        } else if (!trsm128_lds_dev<true, false, true>(v, c0, r0, pk, emu, 0, lds, wait, pub, real)) return;
       } else {
         if (mc_wait_min3(cx, ddone + c, ddone + c, ddone + c, 8u, tr) < 0) return;
         mc_stamp<TRACE>(tr, 8);
         // the substitution is a chain of dependent MFMAs: let it issue ahead of the co-resident workgroup's dense MFMA stream
         __builtin_amdgcn_s_setprio(1);
-        trsm128_lds_dev<true, true>(v, c0, r0, pk, emu, 0, lds);
+        trsm128_lds_dev<true, true>(v, c0, r0, pk, emu, 0, lds, TrsmNoWait(), TrsmNoPub(), real);
       }
       drain_stores();
       __syncthreads();

@@ -55,7 +55,7 @@ struct TrsmNoPub {
 };
 template <bool SC1_OUT = false, bool DEEP = false, bool PIPE = false, class WAIT = TrsmNoWait, class PUB = TrsmNoPub>
 __device__ __forceinline__ bool trsm128_lds_dev(const BatchView& v, int c0, int r0, const double* __restrict__ pk, int emu, int rowblock,
-                                                double* lds, WAIT wait = WAIT(), PUB pub = PUB()) {
+                                                double* lds, WAIT wait = WAIT(), PUB pub = PUB(), int real = 64) {
   // (PUB without PIPE -- with DEEP: the pack is complete, the images are requested two steps ahead, and the solved rows are still
   // published piece by piece for the next diagonal block: a chain task whose GEMM ended after its diagonal block had finished)
   constexpr bool PUBLISH = (PIPE || DEEP) && !std::is_same<PUB, TrsmNoPub>::value;
@@ -118,6 +118,7 @@ __device__ __forceinline__ bool trsm128_lds_dev(const BatchView& v, int c0, int 
   pack_deposit(0, pkb[0]);
   slab_deposit(0, tsb[0]);
   __syncthreads();
+  const bool act = wave * 16 < real;       // (real: see trsm128_tile2_dev -- a slab in the identity padding is zeros and stays zeros)
   v4d_t X[8];
 #pragma unroll
   for (int b = 0; b < 8; ++b) {
@@ -134,15 +135,17 @@ __device__ __forceinline__ bool trsm128_lds_dev(const BatchView& v, int c0, int 
     v4d_t T;
 #pragma unroll
     for (int r = 0; r < 4; ++r) T[r] = ts[i * 18 + g + 4 * r];
-#pragma unroll
-    for (int a = 0; a < b; ++a)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)      // A operand: L[16b + i][16a + g + 4r]
-        T = __builtin_amdgcn_mfma_f64_16x16x4f64(-img[(16 * a + g + 4 * r) * 16 + i], X[a][r], T, 0, 0, 0);
-    const double* inv = img + 112 * 16;
     X[b] = (v4d_t){0., 0., 0., 0.};
+    if (act) {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) X[b] = __builtin_amdgcn_mfma_f64_16x16x4f64(inv[(g + 4 * r) * 16 + i], T[r], X[b], 0, 0, 0);
+      for (int a = 0; a < b; ++a)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)      // A operand: L[16b + i][16a + g + 4r]
+          T = __builtin_amdgcn_mfma_f64_16x16x4f64(-img[(16 * a + g + 4 * r) * 16 + i], X[a][r], T, 0, 0, 0);
+      const double* inv = img + 112 * 16;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) X[b] = __builtin_amdgcn_mfma_f64_16x16x4f64(inv[(g + 4 * r) * 16 + i], T[r], X[b], 0, 0, 0);
+    }
     // X_b leaves through the stage it came in by: full 128-byte row segments
 #pragma unroll
     for (int r = 0; r < 4; ++r) ts[i * 18 + g + 4 * r] = X[b][r];
@@ -213,11 +216,14 @@ __device__ __forceinline__ void trsm128_slab_request(const double* __restrict__ 
 // next to a GEMM partner whichever way the operands arrive -- the partner's MFMAs take their share of the SIMD's pipe).
 // Same arithmetic in the same order as trsm128_lds_dev: bit-identical.  x: C - acc in the accumulator layout of trsm128_tile_dev;
 // P: trsm128_slab_request.  lds: TRSM128T_LDS doubles.
+// real (real_rows, chol_schedule.h; here and in trsm128_tile2_chain_dev): the rows of the tile above the identity padding.  real <= 32: x comes
+// from the half-height GEMM, x[ii] = row sub-tile 2 ii + wr.  A wave whose slab lies in the padding (16 wave >= real) holds zeros: it issues no
+// MFMA, stores the zeros it would have computed and meets every barrier.
 constexpr int TL_TS17 = 16 * 17;
 static_assert(32 * TL_TS17 <= TRSM128T_LDS, "whole-tile stage must fit the LDS of the half-tile form");
 template <bool SC1_OUT>
 __device__ __forceinline__ void trsm128_tile2_dev(const BatchView& v, int c0, int r0, const double* __restrict__ pk, int emu, double* lds,
-                                                  const v4d_t (&x)[2][4], TrsmSlabPre& P, unsigned long long* stamps = nullptr) {
+                                                  const v4d_t (&x)[2][4], TrsmSlabPre& P, unsigned long long* stamps = nullptr, int real = 64) {
   Sc1Buf ab;
   if (SC1_OUT) ab = sc1_buf(v.A + (size_t)emu * v.MS, (unsigned)(v.MS * sizeof(double)));
   const int ld = v.LD;
@@ -256,7 +262,7 @@ __device__ __forceinline__ void trsm128_tile2_dev(const BatchView& v, int c0, in
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
-      for (int q = 0; q < 4; ++q) lds[((2 * wr + ii) * 8 + 4 * wc + j) * TL_TS17 + (g + 4 * q) * 17 + i] = x[ii][j][q];
+      for (int q = 0; q < 4; ++q) lds[((real <= 32 ? 2 * ii + wr : 2 * wr + ii) * 8 + 4 * wc + j) * TL_TS17 + (g + 4 * q) * 17 + i] = x[ii][j][q];
   __syncthreads();
   v4d_t T[8];
 #pragma unroll
@@ -267,6 +273,7 @@ __device__ __forceinline__ void trsm128_tile2_dev(const BatchView& v, int c0, in
   pack_deposit(0, pkb[0]);
   __syncthreads();
   if (stamps && t == 0) stamps[0] = __builtin_amdgcn_s_memrealtime();
+  const bool act = wave * 16 < real;
   v4d_t X[8];
 #pragma unroll
   for (int b = 0; b < 8; ++b) {
@@ -277,12 +284,14 @@ __device__ __forceinline__ void trsm128_tile2_dev(const BatchView& v, int c0, in
     // chain is its 4 + 4 (x_b, then t_{b+1}) and the other 4 (6 - b) MFMAs are independent of it.  Every t_c still receives its updates in the
     // order b = 0, 1, .. with the same operands: bit-identical to the left-looking forms (trsm128_lds_dev, the chain tasks).
     X[b] = (v4d_t){0., 0., 0., 0.};
+    if (act) {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) X[b] = __builtin_amdgcn_mfma_f64_16x16x4f64(img[(g + 4 * r) * 16 + i], T[b][r], X[b], 0, 0, 0);
+      for (int r = 0; r < 4; ++r) X[b] = __builtin_amdgcn_mfma_f64_16x16x4f64(img[(g + 4 * r) * 16 + i], T[b][r], X[b], 0, 0, 0);
 #pragma unroll
-    for (int c = b + 1; c < 8; ++c)
+      for (int c = b + 1; c < 8; ++c)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) T[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(-img[(16 * c + g + 4 * r) * 16 + i], X[b][r], T[c], 0, 0, 0);
+        for (int r = 0; r < 4; ++r) T[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(-img[(16 * c + g + 4 * r) * 16 + i], X[b][r], T[c], 0, 0, 0);
+    }
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int r = 0; r < 4; ++r) ts[i * 18 + g + 4 * r] = X[b][r];
@@ -311,7 +320,7 @@ __device__ __forceinline__ void trsm128_tile2_dev(const BatchView& v, int c0, in
 // factorisation (HISTORY.md).  Same arithmetic in the same order: bit-identical.  Returns false when the launch has been aborted.
 template <bool SC1_OUT, bool LATE, class WAIT, class PUB>
 __device__ __forceinline__ bool trsm128_tile2_chain_dev(const BatchView& v, int c0, int r0, const double* __restrict__ pk, int emu, double* lds,
-                                                        const v4d_t (&x)[2][4], WAIT wait, PUB pub) {
+                                                        const v4d_t (&x)[2][4], WAIT wait, PUB pub, int real = 64) {
   Sc1Buf ab;
   if (SC1_OUT) ab = sc1_buf(v.A + (size_t)emu * v.MS, (unsigned)(v.MS * sizeof(double)));
   const int ld = v.LD;
@@ -363,7 +372,7 @@ __device__ __forceinline__ bool trsm128_tile2_chain_dev(const BatchView& v, int 
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
-      for (int q = 0; q < 4; ++q) lds[((2 * wr + ii) * 8 + 4 * wc + j) * TL_TS17 + (g + 4 * q) * 17 + i] = x[ii][j][q];
+      for (int q = 0; q < 4; ++q) lds[((real <= 32 ? 2 * ii + wr : 2 * wr + ii) * 8 + 4 * wc + j) * TL_TS17 + (g + 4 * q) * 17 + i] = x[ii][j][q];
   __syncthreads();
   v4d_t T[8];
 #pragma unroll
@@ -377,6 +386,7 @@ __device__ __forceinline__ bool trsm128_tile2_chain_dev(const BatchView& v, int 
     pack_deposit(0, pkb[0]);
   }
   __syncthreads();                       // (every wave has taken its slab)
+  const bool act = wave * 16 < real;
   v4d_t X[8];
 #pragma unroll
   for (int b = 0; b < 8; ++b) {
@@ -391,7 +401,7 @@ __device__ __forceinline__ bool trsm128_tile2_chain_dev(const BatchView& v, int 
     // on its CU's pipes in the launches where it matters.  The four operands of the NEXT quad are now requested before the MFMAs of this one,
     // pinned by scheduling barriers; X holds -x from here on (the sign on the four values of x_a, not on every operand): same products.)
     v4d_t Tb = T[b];
-    if (b > 0) {
+    if (b > 0 && act) {
       double an[4], ac[4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) an[r] = img[(g + 4 * r) * 16 + i];
@@ -421,8 +431,10 @@ __device__ __forceinline__ bool trsm128_tile2_chain_dev(const BatchView& v, int 
       if (b + 1 < 8) rows_request(b + 1);      // (row block b + 1 needs the pieces <= b)
     }
     X[b] = (v4d_t){0., 0., 0., 0.};
+    if (act) {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) X[b] = __builtin_amdgcn_mfma_f64_16x16x4f64(invr[r], Tb[r], X[b], 0, 0, 0);
+      for (int r = 0; r < 4; ++r) X[b] = __builtin_amdgcn_mfma_f64_16x16x4f64(invr[r], Tb[r], X[b], 0, 0, 0);
+    }
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int r = 0; r < 4; ++r) ts[i * 18 + g + 4 * r] = X[b][r];
