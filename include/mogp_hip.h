@@ -438,6 +438,19 @@ int mogp_gkdr_R(const double* X, int n, int m, const double* y, int nx, const do
    finite and their squared distances must not overflow: a NaN coordinate is NOT reported (the minimum skips it), and out[t] is
    +infinity when every squared distance of design t overflows.  (The Python shim rejects non-finite designs before the call.) */
 int mogp_design_min_pdist(const double* designs, int T, int n, int D, double* out);
+/* Optimised maximin Latin hypercubes: C >= 1 independent chains of column-swap threshold accepting on Morris & Mitchell's criterion
+   Phi = sum over i < j of 1 / R_ij^q, R_ij the integer squared distance of rows i and j of a level matrix (DESIGN.md section 3 "Design" states
+   every operation; tests/lhs_restate.py restates it in NumPy, bit for bit).  start (C, n, D) row-major: the start of every chain, each column
+   a permutation of 0 .. n-1.  2 <= n, 1 <= D <= 80, n_steps >= 0 proposals per chain, q >= 1, theta0 >= 0 the first threshold, multiplied by
+   0 < rho <= 1 after every stage >= 1 proposals.  Chain c draws proposal t from the Philox4x32-10 block of counter (t low, t high, stream + c, 0)
+   under key `seed`, so chain c of a call equals a one-chain call with stream + c and start c.  The level matrix must fit the LDS of one
+   workgroup: n * D <= 75264 for n <= 65536, n * D <= 70816 above; and (D (n - 1)^2)^q must stay below 2^1000.  Outputs per chain:
+   best_out (C, n, D) the visited state of smallest running Phi (the first on a tie), phi_out (C) its Phi computed from scratch, minr_out (C)
+   its smallest R_ij, pairs_out (C) the number of pairs i < j at that minimum, accepted_out (C) the accepted proposals.  n_steps = 0 returns the
+   starts with their criteria. */
+int mogp_design_anneal_lhs(const int* start, int C, int n, int D, long long n_steps, int q, double theta0, double rho, long long stage,
+                           unsigned long long seed, unsigned int stream, int* best_out, double* phi_out, long long* minr_out,
+                           long long* pairs_out, long long* accepted_out);
 
 /* ---- local approximate GP prediction for large designs (mogp_emulator_amd/LocalGP.py) ---- */
 /* The handle keeps the design `inputs` (N, D) and E rows of residual targets `residuals` (E, N) -- targets minus the mean function -- on

@@ -14,6 +14,10 @@ two classes need neither the library nor a device.
 chunks by one device call each (``libgpgpu.design_min_pdist``, csrc/kernels_design.hip).  There is no CPU fallback for that path
 (DESIGN.md section 1): without the library or a device ``MaxiMinLHC`` raises as ``GaussianProcessGPU`` does.  Only a ``pdist`` keyword
 (``metric=...``) is served by scipy on the host, because the device kernel computes the default Euclidean metric only.
+
+``OptimisedLHC`` searches instead of drawing again: ``n_chains`` independent chains of column-swap threshold accepting on Morris &
+Mitchell's criterion run on the device (``libgpgpu.design_anneal_lhs``, csrc/kernels_lhs.hip; DESIGN.md section 3 "Design"), and the chain
+whose closest pair is furthest apart is kept.  It has no CPU fallback either.
 """
 from inspect import signature
 
@@ -219,3 +223,80 @@ class MaxiMinLHC(LatinHypercubeDesign):
                 best = tries[k].copy()
         assert np.all(best >= 0.0) and np.all(best <= 1.0), "error in generating latin hypercube samples"
         return best
+
+
+class OptimisedLHC(LatinHypercubeDesign):
+    """A maximin Latin hypercube found by search: from ``n_chains`` random hypercubes, each chain exchanges two entries of one column at a
+    time and keeps the exchange when Morris & Mitchell's criterion (q = 5: p = 10 on distances) does not rise above a shrinking threshold;
+    of the chains' best states, the one with the largest minimum distance wins (then the fewest pairs at it, then the first chain).
+
+    ``sample(n_samples, n_chains=64, n_steps=None, q=5, theta0=0.1, rho=0.9, offsets="centre", seed=None, start=None, return_info=False)``
+
+    * the chain starts come from the legacy ``np.random`` stream: per chain one shuffle per parameter, in the parent's order; then, with
+      ``seed=None``, the 64-bit seed of the device's counter-based generator (two 32-bit draws, low word first) -- so ``np.random.seed(s)``
+      fixes the whole result;
+    * ``offsets="centre"`` puts point i at (P_i + 1/2) / n; ``"random"`` adds one ``np.random.random((n, D)) / n`` block after the search,
+      as the parent does;
+    * ``start``: a level matrix (n, D) or several (C, n, D) of the caller (every column a permutation of 0 .. n-1) to polish, in place of the
+      random starts (``n_chains`` is then their number);
+    * ``n_steps=None``: ``STEPS_PER_CELL * n_samples * n_parameters`` proposals per chain (DESIGN.md section 3 "Design" has the scan behind it);
+    * ``return_info=True``: also a dict with the per-chain ``phi``, ``min_r``, ``pairs``, ``accepted``, the ``winner`` and the ``seed``."""
+
+    STEPS_PER_CELL = 15
+
+    def __init__(self, *args):
+        # get_method() answers "Latin Hypercube", as MaxiMinLHC's does
+        super().__init__(*args)
+
+    def sample(self, n_samples, n_chains=64, n_steps=None, q=5, theta0=0.1, rho=0.9, offsets="centre", seed=None, start=None,
+               return_info=False):
+        values = super().sample(n_samples, n_chains=n_chains, n_steps=n_steps, q=q, theta0=theta0, rho=rho, offsets=offsets, seed=seed,
+                                start=start)
+        return (values, self._info) if return_info else values
+
+    def _draw_samples(self, n_samples, n_chains=64, n_steps=None, q=5, theta0=0.1, rho=0.9, offsets="centre", seed=None, start=None):
+        n = int(n_samples)
+        assert n > 0, "number of samples must be positive"
+        D = self.get_n_parameters()
+        if offsets not in ("centre", "random"):
+            raise ValueError("offsets must be 'centre' or 'random'")
+        if not LibGPGPU.HAVE_LIBGPGPU:
+            raise RuntimeError("Cannot draw an OptimisedLHC: The GPU library (libgpgpu) could not be loaded")
+        if not LibGPGPU.gpu_usable():
+            raise RuntimeError("Cannot draw an OptimisedLHC: A compatible GPU could not be found")
+        if start is None:
+            n_chains = int(n_chains)
+            assert n_chains > 0, "n_chains must be a positive integer"
+            levels = np.empty((n_chains, n, D), dtype=np.int32)
+            column = np.empty(n, dtype=np.int32)
+            for c in range(n_chains):
+                for d in range(D):
+                    column[:] = np.arange(n)
+                    np.random.shuffle(column)
+                    levels[c, :, d] = column
+        else:
+            levels = np.asarray(start)
+            if levels.ndim == 2:
+                levels = levels[None]
+            if levels.ndim != 3 or levels.shape[1:] != (n, D):
+                raise ValueError("start must have shape (n_samples, n_parameters) or (n_chains, n_samples, n_parameters)")
+        if seed is None:
+            lo, hi = (int(w) for w in np.random.randint(0, 2 ** 32, size=2, dtype=np.uint64))
+            seed = lo | (hi << 32)
+        seed = int(seed)
+        if n_steps is None:
+            n_steps = self.STEPS_PER_CELL * n * D
+        if n == 1:                      # one point: nothing to exchange
+            best = np.zeros((1, D), dtype=np.int32)
+            self._info = dict(phi=np.zeros(1), min_r=np.zeros(1, dtype=np.int64), pairs=np.zeros(1, dtype=np.int64),
+                              accepted=np.zeros(1, dtype=np.int64), winner=0, seed=seed)
+        else:
+            res = LibGPGPU.design_anneal_lhs(levels, n_steps, q=q, theta0=theta0, rho=rho, seed=seed)
+            best = res.levels[res.winner]
+            self._info = dict(phi=res.phi, min_r=res.min_r, pairs=res.pairs, accepted=res.accepted, winner=res.winner, seed=seed)
+        if offsets == "centre":
+            out = (best + 0.5) / float(n)
+        else:
+            out = best / float(n) + np.random.random((n, D)) / float(n)
+        assert np.all(out >= 0.0) and np.all(out <= 1.0), "error in generating latin hypercube samples"
+        return out

@@ -31,7 +31,7 @@ mogp_emulator_amd -- MI355X (gfx950) native fit + predict backend for mogp_emula
 """
 from .LibGPGPU import HAVE_LIBGPGPU, gpu_usable            # noqa: F401
 from .DimensionReduction import gKDR                        # noqa: F401
-from .ExperimentalDesign import ExperimentalDesign, MonteCarloDesign, LatinHypercubeDesign, MaxiMinLHC   # noqa: F401
+from .ExperimentalDesign import ExperimentalDesign, MonteCarloDesign, LatinHypercubeDesign, MaxiMinLHC, OptimisedLHC   # noqa: F401
 from .Laplace import LaplaceResult, logpost_hessian, laplace_approximation   # noqa: F401
 from .Marginal import predict_marginal, MarginalPredictResult, mixture_weights   # noqa: F401
 from .Sampling import sample_posterior, PosteriorSamples, philox_normals   # noqa: F401

@@ -160,6 +160,8 @@ SIGNATURES = {
     "mogp_gkdr_R": (c_int, [c_double_p, c_int, c_int, c_double_p, c_int, c_double_p, c_int, c_double_p, c_double, c_int, c_double_p,
                             c_int_p]),
     "mogp_design_min_pdist": (c_int, [c_double_p, c_int, c_int, c_int, c_double_p]),
+    "mogp_design_anneal_lhs": (c_int, [c_int_p, c_int, c_int, c_int, c_longlong, c_int, c_double, c_double, c_longlong, c_ulonglong, c_uint,
+                                       c_int_p, c_double_p, POINTER(c_longlong), POINTER(c_longlong), POINTER(c_longlong)]),
     "mogp_local_create": (c_void_p, [c_double_p, c_longlong, c_int, c_double_p, c_int, c_int]),
     "mogp_local_predict": (c_int, [c_void_p, c_int, c_int, c_double_p, c_double, c_double, c_double, c_int, c_double_p, c_int, c_int, c_int, c_int,
                                    c_double_p, c_double_p, c_int_p, c_double_p, c_int_p]),

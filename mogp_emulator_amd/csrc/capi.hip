@@ -119,6 +119,14 @@ int mogp_design_min_pdist(const double* designs, int T, int n, int D, double* ou
   return guarded([&] { design_min_pdist(designs, T, n, D, out); });
 }
 
+int mogp_design_anneal_lhs(const int* start, int C, int n, int D, long long n_steps, int q, double theta0, double rho, long long stage,
+                           unsigned long long seed, unsigned int stream, int* best_out, double* phi_out, long long* minr_out,
+                           long long* pairs_out, long long* accepted_out) {
+  return guarded([&] {
+    design_anneal_lhs(start, C, n, D, n_steps, q, theta0, rho, stage, seed, stream, best_out, phi_out, minr_out, pairs_out, accepted_out);
+  });
+}
+
 // ---- measurement hooks ----------------------------------------------------------------------------
 int mogp_profile_enable(int on) { prof_enable(on != 0); return 0; }
 int mogp_profile_reset(void) { prof_reset(); return 0; }

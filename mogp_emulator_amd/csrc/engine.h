@@ -301,6 +301,12 @@ constexpr size_t DESIGN_SCRATCH_BYTES = (size_t)64 << 20;
 constexpr int DESIGN_MAX_PASS = 32768;      // designs per pass (the second grid dimension)
 constexpr int DESIGN_MAX_N = 370688;        // points per design: 64 x 64 tiles of the lower triangle x 256 threads < 2^32 work-items
 void design_min_pdist(const double* designs, int T, int n, int D, double* out);
+// Optimised maximin Latin hypercubes (kernels_lhs.hip; DESIGN.md section 3 "Design"): C independent chains of column-swap threshold accepting on
+// the level matrices `start` (C, n, D), host pointers throughout.  Chain c draws its proposals from Philox stream `stream + c` under `seed`.
+// Outputs per chain: the best level matrix, its phi, min R and pairs at the minimum, and the accepted proposals.  Limits: lhs_plan.h.
+void design_anneal_lhs(const int* start, int C, int n, int D, long long n_steps, int q, double theta0, double rho, long long stage,
+                       unsigned long long seed, unsigned stream, int* best_out, double* phi_out, long long* minr_out, long long* pairs_out,
+                       long long* accepted_out);
 
 // Local approximate GP prediction (the handle: engine_local.hip, its kernels: kernels_local.hip; DESIGN.md section 3 "Local prediction"): the design (N, D) and E rows of residual
 // targets stay on the device the handle was created on; every predict() finds the k nearest design points of each query in the metric

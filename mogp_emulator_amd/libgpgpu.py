@@ -26,7 +26,7 @@ __all__ = [
     "WeakPrior", "InvGammaPrior", "GammaPrior", "LogNormalPrior",
     "BaseTransform", "CovTransform", "CorrTransform",
     "SquaredExponentialKernel", "Matern52Kernel", "MeanPriors", "set_fit_options", "set_device", "device_count", "pivot_cholesky",
-    "gkdr_R", "design_min_pdist", "LocalGP_GPU",
+    "gkdr_R", "design_min_pdist", "design_anneal_lhs", "AnnealResult", "LocalGP_GPU",
 ]
 
 
@@ -1335,6 +1335,48 @@ def design_min_pdist(designs):
     if T:
         check(_lib.mogp_design_min_pdist(dptr(designs), T, n, D, dptr(out)))
     return out
+
+
+class AnnealResult(object):
+    """What ``design_anneal_lhs`` returns, one entry per chain: ``levels`` (C, n, D) int32 the best level matrix, ``phi`` (C) its criterion,
+    ``min_r`` (C) its smallest integer squared distance, ``pairs`` (C) the pairs at that minimum, ``accepted`` (C) the accepted proposals.
+    ``winner``: the chain with the largest ``min_r``, then the fewest ``pairs``, then the lowest index -- all exact integers."""
+
+    def __init__(self, levels, phi, min_r, pairs, accepted):
+        self.levels, self.phi, self.min_r, self.pairs, self.accepted = levels, phi, min_r, pairs, accepted
+
+    @property
+    def winner(self):
+        return min(range(len(self.min_r)), key=lambda c: (-int(self.min_r[c]), int(self.pairs[c]), c))
+
+
+def design_anneal_lhs(start, n_steps, q=5, theta0=0.1, rho=0.9, stage=None, seed=0, stream=0):
+    """Column-swap threshold accepting on Morris & Mitchell's criterion from every level matrix of ``start`` (C, n, D) (one matrix (n, D)
+    counts as C = 1; every column a permutation of 0 .. n-1), ``n_steps`` proposals per chain, on the device (csrc/kernels_lhs.hip; the
+    algorithm: DESIGN.md section 3 "Design").  ``stage`` (None: max(1, n_steps // 100)) proposals share one threshold, which starts at
+    ``theta0`` and is multiplied by ``rho`` after each stage.  Chain c uses the Philox stream ``stream + c`` under ``seed``.  Returns an
+    ``AnnealResult``.  The library refuses by name what it cannot serve (RuntimeError)."""
+    raw = np.asarray(start)
+    if raw.dtype.kind not in "iu":
+        raise TypeError("start must be an integer array of levels")
+    if raw.ndim == 2:
+        raw = raw[None]
+    if raw.ndim != 3 or raw.size == 0:
+        raise TypeError("start must be a non-empty (C, n, D) integer array")
+    C, n, D = raw.shape
+    if raw.min() < 0 or raw.max() >= n:
+        raise RuntimeError("design_anneal_lhs: the levels of start must lie in 0 .. n-1")
+    levels = np.ascontiguousarray(raw, dtype=np.int32)
+    n_steps = int(n_steps)
+    stage = max(1, n_steps // 100) if stage is None else int(stage)
+    best = np.empty((C, n, D), dtype=np.int32)
+    phi = np.empty(C)
+    min_r, pairs, accepted = (np.empty(C, dtype=np.int64) for _ in range(3))
+    ll = ctypes.POINTER(ctypes.c_longlong)
+    check(_lib.mogp_design_anneal_lhs(iptr(levels), C, n, D, n_steps, int(q), float(theta0), float(rho), stage,
+                                      int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream) & 0xFFFFFFFF, iptr(best), dptr(phi),
+                                      min_r.ctypes.data_as(ll), pairs.ctypes.data_as(ll), accepted.ctypes.data_as(ll)))
+    return AnnealResult(best, phi, min_r, pairs, accepted)
 
 
 class LocalGP_GPU(object):
